@@ -23,19 +23,26 @@ N > 1: one process per GPU.  --mode (sharding.py):
   masked     one song of N*K segments, chunk heads run context-masked (no message, not parity-exact at
              the N-1 cuts: the reference's own i == 0 / always_mask_context behaviour there)
 value = frames of all ranks / max-over-ranks time; per-GPU work is K segments in every mode ("weak").
-The plain N > 1 line (default --mode replicas) also carries a `handoff` leg: BASELINE config 4's partitioning -- the
+
+A plain run does only what the headline figure needs: set up, warm up, time the K steps, write the last step's outputs
+(--dump-outputs DIR: DIR/mel.npy and DIR/scores.npy, float32, what `predict` returned; `_rank<r>` per rank for N > 1)
+and print the line.  Everything else is behind --full.
+
+With --full the N > 1 line (default --mode replicas) also carries a `handoff` leg: BASELINE config 4's partitioning -- the
 10-minute workload, 118 segments, as a wavefront of ceil(118 / N) songs x N segments with the device-to-device context
 hand-off (per-rank segments capped by --handoff-max-segments) -- timed after the replicas region, with each rank's
 idle fraction; a hang anywhere on that message path (first contact with RCCL point-to-point) ends the leg after
 --handoff-timeout seconds and the line is printed with an `error` field instead of never.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline      dominant kernel class: algorithmic FLOP per launch / mean launch
                 duration measured with hipEvents on the launch stream
                 (msd_profile_steps), vs the dense 16-bit MFMA peak (f16 = bf16 rate);
   cpu_baseline  the torch-CPU float32 oracle ("port") timed on a bounded sample
                 (encoders + a few DDPM steps, extrapolated linearly: per-step cost
-                is constant) on rank 0, N = 1 only.
+                is constant) on rank 0, N = 1 only;
+  batched       --batched-songs songs per GPU in one handle, N = 1 only;
+  small         BASELINE config 2 (the `small` model) over --small-segments segments, N = 1 only.
 """
 from __future__ import annotations
 
@@ -918,6 +925,109 @@ def handoff_leg(args, model, spec, dist, rank, world, song_tokens, ctx_shape):
                   % (args.handoff_segments, k_songs, world)}
 
 
+def roofline_leg(args, model, spec, toks, nb, c_len, world, on_gpu, graph_step_ms):
+  """--full: the line's `roofline` object for the dominant kernel class of the DDPM step, measured after the timed
+  region (eager hipEvents profile, this run's own rocprofv3 child, the committed profile); `toks` = the last segment's
+  tokens, `graph_step_ms` = the timed region's sampler milliseconds per DDPM step (replicas mode) or None."""
+  import torch
+  passes = 2 if args.cfg_weight != 1.0 else 1
+  # ---- roofline of the dominant kernel (hipEvents on the launch stream) --------
+  nm = model._get_native()
+  s_valid = float((toks > 0).sum() / nb + (c_len or 0))
+  if on_gpu:
+    with torch.cuda.device(model.device):
+      prof = nm.profile_steps(nb, args.profile_steps, stream=model._stream.cuda_stream)
+  else:
+    prof = nm.profile_steps(nb, args.profile_steps)
+  flops = {k: v * nb for k, v in class_flops(spec, s_valid, passes).items()}
+  abytes = {k: v * nb for k, v in class_bytes(spec, s_valid, passes, 2 if args.precision.endswith('x3') else 1).items()}
+  per_class = {}
+  for name, (ms, launches) in prof.items():
+    if launches:
+      per_class[name] = {'ms_per_launch': ms / launches, 'launches_per_step': launches / args.profile_steps,
+                         'ms_per_step': ms / args.profile_steps}
+  fold_cross_q_work(flops, abytes, per_class)
+  # dominant kernel = the class that carries the most algorithmic FLOP per step (the gated MLP input projection:
+  # 30 % of the step's FLOP and the largest share of its GPU time in the rocprofv3 trace).  NOT "the longest
+  # eager launch": under hipEvents the first launch of a step (in-proj, cold) can outlast it by a microsecond,
+  # which once put a 0.05 GFLOP kernel into this object.  Per-step totals by class: per_class_ms_per_step.
+  dom = max((n for n in per_class if n in flops), key=lambda n: flops[n] * per_class[n]['launches_per_step'])
+  event_ms = per_class[dom]['ms_per_launch']
+  step_flops = sum(flops[n] * per_class[n]['launches_per_step'] for n in per_class if n in flops)
+  prof_entry, prof_src = profile_roofline(dom, args)
+  # `achieved` = algorithmic FLOP per launch / average launch duration.  Duration, in this order: (1) THIS run's own
+  # rocprofv3 kernel trace (self_profile: a child of this script on this box and binary, untimed) -- what the graph
+  # replays, measured where the line is measured; (2) the committed profile's average when it was taken on this binary
+  # (another box: labelled); (3) the live hipEvent figure (eager launches, ~20 % longer).  All are reported.
+  sp, sp_why = (None, 'skipped (--no-self-profile)')
+  if on_gpu and world == 1 and not args.no_self_profile and nb == 1:
+    keep = os.path.join(args.self_profile_keep, 'self_profile_%s_kernel_stats.csv' % args.preset) if args.self_profile_keep else None
+    sp, sp_why = self_profile(args, args.preset, keep_csv=keep)
+  sp_table = sp_whole = None
+  if sp is not None:
+    planes_n = 2 if args.precision.endswith('x3') else 1
+    sp_dom, sp_table, sp_whole, _, _ = roofline_from_self_profile(spec, sp, passes, planes_n, graph_step_ms)
+    if sp_dom != dom or dom not in sp_table:
+      sp, sp_why = None, 'the trace\'s dominant class (%s) is not the eager one (%s)' % (sp_dom, dom)
+  use_prof = bool(prof_entry and prof_entry.get('matches_binary') and prof_entry.get('avg_us'))
+  if sp is not None:
+    dur_ms = sp_table[dom]['us_per_launch'] * 1e-3
+    dur_src = 'rocprofv3 --kernel-trace --stats of THIS run (self_profile: a child of this command on this box, same binary)'
+  elif use_prof:
+    dur_ms = prof_entry['avg_us'] * 1e-3
+    dur_src = 'rocprofv3 kernel-trace average of the COMMITTED profile (profiles/roofline.json: same binary, another box)'
+  else:
+    dur_ms = event_ms
+    dur_src = 'hipEvents around eager launches (msd_profile_steps)'
+  achieved = flops[dom] / (dur_ms * 1e-3) / 1e12
+  return {
+      'bound': 'mfma', 'kernel': dom, 'achieved': round(achieved, 3), 'peak': PEAK_BF16_TFLOPS,
+      'unit': 'TFLOP/s', 'frac': round(achieved / PEAK_BF16_TFLOPS, 5),
+      'traffic': prof_entry.get('fabric_bytes_per_launch') if prof_entry else None,
+      'traffic_source': 'PMC passes of the committed profile (profiles/roofline.json; counter collection serialises the '
+                        'dispatches at ~50 ms each, so it cannot run inside this command)' if prof_entry else None,
+      'duration_source': dur_src,
+      'self_profile': ({k: v for k, v in sp.items() if k != 'per_class'} if sp is not None else {'ok': False, 'why': sp_why}),
+      'per_class_us': sp_table,
+      'whole_step_self_profile': sp_whole,
+      'kernel_ms_per_launch': round(dur_ms, 5),
+      'kernel_ms_per_launch_hipevents': round(event_ms, 5),
+      'achieved_hipevents': round(flops[dom] / (event_ms * 1e-3) / 1e12, 3),
+      'algorithmic_gflop_per_launch': round(flops[dom] / 1e9, 4),
+      'algorithmic_bytes_per_launch': int(abytes.get(dom, 0)),
+      'profile': prof_entry, 'profile_source': prof_src,
+      'library_sha': library_hash('bf16' if args.precision.startswith('bf16') else 'f16'),
+      'whole_step': {
+          'algorithmic_gflop': round(step_flops / 1e9, 2),
+          'eager_ms': round(sum(v['ms_per_step'] for v in per_class.values()), 4),
+          'graph_ms': None if graph_step_ms is None else round(graph_step_ms, 4),
+          'achieved_tflops_graph': None if graph_step_ms is None else round(step_flops / (graph_step_ms * 1e-3) / 1e12, 3),
+          'launches': round(sum(v['launches_per_step'] for v in per_class.values()), 1),
+      },
+      'per_class_ms_per_step': {k: round(v['ms_per_step'], 4) for k, v in per_class.items()},
+  }
+
+
+DUMP_BYTES = 64 * 10**6   # --dump-outputs: at most this much in all (every rank of a run together)
+
+
+def dump_outputs(outdir, arrays, budget=DUMP_BYTES):
+  """--dump-outputs: every array as <outdir>/<name>.npy in float32.  One that does not fit what is left of `budget` is
+  replaced by a fixed sample of its elements (flattened, positions drawn with seed 0, in ascending order), so that two
+  runs with the same arguments write the same elements."""
+  os.makedirs(outdir, exist_ok=True)
+  left = int(budget)
+  for name, a in arrays.items():
+    if hasattr(a, 'detach'):
+      a = a.detach().cpu().numpy()
+    a = np.ascontiguousarray(a, dtype=np.float32)
+    if a.nbytes > left:
+      keep = np.sort(np.random.default_rng(0).choice(a.size, left // a.itemsize, replace=False))
+      a = a.reshape(-1)[keep]
+    np.save(os.path.join(outdir, name + '.npy'), a)
+    left -= a.nbytes
+
+
 def model_kwargs(args):
   """InferenceModel options that are NOT the library default (the default run passes none)."""
   kw = {}
@@ -972,6 +1082,11 @@ def main():
   ap.add_argument('--self-profile-keep', default='', help='directory that keeps the children\'s kernel_stats tables (profiles/ records)')
   ap.add_argument('--model-factory', default='msd_amd:InferenceModel',
                   help='module:attr of the InferenceModel class (tests swap in a CPU stand-in to exercise the multi-rank plumbing)')
+  ap.add_argument('--full', action='store_true',
+                  help='also run everything beyond the headline figure: roofline (hipEvents + rocprofv3 legs), batched and '
+                       'small legs, cpu_baseline; N > 1: the hand-off probe and the `handoff` leg')
+  ap.add_argument('--dump-outputs', default='', metavar='DIR',
+                  help='after the timed steps, write what the last one returned (mel, scores) as DIR/<name>.npy (float32)')
   args = ap.parse_args()
   if args.self_profile_child:
     return self_profile_child(args)
@@ -1045,10 +1160,10 @@ def main():
     if c_len is not None:
       batch['encoder_continuous_inputs'] = pred
       batch['encoder_continuous_mask'] = (np.zeros if k == 0 else np.ones)((nb, c_len), np.int32)
-    out, _ = model.predict(batch, seed=0, segment=k, return_torch=True)
+    out, scores = model.predict(batch, seed=0, segment=k, return_torch=True)
     if c_len is not None:
       pred = out
-    return out
+    return out, scores
 
   for k in range(args.warmup):
     run_segment(k)
@@ -1059,9 +1174,10 @@ def main():
   t0 = time.perf_counter()
   enc_s = smp_s = 0.0
   ctx_shape = (1, c_len or 0, 128)
+  scores = None                # predict's second output (replicas mode; predict_sequence returns the mel only)
   if mode == 'replicas':
     for k in range(args.warmup, n_seg):
-      out = run_segment(k)
+      out, scores = run_segment(k)
       enc_s += model.last_timing['encode_s']
       smp_s += model.last_timing['sample_s']
   elif mode == 'chained':      # one song, world * K segments, rank r owns [r K, (r+1) K)
@@ -1082,6 +1198,12 @@ def main():
   _sync(model.device)
   elapsed = time.perf_counter() - t0
   assert torch.isfinite(torch.as_tensor(out)).all(), 'non-finite mel output'
+  if args.dump_outputs:
+    suffix = '_rank%d' % rank if world > 1 else ''
+    dumped = {'mel' + suffix: out}
+    if scores is not None:
+      dumped['scores' + suffix] = scores
+    dump_outputs(args.dump_outputs, dumped, DUMP_BYTES // world)
   per_rank_seconds = None
   if dist is not None:
     per_rank_seconds = [None] * world
@@ -1102,87 +1224,6 @@ def main():
     frames = world * args.steps * t_frames * nb
     value = frames / elapsed
     audio_s = frames * 320 / 16000.0
-    passes = 2 if args.cfg_weight != 1.0 else 1
-    # ---- roofline of the dominant kernel (hipEvents on the launch stream) --------
-    nm = model._get_native()
-    toks = segs[-1]
-    s_valid = float((toks > 0).sum() / nb + (c_len or 0))
-    # make sure the profiled steps see this rank's last replica-style encode (chained modes end elsewhere)
-    if mode != 'replicas':
-      run_segment(n_seg - 1)
-    if on_gpu:
-      with torch.cuda.device(model.device):
-        prof = nm.profile_steps(nb, args.profile_steps, stream=model._stream.cuda_stream)
-    else:
-      prof = nm.profile_steps(nb, args.profile_steps)
-    flops = {k: v * nb for k, v in class_flops(spec, s_valid, passes).items()}
-    abytes = {k: v * nb for k, v in class_bytes(spec, s_valid, passes, 2 if args.precision.endswith('x3') else 1).items()}
-    per_class = {}
-    for name, (ms, launches) in prof.items():
-      if launches:
-        per_class[name] = {'ms_per_launch': ms / launches, 'launches_per_step': launches / args.profile_steps,
-                           'ms_per_step': ms / args.profile_steps}
-    fold_cross_q_work(flops, abytes, per_class)
-    # dominant kernel = the class that carries the most algorithmic FLOP per step (the gated MLP input projection:
-    # 30 % of the step's FLOP and the largest share of its GPU time in the rocprofv3 trace).  NOT "the longest
-    # eager launch": under hipEvents the first launch of a step (in-proj, cold) can outlast it by a microsecond,
-    # which once put a 0.05 GFLOP kernel into this object.  Per-step totals by class: per_class_ms_per_step.
-    dom = max((n for n in per_class if n in flops), key=lambda n: flops[n] * per_class[n]['launches_per_step'])
-    event_ms = per_class[dom]['ms_per_launch']
-    step_flops = sum(flops[n] * per_class[n]['launches_per_step'] for n in per_class if n in flops)
-    prof_entry, prof_src = profile_roofline(dom, args)
-    graph_step_ms = (smp_s / args.steps / args.num_steps * 1e3) if mode == 'replicas' else None
-    # `achieved` = algorithmic FLOP per launch / average launch duration.  Duration, in this order: (1) THIS run's own
-    # rocprofv3 kernel trace (self_profile: a child of this script on this box and binary, untimed) -- what the graph
-    # replays, measured where the line is measured; (2) the committed profile's average when it was taken on this binary
-    # (another box: labelled); (3) the live hipEvent figure (eager launches, ~20 % longer).  All are reported.
-    sp, sp_why = (None, 'skipped (--no-self-profile)')
-    if on_gpu and world == 1 and not args.no_self_profile and nb == 1:
-      keep = os.path.join(args.self_profile_keep, 'self_profile_%s_kernel_stats.csv' % args.preset) if args.self_profile_keep else None
-      sp, sp_why = self_profile(args, args.preset, keep_csv=keep)
-    sp_table = sp_whole = None
-    if sp is not None:
-      planes_n = 2 if args.precision.endswith('x3') else 1
-      sp_dom, sp_table, sp_whole, _, _ = roofline_from_self_profile(spec, sp, passes, planes_n, graph_step_ms)
-      if sp_dom != dom or dom not in sp_table:
-        sp, sp_why = None, 'the trace\'s dominant class (%s) is not the eager one (%s)' % (sp_dom, dom)
-    use_prof = bool(prof_entry and prof_entry.get('matches_binary') and prof_entry.get('avg_us'))
-    if sp is not None:
-      dur_ms = sp_table[dom]['us_per_launch'] * 1e-3
-      dur_src = 'rocprofv3 --kernel-trace --stats of THIS run (self_profile: a child of this command on this box, same binary)'
-    elif use_prof:
-      dur_ms = prof_entry['avg_us'] * 1e-3
-      dur_src = 'rocprofv3 kernel-trace average of the COMMITTED profile (profiles/roofline.json: same binary, another box)'
-    else:
-      dur_ms = event_ms
-      dur_src = 'hipEvents around eager launches (msd_profile_steps)'
-    achieved = flops[dom] / (dur_ms * 1e-3) / 1e12
-    roofline = {
-        'bound': 'mfma', 'kernel': dom, 'achieved': round(achieved, 3), 'peak': PEAK_BF16_TFLOPS,
-        'unit': 'TFLOP/s', 'frac': round(achieved / PEAK_BF16_TFLOPS, 5),
-        'traffic': prof_entry.get('fabric_bytes_per_launch') if prof_entry else None,
-        'traffic_source': 'PMC passes of the committed profile (profiles/roofline.json; counter collection serialises the '
-                          'dispatches at ~50 ms each, so it cannot run inside this command)' if prof_entry else None,
-        'duration_source': dur_src,
-        'self_profile': ({k: v for k, v in sp.items() if k != 'per_class'} if sp is not None else {'ok': False, 'why': sp_why}),
-        'per_class_us': sp_table,
-        'whole_step_self_profile': sp_whole,
-        'kernel_ms_per_launch': round(dur_ms, 5),
-        'kernel_ms_per_launch_hipevents': round(event_ms, 5),
-        'achieved_hipevents': round(flops[dom] / (event_ms * 1e-3) / 1e12, 3),
-        'algorithmic_gflop_per_launch': round(flops[dom] / 1e9, 4),
-        'algorithmic_bytes_per_launch': int(abytes.get(dom, 0)),
-        'profile': prof_entry, 'profile_source': prof_src,
-        'library_sha': library_hash('bf16' if args.precision.startswith('bf16') else 'f16'),
-        'whole_step': {
-            'algorithmic_gflop': round(step_flops / 1e9, 2),
-            'eager_ms': round(sum(v['ms_per_step'] for v in per_class.values()), 4),
-            'graph_ms': None if graph_step_ms is None else round(graph_step_ms, 4),
-            'achieved_tflops_graph': None if graph_step_ms is None else round(step_flops / (graph_step_ms * 1e-3) / 1e12, 3),
-            'launches': round(sum(v['launches_per_step'] for v in per_class.values()), 1),
-        },
-        'per_class_ms_per_step': {k: round(v['ms_per_step'], 4) for k, v in per_class.items()},
-    }
     par = {'replicas': 'song-parallel x%d' % world,
            'chained': 'one song chained over %d GPUs (context hand-off, serial)' % world,
            'wavefront': 'wavefront of %d songs x %d segments over %d GPUs (context hand-off per segment)' % (args.steps, world, world),
@@ -1207,7 +1248,6 @@ def main():
                    'precision': precision_ran, 'precision_requested': args.precision, 'parallelism': par, 'mode': mode,
                    'attention_query_planes': args.attn_planes or 'library default: hi + lo for Q and for the softmax weights',
                    'knobs': args.knob or 'library defaults'},
-        'roofline': roofline,
     }
     if mode == 'replicas':
       result['encode_ms_per_segment'] = round(enc_s / args.steps * 1e3, 3)
@@ -1218,6 +1258,13 @@ def main():
       result['per_rank_precision'] = precisions_seen  # what each rank's model ended in (range_fallback may switch planes)
       for r_, p_ in zip(result['ranks_seen'], precisions_seen):
         r_['precision'] = p_
+  if rank == 0 and args.full:
+    # ---- --full: everything beyond the headline figure, untimed, after the line's own numbers are in
+    # make sure the profiled steps see this rank's last replica-style encode (chained modes end elsewhere)
+    if mode != 'replicas':
+      run_segment(n_seg - 1)
+    graph_step_ms = (smp_s / args.steps / args.num_steps * 1e3) if mode == 'replicas' else None
+    result['roofline'] = roofline_leg(args, model, spec, segs[-1], nb, c_len, world, on_gpu, graph_step_ms)
     if world == 1 and args.batched_songs > 1 and nb == 1:
       result['batched'] = batched_leg(spec, args)
     if world == 1 and args.small_segments > 0 and nb == 1 and args.preset != 'small':
@@ -1230,7 +1277,7 @@ def main():
         batch['encoder_continuous_inputs'] = np.zeros((1, c_len, 128), np.float32)
         batch['encoder_continuous_mask'] = np.ones((1, c_len), np.int32)
       result['cpu_baseline'] = cpu_baseline(spec, model.params, batch, args.cpu_sample_steps)
-  if dist is not None and c_len:
+  if dist is not None and c_len and args.full:
     # ---- the message path (probe + BASELINE config 4 leg), AFTER the headline figures are safe: first contact with
     # RCCL point-to-point on this node may hang; the watchdog then prints the line as it stands with an error field
     printed = []

@@ -233,3 +233,19 @@ def test_dual_launch_kernels_classify_and_carry_the_folded_query_projection():
   flops2 = {'gemm_attn_out': 10.0, 'gemm_cross_q': 3.0}
   bench.fold_cross_q_work(flops2, {}, {'gemm_attn_out': {}, 'gemm_cross_q': {}})                           # a launch of its own: untouched
   assert flops2['gemm_attn_out'] == 10.0
+
+
+def test_dump_outputs_float32_and_a_fixed_sample_of_what_does_not_fit(tmp_path):
+  """--dump-outputs: float32 .npy files; an array beyond the budget left becomes a seeded sample of its elements (same
+  positions every time, ascending), so that dumps of two builds compare element for element."""
+  import torch
+  big = np.arange(1000, dtype=np.float64).reshape(10, 100)
+  arrays = {'scores': torch.zeros(3), 'mel': big}
+  for d in ('a', 'b'):
+    bench.dump_outputs(str(tmp_path / d), arrays, budget=4 * 3 + 4 * 100)
+  s, m = np.load(tmp_path / 'a' / 'scores.npy'), np.load(tmp_path / 'a' / 'mel.npy')
+  assert s.dtype == np.float32 and s.shape == (3,) and m.dtype == np.float32 and m.shape == (100,)
+  assert (np.diff(m) > 0).all() and np.isin(m, big).all()
+  np.testing.assert_array_equal(m, np.load(tmp_path / 'b' / 'mel.npy'))
+  bench.dump_outputs(str(tmp_path / 'c'), arrays)                       # the default budget (64 MB) holds both whole
+  np.testing.assert_array_equal(np.load(tmp_path / 'c' / 'mel.npy'), big.astype(np.float32))

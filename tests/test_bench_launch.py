@@ -11,14 +11,14 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-STUB = ['--dist-backend', 'gloo', '--model-factory', 'tests.bench_stub:StubInferenceModel', '--no-cpu-baseline',
-        '--batched-songs', '0', '--small-segments', '0']
+STUB_MODEL = ['--dist-backend', 'gloo', '--model-factory', 'tests.bench_stub:StubInferenceModel']
+STUB = STUB_MODEL + ['--no-cpu-baseline', '--batched-songs', '0', '--small-segments', '0']
 
 
-def run_bench(*flags, env_extra=None, timeout=240):
+def run_bench(*flags, env_extra=None, timeout=240, stub=STUB):
   env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
   env.update(env_extra or {})
-  p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + list(flags) + STUB, cwd=ROOT, env=env,
+  p = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py')] + list(flags) + stub, cwd=ROOT, env=env,
                      stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout)
   return p
 
@@ -29,7 +29,7 @@ def json_lines(stdout):
 
 @pytest.mark.parametrize('mode', ['replicas', 'chained', 'wavefront', 'masked'])
 def test_plain_command_starts_its_own_ranks(mode):
-  p = run_bench('--gpus', '2', '--steps', '3', '--warmup', '1', '--mode', mode)
+  p = run_bench('--gpus', '2', '--steps', '3', '--warmup', '1', '--mode', mode, '--full')
   assert p.returncode == 0, p.stderr[-2000:]
   lines = json_lines(p.stdout)
   assert len(lines) == 1, p.stdout            # rank 0 only
@@ -66,7 +66,7 @@ def test_a_hung_handoff_leg_still_prints_the_replicas_line():
   """First contact with RCCL point-to-point must not cost the SCALE record: when the hand-off leg hangs (here: rank 1
   never returns from its segments), every rank's watchdog ends its process after --handoff-timeout and rank 0 prints
   the line it already has -- replicas figures intact, `handoff.error` set."""
-  p = run_bench('--gpus', '2', '--steps', '2', '--warmup', '1', '--handoff-timeout', '6', env_extra={'MSD_STUB_HANG_RANK': '1'},
+  p = run_bench('--gpus', '2', '--steps', '2', '--warmup', '1', '--full', '--handoff-timeout', '6', env_extra={'MSD_STUB_HANG_RANK': '1'},
                 timeout=120)
   lines = json_lines(p.stdout)
   assert len(lines) == 1, (p.stdout, p.stderr[-2000:])
@@ -80,11 +80,44 @@ def test_a_hung_handoff_leg_still_prints_the_replicas_line():
 
 
 def test_single_rank_needs_no_launcher():
-  p = run_bench('--gpus', '1', '--steps', '2', '--warmup', '1')
+  p = run_bench('--gpus', '1', '--steps', '2', '--warmup', '1', '--full')
   assert p.returncode == 0, p.stderr[-2000:]
   d, = json_lines(p.stdout)
   assert d['n_gpus'] == 1 and 'handoff_check' not in d
   assert d['roofline']['kernel'] == 'gemm_mlp_in_geglu' and d['roofline']['bound'] == 'mfma'
+
+
+@pytest.mark.parametrize('gpus', [1, 2])
+def test_plain_line_is_lean_and_dumps_the_last_step(gpus, tmp_path):
+  """Without --full the line holds the headline figure only (no roofline, no side legs, no hand-off probe -- not even
+  when their own switches are left at their defaults), and --dump-outputs writes what the last timed step returned
+  (mel + scores, float32; one set per rank for N > 1), the same arrays from run to run."""
+  import numpy as np
+  dumps = []
+  for run in range(2):
+    out = tmp_path / ('run%d' % run)
+    p = run_bench('--gpus', str(gpus), '--steps', '3', '--warmup', '1', '--dump-outputs', str(out), stub=STUB_MODEL)
+    assert p.returncode == 0, p.stderr[-2000:]
+    d, = json_lines(p.stdout)
+    assert d['n_gpus'] == gpus and d['steps'] == 3 and d['warmup'] == 1
+    assert d['metric'] == 'mel-frames/sec' and d['unit'] == 'mel-frames/sec' and d['higher_is_better'] is True
+    # ms_per_step = the timed region / --steps (the stand-in's steps take well under a millisecond: compare in ms,
+    # within the line's rounding to 0.001 ms)
+    assert d['ms_per_step'] > 0 and abs(gpus * 3 * 256 / d['value'] / 3 * 1e3 - d['ms_per_step']) <= 6e-4
+    assert d['dtype'].startswith('f16x3')
+    for key in ('roofline', 'cpu_baseline', 'batched', 'small', 'handoff_check', 'handoff'):
+      assert key not in d, key
+    names = ['mel', 'scores'] if gpus == 1 else ['%s_rank%d' % (n, r) for r in range(gpus) for n in ('mel', 'scores')]
+    assert sorted(f.name for f in out.iterdir()) == sorted(n + '.npy' for n in names)
+    arrays = {n: np.load(out / (n + '.npy')) for n in names}
+    for n, a in arrays.items():
+      assert a.dtype == np.float32 and np.isfinite(a).all()
+      assert a.shape == ((1, 256, 128) if n.startswith('mel') else (1,))
+    dumps.append(arrays)
+  for n in dumps[0]:
+    np.testing.assert_array_equal(dumps[0][n], dumps[1][n])
+  if gpus == 2:   # the ranks synthesize different songs
+    assert not np.array_equal(dumps[0]['mel_rank0'], dumps[0]['mel_rank1'])
 
 
 def test_world_size_mismatch_is_an_error():

@@ -137,7 +137,7 @@ def test_plain_bench_command_two_ranks_real_model_handoff_leg():
   env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
   p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '2', '--dist-backend', 'gloo', '--steps', '1',
                       '--warmup', '1', '--num-steps', str(steps), '--handoff-max-segments', '2', '--profile-steps', '1',
-                      '--handoff-timeout', '300'], cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                      '--handoff-timeout', '300', '--full'], cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
                      text=True, timeout=900)
   assert p.returncode == 0, p.stderr[-3000:]
   lines = [json.loads(l) for l in p.stdout.splitlines() if l.startswith('{') and l.rstrip().endswith('}')]
@@ -166,3 +166,39 @@ def test_plain_bench_command_two_ranks_real_model_handoff_leg():
     for r in range(2):
       want = hashlib.sha256(np.ascontiguousarray(seq[:, r * t:(r + 1) * t], np.float32).tobytes()).hexdigest()[:16]
       assert rows[r]['segment_sha256_16'][j] == want, (j, r)
+
+
+def test_plain_bench_dumps_what_its_last_timed_step_returned(tmp_path):
+  """The plain `python bench.py --dump-outputs DIR` with the REAL model: DIR/mel.npy is BIT-identical to the last
+  segment of the same song synthesized here through InferenceModel.predict (the bench's seeded tokens, context
+  chaining, seed and segment indices), DIR/scores.npy holds predict's zeros, and the line carries no --full leg."""
+  import json
+  import subprocess
+  import sys
+  import torch
+  import msd_amd
+  root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+  steps, warmup, timed = 20, 1, 2
+  env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_ADDR', 'MASTER_PORT')}
+  p = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--gpus', '1', '--preset', 'tiny_context',
+                      '--num-steps', str(steps), '--steps', str(timed), '--warmup', str(warmup),
+                      '--dump-outputs', str(tmp_path)], cwd=root, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                     text=True, timeout=600)
+  assert p.returncode == 0, p.stderr[-3000:]
+  lines = [json.loads(l) for l in p.stdout.splitlines() if l.startswith('{') and l.rstrip().endswith('}')]
+  assert len(lines) == 1, p.stdout[-2000:]
+  d = lines[0]
+  assert d['steps'] == timed and d['ms_per_step'] > 0 and d['config']['precision'] == 'f16x3'
+  assert not {'roofline', 'batched', 'small', 'cpu_baseline'} & set(d)
+  assert sorted(os.listdir(tmp_path)) == ['mel.npy', 'scores.npy']
+  mel, scores = np.load(tmp_path / 'mel.npy'), np.load(tmp_path / 'scores.npy')
+  assert mel.dtype == np.float32 and scores.dtype == np.float32 and scores.shape == (1,) and (scores == 0).all()
+  spec = msd_amd.config.preset('tiny_context', num_steps=steps, cfg_weight=5.0)
+  model = msd_amd.InferenceModel('synthetic:0', spec)
+  c = model.targets_context_length
+  pred = torch.zeros((1, c, 128), dtype=torch.float32, device=model.device)
+  for k in range(warmup + timed):
+    batch = {'encoder_input_tokens': msd_amd.synthetic.segment_tokens(spec, k), 'encoder_continuous_inputs': pred,
+             'encoder_continuous_mask': (np.zeros if k == 0 else np.ones)((1, c), np.int32)}
+    pred, _ = model.predict(batch, seed=0, segment=k, return_torch=True)
+  np.testing.assert_array_equal(mel, pred.cpu().numpy())

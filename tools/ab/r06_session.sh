@@ -11,7 +11,7 @@ case $WHAT in
 first)
   timeout 900 python -m pytest tests/test_gpu_model.py -m gpu -q -x -k "draws_the_step_noise or staging or exact_launch or philox or explicit_noise" > $OUT/${TAG}_new_tests.log 2>&1; tail -5 $OUT/${TAG}_new_tests.log
   mkdir -p $OUT/${TAG}_selfprof
-  timeout 600 python bench.py --self-profile-keep $OUT/${TAG}_selfprof > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err; tail -c 600 $OUT/${TAG}_bench_default.json; tail -3 $OUT/${TAG}_bench_default.err
+  timeout 600 python bench.py --full --self-profile-keep $OUT/${TAG}_selfprof > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err; tail -c 600 $OUT/${TAG}_bench_default.json; tail -3 $OUT/${TAG}_bench_default.err
   PRESET=small SKIP_TRACE=1 bash tools/profile_round.sh ${TAG}_small
   ;;
 second)  # in-launch merge of the key-split cross-attention: op-level and model-level bitwise tests, then in-process A/B
@@ -21,7 +21,7 @@ second)  # in-launch merge of the key-split cross-attention: op-level and model-
   timeout 400 python tools/ab/knob_ab.py --rounds 3 --tokens 300 --tokens 1300 --json $OUT/${TAG}_merge_ab2.json 'cross_merge_in_launch=False' 'cross_merge_in_launch=True' 2>&1 | grep -v Warning | tee $OUT/${TAG}_merge_ab2.log
   timeout 300 python tools/ab/knob_ab.py --preset small --rounds 4 --json $OUT/${TAG}_merge_ab_small.json 'cross_merge_in_launch=False' 'cross_merge_in_launch=True' 2>&1 | grep -v Warning | tee $OUT/${TAG}_merge_ab_small.log
   mkdir -p $OUT/${TAG}_selfprof
-  timeout 600 python bench.py --no-cpu-baseline --self-profile-keep $OUT/${TAG}_selfprof > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err; tail -c 300 $OUT/${TAG}_bench_default.json; tail -3 $OUT/${TAG}_bench_default.err
+  timeout 600 python bench.py --full --no-cpu-baseline --self-profile-keep $OUT/${TAG}_selfprof > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err; tail -c 300 $OUT/${TAG}_bench_default.json; tail -3 $OUT/${TAG}_bench_default.err
   ;;
 third)  # folded cross-attention query projection (S6): parity tests, in-process A/B, bench with its own kernel trace
   timeout 1500 python -m pytest tests/test_gpu_model.py -m gpu -q -x -s -k "folded_cross_query or exact_launch or sum_cross or encode_and_single or does_not_depend_on_the_batch or batched_songs" > $OUT/${TAG}_fold_tests.log 2>&1; tail -4 $OUT/${TAG}_fold_tests.log; grep "folded vs unfolded" $OUT/${TAG}_fold_tests.log | head -40
@@ -30,7 +30,7 @@ third)  # folded cross-attention query projection (S6): parity tests, in-process
   timeout 300 python tools/ab/knob_ab.py --preset small --rounds 4 --json $OUT/${TAG}_fold_ab_small.json 'cross_q_fold=False' 'cross_q_fold=True' 2>&1 | grep -v Warning | tee $OUT/${TAG}_fold_ab_small.log
   timeout 400 python tools/ab/knob_ab.py --rounds 3 --batch 2 --steps 500 --json $OUT/${TAG}_fold_ab_b2.json 'cross_q_fold=False' 'cross_q_fold=True' 2>&1 | grep -v Warning | tee $OUT/${TAG}_fold_ab_b2.log
   mkdir -p $OUT/${TAG}_selfprof
-  timeout 600 python bench.py --no-cpu-baseline --self-profile-keep $OUT/${TAG}_selfprof > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err; tail -c 300 $OUT/${TAG}_bench_default.json; tail -3 $OUT/${TAG}_bench_default.err
+  timeout 600 python bench.py --full --no-cpu-baseline --self-profile-keep $OUT/${TAG}_selfprof > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err; tail -c 300 $OUT/${TAG}_bench_default.json; tail -3 $OUT/${TAG}_bench_default.err
   ;;
 fourth)  # the fold after: stage 0 peeled in the QS attention kernel, fold matrices behind Wqkv / Wo (no extra prefetch waves)
   timeout 600 python tests/diag/fold_stats.py --seeds 4 2>&1 | grep -v Warning | tee $OUT/${TAG}_fold_stats.log | tail -8
@@ -38,13 +38,13 @@ fourth)  # the fold after: stage 0 peeled in the QS attention kernel, fold matri
   timeout 400 python tools/ab/knob_ab.py --rounds 3 --tokens 300 --tokens 1300 --json $OUT/${TAG}_fold_ab2.json 'cross_q_fold=False' 'cross_q_fold=True' 2>&1 | grep -v Warning | tee $OUT/${TAG}_fold_ab2.log
   timeout 300 python tools/ab/knob_ab.py --preset small --rounds 4 --json $OUT/${TAG}_fold_ab_small.json 'cross_q_fold=False' 'cross_q_fold=True' 2>&1 | grep -v Warning | tee $OUT/${TAG}_fold_ab_small.log
   mkdir -p $OUT/${TAG}_selfprof
-  timeout 600 python bench.py --no-cpu-baseline --batched-songs 0 --small-segments 0 --self-profile-keep $OUT/${TAG}_selfprof > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err; tail -c 300 $OUT/${TAG}_bench_default.json; tail -3 $OUT/${TAG}_bench_default.err
+  timeout 600 python bench.py --full --no-cpu-baseline --batched-songs 0 --small-segments 0 --self-profile-keep $OUT/${TAG}_selfprof > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err; tail -c 300 $OUT/${TAG}_bench_default.json; tail -3 $OUT/${TAG}_bench_default.err
   ;;
 fifth)  # same-box kernel traces of both orders (bench self-profile with --knob)
   mkdir -p $OUT/${TAG}_selfprof_fold $OUT/${TAG}_selfprof_plain
   for v in plain fold; do
     K="cross_q_fold=$([ $v = fold ] && echo True || echo False)"
-    timeout 400 python bench.py --steps 3 --no-cpu-baseline --batched-songs 0 --small-segments 0 --knob $K --self-profile-keep $OUT/${TAG}_selfprof_$v > $OUT/${TAG}_bench_$v.json 2> $OUT/${TAG}_bench_$v.err; tail -c 200 $OUT/${TAG}_bench_$v.json; tail -2 $OUT/${TAG}_bench_$v.err
+    timeout 400 python bench.py --full --steps 3 --no-cpu-baseline --batched-songs 0 --small-segments 0 --knob $K --self-profile-keep $OUT/${TAG}_selfprof_$v > $OUT/${TAG}_bench_$v.json 2> $OUT/${TAG}_bench_$v.err; tail -c 200 $OUT/${TAG}_bench_$v.json; tail -2 $OUT/${TAG}_bench_$v.err
   done
   ;;
 sixth)  # two tools on one box: alternating processes (bench) and one process with both models (knob_ab, both orders)
@@ -80,16 +80,16 @@ final)   # the round's record: tests + smoke + kernel trace + counter passes + s
   fi
   cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/prof_b8
   timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_b8 -- \
-      python $ROOT/bench.py --batch 8 --steps 1 --warmup 1 --no-cpu-baseline --no-self-profile --batched-songs 0 --small-segments 0 --profile-steps 1 > $OUT/${TAG}_bench_b8_under_rocprof.json 2>/dev/null
+      python $ROOT/bench.py --full --batch 8 --steps 1 --warmup 1 --no-cpu-baseline --no-self-profile --batched-songs 0 --small-segments 0 --profile-steps 1 > $OUT/${TAG}_bench_b8_under_rocprof.json 2>/dev/null
   find /tmp/prof_b8 -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/${TAG}_b8_kernel_stats.csv
   cd $ROOT
   mkdir -p $OUT/${TAG}_selfprof
-  timeout 900 python bench.py --self-profile-keep $OUT/${TAG}_selfprof > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err; tail -c 1200 $OUT/${TAG}_bench_default.json
+  timeout 900 python bench.py --full --self-profile-keep $OUT/${TAG}_selfprof > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err; tail -c 1200 $OUT/${TAG}_bench_default.json
   ;;
 driver)   # what the driver runs at round end, on one fresh box: the -m gpu suite (-x), smoke, the default bench
   timeout 2400 python -m pytest tests -x -q -m gpu > $OUT/${TAG}_gpu_tests.log 2>&1; tail -3 $OUT/${TAG}_gpu_tests.log
   timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/${TAG}_smoke.log 2>&1; tail -2 $OUT/${TAG}_smoke.log
-  T0=$(date +%s); timeout 900 python bench.py > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err; echo "bench wall $(( $(date +%s) - T0 )) s" | tee -a $OUT/${TAG}_bench_default.err; tail -c 900 $OUT/${TAG}_bench_default.json; tail -2 $OUT/${TAG}_bench_default.err
+  T0=$(date +%s); timeout 900 python bench.py --full > $OUT/${TAG}_bench_default.json 2> $OUT/${TAG}_bench_default.err; echo "bench wall $(( $(date +%s) - T0 )) s" | tee -a $OUT/${TAG}_bench_default.err; tail -c 900 $OUT/${TAG}_bench_default.json; tail -2 $OUT/${TAG}_bench_default.err
   ;;
 tests)
   timeout 2400 python -m pytest tests -m gpu -q > $OUT/${TAG}_gpu_tests.log 2>&1; tail -6 $OUT/${TAG}_gpu_tests.log

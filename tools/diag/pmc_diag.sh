@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 run_pass() {  # name, counters
   rm -rf /tmp/pmcd_$1
   timeout 300 rocprofv3 --pmc $2 --kernel-trace --output-format csv -d /tmp/pmcd_$1 -- \
-      python $ROOT/bench.py --batch $NB --steps 1 --warmup 0 --num-steps 12 --no-cpu-baseline --batched-songs 0 --small-segments 0 --profile-steps 1 > /tmp/pmcd_$1.log 2>&1
+      python $ROOT/bench.py --full --batch $NB --steps 1 --warmup 0 --num-steps 12 --no-cpu-baseline --batched-songs 0 --small-segments 0 --profile-steps 1 > /tmp/pmcd_$1.log 2>&1
   f=$(find /tmp/pmcd_$1 -name "*counter_collection.csv" | head -1)
   if [ -n "$f" ]; then python $ROOT/tools/pmc_summary.py $f > $OUT/${TAG}_diag_b${NB}_$1.csv; echo "$1 ok"; else echo "no counters for $1"; grep -i "error\|fail\|invalid" /tmp/pmcd_$1.log | head -3; fi
 }

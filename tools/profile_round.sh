@@ -14,7 +14,7 @@ sha256sum $ROOT/music-spectrogram-diffusion_amd/csrc/libmsd_amd.so | cut -c1-16 
 if [ "${SKIP_TRACE:-0}" != "1" ]; then   # (bench.py's own rocprofv3 leg records the same table: --self-profile-keep)
 rm -rf /tmp/prof_$TAG
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$TAG -- \
-    python $ROOT/bench.py --preset $PRESET --steps 1 --warmup 1 --no-cpu-baseline --no-self-profile --batched-songs 0 --small-segments 0 --profile-steps 1 > $OUT/${TAG}_bench_under_rocprof.json 2> /tmp/prof_$TAG.err
+    python $ROOT/bench.py --full --preset $PRESET --steps 1 --warmup 1 --no-cpu-baseline --no-self-profile --batched-songs 0 --small-segments 0 --profile-steps 1 > $OUT/${TAG}_bench_under_rocprof.json 2> /tmp/prof_$TAG.err
 find /tmp/prof_$TAG -name "*kernel_stats.csv" | head -1 | xargs -I{} cp {} $OUT/${TAG}_bench_kernel_stats.csv
 fi
 # 2. PMC passes (one counter group per pass, kernel-trace only).  Counter collection serialises the dispatches at
@@ -24,7 +24,7 @@ fi
 run_pass() {  # name, counters
   rm -rf /tmp/pmc_$1
   timeout 420 rocprofv3 --pmc $2 --kernel-trace --output-format csv -d /tmp/pmc_$1 -- \
-      python $ROOT/bench.py --preset $PRESET --steps 1 --warmup 0 --num-steps 12 --no-cpu-baseline --no-self-profile --batched-songs 0 --small-segments 0 --profile-steps 1 > /tmp/pmc_$1.log 2>&1
+      python $ROOT/bench.py --full --preset $PRESET --steps 1 --warmup 0 --num-steps 12 --no-cpu-baseline --no-self-profile --batched-songs 0 --small-segments 0 --profile-steps 1 > /tmp/pmc_$1.log 2>&1
   f=$(find /tmp/pmc_$1 -name "*counter_collection.csv" | head -1)
   if [ -n "$f" ]; then python $ROOT/tools/pmc_summary.py $f > $OUT/${TAG}_pmc_$1.csv; else echo "no counters for $1"; tail -5 /tmp/pmc_$1.log; fi
 }
