@@ -189,8 +189,9 @@ typedef struct msd_config {
                                      rides on the QKV launch's idle CUs, the second runs beside the self-attention output
                                      projection (same A operand), and the 1/rms of the norm moves onto the logits inside
                                      the attention kernel.  Same float32-class result, NOT bit-identical to the unfolded
-                                     order (3e-7 relative on a decoder pass).  Two-plane precisions, up to 3 songs per
-                                     call.  0 = the library's choice (on), 1 = on, 2 = off */
+                                     order (3e-7 relative on a decoder pass).  Two-plane precisions, up to 1024 decoder
+                                     rows per launch: single passes of up to 4 songs per call, CFG steps (both passes'
+                                     rows) of up to 2.  0 = the library's choice (on), 1 = on, 2 = off */
   int32_t mlp_in_persistent;      /* batched songs (>= 4 per call: 128 x 128 tiles, several per CU): the decoder's gated-MLP
                                      input projection runs as ONE resident block per CU that walks its tiles, with the
                                      epilogue on the accumulator registers and the next tile's operands landing under
@@ -310,6 +311,16 @@ int msd_op_attention_qp(int precision, int qp, const float* q_dev, const float* 
 int msd_op_attention_split(int precision, int qp, int ksplit, int merge_in_launch, int repeats, const float* q_dev,
                            const float* k_dev, const float* v_dev, float* o_dev, int n_q, int n_keys,
                            int n_keys_valid, int heads, void* stream);
+/* (appended to ABI 6) The same with the two launch forms only the decoder reached before.  allow_qb4 = 1 lets the launch run on
+ * 128-row blocks (16 waves) when it has more than 256 64-row blocks and n_q % 128 == 0 (attention.h
+ * attention_query_blocks); 0 keeps 32- / 64-row blocks, as msd_op_attention_split does.  A non-null q_ssq_dev
+ * [n_q][q_tiles] (q_tiles % 4 == 0, <= 32) holds partial sums of squares of each query row's residual stream: the
+ * queries are then UN-normalised and the kernel scales row r's logits by 1 / sqrt(sum_t q_ssq[r][t] / (32 q_tiles) + 1e-6)
+ * (the folded cross-attention query projection; two-plane precisions only, 32- and 64-row blocks). */
+int msd_op_attention_ex(int precision, int qp, int ksplit, int merge_in_launch, int repeats, int allow_qb4,
+                        const float* q_ssq_dev, int q_tiles, const float* q_dev, const float* k_dev,
+                        const float* v_dev, float* o_dev, int n_q, int n_keys, int n_keys_valid, int heads,
+                        void* stream);
 
 
 /* Standalone forms of the FUSED kernels of the step (each restates one reference function and has its

@@ -1155,8 +1155,9 @@ void decoder_layers(Ctx& c, int batch, int P, bool cond0, bool dedup0 = false) {
       if (!launched) gemm<NP, TK_QKV>(c, KC_GEMM_QKV, y, D, w.self.wqkv, D, Ms, 3 * J, D, eq, eq.v_start, &pf);
     }
     const h16_t* kp[2] = {qk.p[0] + J, qk.p[NP - 1] + J};
-    // (a self-attention launch on 128-row blocks -- more than one round of 64-row blocks, i.e. from 6 songs per handle --
-    // has no prefetch wave: its weight target rides on the out-projection below instead)
+    // (a self-attention launch on 128-row blocks -- more than one round of 64-row blocks: from 3 songs per handle when
+    // it carries both passes of a CFG step (layers >= 1), from 6 on one pass's rows -- has no prefetch wave: its weight
+    // target rides on the out-projection below instead)
     const bool self_qb4 = attention_query_blocks(m->H * (T / 64) * Ps * batch, T, NP) == 4;
     const WeightPrefetch pf_self = !cond0 ? prefetch_of<NP>(m, w.mlp.wi, 2 * F, D)
                                           : (fold ? prefetch_of<NP>(m, w.wo_cross[0], D, J) : prefetch_of<NP>(m, w.wq_cross[0], J, D));
@@ -2058,13 +2059,22 @@ int msd_op_attention_qp(int precision, int qp, const float* q_dev, const float* 
 int msd_op_attention_split(int precision, int qp, int ksplit, int merge_in_launch, int repeats, const float* q_dev,
                            const float* k_dev, const float* v_dev, float* o_dev, int n_q, int n_keys, int n_keys_valid,
                            int heads, void* stream) {
+  return msd_op_attention_ex(precision, qp, ksplit, merge_in_launch, repeats, 0, nullptr, 0, q_dev, k_dev, v_dev, o_dev, n_q,
+                             n_keys, n_keys_valid, heads, stream);
+}
+
+int msd_op_attention_ex(int precision, int qp, int ksplit, int merge_in_launch, int repeats, int allow_qb4,
+                        const float* q_ssq_dev, int q_tiles, const float* q_dev, const float* k_dev, const float* v_dev,
+                        float* o_dev, int n_q, int n_keys, int n_keys_valid, int heads, void* stream) {
   if (qp < 0 || qp > 3 || ksplit < 1 || ksplit > 8 || repeats < 1 || repeats > 1000) return MSD_ERR_INVALID_ARGUMENT;
   if (n_q % 64 || n_keys % 32 || n_q <= 0 || n_keys <= 0 || heads <= 0 || n_keys_valid < 0 ||
       n_keys_valid > n_keys)
     return MSD_ERR_INVALID_ARGUMENT;
+  if (q_ssq_dev != nullptr && (q_tiles <= 0 || q_tiles > kAuxMaxTiles || q_tiles % 4)) return MSD_ERR_INVALID_ARGUMENT;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int NP = op_planes(precision);
   if (NP < 0) return MSD_ERR_UNSUPPORTED;
+  if (q_ssq_dev != nullptr && NP != 2) return MSD_ERR_UNSUPPORTED;   // (un-normalised queries: two-plane kernels only)
   const int J = heads * kHeadDim;
   Scratch sc;
   OpFlags fl;
@@ -2096,6 +2106,8 @@ int msd_op_attention_split(int precision, int qp, int ksplit, int merge_in_launc
   AttnParams p;
   fl.arm(p);
   p.qp = qp;
+  p.allow_qb4 = allow_qb4 != 0;
+  if (q_ssq_dev != nullptr) { p.q_ssq = q_ssq_dev; p.q_tiles = q_tiles; p.q_inv_d = 1.0f / (float)(kNarrowTile * q_tiles); }
   for (int i = 0; i < 2; ++i) {
     const int j = i < NP ? i : 0;
     p.q[i] = q.p[j]; p.k[i] = k.p[j]; p.vt[i] = vt.p[j]; p.o[i] = o.p[j];

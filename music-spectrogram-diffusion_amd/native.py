@@ -52,7 +52,7 @@ EXPORTED_SYMBOLS = (
     'msd_num_weights', 'msd_weight_info', 'msd_set_weight', 'msd_finalize_weights',
     'msd_encode', 'msd_sample', 'msd_reset_graph', 'msd_decoder_pass', 'msd_fill_normal', 'msd_get_schedule',
     'msd_debug_read', 'msd_profile_steps', 'msd_op_gemm_h16', 'msd_op_gemm_bf16', 'msd_op_gemm_f32',
-    'msd_op_attention', 'msd_op_attention_qp', 'msd_op_attention_split', 'msd_op_sampler_step', 'msd_op_residual_norm_gemm', 'msd_op_geglu',
+    'msd_op_attention', 'msd_op_attention_qp', 'msd_op_attention_split', 'msd_op_attention_ex', 'msd_op_sampler_step', 'msd_op_residual_norm_gemm', 'msd_op_geglu',
     'msd_op_qkv', 'msd_op_final_proj')
 
 
@@ -171,6 +171,8 @@ def load(planes: str = 'f16') -> ctypes.CDLL:
     lib.msd_op_attention_qp.argtypes = [i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]
   if 'msd_op_attention_split' in present:
     lib.msd_op_attention_split.argtypes = [i32, i32, i32, i32, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]
+  if 'msd_op_attention_ex' in present:
+    lib.msd_op_attention_ex.argtypes = [i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, vp, vp, i32, i32, i32, i32, vp]
   lib.msd_op_sampler_step.argtypes = [c.POINTER(MsdConfig), i32, vp, vp, vp, vp, vp, i64, vp]
   lib.msd_op_residual_norm_gemm.argtypes = [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
   lib.msd_op_geglu.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
@@ -383,6 +385,24 @@ def op_attention_split(precision: str, q, k, v, o, heads: int, ksplit: int, merg
                                   _ptr(v), _ptr(o), n_q, n_keys, nv, heads, stream)
   if rc:
     raise _EXC.get(rc, RuntimeError)('msd_op_attention_split failed (%d)' % rc)
+
+
+def op_attention_ex(precision: str, q, k, v, o, heads: int, ksplit: int = 1, merge_in_launch: bool = False, repeats: int = 1,
+                    allow_qb4: bool = False, q_ssq=None, n_keys_valid: Optional[int] = None, stream: int = 0, qp: int = 0):
+  """op_attention_split with the decoder's two other launch forms: allow_qb4 lets a launch of more than 256 64-row blocks
+  (n_q % 128 == 0) run on 128-row blocks; q_ssq (float32 [n_q, q_tiles] on the device) makes the queries UN-normalised,
+  row r's logits scaled by 1 / sqrt(sum(q_ssq[r]) / (32 q_tiles) + 1e-6)."""
+  lib = load(plane_format(precision))
+  n_q, n_keys = q.shape[0], k.shape[0]
+  nv = n_keys if n_keys_valid is None else n_keys_valid
+  q_tiles = 0 if q_ssq is None else q_ssq.shape[1]
+  if q_ssq is not None and tuple(q_ssq.shape) != (n_q, q_tiles):
+    raise ValueError('q_ssq must be [n_q, q_tiles]')
+  rc = lib.msd_op_attention_ex(PRECISIONS[precision], qp, ksplit, int(bool(merge_in_launch)), repeats, int(bool(allow_qb4)),
+                               None if q_ssq is None else _ptr(q_ssq), q_tiles, _ptr(q), _ptr(k), _ptr(v), _ptr(o), n_q,
+                               n_keys, nv, heads, stream)
+  if rc:
+    raise _EXC.get(rc, RuntimeError)('msd_op_attention_ex failed (%d)' % rc)
 
 
 def _op_check(rc, what):

@@ -599,7 +599,8 @@ def test_exact_launch_shortcuts_are_bit_identical(preset, steps):
 
 @pytest.mark.parametrize('preset,style,nb', [('tiny_context', 'concat', 2), ('tiny_context', 'sum', 2), ('tiny', 'concat', 1),
                                              ('small', 'concat', 1), ('base_with_context', 'concat', 1),
-                                             ('base_with_context', 'concat', 3), ('base_with_context', 'sum', 1)])
+                                             ('base_with_context', 'concat', 2), ('base_with_context', 'concat', 3),
+                                             ('base_with_context', 'sum', 1)])
 def test_folded_cross_query_projection_is_the_same_function(preset, style, nb):
   """S6 (round 6; msd_config.cross_q_fold): the cross-attention's query projection has no launch of its own.  With
   x1 = x0 + ao . Wo (network.py:174-193) the projection's input is rstd(x1) (x1 (.) gamma) (network.py:196-198, layers.py:632-666), so
@@ -608,7 +609,12 @@ def test_folded_cross_query_projection_is_the_same_function(preset, style, nb):
   the logits inside the attention kernel.  Exact algebra, another rounding order: single decoder passes with the fold on
   (library default) and off must agree to float32 rounding AND both must sit on the float64 oracle like every other
   pass (2e-4 max-rel: tests above); a CFG segment of a few steps must stay in the float32 class.  Both cross-attention
-  styles (one and two modules), the duplicating layer 0 (CFG), 1 - 3 songs (M = 512 ... 1536: narrow tiles)."""
+  styles (one and two modules), the duplicating layer 0 (CFG), 1 - 3 songs.  The fold takes launches of up to 1024
+  decoder rows (msd_api.hip fold_cross_q): every single pass here folds (M = nb T <= 768), a CFG step only up to 2 songs
+  at base (M = 2 nb T: 1024 at 2 songs; at 3, M = 1536, both handles run the unfolded order and the segment comparison
+  is of that order with itself).  Asserted per case: the folded handle's single conditional pass writes the `qp` buffer
+  (the QKV launch's half of the folded queries; zero in a fresh handle), and a CFG step launches no cross-attention
+  query projection when folded, one per decoder layer and module otherwise (msd_profile_steps' eager steps)."""
   import dataclasses
   import torch
   from oracle import backend, fast
@@ -633,6 +639,8 @@ def test_folded_cross_query_projection_is_the_same_function(preset, style, nb):
   zd = torch.as_tensor(z).cuda()
   init_z, noise = helpers.make_noise(spec, batch=nb)
   eps, seg = {}, {}
+  cfg_folds = 2 * nb * t <= 1024   # (every single pass of these cases folds: nb t <= 768)
+  n_cross = 2 if style == 'sum' else 1
   for fold in (True, False):
     model = msd_amd.InferenceModel(params, spec, batch_size=nb, cross_q_fold=fold, **helpers.ALL_PLANES)
     nm = model._get_native()
@@ -641,17 +649,24 @@ def test_folded_cross_query_projection_is_the_same_function(preset, style, nb):
                 batch['encoder_continuous_mask'])
     else:
       nm.encode(nb, batch['encoder_input_tokens'])
+    if fold:
+      assert not nm.debug_read('qp').any()
     for step, cond in ((steps - 1, True), (1, True), (0, False)):
       out = torch.zeros_like(zd)
       nm.decoder_pass(nb, step, zd, cond, out)
       torch.cuda.synchronize()
       eps[fold, step] = out.cpu().numpy()
+      if fold and step == steps - 1:   # the single conditional pass ran folded
+        assert np.abs(nm.debug_read('qp', nb * t * n_cross * spec.t5.num_heads * 64)).max() > 0, (preset, style, nb)
       if fm is not None:
         want = fm.decoder_pass(z.astype(np.float64), step, cond)
         err = np.abs(eps[fold, step] - want).max() / np.abs(want).max()
         assert err < 2e-4, (preset, style, fold, step, cond, err)
     got, _ = model.predict(batch, init_z=init_z, noise=noise)   # CFG steps: the duplicating layer 0 + the fold
     seg[fold] = np.asarray(got)
+    cross_q = nm.profile_steps(nb, 1)['gemm_cross_q'][1]
+    print('%s/%s, %d song(s), fold %s: cross-q launches per CFG step %d' % (preset, style, nb, fold, cross_q))
+    assert cross_q == (0 if fold and cfg_folds else spec.t5.num_decoder_layers * n_cross), (preset, style, nb, fold, cross_q)
     del model, nm
     torch.cuda.empty_cache()
   for step in (steps - 1, 1, 0):

@@ -265,6 +265,153 @@ def test_attention_spiked_key_forces_online_rescale(env):
   assert np.abs(o.cpu().numpy() - ref).max() < 1e-4
 
 
+def _attention_ref(q, k, v, heads, valid, rstd=None):
+  """float64 oracle attention of [n_q, heads*64] queries on the first `valid` keys; rstd (per query row) scales the
+  queries first -- the un-normalised form's algebra."""
+  from oracle import backend, ops
+  xp = backend.TorchBackend('float64')
+  nq = q.shape[0]
+  q64 = q.astype(np.float64) if rstd is None else q.astype(np.float64) * rstd[:, None]
+  sh = lambda x, n: xp.asarray(np.ascontiguousarray(x, np.float64).reshape(1, n, heads, 64))
+  out = ops.dot_product_attention(xp, sh(q64, nq), sh(k[:valid], valid), sh(v[:valid], valid))
+  return xp.to_numpy(out).reshape(nq, heads * 64).astype(np.float64)
+
+
+def _blocks64(nq, heads, ksplit):   # attention.h attention_query_blocks: 128-row blocks need > 256 64-row blocks
+  return heads * (nq // 64) * ksplit
+
+
+@pytest.mark.parametrize('prec,tol', [('f16x3', 2e-5), ('bf16x3', 3e-5)])
+@pytest.mark.parametrize('nq,nk,heads,ksplit,inl', [(2048, 512, 12, 1, False), (768, 1024, 12, 2, True),
+                                                    (768, 1024, 12, 4, True), (768, 1024, 12, 4, False)])
+def test_attention_128_row_blocks_against_float64(env, prec, tol, nq, nk, heads, ksplit, inl):
+  """The 128-row blocks (attention_kernel<NP, NS, QB = 4>: 16 waves, no prefetch wave) that the batched decoder's
+  attentions run on (msd_op_attention_ex allow_qb4; the other op entries never reach them) against the float64 oracle,
+  at the decoder's head count, unsplit and key-split with the separate and the in-launch merge, on key counts of 1, 33,
+  100 (every key in the first split part: the other parts of a group are empty), 129, a ragged count, the full axis and
+  0 (the all-masked -> 0 rule: exact zeros).  The same launch on 64-row blocks (allow_qb4 = 0) must give the SAME bits:
+  a query row's keys, their order and every fma are those of the 64-row block (only the rows per block change), and
+  three back-to-back launches with the in-launch merge must too (the arrival counters reset under 128-row groups)."""
+  torch, native = env
+  assert _blocks64(nq, heads, ksplit) > 256 and nq % 128 == 0   # the launch runs QB = 4
+  rng = np.random.default_rng(nq + nk + ksplit)
+  j = heads * 64
+  q = (rng.standard_normal((nq, j)) * 0.35).astype(np.float32)
+  k = (rng.standard_normal((nk, j)) * 0.35).astype(np.float32)
+  v = rng.standard_normal((nk, j)).astype(np.float32)
+  qd, kd, vd = _dev(torch, q), _dev(torch, k), _dev(torch, v)
+  for valid in (1, 33, 100, 129, nk - 37, nk, 0):
+    outs = {}
+    for name, qb4, reps in (('qb4', True, 1), ('qb2', False, 1), ('qb4 x3', True, 3)):
+      if reps > 1 and not (inl and ksplit > 1):
+        continue
+      o = torch.full((nq, j), float('nan'), dtype=torch.float32, device='cuda')
+      native.op_attention_ex(prec, qd, kd, vd, o, heads, ksplit=ksplit, merge_in_launch=inl, repeats=reps,
+                             allow_qb4=qb4, n_keys_valid=valid)
+      outs[name] = o.cpu().numpy()
+    for name, got in outs.items():
+      assert np.array_equal(got, outs['qb2']), (valid, name, np.abs(got - outs['qb2']).max())
+    got = outs['qb4']
+    if valid == 0:
+      np.testing.assert_array_equal(got, 0.0)
+      continue
+    ref = _attention_ref(q, k, v, heads, valid)
+    err = np.abs(got - ref).max() / max(1.0, np.abs(ref).max())
+    print('%s 128-row blocks, n_q %d, %d keys valid of %d, split %d%s: max err %.2e'
+          % (prec, nq, valid, nk, ksplit, ' (merge in launch)' if inl else '', err))
+    assert err < tol, (valid, err)
+
+
+@pytest.mark.parametrize('s_std', [10.0, 20.0])
+def test_attention_128_row_blocks_sharp_logits_and_spiked_key(env, s_std):
+  """The sharp-logit (logit std 10 / 20) and spiked-key (a key block whose max jumps to ~200: the online rescale)
+  inputs of the tests above on 128-row blocks (split 2, merge in launch): the all-planes bounds hold, and the bits are
+  those of the 64-row blocks."""
+  torch, native = env
+  rng = np.random.default_rng(int(s_std) + 128)
+  nq, nk, heads = 768, 512, 12
+  j = heads * 64
+  scale = np.sqrt(s_std / 8.0)
+  q = (rng.standard_normal((nq, j)) * scale).astype(np.float32)
+  k = (rng.standard_normal((nk, j)) * scale).astype(np.float32)
+  v = rng.standard_normal((nk, j)).astype(np.float32)
+  spiked = k.copy()
+  spiked[300] = q[3] * (25.0 / s_std)   # |q_h|^2 ~ 8 s_std: q[3].k[300] ~ 200 per head, in key stage 2 (split part 0)
+  for name, kk, bound in (('sharp', k, 2e-5), ('spiked key', spiked, 1e-4)):
+    got = {}
+    for qb4 in (True, False):
+      o = torch.full((nq, j), float('nan'), dtype=torch.float32, device='cuda')
+      native.op_attention_ex('f16x3', _dev(torch, q), _dev(torch, kk), _dev(torch, v), o, heads, ksplit=2,
+                             merge_in_launch=True, allow_qb4=qb4)
+      got[qb4] = o.cpu().numpy()
+    assert np.array_equal(got[True], got[False]), name
+    ref = _attention_ref(q, kk, v, heads, nk)
+    err = np.abs(got[True] - ref).max() / max(1.0, np.abs(ref).max())
+    print('128-row blocks, logit std %.0f, %s: max err %.2e' % (s_std, name, err))
+    assert err < bound, (name, err)
+
+
+def _unnormalised_queries(rng, nq, j, d=768):
+  """(q_unnorm, ssq [nq, d / 32], rstd): queries of O(1) logits times the 1/rstd of a random residual stream x [nq, d]
+  whose row rms spans 1e-1 ... 1e3 (log-uniform), with rows 1e4 apart side by side in the first query block."""
+  rms = 10.0 ** rng.uniform(-1, 3, nq)
+  rms[:32:2], rms[1:32:2] = 0.1, 1e3
+  x = rng.standard_normal((nq, d)) * rms[:, None]
+  x = x.astype(np.float32).astype(np.float64)
+  ssq = (x * x).reshape(nq, d // 32, 32).sum(-1).astype(np.float32)
+  rstd = 1.0 / np.sqrt(ssq.astype(np.float64).sum(-1) / d + 1e-6)
+  q = (rng.standard_normal((nq, j)) * 0.35 / rstd[:, None]).astype(np.float32)
+  assert np.abs(q).max() < 65504
+  return q, ssq, rstd
+
+
+@pytest.mark.parametrize('prec', ['f16x3', 'bf16x3'])
+@pytest.mark.parametrize('nq,nk,valid,heads,ksplit,inl', [(256, 640, 600, 1, 1, False), (256, 640, 131, 2, 2, False),
+                                                          (768, 1024, 1000, 12, 2, True), (768, 1024, 77, 12, 4, True)])
+def test_attention_unnormalised_queries_against_float64(env, prec, nq, nk, valid, heads, ksplit, inl):
+  """UN-normalised queries (QP bit 2, AttnParams::q_ssq: the folded cross-attention query projection): the kernel
+  scales row r's logits by rstd[r] = 1 / sqrt(sum_t ssq[r][t] / 768 + 1e-6) from 24 partial sums of squares, against
+  the float64 oracle on q_unnorm * rstd -- residual rows of rms 1e-1 ... 1e3, rows 1e4 apart in one query block, 32-
+  and 64-row blocks (the 12-head launches ask for 128-row blocks, which the un-normalised form does not take: the
+  launcher keeps 64), with and without a key split; all planes and, on half planes, Q as one plane (qp 1, the bound of test_attention)."""
+  torch, native = env
+  rng = np.random.default_rng(nq + valid + heads)
+  j = heads * 64
+  q, ssq, rstd = _unnormalised_queries(rng, nq, j)
+  k = (rng.standard_normal((nk, j)) * 0.35).astype(np.float32)
+  v = rng.standard_normal((nk, j)).astype(np.float32)
+  ref = _attention_ref(q, k, v, heads, valid, rstd)
+  tol = 2e-5 if prec == 'f16x3' else 3e-5
+  for qp, bound in ((0, tol), (1, 6e-4)) if prec == 'f16x3' else ((0, tol),):   # (one bfloat16 plane: 8 bits, no bar)
+    o = torch.full((nq, j), float('nan'), dtype=torch.float32, device='cuda')
+    native.op_attention_ex(prec, _dev(torch, q), _dev(torch, k), _dev(torch, v), o, heads, ksplit=ksplit,
+                           merge_in_launch=inl, allow_qb4=True, q_ssq=_dev(torch, ssq), n_keys_valid=valid, qp=qp)
+    got = o.cpu().numpy()
+    err = np.abs(got - ref).max() / max(1.0, np.abs(ref).max())
+    print('%s un-normalised queries, n_q %d, %d heads, %d keys, split %d, qp %d: max err %.2e'
+          % (prec, nq, heads, valid, ksplit, qp, err))
+    assert err < bound, (qp, err)
+
+
+def test_attention_ex_argument_checks(env):
+  """q_ssq needs q_tiles % 4 == 0 and <= 32 (the kernel stages whole 16-byte rows); one-plane precisions have no
+  un-normalised form; without the new arguments the entry is msd_op_attention_split."""
+  torch, native = env
+  rng = np.random.default_rng(9)
+  q = _dev(torch, rng.standard_normal((64, 64)) * 0.35)
+  k = _dev(torch, rng.standard_normal((64, 64)) * 0.35)
+  o = torch.zeros((64, 64), dtype=torch.float32, device='cuda')
+  for tiles in (6, 36):
+    with pytest.raises(ValueError):
+      native.op_attention_ex('f16x3', q, k, k, o, 1, q_ssq=torch.ones((64, tiles), dtype=torch.float32, device='cuda'))
+  with pytest.raises(NotImplementedError):
+    native.op_attention_ex('f16', q, k, k, o, 1, q_ssq=torch.ones((64, 24), dtype=torch.float32, device='cuda'))
+  o2 = torch.zeros_like(o)
+  native.op_attention_ex('f16x3', q, k, k, o, 1)
+  native.op_attention_split('f16x3', q, k, k, o2, 1, 1, False)
+  assert torch.equal(o, o2)
+
+
 def test_philox_normal_matches_oracle(env):
   torch, native = env
   from oracle import philox
