@@ -41,7 +41,9 @@
 extern "C" {
 #endif
 
-#define MSD_AMD_ABI_VERSION 6   /* 6: cross_merge_in_launch, cross_q_fold, mlp_in_persistent appended to msd_config.
+#define MSD_AMD_ABI_VERSION 7   /* 7: msd_sample_rng, msd_fill_normal_threefry, msd_op_threefry (the reference's Threefry draws on the
+                                      device); msd_config unchanged.
+                                   6: cross_merge_in_launch, cross_q_fold, mlp_in_persistent appended to msd_config.
                                    5: dedup_layer0, cross_key_split, keep_raw_weights, kv_touch_ahead appended to msd_config.
                                    4: every caller-selectable knob is a msd_config field (attn_q_planes / attn_p_planes
                                       replace ABI 3's attn_query_planes; graph_steps; weight_prefetch): the library reads
@@ -247,10 +249,25 @@ int msd_encode(msd_model* m, int batch, const int32_t* tokens, const float* ctx_
  *   stream     NULL = the legacy stream: the call waits for it (hipStreamSynchronize(NULL)) and runs on the handle's
  *              own stream (the legacy stream cannot be captured); other handles' streams are not waited for
  *   seed/stream_id key the generator when a pointer is NULL (stream_id = segment)
- *   out_dev    float [batch,T,n] mel units                                    */
+ *   out_dev    float [batch,T,n] mel units
+ * The generator is the library's own (Philox); msd_sample_rng names another.  */
 int msd_sample(msd_model* m, int batch, uint64_t seed, uint64_t stream_id,
                const float* init_z_dev, const float* noise_dev, float* out_dev,
                void* stream);
+
+/* ABI 7: the generator of the NULL pointers.  MSD_RNG_PHILOX is the library's own (msd_fill_normal);
+ * MSD_RNG_THREEFRY makes the draws of the reference's `predict(batch, seed)` -- jax.random with the default
+ * (non-partitionable) Threefry layout of jax <= 0.4 -- on the device, with no noise buffer and no host work. */
+enum { MSD_RNG_PHILOX = 0, MSD_RNG_THREEFRY = 1 };
+/* msd_sample with the generator named; msd_sample(...) == msd_sample_rng(..., MSD_RNG_PHILOX, ...).
+ * MSD_RNG_THREEFRY: init_z = normal(PRNGKey(seed), [batch,T,n]), step i = normal(fold_in(PRNGKey(seed), i), [batch,T,n])
+ * (inference.py:203, diffusion_utils.py:389-390,462), drawn inside the sampler kernel; the values are those
+ * msd_fill_normal_threefry(seed, -1 / i, ..., batch*T*n) writes, bit for bit.  One draw covers the WHOLE [batch,T,n] array, as
+ * in the reference: row b of a batched call is not the draw of a one-row call.  stream_id is ignored, as the reference
+ * ignores the segment (beam/evaluation.py:209-210).  An unknown rng is MSD_ERR_INVALID_ARGUMENT.  A DDIM sampler
+ * uses init_z only.  The step graphs are shared by both generators (the kind lives in device memory). */
+int msd_sample_rng(msd_model* m, int batch, int rng, uint64_t seed, uint64_t stream_id,
+                   const float* init_z_dev, const float* noise_dev, float* out_dev, void* stream);
 
 /* Drop the captured hipGraph of the DDPM step; the next msd_sample captures it again. */
 int msd_reset_graph(msd_model* m);
@@ -267,6 +284,12 @@ int msd_decoder_pass(msd_model* m, int batch, int step_index, const float* z_dev
  * subseq: 0 = init_z, 1 + i = step-i noise.                                   */
 int msd_fill_normal(uint64_t seed, uint64_t stream_id, uint32_t subseq,
                     float* out_dev, int64_t n, void* stream);
+
+/* jax.random.normal(key, [n]) (float32) for key = PRNGKey(seed), or fold_in(PRNGKey(seed), fold) when fold >= 0:
+ * threefry2x32-20, element e < ceil(n/2) = word 0 of block (e, e + ceil(n/2)), the others word 1 (an odd n pads the
+ * last counter with 0); uniform in [nextafter(-1,0), 1) by the mantissa trick; sqrt(2) * XLA's float32 erf^-1, every
+ * operation rounded on its own.  Restated on the host in jax_random.py; n < 2^32, fold < 2^32. */
+int msd_fill_normal_threefry(uint64_t seed, int64_t fold, float* out_dev, int64_t n, void* stream);
 
 /* Step-indexed tables, for parity tests: copies [num_steps, 8] floats to host:
  * {logsnr_t, logsnr_s, x0_scale, x0_eps_coef, mean_z_coef, mean_x0_coef, std,
@@ -361,6 +384,13 @@ int msd_op_qkv(const float* a_dev, const float* wq_dev, const float* wk_dev, con
 /* decoder_norm + spec_out_dense in exact fp32 (network.py:445-456): out [m,n] = RMSNorm(x; gamma).w */
 int msd_op_final_proj(const float* x_dev, const float* gamma_dev, const float* w_dev, float* out_dev,
                       int m, int d, int n, void* stream);
+
+/* The stages of msd_fill_normal_threefry's draw (seed, fold, n): stage 0 = raw bits (uint32 written into out),
+ * 1 = uniform u, 2 = normal, 3 = w = -log1p(-u*u), the normal stage's one operation whose rounding the host
+ * restatement does not share (a test finishes the stage on the host from it).  bits_in_dev != NULL (uint32 [n]): stages 1 / 2 applied to the caller's words instead
+ * (the float stages over all 2^23 mantissas: stages 1 - 3); stage 0 then is MSD_ERR_INVALID_ARGUMENT.  Does not synchronise. */
+int msd_op_threefry(int stage, uint64_t seed, int64_t fold, const uint32_t* bits_in_dev, float* out_dev, int64_t n,
+                    void* stream);
 
 #ifdef __cplusplus
 }

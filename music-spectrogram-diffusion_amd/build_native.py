@@ -64,10 +64,39 @@ def check_prefetch_registers(listing: str) -> str:
   return out.stdout.strip().split('\n')[-1]
 
 
+# kernels that must not spill: elementwise launches on the step's critical path (the sampler once went through scratch
+# memory, csrc/elementwise.h) and the Threefry fill
+NO_SCRATCH_KERNELS = ('sampler_step_kernel', 'threefry_normal_kernel')
+
+
+def check_no_scratch(listing: str, kernels=NO_SCRATCH_KERNELS) -> str:
+  """Every instance of `kernels` in the device listing must report a private segment (scratch) of 0 bytes and no
+  dynamic stack; each name must be present at least once.  An instance that spills fails the build."""
+  import re
+  text = open(listing).read()
+  seen = {k: 0 for k in kernels}
+  bad = []
+  for m in re.finditer(r'^\s*\.amdhsa_kernel\s+(\S+)(.*?)^\s*\.end_amdhsa_kernel', text, flags=re.M | re.S):
+    name, body = m.group(1), m.group(2)
+    for k in kernels:
+      if k in name:
+        seen[k] += 1
+        size = re.search(r'\.amdhsa_private_segment_fixed_size\s+(\d+)', body)
+        dyn = re.search(r'\.amdhsa_uses_dynamic_stack\s+(\d+)', body)
+        if size is None or int(size.group(1)) != 0 or (dyn is not None and int(dyn.group(1)) != 0):
+          bad.append('%s: private segment %s, dynamic stack %s' % (name, size.group(1) if size else '?', dyn.group(1) if dyn else '0'))
+  missing = [k for k, c in seen.items() if c == 0]
+  if missing:
+    raise RuntimeError('scratch check: no kernel descriptor of %s in %s' % (missing, listing))
+  if bad:
+    raise RuntimeError('scratch check failed on %s: these kernels use scratch memory:\n  %s' % (listing, '\n  '.join(bad)))
+  return 'OK: no scratch in ' + ', '.join('%d x %s' % (c, k) for k, c in seen.items())
+
+
 def build(force: bool = False, verbose: bool = True, experiments: bool = False) -> str:
   """Builds both product libraries (each only if older than its sources) and, with `experiments`, the A/B library of
   tools/ubench/exp; returns the default one.  Each compile keeps its device listing (-save-temps, in a scratch
-  directory) and runs the prefetch register check on it."""
+  directory) and runs the prefetch register check and the scratch check on it."""
   import tempfile
   targets = [(lib, defs, CSRC) for lib, defs in LIBS.values()]
   if experiments:
@@ -99,6 +128,10 @@ def build(force: bool = False, verbose: bool = True, experiments: bool = False) 
         verdict = check_prefetch_registers(l)
         if verbose:
           print('[build_native] prefetch registers:', verdict, flush=True)
+        if src == CSRC:   # (the experiments library is built from frozen sources that have no Threefry kernel)
+          verdict = check_no_scratch(l)
+          if verbose:
+            print('[build_native] scratch:', verdict, flush=True)
       shutil.copyfile(out, lib + '.tmp')
       os.chmod(lib + '.tmp', 0o755)
       os.replace(lib + '.tmp', lib)

@@ -130,6 +130,112 @@ __global__ void philox_normal_kernel(float* out, int64_t n, uint32_t seed_lo, ui
 }
 
 // ---------------------------------------------------------------------------
+// The reference's generator (rng = MSD_RNG_THREEFRY): jax.random.normal for the default, non-partitionable
+// Threefry layout, restated on the host in jax_random.py -- this is that file, per element.
+//   key = PRNGKey(seed) = (seed >> 32, seed & 0xffffffff);  fold_in(key, d) = threefry(key, (0, d))
+//   one draw of n_total values: half = ceil(n_total / 2); element e < half = word 0 of threefry(key, (e, e + half)),
+//   element e >= half = word 1 of threefry(key, (e - half, e)); odd n_total: the last counter of the second half is 0
+//   u = max(lo, ((bits >> 9 | 0x3f800000) - 1) * scale + lo), lo = nextafter(-1, 0);  normal = sqrt(2) * erfinv(u)
+// The host rounds after every operation: the float stages are compiled with contraction OFF (an FMA would change
+// the last bit); log1p is the one operation whose rounding neither side controls.
+// ---------------------------------------------------------------------------
+__host__ __device__ __forceinline__ void threefry2x32(uint32_t k0, uint32_t k1, uint32_t& x0, uint32_t& x1) {
+  const uint32_t ks[3] = {k0, k1, k0 ^ k1 ^ 0x1BD11BDAu};
+  x0 += ks[0];
+  x1 += ks[1];
+#define MSD_TF_ROUND(r) x0 += x1; x1 = ((x1 << (r)) | (x1 >> (32 - (r)))) ^ x0;
+#pragma unroll
+  for (int g = 0; g < 5; ++g) {
+    if (g % 2 == 0) { MSD_TF_ROUND(13) MSD_TF_ROUND(15) MSD_TF_ROUND(26) MSD_TF_ROUND(6) }
+    else { MSD_TF_ROUND(17) MSD_TF_ROUND(29) MSD_TF_ROUND(16) MSD_TF_ROUND(24) }
+    x0 += ks[(g + 1) % 3];
+    x1 += ks[(g + 2) % 3] + (uint32_t)(g + 1);
+  }
+#undef MSD_TF_ROUND
+}
+
+// bits -> uniform in [nextafter(-1, 0), 1).  The constants are the host code's bit patterns (jax_random.normal):
+// lo = 0xBF7FFFFF; scale = float32(1 - lo) = 0x40000000 (the exact 2 - 2^-24 is a tie, rounded to even)
+__device__ __forceinline__ float threefry_uniform(uint32_t bits) {
+#pragma clang fp contract(off)
+  const float lo = __uint_as_float(0xBF7FFFFFu), scale = __uint_as_float(0x40000000u);
+  const float f = __uint_as_float((bits >> 9) | 0x3F800000u) - 1.0f;
+  const float prod = f * scale;
+  const float u = prod + lo;
+  return u < lo ? lo : u;   // (no NaN can reach this max)
+}
+
+// w = -log1p(-x^2): the one operation of the float stages whose rounding the host does not share.  msd_op_threefry's stage 3
+// hands it to the test, which runs everything after it on the host and asks for the device's normal bit for bit.
+__device__ __forceinline__ float threefry_log_term(float x) {
+#pragma clang fp contract(off)
+  const float xx = x * x;
+  return -log1pf(-xx);
+}
+
+// sqrt(2) * XLA's float32 ErfInv (Giles' single-precision polynomial), every operation rounded on its own
+__device__ __forceinline__ float threefry_normal_of_uniform(float x) {
+#pragma clang fp contract(off)
+  float w = threefry_log_term(x);
+  const bool lt = w < 5.0f;
+  w = lt ? w - 2.5f : sqrtf(w) - 3.0f;
+  float p = lt ? 2.81022636e-08f : -0.000200214257f;
+#define MSD_TF_HORNER(a, b) { const float pw = p * w; p = (lt ? (a) : (b)) + pw; }
+  MSD_TF_HORNER(3.43273939e-07f, 0.000100950558f)
+  MSD_TF_HORNER(-3.5233877e-06f, 0.00134934322f)
+  MSD_TF_HORNER(-4.39150654e-06f, -0.00367342844f)
+  MSD_TF_HORNER(0.00021858087f, 0.00573950773f)
+  MSD_TF_HORNER(-0.00125372503f, -0.0076224613f)
+  MSD_TF_HORNER(-0.00417768164f, 0.00943887047f)
+  MSD_TF_HORNER(0.246640727f, 1.00167406f)
+  MSD_TF_HORNER(1.50140941f, 2.83297682f)
+#undef MSD_TF_HORNER
+  const float px = p * x;
+  const float e = fabsf(x) == 1.0f ? copysignf(__uint_as_float(0x7F800000u), x) : px;
+  return __uint_as_float(0x3FB504F3u) * e;   // float32(sqrt(2))
+}
+
+__device__ __forceinline__ float threefry_normal_of_bits(uint32_t bits) {
+  return threefry_normal_of_uniform(threefry_uniform(bits));
+}
+
+// Element e of one draw of n_total values (n_total EVEN: no zero pad) -- what a thread of the sampler computes:
+// one Threefry block per element, one of its two words used (jax_random.normal_at is this function on the host).
+__device__ __forceinline__ float threefry_normal_at(uint32_t k0, uint32_t k1, uint32_t e, uint32_t half) {
+  const bool first = e < half;
+  uint32_t x0 = first ? e : e - half, x1 = first ? e + half : e;
+  threefry2x32(k0, k1, x0, x1);
+  return threefry_normal_of_bits(first ? x0 : x1);
+}
+
+// One draw of n values under key (k0, k1): thread t < half takes the counter pair (t, t + half) and writes both words
+// of its block (elements t and t + half).  stage: 0 = raw bits (uint32 stored into out), 1 = uniform, 2 = normal,
+// 3 = the normal stage's log term of the uniform (threefry_log_term).
+// bits_in != nullptr: the caller's words instead of the generator's (the float stages' exhaustive test).
+__global__ void __launch_bounds__(256) threefry_normal_kernel(float* out, int64_t n, uint32_t k0, uint32_t k1, int stage,
+                                                              const uint32_t* bits_in) {
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t half = (n + 1) / 2;
+  if (t >= half) return;
+  const bool second = t + half < n;   // false only for the zero pad of an odd n
+  uint32_t x0, x1;
+  if (bits_in) {
+    x0 = bits_in[t];
+    x1 = second ? bits_in[t + half] : 0u;
+  } else {
+    x0 = (uint32_t)t;
+    x1 = second ? (uint32_t)(t + half) : 0u;
+    threefry2x32(k0, k1, x0, x1);
+  }
+  if (stage == 1) { x0 = __float_as_uint(threefry_uniform(x0)); x1 = __float_as_uint(threefry_uniform(x1)); }
+  else if (stage == 2) { x0 = __float_as_uint(threefry_normal_of_bits(x0)); x1 = __float_as_uint(threefry_normal_of_bits(x1)); }
+  else if (stage == 3) { x0 = __float_as_uint(threefry_log_term(threefry_uniform(x0))); x1 = __float_as_uint(threefry_log_term(threefry_uniform(x1))); }
+  uint32_t* o = reinterpret_cast<uint32_t*>(out);   // stored as words: stage 0's bit patterns are not floats
+  o[t] = x0;
+  if (second) o[t + half] = x1;
+}
+
+// ---------------------------------------------------------------------------
 // Fused sampler update = everything in eval_step.body after the decoder calls
 // (diffusion_utils.py:416-452): CFG combine, x0-from-eps, clip, posterior mean,
 // + std * noise (DDPM, diffusion_utils.py:120-163,382-395) or the DDIM update
@@ -145,15 +251,21 @@ enum { kCoefLogsnrT = 0, kCoefLogsnrS, kCoefX0Scale, kCoefX0Eps, kCoefMeanZ, kCo
        kCoefMLogsnr, kCoefMX0Scale, kCoefMX0Eps, kCoefMEpsScale, kCoefMEpsX0, kCoefMAlpha, kCoefMSigma,
        kCoefPad0, kCoefPad1, kCoefCount };
 enum { kOutEps = 0, kOutX0 = 1, kOutV = 2 };   // = msd_model_output
+// words of SamplerParams::rng_key: 0..3 the Philox key and stream, then the generator kind (= MSD_RNG_*) and the
+// Threefry key PRNGKey(seed)
+enum { kRngKind = 4, kRngTfKey0 = 5, kRngTfKey1 = 6, kRngWords = 8 };
+enum { kRngPhilox = 0, kRngThreefry = 1 };
 
 struct SamplerParams {
   const float* eps;     // [passes][n] decoder outputs (pass 0 = conditional)
   float* z;             // [n] in/out
   const float* const* noise_slot;  // device slot holding the [N][n] per-step draws pointer; a NULL pointer there = draw here
-  const uint32_t* rng_key = nullptr;   // device words {seed_lo, seed_hi, stream_lo, stream_hi} of the in-kernel draw (round 6):
+  const uint32_t* rng_key = nullptr;   // kRngWords device words, ALWAYS read (set at every launch): {seed_lo, seed_hi, stream_lo, stream_hi} of the in-kernel draw (round 6):
                                        // step i's noise = sub-sequence 1 + i of the caller's Philox stream, element block =
                                        // this thread -- exactly the row philox_normal_kernel used to write for it (the
                                        // [N][n] buffer: 131 MB x songs at base, a hipMalloc inside msd_sample)
+                                       // followed by {generator kind, PRNGKey(seed) word 0, word 1} (kRng*): the kind lives in
+                                       // device memory so that ONE captured graph serves both generators
   const float* coef;    // [N][kCoefCount]
   int* step_ptr;        // scan index i (device); see step_from_slot1
   int step_from_slot1 = 0;
@@ -217,6 +329,16 @@ __global__ void __launch_bounds__(256) sampler_step_kernel(SamplerParams p) {
   // step_from_slot1: the step's first kernel (in_proj) copied the index to slot 1 and nobody else
   // reads slot 0 any more in this step, so this launch may decrement slot 0 itself
   const int i = p.step_from_slot1 ? p.step_ptr[1] : p.step_ptr[0];
+  // The noise slot and the words of the in-kernel draw (generator kind, keys: always valid memory) travel WITH the index:
+  // fetched where they are used, inside the branches below, slot -> kind -> key are three dependent round trips to
+  // memory in front of the draw (measured: +0.5 % on a segment).  The empty asm pins the loads here (the
+  // compiler sinks them into the branches otherwise); it also makes the values per-lane for the compiler, so the two
+  // tests below are vector compares whose outcome is the same in every lane.  This is the form that was measured.
+  typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+  const float* noise = *p.noise_slot;
+  u32x4 rk0 = reinterpret_cast<const u32x4*>(p.rng_key)[0], rk1 = reinterpret_cast<const u32x4*>(p.rng_key)[1];
+  static_assert(kRngKind == 4 && kRngTfKey0 == 5 && kRngTfKey1 == 6, "rk1 = {kind, Threefry key, pad}");
+  asm volatile("" : "+v"(noise), "+v"(rk0), "+v"(rk1));
   const int idx = (blockIdx.x * 256 + threadIdx.x) * 4;
   if (idx < p.n) {
     // Loads that do not depend on the scan index go out first; the coefficient row (20 floats = five 16-byte loads,
@@ -232,13 +354,18 @@ __global__ void __launch_bounds__(256) sampler_step_kernel(SamplerParams p) {
 #pragma unroll
     for (int k = 0; k < 5; ++k) cr[k] = reinterpret_cast<const f32x4*>(p.coef + (size_t)i * kCoefCount)[k];
     if (!p.ddim && i != 0) {
-      const float* const noise = *p.noise_slot;   // (wave-uniform: one branch)
-      if (noise != nullptr) {
+      if (noise != nullptr) {   // (the same in every lane)
         nz = *reinterpret_cast<const f32x4*>(noise + (size_t)i * p.n + idx);
+      } else if (rk1[0] == kRngThreefry) {   // (the same in every lane) the reference's generator: this thread's four
+        // elements of normal(fold_in(PRNGKey(seed), i), [batch, T, n]); the folded key is the same for every thread
+        uint32_t f0 = 0u, f1 = (uint32_t)i;
+        threefry2x32(rk1[1], rk1[2], f0, f1);
+        const uint32_t half = (uint32_t)p.n >> 1;   // p.n % 4 == 0: no zero pad
+#pragma unroll
+        for (int k = 0; k < 4; ++k) nz[k] = threefry_normal_at(f0, f1, (uint32_t)(idx + k), half);
       } else {   // no buffer: this thread's four draws of sub-sequence 1 + i (idx / 4 = the counter block)
-        const uint32_t k0 = p.rng_key[0], k1 = p.rng_key[1], s0 = p.rng_key[2], s1 = p.rng_key[3];
         float d[4];
-        philox_normal4((uint32_t)(idx >> 2), 1u + (uint32_t)i, k0, k1, s0, s1, d);
+        philox_normal4((uint32_t)(idx >> 2), 1u + (uint32_t)i, rk0[0], rk0[1], rk0[2], rk0[3], d);
         nz = f32x4{d[0], d[1], d[2], d[3]};
       }
     }

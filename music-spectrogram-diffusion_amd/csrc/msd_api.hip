@@ -137,7 +137,7 @@ struct msd_model {
   float* eps = nullptr;
   float* z = nullptr;
   const float** d_noise_slot = nullptr;
-  uint32_t* d_rng_key = nullptr;       // {seed_lo, seed_hi, stream_lo, stream_hi} of the current msd_sample (elementwise.h SamplerParams::rng_key)
+  uint32_t* d_rng_key = nullptr;       // {seed_lo, seed_hi, stream_lo, stream_hi, generator kind, PRNGKey(seed) words} of the current msd_sample (elementwise.h SamplerParams::rng_key, kRng*)
   int* d_step = nullptr;       // [2]
   int* d_nkeys_self = nullptr; // [passes*Bmax] = T
   int* d_nkeys_cross = nullptr;// [n_cross][Bmax] valid keys per key region and song
@@ -1357,7 +1357,7 @@ void set_func_attrs() {
 extern "C" {
 
 const char* msd_version(void) {
-  static const std::string v = std::string("msd_amd 0.7.0 (gfx950, abi 6, ") + kPlaneName + ")";
+  static const std::string v = std::string("msd_amd 0.7.0 (gfx950, abi 7, ") + kPlaneName + ")";
   return v.c_str();
 }
 
@@ -1495,7 +1495,7 @@ int msd_create(const msd_config* cfg, msd_model** out) {
   TRY(dalloc(m, &m->eps, Mmax * m->ND));
   TRY(dalloc(m, &m->z, (size_t)m->Bmax * T * m->ND));
   TRY(dalloc(m, &m->d_noise_slot, 1));
-  TRY(dalloc(m, &m->d_rng_key, 4));
+  TRY(dalloc(m, &m->d_rng_key, kRngWords));
   TRY(dalloc(m, &m->d_step, 2));
   TRY(dalloc(m, &m->d_absmax, 1));
   TRY(dalloc(m, &m->d_sat, 1));
@@ -1735,9 +1735,50 @@ int msd_fill_normal(uint64_t seed, uint64_t stream_id, uint32_t subseq, float* o
   return hipGetLastError() == hipSuccess ? MSD_OK : MSD_ERR_HIP;
 }
 
+// jax.random.normal(key, [n]) for key = PRNGKey(seed) or fold_in(PRNGKey(seed), fold); stage / bits_in: msd_op_threefry
+static int threefry_fill(int stage, uint64_t seed, int64_t fold, const uint32_t* bits_in, float* out_dev, int64_t n,
+                         hipStream_t s) {
+  if (!out_dev || n < 0 || n > 0xFFFFFFFFll || fold > 0xFFFFFFFFll || stage < 0 || stage > 3) return MSD_ERR_INVALID_ARGUMENT;
+  if (n == 0) return MSD_OK;
+  uint32_t k0 = (uint32_t)(seed >> 32), k1 = (uint32_t)seed;
+  if (fold >= 0) {
+    uint32_t f0 = 0u, f1 = (uint32_t)fold;
+    threefry2x32(k0, k1, f0, f1);
+    k0 = f0; k1 = f1;
+  }
+  const int64_t half = (n + 1) / 2;
+  hipLaunchKernelGGL(threefry_normal_kernel, dim3((unsigned)((half + 255) / 256)), dim3(256), 0, s, out_dev, n, k0, k1,
+                     stage, bits_in);
+  return hipGetLastError() == hipSuccess ? MSD_OK : MSD_ERR_HIP;
+}
+
+int msd_fill_normal_threefry(uint64_t seed, int64_t fold, float* out_dev, int64_t n, void* stream) {
+  return threefry_fill(2, seed, fold, nullptr, out_dev, n, static_cast<hipStream_t>(stream));
+}
+
+int msd_op_threefry(int stage, uint64_t seed, int64_t fold, const uint32_t* bits_in_dev, float* out_dev, int64_t n,
+                    void* stream) {
+  if (bits_in_dev && stage == 0) return MSD_ERR_INVALID_ARGUMENT;
+  return threefry_fill(stage, seed, fold, bits_in_dev, out_dev, n, static_cast<hipStream_t>(stream));
+}
+
+// the words the sampler kernel's own draw reads (SamplerParams::rng_key): EVERY place that launches the step with a
+// NULL noise slot writes all of them, the generator kind included
+static void fill_rng_key(uint32_t (&key)[kRngWords], int rng, uint64_t seed, uint64_t stream_id) {
+  const uint32_t k[kRngWords] = {(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)stream_id, (uint32_t)(stream_id >> 32),
+                                 (uint32_t)rng, (uint32_t)(seed >> 32), (uint32_t)seed, 0u};
+  memcpy(key, k, sizeof(k));
+}
+
 int msd_sample(msd_model* m, int batch, uint64_t seed, uint64_t stream_id, const float* init_z_dev,
                const float* noise_dev, float* out_dev, void* stream) {
+  return msd_sample_rng(m, batch, MSD_RNG_PHILOX, seed, stream_id, init_z_dev, noise_dev, out_dev, stream);
+}
+
+int msd_sample_rng(msd_model* m, int batch, int rng, uint64_t seed, uint64_t stream_id, const float* init_z_dev,
+                   const float* noise_dev, float* out_dev, void* stream) {
   if (!m) return MSD_ERR_INVALID_ARGUMENT;
+  if (rng != MSD_RNG_PHILOX && rng != MSD_RNG_THREEFRY) return fail(m, MSD_ERR_INVALID_ARGUMENT, "unknown rng %d", rng);
   if (!m->encoded) return fail(m, MSD_ERR_BAD_STATE, "msd_encode has not run");
   if (batch != m->encoded_batch) return fail(m, MSD_ERR_INVALID_ARGUMENT, "batch %d != encoded batch %d", batch, m->encoded_batch);
   if (!out_dev) return fail(m, MSD_ERR_INVALID_ARGUMENT, "out is null");
@@ -1757,16 +1798,20 @@ int msd_sample(msd_model* m, int batch, uint64_t seed, uint64_t stream_id, const
   if (init_z_dev) {
     HIP_TRY(m, hipMemcpyAsync(m->z, init_z_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
   } else {
-    int rc = msd_fill_normal(seed, stream_id, 0, m->z, n, s);
-    if (rc) return fail(m, rc, "philox fill failed");
+    int rc = rng == MSD_RNG_THREEFRY ? msd_fill_normal_threefry(seed, -1, m->z, n, s)   // normal(PRNGKey(seed), [batch, T, n])
+                                     : msd_fill_normal(seed, stream_id, 0, m->z, n, s);
+    if (rc) return fail(m, rc, "init_z fill failed");
   }
   split_z(m, n, s);
   // Step noise: the caller's buffer, or -- noise_dev == NULL -- drawn INSIDE sampler_step_kernel (round 6): step i's draw is
   // sub-sequence 1 + i of the (seed, stream_id) Philox stream, the row philox_normal_kernel used to write into an
   // [N][n] buffer up front (131 MB x songs at base, with a hipMalloc in here on the first call of a batch size).  Same
   // function, same counters: bit-identical to the buffered form (tests/test_gpu_model.py).  The slot holds NULL then.
+  // MSD_RNG_THREEFRY: step i's draw is normal(fold_in(PRNGKey(seed), i), [batch, T, n]) instead, what
+  // msd_fill_normal_threefry(seed, i, ...) writes; the kind travels in device memory, so the captured graphs below serve both.
   const float* noise = noise_dev;
-  const uint32_t key[4] = {(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)stream_id, (uint32_t)(stream_id >> 32)};
+  uint32_t key[kRngWords];
+  fill_rng_key(key, rng, seed, stream_id);
   HIP_TRY(m, hipMemcpyAsync(m->d_rng_key, key, sizeof(key), hipMemcpyHostToDevice, s));
   (void)ddpm;
   // arrival counters of the in-launch merge: zero between launches by construction (the reducer resets its own); once
@@ -1930,7 +1975,8 @@ int msd_profile_steps(msd_model* m, int batch, int n_steps, const char* const** 
   if (rc) return rc;
   split_z(m, n, s);
   const float* noise = nullptr;   // the sampler kernel draws the steps' noise itself (Philox stream (1, 0): elementwise.h)
-  const uint32_t key[4] = {1u, 0u, 0u, 0u};
+  uint32_t key[kRngWords];
+  fill_rng_key(key, kRngPhilox, 1, 0);
   HIP_TRY(m, hipMemcpyAsync(m->d_rng_key, key, sizeof(key), hipMemcpyHostToDevice, s));
   HIP_TRY(m, hipMemcpyAsync(m->d_noise_slot, &noise, sizeof(float*), hipMemcpyHostToDevice, s));
   const int start[2] = {m->N - 1, m->N - 1};
@@ -2184,7 +2230,8 @@ int msd_op_sampler_step(const msd_config* cfg, int step_index, const float* z_de
   float* noise = sc.get<float>((size_t)n);   // one step's draw (zeros) when the caller gives none
   const float** slot = sc.get<const float*>(1);
   int* step = sc.get<int>(2);
-  if (!coef || !eps || !noise || !slot || !step) return MSD_ERR_HIP;
+  uint32_t* key = sc.get<uint32_t>(kRngWords);   // the kernel fetches the words of its own draw up front, used or not
+  if (!coef || !eps || !noise || !slot || !step || !key) return MSD_ERR_HIP;
   // the kernel indexes noise as base + i * n: hand it base = draw - i * n
   const float* base = (noise_dev ? noise_dev : noise) - (size_t)step_index * n;
   const int st[2] = {step_index, step_index};
@@ -2197,7 +2244,7 @@ int msd_op_sampler_step(const msd_config* cfg, int step_index, const float* z_de
       hipStreamSynchronize(s) != hipSuccess)
     return MSD_ERR_HIP;
   SamplerParams sp;
-  sp.eps = eps; sp.z = z_out_dev; sp.noise_slot = slot; sp.coef = coef; sp.step_ptr = step;
+  sp.eps = eps; sp.z = z_out_dev; sp.noise_slot = slot; sp.coef = coef; sp.step_ptr = step; sp.rng_key = key;
   sp.n = (int)n; sp.passes = passes; sp.cond_wt = cfg->cfg_weight; sp.clip_x0 = cfg->clip_x0;
   sp.ddim = cfg->sampler == MSD_SAMPLER_DDIM; sp.model_output = cfg->model_output;
   sp.z_hi = nullptr; sp.z_lo = nullptr; sp.step_from_slot1 = 1;

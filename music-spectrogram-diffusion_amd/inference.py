@@ -205,6 +205,9 @@ def _load_checkpoint(path, spec: config_lib.ModelSpec) -> Tuple[Dict[str, np.nda
   return {k: np.asarray(v, np.float32) for k, v in flat.items()}, step
 
 
+RNG_MODES = ('philox', 'threefry', 'jax')
+
+
 class InferenceModel(object):
   """Wrapper of the HIP synthesizer with the reference's InferenceModel API."""
 
@@ -214,7 +217,7 @@ class InferenceModel(object):
                weight_prefetch: Optional[bool] = None, dedup_layer0: Optional[bool] = None,
                cross_key_split: int = 0, keep_raw_weights: bool = False, kv_touch_ahead: Optional[int] = None,
                cross_merge_in_launch: Optional[bool] = None, cross_q_fold: Optional[bool] = None,
-               mlp_in_persistent: Optional[bool] = None):
+               mlp_in_persistent: Optional[bool] = None, rng: Optional[str] = None):
     """Args mirror inference.py:71-88.
 
     gin_config: the parsed gin string (``parse_training_gin_file``) or a typed
@@ -244,6 +247,8 @@ class InferenceModel(object):
       CU walking its tiles (register epilogue, the next tile's operands land under it); None = the library's choice (on)
     keep_raw_weights: keep the float32 staging copies of the packed matrices on the device (default: freed after
       packing -- 1.5 GB per handle at base_with_context).
+    rng: the generator of a predict / predict_sequence call that does not name one: 'philox' (None: the library's own),
+      'threefry' (the reference's draws, made on the device) or 'jax' (the same draws, made on the host); see predict.
     range_fallback: what to do when an activation leaves the range of the half planes (|x| > 65504; the
       library detects it and fails the call with native.RangeError -- the reference is float32 and has no such
       limit): True (default) switches this model to 'bf16x3' (bfloat16 planes: float32's exponent range, twice
@@ -268,6 +273,9 @@ class InferenceModel(object):
     self.kv_touch_ahead = kv_touch_ahead
     self.cross_merge_in_launch, self.cross_q_fold = cross_merge_in_launch, cross_q_fold
     self.mlp_in_persistent = mlp_in_persistent
+    if rng is not None and rng not in RNG_MODES:
+      raise ValueError('rng must be one of %s: %r' % (RNG_MODES, rng))
+    self.rng = rng or 'philox'
 
     self.sequence_length = dict(spec.task_feature_lengths)
     self.inputs_length = self.sequence_length['inputs']
@@ -355,20 +363,27 @@ class InferenceModel(object):
 
   # -- predict (inference.py:200-203) -----------------------------------------------
   def predict(self, batch: Mapping[str, Any], seed: int = 0, segment: int = 0,
-              init_z=None, noise=None, return_torch: bool = False, rng: str = 'philox'):
+              init_z=None, noise=None, return_torch: bool = False, rng: Optional[str] = None):
     """Predict one batch of 256-frame segments.
 
     batch: the model features of inference.py:113-136 (NumPy arrays or torch
       tensors); ``decoder_target_tokens`` is used for its shape only.
     seed / segment: key of the Philox generator (replaces PRNGKey(seed)).
     init_z [B,T,n] / noise [N,B,T,n]: explicit draws (the parity contract).
-    rng: 'philox' (default: the library's device generator, one stream per segment) or 'jax':
-      the draws jax.random would make for PRNGKey(seed) -- init_z = normal(key), step-i noise =
-      normal(fold_in(key, i)) -- restated on the host (jax_random.py) and cached per
-      (seed, batch).  Like the reference (beam/evaluation.py:209 calls predict(batch) with the default
-      seed for EVERY segment), `segment` does not enter the key in this mode.
+    rng: None = the model's default (InferenceModel(rng=), 'philox' unless given).
+      'philox': the library's device generator, one stream per segment.
+      'threefry': the draws jax.random would make for PRNGKey(seed) -- init_z = normal(key), step-i noise =
+      normal(fold_in(key, i)), one draw per [B,T,n] array -- made ON THE DEVICE: init_z by a fill kernel, step i's
+      noise inside the sampler kernel (msd_sample_rng, MSD_RNG_THREEFRY).  No host work, no noise tensor.
+      'jax': the same draws restated on the host (jax_random.py), uploaded as a [N,B,T,n] tensor
+      and cached per (seed, batch): the specification the device generator is tested against (they agree to
+      the rounding of log1p: <= 3 ulp on about one value in a hundred).
+      Like the reference (beam/evaluation.py:209 calls predict(batch) with the default seed for EVERY segment),
+      `segment` does not enter the key in the 'threefry' and 'jax' modes.
     Returns (decodes float32 [B,T,n] in mel units, scores float32 [B] zeros).
     """
+    if rng is None:
+      rng = self.rng
     try:
       return self._predict_once(batch, seed, segment, init_z, noise, return_torch, rng)
     except native.RangeError:
@@ -419,15 +434,17 @@ class InferenceModel(object):
       out = torch.empty((b, t, n), dtype=torch.float32, device=dev)
       if rng == 'jax' and init_z is None and noise is None:
         init_z, noise = self._jax_noise(seed, b)
-      elif rng not in ('philox', 'jax'):
-        raise ValueError("rng must be 'philox' or 'jax': %r" % (rng,))
+      elif rng not in RNG_MODES:
+        raise ValueError('rng must be one of %s: %r' % (RNG_MODES, rng))
       z0 = None if init_z is None else _to_device(torch, init_z, dev, torch.float32)
       nz = None if noise is None else _to_device(torch, noise, dev, torch.float32)
       if z0 is not None and tuple(z0.shape) != (b, t, n):
         raise ValueError('init_z must be [batch, %d, %d]' % (t, n))
       if nz is not None and tuple(nz.shape) != (self.spec.diffusion.sampler.schedule.num_steps, b, t, n):
         raise ValueError('noise must be [num_steps, batch, %d, %d]' % (t, n))
-      nm.sample(b, out, seed=seed, stream_id=segment, init_z=z0, noise=nz, stream=s)
+      # explicit draws keep precedence in every mode; 'jax' has none left to generate
+      nm.sample(b, out, seed=seed, stream_id=segment, init_z=z0, noise=nz, stream=s,
+                rng='threefry' if rng == 'threefry' else 'philox')
       self._stream.synchronize()
     t2 = time.perf_counter()
     self.last_timing = {'encode_s': t1 - t0, 'sample_s': t2 - t1, 'total_s': t2 - t0}
@@ -451,7 +468,7 @@ class InferenceModel(object):
   # -- InferSong.process segment loop (beam/evaluation.py:161-223) ---------------------
   def predict_sequence(self, segments_tokens: Sequence[np.ndarray], seed: int = 0,
                        always_mask_context: bool = False, init_context: Optional[np.ndarray] = None,
-                       first_segment_index: int = 0, return_timing: bool = False, rng: str = 'philox',
+                       first_segment_index: int = 0, return_timing: bool = False, rng: Optional[str] = None,
                        return_torch: bool = False):
     """Synthesize a whole song: segments of int32 [inputs_length] (or [1, L]).
 

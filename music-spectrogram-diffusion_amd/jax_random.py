@@ -78,11 +78,15 @@ _ERFINV_GE5 = np.array([-0.000200214257, 0.000100950558, 0.00134934322, -0.00367
                         -0.0076224613, 0.00943887047, 1.00167406, 2.83297682], np.float32)
 
 
-def erfinv_f32(x: np.ndarray) -> np.ndarray:
-  """XLA's float32 ErfInv (M. Giles, 'Approximating the erfinv function')."""
+def erfinv_f32(x: np.ndarray, w=None) -> np.ndarray:
+  """XLA's float32 ErfInv (M. Giles, 'Approximating the erfinv function').  w: -log1p(-x*x) in float32 computed
+  elsewhere (log1p is the one operation here whose rounding depends on the libm; a test hands in the device's)."""
   x = np.asarray(x, np.float32)
-  with np.errstate(divide='ignore'):
-    w = -np.log1p(-(x * x)).astype(np.float32)
+  if w is not None:
+    w = np.asarray(w, np.float32)
+  else:
+    with np.errstate(divide='ignore'):
+      w = -np.log1p(-(x * x)).astype(np.float32)
   lt = w < np.float32(5.0)
   w = np.where(lt, w - np.float32(2.5), np.sqrt(w) - np.float32(3.0)).astype(np.float32)
   p = np.where(lt, _ERFINV_LT5[0], _ERFINV_GE5[0]).astype(np.float32)
@@ -103,6 +107,26 @@ def normal(key: Tuple[int, int], shape: Sequence[int]) -> np.ndarray:
   lo = np.nextafter(np.float32(-1.0), np.float32(0.0))
   u = uniform_f32(key, n, lo, np.float32(1.0))
   return (np.float32(np.sqrt(2)) * erfinv_f32(u)).reshape(shape)
+
+
+def normal_at(key: Tuple[int, int], n_total: int, indices) -> np.ndarray:
+  """normal(key, [n_total]).ravel()[indices] without the other elements: the random-access form of the layout, one
+  Threefry block per requested element (what one thread of the device generator computes, csrc/elementwise.h)."""
+  n_total = int(n_total)
+  e = np.asarray(indices, np.int64).ravel()
+  if e.size and (e.min() < 0 or e.max() >= n_total):
+    raise IndexError('indices outside [0, %d)' % n_total)
+  half = (n_total + 1) // 2
+  first = e < half
+  c0 = np.where(first, e, e - half)
+  c1 = np.where(first, e + half, e)
+  c1 = np.where(c1 >= n_total, 0, c1)      # odd n_total: the block of element half - 1 has the zero pad as its second counter
+  a, b = threefry2x32(key, c0.astype(_U32), c1.astype(_U32))
+  bits = np.where(first, a, b).astype(_U32)
+  lo = np.nextafter(np.float32(-1.0), np.float32(0.0))
+  floats = ((bits >> _U32(9)) | _U32(0x3F800000)).view(np.float32) - np.float32(1.0)
+  u = np.maximum(lo, floats * np.float32(np.float32(1.0) - lo) + lo).astype(np.float32)
+  return (np.float32(np.sqrt(2)) * erfinv_f32(u)).reshape(np.shape(indices))
 
 
 def reference_noise(seed: int, shape: Sequence[int], num_steps: int):

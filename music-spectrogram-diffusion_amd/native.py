@@ -26,9 +26,12 @@ MSD_PREC_F16 = 0      # one IEEE-half plane per operand
 MSD_PREC_F16X3 = 1    # hi + lo half planes, three MFMAs per product (the parity mode, the default)
 MSD_PREC_BF16 = 2     # one bfloat16 plane                       } libmsd_amd_bf16.so; msd_create of the other
 MSD_PREC_BF16X3 = 3   # hi + lo bfloat16 planes                  } build answers MSD_ERR_UNSUPPORTED
-ABI_VERSION = 6        # MSD_AMD_ABI_VERSION of include/msd_amd.h (tests/test_abi.py)
+ABI_VERSION = 7        # MSD_AMD_ABI_VERSION of include/msd_amd.h (tests/test_abi.py)
 MSD_SAMPLER_DDPM = 0
 MSD_SAMPLER_DDIM = 1
+MSD_RNG_PHILOX = 0    # the library's own generator (msd_fill_normal)
+MSD_RNG_THREEFRY = 1  # the reference's: jax.random's Threefry draws for PRNGKey(seed), made on the device (ABI 7)
+RNGS = {'philox': MSD_RNG_PHILOX, 'threefry': MSD_RNG_THREEFRY}
 MAX_KERNEL_CLASSES = 16
 
 # precision name -> (msd_precision value, plane format).  The plane format is a property of the LIBRARY build
@@ -53,7 +56,7 @@ EXPORTED_SYMBOLS = (
     'msd_encode', 'msd_sample', 'msd_reset_graph', 'msd_decoder_pass', 'msd_fill_normal', 'msd_get_schedule',
     'msd_debug_read', 'msd_profile_steps', 'msd_op_gemm_h16', 'msd_op_gemm_bf16', 'msd_op_gemm_f32',
     'msd_op_attention', 'msd_op_attention_qp', 'msd_op_attention_split', 'msd_op_attention_ex', 'msd_op_sampler_step', 'msd_op_residual_norm_gemm', 'msd_op_geglu',
-    'msd_op_qkv', 'msd_op_final_proj')
+    'msd_op_qkv', 'msd_op_final_proj', 'msd_sample_rng', 'msd_fill_normal_threefry', 'msd_op_threefry')
 
 
 class NativeLibraryError(RuntimeError):
@@ -73,7 +76,7 @@ MODEL_OUTPUTS = {'eps': MSD_OUTPUT_EPS, 'x0': MSD_OUTPUT_X0, 'v': MSD_OUTPUT_V}
 
 
 class MsdConfig(ctypes.Structure):
-  """msd_config of include/msd_amd.h (ABI 6), field for field."""
+  """msd_config of include/msd_amd.h (ABI 6 and 7), field for field."""
   _fields_ = [(n, ctypes.c_int32) for n in (
       'struct_size', 'has_context', 'vocab_size', 'emb_dim', 'num_heads', 'head_dim',
       'mlp_dim', 'num_encoder_layers', 'num_decoder_layers', 'inputs_length',
@@ -96,7 +99,8 @@ class MsdConfig(ctypes.Structure):
 
 # msd_config only ever grows at its end, so an OLDER library can be driven by passing it the struct size it knows
 # (same-box A/B of a previous round's binary through MSD_AMD_LIB: tools/ab/); the newer fields are then simply not seen.
-ABI_STRUCT_SIZES = {4: MsdConfig.weight_prefetch.offset + 4, 5: MsdConfig.kv_touch_ahead.offset + 4, 6: ctypes.sizeof(MsdConfig)}
+ABI_STRUCT_SIZES = {4: MsdConfig.weight_prefetch.offset + 4, 5: MsdConfig.kv_touch_ahead.offset + 4, 6: ctypes.sizeof(MsdConfig),
+                    7: ctypes.sizeof(MsdConfig)}   # ABI 7 appends entry points only
 
 _libs = {}
 
@@ -158,6 +162,12 @@ def load(planes: str = 'f16') -> ctypes.CDLL:
   lib.msd_decoder_pass.argtypes = [vp, i32, i32, vp, i32, vp, vp]
   lib.msd_reset_graph.argtypes = [vp]
   lib.msd_fill_normal.argtypes = [u64, u64, u32, vp, i64, vp]
+  if 'msd_sample_rng' in present:
+    lib.msd_sample_rng.argtypes = [vp, i32, i32, u64, u64, vp, vp, vp, vp]
+  if 'msd_fill_normal_threefry' in present:
+    lib.msd_fill_normal_threefry.argtypes = [u64, i64, vp, i64, vp]
+  if 'msd_op_threefry' in present:
+    lib.msd_op_threefry.argtypes = [i32, u64, i64, vp, vp, i64, vp]
   lib.msd_get_schedule.argtypes = [vp, vp]
   lib.msd_debug_read.argtypes = [vp, c.c_char_p, vp, i64, c.POINTER(i64)]
   lib.msd_profile_steps.argtypes = [vp, i32, i32, c.POINTER(c.POINTER(c.c_char_p)),
@@ -283,10 +293,17 @@ class NativeModel:
            'msd_encode')
 
   def sample(self, batch: int, out, seed: int = 0, stream_id: int = 0, init_z=None,
-             noise=None, stream: int = 0):
-    _check(self.lib, self.handle,
-           self.lib.msd_sample(self.handle, batch, seed, stream_id, _ptr(init_z), _ptr(noise),
-                               _ptr(out), stream), 'msd_sample')
+             noise=None, stream: int = 0, rng: str = 'philox'):
+    """rng: the generator of the draws that are not given -- 'philox' (the library's own, keyed by seed and stream_id)
+    or 'threefry' (the reference's jax.random draws for PRNGKey(seed), made on the device; stream_id is ignored)."""
+    if rng not in RNGS:
+      raise ValueError('rng must be one of %s: %r' % (sorted(RNGS), rng))
+    if rng == 'philox':   # (the entry point every ABI has: an older library under MSD_AMD_LIB still runs)
+      rc = self.lib.msd_sample(self.handle, batch, seed, stream_id, _ptr(init_z), _ptr(noise), _ptr(out), stream)
+    else:
+      rc = self.lib.msd_sample_rng(self.handle, batch, RNGS[rng], seed, stream_id, _ptr(init_z), _ptr(noise),
+                                   _ptr(out), stream)
+    _check(self.lib, self.handle, rc, 'msd_sample')
 
   def reset_graph(self):
     _check(self.lib, self.handle, self.lib.msd_reset_graph(self.handle), 'msd_reset_graph')
@@ -337,6 +354,23 @@ def fill_normal(out, seed: int, stream_id: int, subseq: int, stream: int = 0):
   rc = lib.msd_fill_normal(seed, stream_id, subseq, _ptr(out), out.numel(), stream)
   if rc:
     raise RuntimeError('msd_fill_normal failed (%d)' % rc)
+
+
+def fill_normal_threefry(out, seed: int, fold: int = -1, stream: int = 0):
+  """jax.random.normal(key, [out.numel()]) into the float32 device tensor `out`; key = PRNGKey(seed), or
+  fold_in(PRNGKey(seed), fold) when fold >= 0."""
+  lib = load()
+  _op_check(lib.msd_fill_normal_threefry(seed, fold, _ptr(out), out.numel(), stream), 'msd_fill_normal_threefry')
+
+
+def op_threefry(stage: int, out, seed: int = 0, fold: int = -1, bits_in=None, stream: int = 0):
+  """The stages of that draw into `out` (4-byte elements): 0 = raw bits, 1 = uniform, 2 = normal, 3 = the normal stage's
+  -log1p(-u*u); bits_in (int32 /
+  uint32 device words, same count): stages 1 / 2 of the caller's words instead."""
+  lib = load()
+  if bits_in is not None and bits_in.numel() != out.numel():
+    raise ValueError('bits_in and out must have the same element count')
+  _op_check(lib.msd_op_threefry(stage, seed, fold, _ptr(bits_in), _ptr(out), out.numel(), stream), 'msd_op_threefry')
 
 
 def op_gemm_h16(precision: str, a, w, c, stream: int = 0):

@@ -4,7 +4,7 @@ beam/evaluation.py:161-223) on the MI355X path.
 
   python -m msd_amd.synthesize song.mid --checkpoint /path/to/base_with_context/checkpoint_500000 \\
       --out song_mel.npy [--preset base_with_context] [--gin-file train.gin --gin-bindings ...]
-      [--seed 0] [--rng jax] [--num-steps 1000] [--dry-run]
+      [--seed 0] [--rng threefry|jax] [--num-steps 1000] [--dry-run]
 
 --dry-run tokenises only (no GPU): prints the segment / token statistics the synthesis would see."""
 from __future__ import annotations
@@ -27,7 +27,8 @@ def main(argv=None) -> int:
   ap.add_argument('--num-steps', type=int, default=1000)
   ap.add_argument('--cfg-weight', type=float, default=5.0)
   ap.add_argument('--seed', type=int, default=0)
-  ap.add_argument('--rng', choices=['philox', 'jax'], default='philox')
+  ap.add_argument('--rng', choices=['philox', 'threefry', 'jax'], default='philox',
+                  help="'threefry': the reference's jax.random draws for --seed, made on the device; 'jax': the same on the host")
   ap.add_argument('--precision', choices=['f16x3', 'f16', 'bf16x3', 'bf16'], default='f16x3',
                   help="'f16x3' (default): hi + lo IEEE-half operand planes, float32-class; 'bf16x3': bfloat16 planes "
                        "(float32's exponent range, twice the rounding error); 'f16' / 'bf16': one plane, not parity-grade")
