@@ -335,9 +335,9 @@ struct Ctx {
     if (m->prof.on) (void)hipEventRecord(m->prof.e0, s);
     (void)kc;
   }
+  void latch(hipError_t e) { if (err == hipSuccess) err = e; }   // the first error of the chain is the one reported
   void end(int kc) {
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess && err == hipSuccess) err = e;
+    latch(hipGetLastError());
     if (m->prof.on) {
       (void)hipEventRecord(m->prof.e1, s);
       (void)hipEventSynchronize(m->prof.e1);
@@ -372,51 +372,28 @@ GemmParams gp(const Planes& a, int lda, const Planes& b, int ldb, int M, int N, 
 // (~31 B/clk with one block per CU), hence the small tiles there.
 constexpr int kNarrowTile = 32;  // BN of every GEMM that feeds the folded-norm ssq partials
 constexpr int kTallNS = 4;       // ring depth of the 64 x 32 tiles (6 measured equal in situ: 1.200 vs 1.198 ms)
+constexpr int kWideNS = 3;       // 64 x 64 wide tiles: 3-deep ring (cold weights: deeper is better)
 enum TileKind { TK_NARROW = 0, TK_TALL = 1, TK_QKV = 2, TK_MLP_IN = 3, TK_SQUARE = 4 };
 
 // XCD grid (gemm_h16.h): 2 row groups x 4 column groups.  Same-box A/B over the whole step
 // (tools/env_ab.sh): 1 x 8 -> 1.196 ms, 2 x 4 -> 1.167 ms, 4 x 2 -> 1.187 ms; choosing per launch by
 // the bytes each L2 has to fetch (A / rx + B * rx / 8) picked 1 x 8 for the wide GEMMs and was no
 // better than 1 x 8 everywhere.
-void set_xcd_grid(const msd_model* m, GemmParams& p, int kc, int M, int BM) {
-  int rx = 2, walk_n = 1;
-  (void)m; (void)kc;
-  p.xcd_rows = (rx == 1 || rx == 2 || rx == 4 || rx == 8) && ((M / BM) % rx == 0) ? rx : 1;
-  p.xcd_walk_n = walk_n;
+void set_xcd_grid(GemmParams& p, int M, int BM) {
+  p.xcd_rows = (M / BM) % 2 == 0 ? 2 : 1;
+  p.xcd_walk_n = 1;
 }
 
-template <int NP, int BM, int BN, int NS, class Epi>
-void gemm_t(Ctx& c, int kc, const Planes& a, int lda, const Planes& b, int ldb, int M, int N, int K,
-            const Epi& epi, const WeightPrefetch* pf = nullptr) {
-  c.begin(kc);
-  GemmParams p = gp<NP>(a, lda, b, ldb, M, N, K);
-  if (pf) p.pf = *pf;
-  p.sat = c.m->d_sat; p.sat_tag = (unsigned)kc + 1u;
-  set_xcd_grid(c.m, p, kc, M, BM);
-  hipError_t e = launch_gemm_h16_dma<NP, BM, BN, NS, Epi>(p, epi, c.s);
-  if (e != hipSuccess && c.err == hipSuccess) c.err = e;
-  c.end(kc);
-}
-
-// launch parameters of one problem of a dual launch (gemm_h16.h gemm_h16_dual_kernel), as gemm_t sets them
+// launch parameters of one GEMM problem on tiles of BM rows: operands, the weight prefetch it carries, range flag, XCD grid
 template <int NP>
 GemmParams gp_launch(Ctx& c, int kc, const Planes& a, int lda, const Planes& b, int ldb, int M, int N, int K, int BM,
                      const WeightPrefetch* pf = nullptr) {
   GemmParams p = gp<NP>(a, lda, b, ldb, M, N, K);
   if (pf) p.pf = *pf;
   p.sat = c.m->d_sat; p.sat_tag = (unsigned)kc + 1u;
-  set_xcd_grid(c.m, p, kc, M, BM);
+  set_xcd_grid(p, M, BM);
   return p;
 }
-template <int NP, int BM1, int BN1, int NS1, int BM2, int BN2, int NS2, class Epi1, class Epi2>
-void gemm_dual_t(Ctx& c, int kc, const GemmParams& p1, const Epi1& e1, const GemmParams& p2, const Epi2& e2) {
-  c.begin(kc);
-  hipError_t e = launch_gemm_h16_dual<NP, BM1, BN1, NS1, Epi1, BM2, BN2, NS2, Epi2>(p1, e1, p2, e2, c.s);
-  if (e != hipSuccess && c.err == hipSuccess) c.err = e;
-  c.end(kc);
-}
-
-constexpr int wide_ns(int np) { return 3; }   // 64 x 64 wide tiles: 3-deep ring (cold weights: deeper is better)
 
 // rounds of blocks over the 256 CUs x rows of operand per K-tile: the GEMMs sit on the per-CU ingest
 // path, so a launch costs about that; used to pick between tile shapes for a given (M, N)
@@ -479,63 +456,149 @@ TileShape pick_tile(int M, int N, int align, bool wide48 = false, int K = 0) {
   return t;
 }
 
-template <int NP, int TK, class Epi>
-void gemm(Ctx& c, int kc, const Planes& a, int lda, const Planes& b, int ldb, int M, int N, int K,
-          const Epi& epi, int align = 0, const WeightPrefetch* pf = nullptr) {
-  constexpr bool wide48 = epi_takes_48<Epi>::value;
-  const TileShape t = pick_tile<NP, TK>(M, N, align, wide48, K);
-#define MSD_GO(BM_, BN_, NS_) return gemm_t<NP, BM_, BN_, NS_, Epi>(c, kc, a, lda, b, ldb, M, N, K, epi, pf)
+// ---- the tile table ---------------------------------------------------------------------------------------------
+// The ONLY place that names a GEMM tile (BM x BN, ring depth NS).  Dispatch (gemm, gemm_dual) walks a list in order and
+// takes the entry of the shape pick_tile chose, the LAST entry otherwise; prepare_gemms opts every entry of every launch
+// site into its dynamic LDS.  A new tile is one line here (and a pick_tile rule that returns its shape).
+template <class... T> struct List {};
+template <class... A, class... B> constexpr List<A..., B...> operator+(List<A...>, List<B...>) { return {}; }
+template <bool C, class L> using list_if = std::conditional_t<C, L, List<>>;
+template <class X, class... T> constexpr bool in_list(List<T...>) { return (std::is_same<X, T>::value || ...); }
+
+template <int BM_, int BN_, int NS_> struct Tile {
+  static constexpr int BM = BM_, BN = BN_, NS = NS_;
+  static bool is(TileShape t) { return t.bm == BM_ && t.bn == BN_; }
+};
 // Batched songs: 128-row tiles, 2-deep ring of K = 64 tiles.  A 4-deep ring of K = 32 tiles (64-byte rows, its own
 // swizzle and a plain one-barrier-per-tile loop: tools/ubench/gemm_h16_k32.h) was built in round 3, is parity-green on
 // the batched test and measured 10 % SLOWER end to end at 8 and 16 songs (profiles/r03m_k32_ab.log: 465 vs 516 and
 // 498 vs 550 mel-frames/s; gated MLP input 1.34 vs 1.13 ms per step): twice the barriers per K and one wave per SIMD
 // at 340 registers cost more than the deeper ring hides.  Not in the product build.
-#define MSD_GO_BIG(BM_, BN_) MSD_GO(BM_, BN_, 2);
+using BigTile = Tile<128, 96, 2>;
+using BigMlpInTile = Tile<128, 128, 2>;   // EpiGeglu<2> has a persistent form on it (gemm_t)
+using Wide96Tile = Tile<64, 96, 3>;
+using Wide128Tile = Tile<64, 128, 3>;
+using WideTile = Tile<64, 64, kWideNS>;
+using TallTile = Tile<64, kNarrowTile, kTallNS>;
+using Narrow96Tile = Tile<kNarrowTile, 96, 4>;   // second problem of the folded attention-out launch only
+using Narrow48Tile = Tile<kNarrowTile, kWide48, 4>;
+using NarrowTile = Tile<kNarrowTile, kNarrowTile, 4>;
+
+template <class Epi> struct epi_is_y2 : std::false_type {};   // EpiResidualNorm Y2: folded layers only, never on the batched path's tiles
+template <int NP> struct epi_is_y2<EpiResidualNorm<NP, false, true>> : std::true_type {};
+
+template <int NP, int TK, class Epi>
+constexpr auto tile_table() {
   if constexpr (TK == TK_QKV) {
-    if constexpr (NP == 2) {
-      if (t.bm == 128) MSD_GO_BIG(128, 96)
-      if (t.bn == 96) MSD_GO(64, 96, 3);
-    }
-    MSD_GO(64, 64, wide_ns(NP));
+    return list_if<NP == 2, List<BigTile, Wide96Tile>>{} + List<WideTile>{};
   } else if constexpr (TK == TK_MLP_IN) {
-    if constexpr (NP == 2) {
-      if constexpr (std::is_same<Epi, EpiGeglu<NP>>::value) {
-        // batched songs, decoder MLP blocks: the persistent tile loop with the register epilogue (gemm_h16.h) -- one
-        // resident block per CU walks its 4 .. 8 tiles, the next tile's ring stages land under the current epilogue
-        if (t.bm == 128 && c.m->persist_mlp_in && epi.rsc.ssq && epi.rsc.bias && K >= 2 * kGemmBK) {
-          c.begin(kc);
-          GemmParams p = gp<NP>(a, lda, b, ldb, M, N, K);
-          if (pf) p.pf = *pf;
-          p.sat = c.m->d_sat; p.sat_tag = (unsigned)kc + 1u;
-          set_xcd_grid(c.m, p, kc, M, 128);
-          const int cus = c.m->cus > 0 ? c.m->cus : 256;
-          hipError_t e = launch_gemm_h16_geglu_persist<NP, 128, 128, 2>(p, epi, cus / 8 * 8, c.s);
-          if (e != hipSuccess && c.err == hipSuccess) c.err = e;
-          c.end(kc);
-          return;
-        }
-      }
-      if (t.bm == 128) MSD_GO_BIG(128, 128)
-      if (t.bn == 128) MSD_GO(64, 128, 3);
-    }
-    MSD_GO(64, 64, wide_ns(NP));
+    return list_if<NP == 2, List<BigMlpInTile, Wide128Tile>>{} + List<WideTile>{};
   } else {
-    if constexpr (NP == 2 && (TK == TK_TALL || TK == TK_SQUARE)) {
-      if (t.bm == 128) MSD_GO_BIG(128, 96)
-      if (t.bm == 64 && t.bn == 96) MSD_GO(64, 96, 3);
-    }
-    if constexpr (TK == TK_TALL) {
-      if (t.bm == 64) MSD_GO(64, kNarrowTile, kTallNS);
-    }
-    if constexpr (NP == 2 && epi_takes_48<Epi>::value) {
-      if (t.bn == kWide48) MSD_GO(kNarrowTile, kWide48, 4);
-    }
-    MSD_GO(kNarrowTile, kNarrowTile, 4);
+    return list_if<NP == 2 && (TK == TK_TALL || TK == TK_SQUARE) && !epi_is_y2<Epi>::value, List<BigTile, Wide96Tile>>{} +
+           list_if<TK == TK_TALL, List<TallTile>>{} +
+           list_if<NP == 2 && epi_takes_48<Epi>::value, List<Narrow48Tile>>{} + List<NarrowTile>{};
   }
-#undef MSD_GO_BIG
-#undef MSD_GO
+}
+template <int NP, int TK, class Epi> using TileTable = decltype(tile_table<NP, TK, Epi>());
+
+// Dual launches of the folded cross-attention query projection (decoder_layers; two-plane modes): (problem 1's tile,
+// problem 2's tile) pairs.  QKV: the same tile for both problems; attention-out: each problem its own.
+template <class T1, class T2> struct TilePair { using P1 = T1; using P2 = T2; };
+template <class T1, class... T2> constexpr List<TilePair<T1, T2>...> pairs_of(List<T2...>) { return {}; }
+template <class... T1, class L2> constexpr auto cross(List<T1...>, L2) { return (pairs_of<T1>(L2{}) + ...); }
+using FoldQkvTiles = List<TilePair<Wide96Tile, Wide96Tile>, TilePair<WideTile, WideTile>>;
+using FoldOutTiles = decltype(cross(List<TallTile, NarrowTile>{}, List<Narrow96Tile, NarrowTile>{}));
+
+// Launch sites: every (tile kind, epilogue) gemm<NP> is called with and every (pairs, epilogues) gemm_dual is.  A site
+// that is missing here does not compile; one that is here has all its tiles prepared outside stream capture.
+template <int TK, class Epi> struct Site {};
+template <class Pairs, class Epi1, class Epi2> struct DualSite {};
+template <int NP> using GemmSites = decltype(
+    List<Site<TK_QKV, EpiQKV<NP>>, Site<TK_MLP_IN, EpiGeglu<NP>>, Site<TK_SQUARE, EpiResidual>, Site<TK_TALL, EpiResidual>,
+         Site<TK_TALL, EpiResidualNorm<NP>>, Site<TK_TALL, EpiResidualNorm<NP, true>>, Site<TK_SQUARE, EpiResidualNorm<NP>>,
+         Site<TK_SQUARE, EpiStoreH16<NP>>, Site<TK_NARROW, EpiStoreF32>, Site<TK_NARROW, EpiInProj<NP>>>{} +
+    list_if<NP == 2, List<Site<TK_TALL, EpiResidualNorm<NP, false, true>>>>{});
+using DualSites = List<DualSite<FoldQkvTiles, EpiQKV<2>, EpiStoreF32>,
+                       DualSite<FoldOutTiles, EpiResidualNorm<2>, EpiAddStoreH16<2>>,
+                       DualSite<FoldOutTiles, EpiResidualNorm<2, true>, EpiAddStoreH16<2>>>;
+
+// EpiGeglu<2> on the batched path's tile, decoder MLP blocks: the persistent tile loop with the register epilogue
+// (gemm_h16.h) -- one resident block per CU walks its 4 .. 8 tiles, the next tile's ring stages land under the current
+// epilogue
+template <int NP, class T, class Epi>
+constexpr bool kHasPersistentForm = NP == 2 && std::is_same<T, BigMlpInTile>::value && std::is_same<Epi, EpiGeglu<2>>::value;
+
+template <int NP, class T, class Epi>
+void gemm_t(Ctx& c, int kc, const GemmParams& p, const Epi& epi) {
+  c.begin(kc);
+  if constexpr (kHasPersistentForm<NP, T, Epi>) {
+    if (c.m->persist_mlp_in && epi.rsc.ssq && epi.rsc.bias && p.K >= 2 * kGemmBK) {
+      c.latch(launch_gemm_h16_geglu_persist<NP, T::BM, T::BN, T::NS>(p, epi, (c.m->cus > 0 ? c.m->cus : 256) / 8 * 8, c.s));
+      return c.end(kc);
+    }
+  }
+  c.latch(launch_gemm_h16_dma<NP, T::BM, T::BN, T::NS, Epi>(p, epi, c.s));
+  c.end(kc);
 }
 
+// One-time opt-in to > 64 KiB dynamic LDS of everything gemm_t / gemm_dual may launch: every tile of every launch site.
+// Called OUTSIDE stream capture (set_func_attrs).
+template <class... E> hipError_t first_error(E... e) { hipError_t r = hipSuccess; ((r = r != hipSuccess ? r : e), ...); return r; }
+template <int NP, class T, class Epi>
+hipError_t prepare_tile() {
+  if constexpr (kHasPersistentForm<NP, T, Epi>)
+    return first_error(gemm_h16_dma_prepare<NP, T::BM, T::BN, T::NS, Epi>(), gemm_h16_geglu_persist_prepare<NP, T::BM, T::BN, T::NS>());
+  else return gemm_h16_dma_prepare<NP, T::BM, T::BN, T::NS, Epi>();
+}
+template <int NP, class Epi, class... T> hipError_t prepare_tiles(List<T...>) { return first_error(prepare_tile<NP, T, Epi>()...); }
+template <class Epi1, class Epi2, class... P>
+hipError_t prepare_pairs(List<P...>) {
+  return first_error(gemm_h16_dual_prepare<2, P::P1::BM, P::P1::BN, P::P1::NS, Epi1, P::P2::BM, P::P2::BN, P::P2::NS, Epi2>()...);
+}
+template <int NP, int... TK, class... Epi>
+hipError_t prepare_sites(List<Site<TK, Epi>...>) { return first_error(prepare_tiles<NP, Epi>(TileTable<NP, TK, Epi>{})...); }
+template <class... Pairs, class... Epi1, class... Epi2>
+hipError_t prepare_sites(List<DualSite<Pairs, Epi1, Epi2>...>) { return first_error(prepare_pairs<Epi1, Epi2>(Pairs{})...); }
+template <int NP>
+hipError_t prepare_gemms() {
+  if constexpr (NP == 2) return first_error(prepare_sites<NP>(GemmSites<NP>{}), prepare_sites(DualSites{}));
+  else return prepare_sites<NP>(GemmSites<NP>{});
+}
+
+// launches p on the list's tile of shape t; the last entry is the fall-back
+template <int NP, class Epi, class T0, class... T>
+void gemm_on(List<T0, T...>, TileShape t, Ctx& c, int kc, const GemmParams& p, const Epi& epi) {
+  if constexpr (sizeof...(T) > 0) {
+    if (!T0::is(t)) return gemm_on<NP>(List<T...>{}, t, c, kc, p, epi);
+  }
+  gemm_t<NP, T0, Epi>(c, kc, p, epi);
+}
+
+template <int NP, int TK, class Epi>
+void gemm(Ctx& c, int kc, const Planes& a, int lda, const Planes& b, int ldb, int M, int N, int K,
+          const Epi& epi, int align = 0, const WeightPrefetch* pf = nullptr) {
+  static_assert(in_list<Site<TK, Epi>>(GemmSites<NP>{}), "a new launch site: add it to GemmSites, or its kernels are never prepared");
+  const TileShape t = pick_tile<NP, TK>(M, N, align, epi_takes_48<Epi>::value, K);
+  gemm_on<NP>(TileTable<NP, TK, Epi>{}, t, c, kc, gp_launch<NP>(c, kc, a, lda, b, ldb, M, N, K, t.bm, pf), epi);
+}
+
+// Two GEMMs in one launch (gemm_h16.h gemm_h16_dual_kernel), problem i on the tile of shape ti; p1 carries the prefetch
+template <class Epi1, class Epi2, class P0, class... P>
+void gemm_dual_on(List<P0, P...>, TileShape t1, TileShape t2, Ctx& c, int kc, const GemmParams& p1, const Epi1& e1,
+                  const GemmParams& p2, const Epi2& e2) {
+  using T1 = typename P0::P1; using T2 = typename P0::P2;
+  if constexpr (sizeof...(P) > 0) {
+    if (!T1::is(t1) || !T2::is(t2)) return gemm_dual_on(List<P...>{}, t1, t2, c, kc, p1, e1, p2, e2);
+  }
+  c.begin(kc);
+  c.latch(launch_gemm_h16_dual<2, T1::BM, T1::BN, T1::NS, Epi1, T2::BM, T2::BN, T2::NS, Epi2>(p1, e1, p2, e2, c.s));
+  c.end(kc);
+}
+template <class Pairs, class Epi1, class Epi2>
+void gemm_dual(Ctx& c, int kc, TileShape t1, const GemmParams& p1, const Epi1& e1, TileShape t2, const GemmParams& p2, const Epi2& e2) {
+  static_assert(in_list<DualSite<Pairs, Epi1, Epi2>>(DualSites{}), "a new dual launch site: add it to DualSites");
+  gemm_dual_on(Pairs{}, t1, t2, c, kc, p1, e1, p2, e2);
+}
 
 // Prefetch target = the packed W^T planes [N, K] of a later GEMM (gemm_h16.h PrefetchTarget)
 template <int NP>
@@ -549,46 +612,6 @@ WeightPrefetch prefetch_of(const msd_model* m, const Planes& w, int N, int K) {
   WeightPrefetch pf;
   pf.add(weights_target<NP>(m, w, N, K));
   return pf;
-}
-
-template <int NP>
-hipError_t prepare_gemms() {
-  hipError_t e = hipSuccess, r;
-#define PREP(BM, BN, NS, EPI) if ((r = gemm_h16_dma_prepare<NP, BM, BN, NS, EPI>()) != hipSuccess) e = r;
-  PREP(64, 64, wide_ns(NP), EpiQKV<NP>) PREP(64, 64, wide_ns(NP), EpiGeglu<NP>)
-  if constexpr (NP == 2) {
-    PREP(64, 96, 3, EpiQKV<NP>) PREP(64, 128, 3, EpiGeglu<NP>)
-    PREP(128, 96, 2, EpiQKV<NP>) PREP(128, 128, 2, EpiGeglu<NP>)
-    PREP(128, 96, 2, EpiResidual) PREP(128, 96, 2, EpiResidualNorm<NP>) PREP(128, 96, 2, EpiStoreH16<NP>)
-    PREP(64, 96, 3, EpiResidual) PREP(64, 96, 3, EpiResidualNorm<NP>) PREP(64, 96, 3, EpiStoreH16<NP>)
-    { using EpiDup = EpiResidualNorm<NP, true>; PREP(128, 96, 2, EpiDup) PREP(64, 96, 3, EpiDup) }
-    if ((r = gemm_h16_geglu_persist_prepare<NP, 128, 128, 2>()) != hipSuccess) e = r;
-    PREP(32, kWide48, 4, EpiResidualNorm<NP>)
-  }
-  PREP(32, 32, 4, EpiResidual) PREP(32, 32, 4, EpiResidualNorm<NP>) PREP(32, 32, 4, EpiStoreH16<NP>)
-  PREP(32, 32, 4, EpiStoreF32) PREP(32, 32, 4, EpiInProj<NP>)
-  PREP(64, 32, kTallNS, EpiResidual) PREP(64, 32, kTallNS, EpiResidualNorm<NP>)
-  { using EpiDup = EpiResidualNorm<NP, true>; PREP(32, 32, 4, EpiDup) PREP(64, 32, kTallNS, EpiDup) }
-  PREP(64, 64, 3, EpiStoreF32)
-#undef PREP
-  if constexpr (NP == 2) {   // the folded cross-attention query projection's dual launches (decoder_layers)
-#define PREP2(BM1, BN1, NS1, E1, BM2, BN2, NS2, E2) \
-    if ((r = gemm_h16_dual_prepare<NP, BM1, BN1, NS1, E1, BM2, BN2, NS2, E2>()) != hipSuccess) e = r;
-    PREP2(64, 96, 3, EpiQKV<NP>, 64, 96, 3, EpiStoreF32) PREP2(64, 64, 3, EpiQKV<NP>, 64, 64, 3, EpiStoreF32)
-    using EpiRN = EpiResidualNorm<NP>; using EpiDup = EpiResidualNorm<NP, true>; using EpiAdd = EpiAddStoreH16<NP>;
-    PREP2(64, 32, kTallNS, EpiRN, 32, 96, 4, EpiAdd) PREP2(32, 32, 4, EpiRN, 32, 96, 4, EpiAdd)
-    PREP2(64, 32, kTallNS, EpiRN, 32, 32, 4, EpiAdd) PREP2(32, 32, 4, EpiRN, 32, 32, 4, EpiAdd)
-    PREP2(64, 32, kTallNS, EpiDup, 32, 96, 4, EpiAdd) PREP2(32, 32, 4, EpiDup, 32, 96, 4, EpiAdd)
-    PREP2(64, 32, kTallNS, EpiDup, 32, 32, 4, EpiAdd) PREP2(32, 32, 4, EpiDup, 32, 32, 4, EpiAdd)
-    {
-      using EpiY2 = EpiResidualNorm<NP, false, true>;
-      if ((r = gemm_h16_dma_prepare<NP, 32, kWide48, 4, EpiY2>()) != hipSuccess) e = r;
-      if ((r = gemm_h16_dma_prepare<NP, 32, 32, 4, EpiY2>()) != hipSuccess) e = r;
-      if ((r = gemm_h16_dma_prepare<NP, 64, 32, kTallNS, EpiY2>()) != hipSuccess) e = r;
-    }
-#undef PREP2
-  }
-  return e;
 }
 
 template <int NP>
@@ -648,8 +671,7 @@ void attention(Ctx& c, int kc, const Planes& q, int ldq, const h16_t* const k[2]
   // a key-split cross-attention merges its partials inside the launch (attention.h attention_inlaunch_merge)
   p.tickets = (kc == KC_ATTN_CROSS && ksplit > 1 && c.m->merge_in_launch) ? c.m->att_tickets : nullptr;
   c.begin(kc);
-  hipError_t e = launch_attention<NP>(p, heads, segs, c.s);
-  if (e != hipSuccess && c.err == hipSuccess) c.err = e;
+  c.latch(launch_attention<NP>(p, heads, segs, c.s));
   c.end(kc);
   if (c.m->prof.on && ksplit > 1 && p.tickets == nullptr) c.m->prof.launches[kc] += 1;  // + attention_merge_kernel
 }
@@ -660,8 +682,7 @@ void gemm32(Ctx& c, int kc, const float* A, int lda, const float* B, int ldb, in
   GemmF32Params p;
   p.A = A; p.B = B; p.lda = lda; p.ldb = ldb; p.M = M; p.N = N; p.K = K;
   c.begin(kc);
-  hipError_t e = launch_gemm_f32(p, epi, c.s);
-  if (e != hipSuccess && c.err == hipSuccess) c.err = e;
+  c.latch(launch_gemm_f32(p, epi, c.s));
   c.end(kc);
 }
 
@@ -1143,12 +1164,11 @@ void decoder_layers(Ctx& c, int batch, int P, bool cond0, bool dedup0 = false) {
       if constexpr (NP == 2) {
         if (fold) {   // + (x0 (.) gamma_cross) . Wq on the launch's idle CUs, left in float32 for the attention-out launch
           const TileShape tq = pick_tile<NP, TK_QKV>(Ms, 3 * J, eq.v_start);
-          const GemmParams p1 = gp_launch<NP>(c, KC_GEMM_QKV, y, D, w.self.wqkv, D, Ms, 3 * J, D, 64, &pf);
-          const GemmParams p2 = gp_launch<NP>(c, KC_GEMM_QKV, m->xg, D, w.wq_fold, D, BT, nq, D, 64);
+          const GemmParams p1 = gp_launch<NP>(c, KC_GEMM_QKV, y, D, w.self.wqkv, D, Ms, 3 * J, D, tq.bm, &pf);
+          const GemmParams p2 = gp_launch<NP>(c, KC_GEMM_QKV, m->xg, D, w.wq_fold, D, BT, nq, D, tq.bm);
           EpiStoreF32 ef;
           ef.out = m->qp; ef.ldc = nq;
-          if (tq.bn == 96) gemm_dual_t<NP, 64, 96, 3, 64, 96, 3>(c, KC_GEMM_QKV, p1, eq, p2, ef);
-          else gemm_dual_t<NP, 64, 64, wide_ns(NP), 64, 64, wide_ns(NP)>(c, KC_GEMM_QKV, p1, eq, p2, ef);
+          gemm_dual<FoldQkvTiles>(c, KC_GEMM_QKV, tq, p1, eq, tq, p2, ef);
           launched = true;
         }
       }
@@ -1172,22 +1192,16 @@ void decoder_layers(Ctx& c, int batch, int P, bool cond0, bool dedup0 = false) {
     auto attn_out_folded = [&](const auto& epi1, int M1) {
       if constexpr (NP == 2) {
         TileShape t1 = pick_tile<NP, TK_TALL>(M1, D, 0, true, J);
-        const bool wide2 = nq % 96 == 0;
+        const TileShape t2 = {kNarrowTile, nq % 96 == 0 ? 96 : kNarrowTile};
         // the launch should stay within ONE round of the chip: 32 x 32 tiles that fill it by themselves (the small model:
         // 256 blocks) leave no CU for the second problem -- 64 x 32 then (half the blocks)
         if (t1.bm == kNarrowTile && M1 % 64 == 0 &&
-            (M1 / 32) * (D / 32) + (BT / 32) * (nq / (wide2 ? 96 : 32)) > 256) t1 = {64, kNarrowTile};
+            (M1 / 32) * (D / 32) + (BT / 32) * (nq / t2.bn) > 256) t1 = {64, kNarrowTile};
         const GemmParams p1 = gp_launch<NP>(c, KC_GEMM_ATTN_OUT, ao, J, w.self.wo, J, M1, D, J, t1.bm, pf_out);
-        const GemmParams p2 = gp_launch<NP>(c, KC_GEMM_ATTN_OUT, ao, J, w.w2_fold, J, BT, nq, J, kNarrowTile);
+        const GemmParams p2 = gp_launch<NP>(c, KC_GEMM_ATTN_OUT, ao, J, w.w2_fold, J, BT, nq, J, t2.bm);
         EpiAddStoreH16<NP> ea;
         ea.out[0] = m->cq.p[0]; ea.out[1] = m->cq.p[NP - 1]; ea.ldc = nq; ea.addend = m->qp; ea.ld_add = nq;
-        if (t1.bm == 64) {
-          if (wide2) gemm_dual_t<NP, 64, kNarrowTile, kTallNS, 32, 96, 4>(c, KC_GEMM_ATTN_OUT, p1, epi1, p2, ea);
-          else gemm_dual_t<NP, 64, kNarrowTile, kTallNS, 32, 32, 4>(c, KC_GEMM_ATTN_OUT, p1, epi1, p2, ea);
-        } else {
-          if (wide2) gemm_dual_t<NP, kNarrowTile, kNarrowTile, 4, 32, 96, 4>(c, KC_GEMM_ATTN_OUT, p1, epi1, p2, ea);
-          else gemm_dual_t<NP, kNarrowTile, kNarrowTile, 4, 32, 32, 4>(c, KC_GEMM_ATTN_OUT, p1, epi1, p2, ea);
-        }
+        gemm_dual<FoldOutTiles>(c, KC_GEMM_ATTN_OUT, t1, p1, epi1, t2, p2, ea);
       }
     };
     // out-projection + residual; produces y for the cross-attention norm (conditional rows:
@@ -1261,9 +1275,8 @@ void decoder_layers(Ctx& c, int batch, int P, bool cond0, bool dedup0 = false) {
     eg.out[0] = gb.p[0]; eg.out[1] = gb.p[NP - 1]; eg.ldc = F;
     eg.rsc = rowscale(m->d_bw_mlp + (size_t)l * 2 * F, m->Ld * 2 * F);
     EpiResidualNorm<NP> eo = er;
-    const bool last = last_layer;
-    eo.g_lo = eo.g_hi = last ? m->dec_final_ln : g_tab(2 * (l + 1));  // decoder_norm has no FiLM
-    eo.g_lo_stride = eo.g_hi_stride = last ? 0 : slots * D;
+    eo.g_lo = eo.g_hi = last_layer ? m->dec_final_ln : g_tab(2 * (l + 1));  // decoder_norm has no FiLM
+    eo.g_lo_stride = eo.g_hi_stride = last_layer ? 0 : slots * D;
     eo.split_row = 0;
     {
       const WeightPrefetch pf_out = prefetch_of<NP>(m, w.mlp.wo, D, F);
@@ -1272,10 +1285,12 @@ void decoder_layers(Ctx& c, int batch, int P, bool cond0, bool dedup0 = false) {
       // (and its stacked Wq sits right behind Wq|Wk|Wv: one prefetch target)
       const bool fold_next = !last_layer && fold_cross_q<NP>(m, batch, P, cond0, false);
       WeightPrefetch pf_qkv = last_layer ? WeightPrefetch() : prefetch_of<NP>(m, m->dec[l + 1].self.wqkv, 3 * J + (fold_next ? nq : 0), D);
-      if (fold_next)
-        gemm<NP, TK_TALL>(c, KC_GEMM_MLP_OUT, gb, F, w.mlp.wo, F, M, D, F, with_y2<NP>(eo, m->xg, m->dec[l + 1].ln_cross, BT), 0, &pf_qkv);
-      else
-      gemm<NP, TK_TALL>(c, KC_GEMM_MLP_OUT, gb, F, w.mlp.wo, F, M, D, F, eo, 0, &pf_qkv);
+      if (fold_next) {
+        if constexpr (NP == 2)   // (the fold exists in the two-plane modes only: no single-plane Y2 kernels)
+          gemm<NP, TK_TALL>(c, KC_GEMM_MLP_OUT, gb, F, w.mlp.wo, F, M, D, F, with_y2<NP>(eo, m->xg, m->dec[l + 1].ln_cross, BT), 0, &pf_qkv);
+      } else {
+        gemm<NP, TK_TALL>(c, KC_GEMM_MLP_OUT, gb, F, w.mlp.wo, F, M, D, F, eo, 0, &pf_qkv);
+      }
     }
   }
   // decoder_norm + spec_out_dense (network.py:445-456).  The reference keeps this
@@ -1793,7 +1808,6 @@ int msd_sample_rng(msd_model* m, int batch, int rng, uint64_t seed, uint64_t str
     s = m->own_stream;
   }
   const int64_t n = (int64_t)batch * m->T * m->ND;
-  const bool ddpm = m->cfg.sampler == MSD_SAMPLER_DDPM;
   if (int rc0 = arm_range(m, s)) return rc0;
   if (init_z_dev) {
     HIP_TRY(m, hipMemcpyAsync(m->z, init_z_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1813,7 +1827,6 @@ int msd_sample_rng(msd_model* m, int batch, int rng, uint64_t seed, uint64_t str
   uint32_t key[kRngWords];
   fill_rng_key(key, rng, seed, stream_id);
   HIP_TRY(m, hipMemcpyAsync(m->d_rng_key, key, sizeof(key), hipMemcpyHostToDevice, s));
-  (void)ddpm;
   // arrival counters of the in-launch merge: zero between launches by construction (the reducer resets its own); once
   // per call in case an aborted launch left a count behind
   HIP_TRY(m, hipMemsetAsync(m->att_tickets, 0, (size_t)m->att_ticket_count * sizeof(int), s));
