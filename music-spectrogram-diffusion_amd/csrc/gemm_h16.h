@@ -926,8 +926,8 @@ __device__ __forceinline__ void gain8(const float (&v)[8], float4 g0, float4 g1,
 // Y2 (the folded cross-attention query projection, msd_api.hip decoder_layers / DESIGN.md 5 S6): rows < y2_rows are ALSO
 // written as y2 = x (.) g2 -- g2 = the next cross-attention norm's plain scale, not step-indexed -- the A operand of the
 // half of that projection which does not wait for the self-attention block (narrow tiles only).
-template <int NP, bool DUP = false, bool Y2 = false>
-struct EpiResidualNorm {
+// The three forms take the same arguments (ResidualNormArgs): the host converts one form into another by assigning the base.
+struct ResidualNormArgs {
   float* x;
   int ldx;
   h16_t* y[2];
@@ -941,6 +941,9 @@ struct EpiResidualNorm {
   h16_t* y2[2] = {nullptr, nullptr};   // Y2 only
   const float* g2 = nullptr;
   int y2_rows = 0;
+};
+template <int NP, bool DUP = false, bool Y2 = false>
+struct EpiResidualNorm : ResidualNormArgs {
   // aux layout (BN == 32 or 48): [x tile BM x BN fp32][g_lo slice, 1 KiB][g_hi slice, 1 KiB][Y2: g2 slice, 1 KiB]
   template <int BN> static constexpr bool narrow() { return BN == 32 || BN == 48; }
   template <int BM, int BN> static constexpr int aux_bytes() { return narrow<BN>() ? BM * BN * 4 + 2048 + (Y2 ? 1024 : 0) : 0; }
@@ -1029,7 +1032,7 @@ struct EpiResidualNorm {
     static_assert(BN % 32 == 0, "partial sums of squares are per 32-column group (tiles = D / 32)");
     static_assert(!Y2 || !DUP, "the duplicating form never feeds a folded query projection");
     // (Y2 on a tile wider than 32 columns -- the batched path's -- writes no second pair: the launcher folds the query
-    // projection only where the producer runs on narrow tiles, msd_api.hip fold_cross_q)
+    // projection only where the producer runs on narrow tiles, msd_api.hip plan_step)
     const bool pre = BN == 32 && aux_present(aux);
     const int step = pre ? 0 : *step_ptr;
     RangeCheck rc;

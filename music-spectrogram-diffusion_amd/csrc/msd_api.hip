@@ -84,6 +84,45 @@ struct EncoderW {
   const float* final_ln = nullptr;
 };
 
+struct TileShape { int bm, bn; };   // a GEMM tile, BM x BN (pick_tile)
+
+// ---- the step plan -------------------------------------------------------------------------------------------------
+// Everything one decoder evaluation decides about its launches, computed ONCE by plan_step and handed to in_proj and the
+// blocks of decoder_layers: a launch and whoever produces its operands or warms its weights read the same value.
+// P passes of `batch` songs: rows [0, BT) are the conditional pass when `cond0`, rows [BT, 2 BT) the unconditional one.
+enum WarmTarget { WARM_CROSS_Q = 0, WARM_CROSS_OUT, WARM_MLP_IN };
+struct StepPlan {
+  int batch, P;
+  // The self-attention block of layer 0 ([0]) and of layers >= 1 ([1]).  They differ under S5 (`dup`; a CFG step whose
+  // input projection wrote pass 0 only): up to layer 0's first cross-attention both passes hold the same rows (same z,
+  // same FiLM, same self-attention: models.py:373-386, network.py:174-193), so layer 0's QKV / self-attention /
+  // attention-out run on BT rows and the attention-out epilogue writes every row twice (gemm_h16.h
+  // EpiResidualNorm<NP, true>).  Exact: bit-identical to the 2 BT-row form.
+  struct SelfBlock {
+    int Ms, Ps;                 // rows and passes the block runs on (dup: BT, 1)
+    TileShape qkv, out, out2;   // fold only: the tile of the QKV launch (both problems), of attention-out's two problems
+    int warms;                  // WarmTarget: the first projection behind the block; the block warms its weights ...
+    bool warm_on_out;           // ... from the attention-out launch -- the self-attention runs 128-row blocks, which
+                                // have no prefetch wave -- and not from the self-attention
+    bool qb4;                   // the self-attention runs 128-row blocks (more than one round of 64-row blocks: from 3
+                                // songs per handle when it carries both passes of a CFG step, from 6 on one pass's rows)
+    bool dup;
+    bool fold;                  // S6: the cross-attention query projection rides on the QKV and attention-out launches
+  } self[2];
+  const SelfBlock& of(int layer) const { return self[layer > 0]; }
+  // cross-attention module e (conditional passes only): its key split; whether that makes more than one round of
+  // 64-row blocks.  MLP-in's weights ride on the last module's attention launch -- unless that one runs 16 compute waves
+  // per block (128-row blocks at batch: no room for a prefetch wave); its output projection carries them then.
+  // (A folded layer's launch stays on 64-row blocks whatever `cross_qb4` says -- attention.h: no 128-row kernel for
+  // un-normalised queries -- and its output projection still carries the target: a single pass of 4 songs.)
+  int ks[2];
+  bool cross_qb4[2];
+  bool cond0, mlp_in_on_cross_out;
+};
+// Captured step graphs are looked up by comparing plans bytewise (msd_sample_rng)
+static_assert(std::has_unique_object_representations<StepPlan>::value, "StepPlan must not have padding bytes: group its bools in fours");
+
+
 struct Profiler {
   bool on = false;
   hipEvent_t e0 = nullptr, e1 = nullptr;
@@ -153,9 +192,11 @@ struct msd_model {
   int *d_tokens = nullptr, *d_pos = nullptr, *d_nkeys_enc = nullptr;
   float *ctx_scaled = nullptr, *ctx_full = nullptr;
 
-  // instantiated step graphs, one set per (batch, key split of each cross-attention module): the split is chosen per
-  // msd_encode from the segment's key count (cross_split), and a graph bakes its grids in
-  struct StepGraphs { int batch = 0, ks[2] = {0, 0}; hipGraphExec_t exec = nullptr, exec1 = nullptr; };
+  // instantiated step graphs, one set per step plan -- a graph bakes its launches and their grids in.  Invariant: the
+  // plan of a CFG step is a function of the handle's constants, the batch and the key counts msd_encode saw (they choose
+  // the cross-attention's key splits, cross_split), and the launch sequence of a step is a function of the handle's
+  // constants and the plan: equal plans, same graph.
+  struct StepGraphs { StepPlan plan; hipGraphExec_t exec = nullptr, exec1 = nullptr; };
   std::vector<StepGraphs> graphs;
   int graph_steps = 8;              // DDPM steps per graph launch (msd_config.graph_steps; 1 -> 4 -> 10: 1.2000 -> 1.1963 -> 1.1955 ms/step)
   bool prefetch = true;        // producers warm the next GEMM's weights (msd_config.weight_prefetch; default: by model size)
@@ -387,9 +428,9 @@ void set_xcd_grid(GemmParams& p, int M, int BM) {
 // launch parameters of one GEMM problem on tiles of BM rows: operands, the weight prefetch it carries, range flag, XCD grid
 template <int NP>
 GemmParams gp_launch(Ctx& c, int kc, const Planes& a, int lda, const Planes& b, int ldb, int M, int N, int K, int BM,
-                     const WeightPrefetch* pf = nullptr) {
+                     const WeightPrefetch& pf = WeightPrefetch()) {
   GemmParams p = gp<NP>(a, lda, b, ldb, M, N, K);
-  if (pf) p.pf = *pf;
+  p.pf = pf;
   p.sat = c.m->d_sat; p.sat_tag = (unsigned)kc + 1u;
   set_xcd_grid(p, M, BM);
   return p;
@@ -416,7 +457,6 @@ template <> struct epi_takes_48<EpiResidualNorm<2, false, true>> : std::true_typ
 
 // The tile a GEMM of kind TK runs on, (BM, BN): ONE rule for the launch below and for whoever prefetches that
 // launch's weights (the prefetcher needs the consumer's column tile and XCD grid).
-struct TileShape { int bm, bn; };
 constexpr int kWide48 = 48;
 template <int NP, int TK>
 TileShape pick_tile(int M, int N, int align, bool wide48 = false, int K = 0) {
@@ -565,6 +605,16 @@ hipError_t prepare_gemms() {
   else return prepare_sites<NP>(GemmSites<NP>{});
 }
 
+// opt in to > 64 KiB dynamic LDS once, outside any stream capture (msd_create).  Defined AHEAD of every other function that
+// names a GEMM or attention kernel: the compiler emits kernels in the order they are first named, and the code of
+// gemm_h16_dma_kernel<2, 128, 96, 2, EpiQKV<2>> was seen to differ (equivalent address arithmetic) with its place in the module
+void set_func_attrs() {
+  (void)attention_prepare<1, 3>();
+  (void)attention_prepare<2, 2>();
+  (void)prepare_gemms<1>();
+  (void)prepare_gemms<2>();
+}
+
 // launches p on the list's tile of shape t; the last entry is the fall-back
 template <int NP, class Epi, class T0, class... T>
 void gemm_on(List<T0, T...>, TileShape t, Ctx& c, int kc, const GemmParams& p, const Epi& epi) {
@@ -576,7 +626,7 @@ void gemm_on(List<T0, T...>, TileShape t, Ctx& c, int kc, const GemmParams& p, c
 
 template <int NP, int TK, class Epi>
 void gemm(Ctx& c, int kc, const Planes& a, int lda, const Planes& b, int ldb, int M, int N, int K,
-          const Epi& epi, int align = 0, const WeightPrefetch* pf = nullptr) {
+          const Epi& epi, int align = 0, const WeightPrefetch& pf = WeightPrefetch()) {
   static_assert(in_list<Site<TK, Epi>>(GemmSites<NP>{}), "a new launch site: add it to GemmSites, or its kernels are never prepared");
   const TileShape t = pick_tile<NP, TK>(M, N, align, epi_takes_48<Epi>::value, K);
   gemm_on<NP>(TileTable<NP, TK, Epi>{}, t, c, kc, gp_launch<NP>(c, kc, a, lda, b, ldb, M, N, K, t.bm, pf), epi);
@@ -614,6 +664,65 @@ WeightPrefetch prefetch_of(const msd_model* m, const Planes& w, int N, int K) {
   return pf;
 }
 
+// ---- operands and epilogues: one builder each ---------------------------------------------------------------------
+// Two single-plane conventions, kept apart: OPERAND planes at an element offset keep p[1] == nullptr when NP == 1
+// (planes_at); the OUTPUT pair of an epilogue aliases plane 0 then (out_pair).
+template <int NP>
+Planes planes_at(const Planes& base, size_t off) { return {{base.p[0] + off, NP == 2 ? base.p[1] + off : nullptr}}; }
+template <int NP>
+void out_pair(h16_t* (&dst)[2], const Planes& pl) { dst[0] = pl.p[0]; dst[1] = pl.p[NP - 1]; }
+
+// rstd of the folded norm from the `tiles` partial sums of squares per row (+ the step-indexed bias.W row)
+RowScale row_scale(const float* ssq, int tiles, const int* step_ptr, const float* bias = nullptr, int bias_step_stride = 0) {
+  RowScale r;
+  r.ssq = ssq; r.tiles = tiles; r.inv_d = 1.0f / (float)(tiles * kNarrowTile); r.bias = bias; r.bias_step_stride = bias_step_stride;
+  r.step_ptr = step_ptr;
+  return r;
+}
+// fused q|k|v (or k|v) projection: columns [0, ld_qk) row-major into `qk`, the rest as V^T [seg][vt_rows][seg_len] into `vt`
+template <int NP>
+EpiQKV<NP> epi_qkv(const Planes& qk, const Planes& vt, int ld_qk, int seg_len, int vt_rows, const RowScale& rsc = RowScale()) {
+  EpiQKV<NP> e;
+  out_pair<NP>(e.qk, qk); out_pair<NP>(e.vt, vt);
+  e.ld_qk = ld_qk; e.v_start = ld_qk; e.seg_len = seg_len; e.vt_ld = seg_len; e.vt_rows = vt_rows; e.rsc = rsc;
+  return e;
+}
+// the epilogues that store C as planes [M, ldc]: Epi = EpiStoreH16, EpiGeglu (ldc = F) ... or as float32
+template <template <int> class Epi, int NP>
+Epi<NP> epi_out(const Planes& out, int ldc, const RowScale& rsc = RowScale()) {
+  Epi<NP> e;
+  out_pair<NP>(e.out, out); e.ldc = ldc; e.rsc = rsc;
+  return e;
+}
+EpiStoreF32 epi_store_f32(float* out, int ldc, const RowScale& rsc = RowScale()) { return {out, ldc, rsc}; }
+// x += acc, partial sums of squares into `ssq`, y = x (.) g: `lo` for rows < split_row, `hi` from there.  A gain is a
+// table base + its stride between steps (0: not step-indexed); a null base writes no y for its rows.
+struct Gain { const float* g = nullptr; int step_stride = 0; };
+template <int NP>
+EpiResidualNorm<NP> epi_residual_norm(float* x, int D, const Planes& y, float* ssq, const int* step_ptr, Gain lo, Gain hi,
+                                      int split_row) {
+  EpiResidualNorm<NP> e;
+  e.x = x; e.ldx = D; out_pair<NP>(e.y, y); e.ssq = ssq; e.tiles = D / kNarrowTile; e.step_ptr = step_ptr;
+  e.g_lo = lo.g; e.g_lo_stride = lo.step_stride; e.g_hi = hi.g; e.g_hi_stride = hi.step_stride; e.split_row = split_row;
+  return e;
+}
+// ... and its DUP / Y2 forms (gemm_h16.h): the same arguments; the caller sets dup_rows or y2 / g2 / y2_rows
+template <bool DUP, bool Y2, int NP>
+EpiResidualNorm<NP, DUP, Y2> residual_form(const EpiResidualNorm<NP>& e) {
+  EpiResidualNorm<NP, DUP, Y2> o;
+  static_cast<ResidualNormArgs&>(o) = e;
+  return o;
+}
+
+// fp32 -> operand planes / back (a single-plane operand has p[1] == nullptr)
+void split(const float* in, const Planes& out, int64_t n, hipStream_t s, unsigned* sat = nullptr, unsigned sat_tag = 1u) {
+  hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, out.p[0], out.p[1], n, sat, sat_tag);
+}
+void merge(const Planes& pl, float* out, int64_t n, hipStream_t s) {
+  hipLaunchKernelGGL(merge_planes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s,
+                     (const h16_t*)pl.p[0], (const h16_t*)pl.p[1], out, n);
+}
+
 template <int NP>
 void norm(Ctx& c, const float* x, const float* gamma, int rows, int D, const float* film,
           int slots, int slot, const Planes* out, float* out_f32) {
@@ -637,23 +746,30 @@ void norm(Ctx& c, const float* x, const float* gamma, int rows, int D, const flo
   c.end(KC_NORM);
 }
 
+// The memory side of an attention launch: K rows and V^T of every segment, and the segments' valid key counts
+struct AttnKV {
+  Planes k; int ldk; size_t k_seg_stride; int k_rows;
+  Planes vt; int vt_ld; size_t vt_seg_stride; int vt_cols;   // vt_cols: AttnParams::vt_cols (0 = vt_ld)
+  const int* n_keys;
+};
+
+// `qb4`: the launch may run on 128-row blocks (attention.h attention_query_blocks) -- such a launch has no prefetch wave,
+// so its caller carries no weight target on it (StepPlan)
 template <int NP>
-void attention(Ctx& c, int kc, const Planes& q, int ldq, const h16_t* const k[2], int ldk,
-               size_t k_seg_stride, int k_rows, const Planes& vt, int vt_ld, size_t vt_seg_stride,
-               const Planes& o, int ldo, const int* n_keys, int q_rows_per_seg, int heads,
-               int segs, int ksplit = 1, int vt_cols = 0, const WeightPrefetch* pf = nullptr, int qp = -1,
-               const float* q_ssq = nullptr) {
+void attention(Ctx& c, int kc, const Planes& q, int ldq, const AttnKV& kv, const Planes& o, int ldo, int q_rows_per_seg,
+               int heads, int segs, int ksplit = 1, const WeightPrefetch& pf = WeightPrefetch(), bool qb4 = false,
+               int qp = -1, const float* q_ssq = nullptr) {
   AttnParams p;
   for (int i = 0; i < 2; ++i) {
     const int j = i < NP ? i : 0;
-    p.q[i] = q.p[j]; p.k[i] = k[j]; p.vt[i] = vt.p[j]; p.o[i] = o.p[j];
+    p.q[i] = q.p[j]; p.k[i] = kv.k.p[j]; p.vt[i] = kv.vt.p[j]; p.o[i] = o.p[j];
   }
-  p.n_keys = n_keys; p.ldq = ldq; p.ldk = ldk; p.ldo = ldo; p.vt_ld = vt_ld;
-  p.q_rows_per_seg = q_rows_per_seg; p.k_seg_stride = k_seg_stride;
-  p.vt_seg_stride = vt_seg_stride; p.k_rows = k_rows; p.vt_cols = vt_cols;
+  p.n_keys = kv.n_keys; p.ldq = ldq; p.ldk = kv.ldk; p.ldo = ldo; p.vt_ld = kv.vt_ld;
+  p.q_rows_per_seg = q_rows_per_seg; p.k_seg_stride = kv.k_seg_stride;
+  p.vt_seg_stride = kv.vt_seg_stride; p.k_rows = kv.k_rows; p.vt_cols = kv.vt_cols;
   p.ksplit = ksplit; p.part_o = c.m->att_part_o; p.part_ml = c.m->att_part_ml;
   p.total_rows = q_rows_per_seg * segs;
-  if (pf) p.pf = *pf;
+  p.pf = pf;
   p.sat = c.m->d_sat; p.sat_tag = (unsigned)kc + 1u;
   p.qp = qp >= 0 ? qp : (kc == KC_ATTN_SELF ? c.m->att_qp_self : (kc == KC_ATTN_CROSS ? c.m->att_qp_cross : 0));
   // un-normalised queries (the folded cross-attention query projection): 1/rms from the residual stream's partial sums
@@ -665,9 +781,7 @@ void attention(Ctx& c, int kc, const Planes& q, int ldq, const h16_t* const k[2]
   // requests -- so the library turns it on for one song only, whatever msd_config.kv_touch_ahead asks for beyond that.
   p.touch_ahead = (kc == KC_ATTN_CROSS && segs == 1) ? c.m->kv_touch_ahead : 0;
   p.pf_late = 1;   // (such a launch's prefetch wave holds its touches back until the block's first stage has landed: attention.h)
-  // 128-row blocks (attention.h attention_query_blocks) for the DECODER's attentions at batch: the cross-attention, and
-  // the self-attention when its caller has taken the weight target off the launch (an empty, non-null prefetch)
-  p.allow_qb4 = kc == KC_ATTN_CROSS || (kc == KC_ATTN_SELF && pf != nullptr && pf->n == 0);
+  p.allow_qb4 = qb4;
   // a key-split cross-attention merges its partials inside the launch (attention.h attention_inlaunch_merge)
   p.tickets = (kc == KC_ATTN_CROSS && ksplit > 1 && c.m->merge_in_launch) ? c.m->att_tickets : nullptr;
   c.begin(kc);
@@ -910,19 +1024,13 @@ void encoder_stack(Ctx& c, const EncoderW& w, int rows, int n_valid_slot) {
   for (size_t l = 0; l < w.layers.size(); ++l) {
     const EncLayerW& lw = w.layers[l];
     norm<NP>(c, m->ex, lw.ln_attn, rows, D, nullptr, 0, 0, &m->eh, nullptr);
-    EpiQKV<NP> eq;
-    eq.qk[0] = m->eqk.p[0]; eq.qk[1] = m->eqk.p[NP - 1];
-    eq.vt[0] = m->evt.p[0]; eq.vt[1] = m->evt.p[NP - 1];
-    eq.ld_qk = 2 * J; eq.v_start = 2 * J; eq.seg_len = m->Lenc_pad; eq.vt_ld = m->Lenc_pad; eq.vt_rows = J;
+    const EpiQKV<NP> eq = epi_qkv<NP>(m->eqk, m->evt, 2 * J, m->Lenc_pad, J);
     gemm<NP, TK_QKV>(c, KC_GEMM_QKV, m->eh, D, lw.attn.wqkv, D, rows, 3 * J, D, eq, eq.v_start);
-    const h16_t* kp[2] = {m->eqk.p[0] + J, m->eqk.p[NP - 1] + J};
-    attention<NP>(c, KC_ATTN_SELF, m->eqk, 2 * J, kp, 2 * J, 0, m->Lenc_pad, m->evt, m->Lenc_pad, 0, m->eao, J,
-                  m->d_nkeys_enc + n_valid_slot, rows, m->H, 1, 1, 0, nullptr, /*qp=*/0);
+    const AttnKV kv = {planes_at<NP>(m->eqk, J), 2 * J, 0, m->Lenc_pad, m->evt, m->Lenc_pad, 0, 0, m->d_nkeys_enc + n_valid_slot};
+    attention<NP>(c, KC_ATTN_SELF, m->eqk, 2 * J, kv, m->eao, J, rows, m->H, 1, 1, WeightPrefetch(), false, /*qp=*/0);
     gemm<NP, TK_SQUARE>(c, KC_GEMM_ATTN_OUT, m->eao, J, lw.attn.wo, J, rows, D, J, EpiResidual{m->ex, D});
     norm<NP>(c, m->ex, lw.ln_mlp, rows, D, nullptr, 0, 0, &m->eh, nullptr);
-    EpiGeglu<NP> eg;
-    eg.out[0] = m->eg.p[0]; eg.out[1] = m->eg.p[NP - 1]; eg.ldc = F;
-    gemm<NP, TK_MLP_IN>(c, KC_GEMM_MLP_IN, m->eh, D, lw.mlp.wi, D, rows, 2 * F, D, eg);
+    gemm<NP, TK_MLP_IN>(c, KC_GEMM_MLP_IN, m->eh, D, lw.mlp.wi, D, rows, 2 * F, D, epi_out<EpiGeglu, NP>(m->eg, F));
     gemm<NP, TK_TALL>(c, KC_GEMM_MLP_OUT, m->eg, F, lw.mlp.wo, F, rows, D, F, EpiResidual{m->ex, D});
   }
 }
@@ -989,12 +1097,10 @@ int encode_impl(msd_model* m, int batch, const int32_t* tokens_h, const float* c
         hipLaunchKernelGGL(gather_rows_kernel, dim3(rows), dim3(256), 0, s, m->ctx_full, m->d_pos, Cv,
                            m->ex, D);
         encoder_stack<NP>(c, m->ctx_enc, rows, 1);
-        Planes enc_ctx;
         // concat_encodings: right behind the valid tokens (one compact key axis); sum_cross_attends: its own
         // key region at a fixed offset
         const size_t ctx_row = m->n_cross == 2 ? (size_t)m->key_off[1] : (size_t)Lv;
-        enc_ctx.p[0] = m->enc.p[0] + ctx_row * D;
-        enc_ctx.p[1] = NP == 2 ? m->enc.p[1] + ctx_row * D : nullptr;
+        const Planes enc_ctx = planes_at<NP>(m->enc, ctx_row * D);
         norm<NP>(c, m->ex, m->ctx_enc.final_ln, rows, D, nullptr, 0, 0, &enc_ctx, nullptr);
         HIP_TRY(m, hipStreamSynchronize(s));
       }
@@ -1014,16 +1120,11 @@ int encode_impl(msd_model* m, int batch, const int32_t* tokens_h, const float* c
     for (int l = 0; l < m->Ld; ++l)
       for (int e = 0; e < m->n_cross; ++e) {
         if (reg_rows[e] == 0) continue;   // no valid key: the attention kernel never reads this region
-        EpiQKV<NP> ek;
         const size_t koff = ((size_t)l * m->Bmax + b) * m->S_pad * J;
         const size_t r0 = (size_t)m->key_off[e];
-        ek.qk[0] = m->kc.p[0] + koff + r0 * J; ek.qk[1] = m->kc.p[NP - 1] + koff + r0 * J;
-        ek.vt[0] = m->vtc.p[0] + koff + r0; ek.vt[1] = m->vtc.p[NP - 1] + koff + r0;
-        ek.ld_qk = J; ek.v_start = J; ek.seg_len = m->S_pad; ek.vt_ld = m->S_pad; ek.vt_rows = J;
-        Planes a;
-        a.p[0] = m->enc.p[0] + r0 * D;
-        a.p[1] = NP == 2 ? m->enc.p[1] + r0 * D : nullptr;
-        gemm<NP, TK_QKV>(c, KC_GEMM_QKV, a, D, m->dec[l].wkv_cross[e], D, round_up(reg_rows[e], 64), 2 * J, D, ek, ek.v_start);
+        const EpiQKV<NP> ek = epi_qkv<NP>(planes_at<NP>(m->kc, koff + r0 * J), planes_at<NP>(m->vtc, koff + r0), J, m->S_pad, J);
+        gemm<NP, TK_QKV>(c, KC_GEMM_QKV, planes_at<NP>(m->enc, r0 * D), D, m->dec[l].wkv_cross[e], D, round_up(reg_rows[e], 64),
+                         2 * J, D, ek, ek.v_start);
       }
     for (int e = 0; e < m->n_cross; ++e) m->h_nkeys_cross[(size_t)e * m->Bmax + b] = reg_rows[e];
   }
@@ -1081,268 +1182,245 @@ inline int cross_split(const msd_model* m, int batch, int e) {
   return ks;
 }
 
-// S6 (round 6): does decoder layer `l`'s cross-attention query projection run FOLDED into the QKV and attention-out launches
-// (gemm_h16.h "The folded cross-attention query projection")?  One rule for the layer itself, for the producer of its
-// x (.) gamma_cross planes (the previous layer's MLP output projection / the input projection) and for the prefetch plan.
-// `dup`: the layer's self-attention block runs on one pass's rows (S5, layer 0 of a CFG step).  Two-plane modes, narrow
-// tiles (below the batched path's threshold) and a conditional pass only.
-template <int NP>
-bool fold_cross_q(const msd_model* m, int batch, int P, bool cond0, bool dup) {
-  if constexpr (NP != 2) {
-    return false;
-  } else {
-    const int D = m->D, J = m->J, BT = batch * m->T, M = P * BT, Ms = dup ? BT : M, nq = m->n_cross * J;
-    // (up to two songs per call: at three -- M = 1536, several rounds of blocks per launch -- the fold measured +2.4 %,
-    // profiles/r06g_fold_ab_b3.log; the batched path's 128-row tiles from four songs have no narrow epilogue anyway)
-    if (!m->fold_q || !cond0 || M > 1024 || M >= big_m_threshold() || BT % 64 || D / kNarrowTile > kAuxMaxTiles || D % 128) return false;
-    const TileShape tq = pick_tile<NP, TK_QKV>(Ms, 3 * J, 2 * J);
-    if (tq.bm != 64 || nq % tq.bn) return false;
-    const TileShape to = pick_tile<NP, TK_TALL>(Ms, D, 0, true, J);
-    return to.bn == kNarrowTile;
+// ---- the planner of a step (StepPlan, at the top of this file) -------------------------------------------------------
+// No HIP calls: safe before and during stream capture.
+StepPlan plan_step(const msd_model* m, int batch, int P, bool cond0, bool dedup0) {
+  const int NP = m->NP, D = m->D, J = m->J, T = m->T, BT = batch * T, M = P * BT, nq = m->n_cross * J;
+  StepPlan p = {};
+  p.batch = batch; p.P = P; p.cond0 = cond0;
+  // S6 (round 6): a layer's cross-attention query projection runs FOLDED into its QKV and attention-out launches
+  // (gemm_h16.h "The folded cross-attention query projection") in the two-plane modes (fold_q is off in the others), on
+  // narrow tiles (below the batched path's threshold) and on a conditional pass only.
+  // (up to two songs per call: at three -- M = 1536, several rounds of blocks per launch -- the fold measured +2.4 %,
+  // profiles/r06g_fold_ab_b3.log; the batched path's 128-row tiles from four songs have no narrow epilogue anyway)
+  const bool may_fold = m->fold_q && cond0 && M <= 1024 && M < big_m_threshold() && BT % 64 == 0 &&
+                        D / kNarrowTile <= kAuxMaxTiles && D % 128 == 0;
+  for (int i = 0; i < 2; ++i) {
+    StepPlan::SelfBlock& s = p.self[i];
+    s.dup = dedup0 && i == 0;
+    s.Ms = s.dup ? BT : M; s.Ps = s.dup ? 1 : P;
+    const TileShape tq = pick_tile<2, TK_QKV>(s.Ms, 3 * J, 2 * J), to = pick_tile<2, TK_TALL>(s.Ms, D, 0, true, J);
+    s.fold = may_fold && tq.bm == 64 && nq % tq.bn == 0 && to.bn == kNarrowTile;
+    if (s.fold) {
+      s.qkv = tq; s.out = to; s.out2 = {kNarrowTile, nq % 96 == 0 ? 96 : kNarrowTile};
+      // the attention-out launch should stay within ONE round of the chip: 32 x 32 tiles that fill it by themselves (the
+      // small model: 256 blocks) leave no CU for the second problem -- 64 x 32 then (half the blocks)
+      if (to.bm == kNarrowTile && s.Ms % 64 == 0 && (s.Ms / 32) * (D / 32) + (BT / 32) * (nq / s.out2.bn) > 256) s.out = {64, kNarrowTile};
+    }
+    s.qb4 = attention_query_blocks(m->H * (T / 64) * s.Ps * batch, T, NP) == 4;
+    s.warms = !cond0 ? WARM_MLP_IN : (s.fold ? WARM_CROSS_OUT : WARM_CROSS_Q);
+    s.warm_on_out = s.qb4;
   }
+  for (int e = 0; e < m->n_cross && cond0; ++e) {
+    p.ks[e] = cross_split(m, batch, e);
+    p.cross_qb4[e] = attention_query_blocks(m->H * (T / 64) * p.ks[e] * batch, T, NP) == 4;
+    if (e + 1 == m->n_cross) p.mlp_in_on_cross_out = p.cross_qb4[e];
+  }
+  return p;
+}
+// S5: a CFG step computes layer 0's self-attention block once for both passes
+inline StepPlan plan_cfg_step(const msd_model* m, int batch) {
+  return plan_step(m, batch, m->passes, true, m->passes == 2 && m->dedup_layer0);
 }
 
-template <int NP>
-EpiResidualNorm<NP, false, true> with_y2(const EpiResidualNorm<NP>& e, const Planes& y2, const float* g2, int rows) {
-  EpiResidualNorm<NP, false, true> o;
-  o.x = e.x; o.ldx = e.ldx; o.y[0] = e.y[0]; o.y[1] = e.y[1]; o.ssq = e.ssq; o.tiles = e.tiles;
-  o.g_lo = e.g_lo; o.g_lo_stride = e.g_lo_stride; o.g_hi = e.g_hi; o.g_hi_stride = e.g_hi_stride;
-  o.split_row = e.split_row; o.step_ptr = e.step_ptr; o.dup_rows = e.dup_rows;
-  o.y2[0] = y2.p[0]; o.y2[1] = y2.p[NP - 1]; o.g2 = g2; o.y2_rows = rows;
-  return o;
+// ---- the decoder's tables and buffers, named once -------------------------------------------------------------------
+inline Gain g_tab(const msd_model* m, int slot) { return {m->d_g + (size_t)slot * m->D, 2 * m->Ld * m->D}; }
+inline RowScale dec_row_scale(const msd_model* m, const float* bias = nullptr, int bias_step_stride = 0) {
+  return row_scale(m->ssq, m->D / kNarrowTile, m->d_step, bias, bias_step_stride);
 }
-
 template <int NP>
-void decoder_layers(Ctx& c, int batch, int P, bool cond0, bool dedup0 = false) {
-  // P passes of `batch` songs: rows [0, BT) are the conditional pass when `cond0`, rows [BT, 2 BT) the unconditional one.
-  // `dedup0` (a CFG step: P == 2, cond0; the input projection wrote pass 0 only): S5 -- up to layer 0's first
-  // cross-attention both passes hold the same rows (same z, same FiLM, same self-attention: models.py:373-386,
-  // network.py:174-193), so layer 0's QKV / self-attention / attention-out run on BT rows and the attention-out
-  // epilogue writes every row twice (gemm_h16.h EpiResidualNorm<NP, true>).  Exact: bit-identical to the 2 BT-row form.
+EpiResidualNorm<NP> dec_residual(const msd_model* m, Gain lo, Gain hi, int split_row) {
+  return epi_residual_norm<NP>(m->x, m->D, m->y, m->ssq, m->d_step, lo, hi, split_row);
+}
+template <int NP>
+WeightPrefetch mlp_in_weights(const msd_model* m, int l) { return prefetch_of<NP>(m, m->dec[l].mlp.wi, 2 * m->F, m->D); }
+
+// Weight prefetch plan of a layer (gemm_h16.h WeightPrefetch; every producer warms a LATER GEMM's weights from a
+// wave of its own): QKV -> attention-out . self-attention -> cross-q (or MLP-in on an unconditional pass) .
+// cross-q -> cross-out . cross-attention -> MLP-in . MLP-in -> MLP-out . MLP-out -> next layer's QKV; the exceptions are
+// StepPlan's warms / warm_on_out / mlp_in_on_cross_out.
+
+// (i) self-attention block (network.py:174-193).  Layer 0 is fed by the input projection; later layers consume
+// the folded-norm planes `y` written by the previous layer's MLP output projection.
+template <int NP>
+void self_attention_block(Ctx& c, const StepPlan& p, int l) {
   msd_model* m = c.m;
-  const int D = m->D, J = m->J, F = m->F, T = m->T;
-  const int BT = batch * T, M = P * BT;
-  const int slots = 2 * m->Ld, tiles = D / kNarrowTile;
-  const Planes &y = m->y, &qk = m->qk, &vts = m->vt, &ao = m->ao, &gb = m->g;
-  float* const x = m->x;
-  float* const ssq = m->ssq;
-  float* const eps = m->eps;
-  const int* const nkeys_self = m->d_nkeys_self;
-  auto rowscale = [&](const float* bias, int stride) {
-    RowScale r;
-    r.ssq = ssq; r.tiles = tiles; r.inv_d = 1.0f / (float)D; r.bias = bias; r.bias_step_stride = stride;
-    r.step_ptr = m->d_step;
-    return r;
-  };
-  auto g_tab = [&](int slot) { return m->d_g + (size_t)slot * D; };  // + step * slots * D in the kernel
-  // fused q|k|v projection of layer l (network.py:181-189 via layers.py:262-264) on the folded-norm planes y
-  auto qkv_epi = [&](int l) {
-    EpiQKV<NP> eq;
-    eq.qk[0] = qk.p[0]; eq.qk[1] = qk.p[NP - 1];
-    eq.vt[0] = vts.p[0]; eq.vt[1] = vts.p[NP - 1];
-    eq.ld_qk = 2 * J; eq.v_start = 2 * J; eq.seg_len = T; eq.vt_ld = T; eq.vt_rows = J;
-    eq.rsc = rowscale(m->d_bw_self + (size_t)l * 3 * J, m->Ld * 3 * J);
-    return eq;
-  };
-  for (int l = 0; l < m->Ld; ++l) {
-    const DecLayerW& w = m->dec[l];
-    // (i) self-attention block (network.py:174-193).  Layer 0 is fed by the input projection; later layers consume
-    // the folded-norm planes `y` written by the previous layer's MLP output projection.
-    // Weight prefetch plan of a layer (gemm_h16.h WeightPrefetch; every producer warms a LATER GEMM's weights from a
-    // wave of its own): QKV -> attention-out . self-attention -> cross-q (or MLP-in on an unconditional pass) .
-    // cross-q -> cross-out . cross-attention -> MLP-in . MLP-in -> MLP-out . MLP-out -> next layer's QKV
-    const bool last_layer = (l + 1 == m->Ld);
-    const bool dup = dedup0 && l == 0;          // this layer's self-attention block runs on one pass's rows
-    const int Ms = dup ? BT : M, Ps = dup ? 1 : P;
-    // S6: this layer's cross-attention query projection is folded into the QKV and attention-out launches
-    const bool fold = fold_cross_q<NP>(m, batch, P, cond0, dup);
-    const int nq = m->n_cross * J;              // the modules' queries, stacked
-    {
-      const EpiQKV<NP> eq = qkv_epi(l);
-      WeightPrefetch pf = prefetch_of<NP>(m, w.self.wo, fold ? D + nq : D, J);   // (folded: + W2, right behind Wo)
-      bool launched = false;
-      if constexpr (NP == 2) {
-        if (fold) {   // + (x0 (.) gamma_cross) . Wq on the launch's idle CUs, left in float32 for the attention-out launch
-          const TileShape tq = pick_tile<NP, TK_QKV>(Ms, 3 * J, eq.v_start);
-          const GemmParams p1 = gp_launch<NP>(c, KC_GEMM_QKV, y, D, w.self.wqkv, D, Ms, 3 * J, D, tq.bm, &pf);
-          const GemmParams p2 = gp_launch<NP>(c, KC_GEMM_QKV, m->xg, D, w.wq_fold, D, BT, nq, D, tq.bm);
-          EpiStoreF32 ef;
-          ef.out = m->qp; ef.ldc = nq;
-          gemm_dual<FoldQkvTiles>(c, KC_GEMM_QKV, tq, p1, eq, tq, p2, ef);
-          launched = true;
-        }
-      }
-      if (!launched) gemm<NP, TK_QKV>(c, KC_GEMM_QKV, y, D, w.self.wqkv, D, Ms, 3 * J, D, eq, eq.v_start, &pf);
-    }
-    const h16_t* kp[2] = {qk.p[0] + J, qk.p[NP - 1] + J};
-    // (a self-attention launch on 128-row blocks -- more than one round of 64-row blocks: from 3 songs per handle when
-    // it carries both passes of a CFG step (layers >= 1), from 6 on one pass's rows -- has no prefetch wave: its weight
-    // target rides on the out-projection below instead)
-    const bool self_qb4 = attention_query_blocks(m->H * (T / 64) * Ps * batch, T, NP) == 4;
-    const WeightPrefetch pf_self = !cond0 ? prefetch_of<NP>(m, w.mlp.wi, 2 * F, D)
-                                          : (fold ? prefetch_of<NP>(m, w.wo_cross[0], D, J) : prefetch_of<NP>(m, w.wq_cross[0], J, D));
-    {
-      const WeightPrefetch none;
-      attention<NP>(c, KC_ATTN_SELF, qk, 2 * J, kp, 2 * J, (size_t)T * 2 * J, T, vts, T,
-                    (size_t)J * T, ao, J, nkeys_self, T, m->H, Ps * batch, 1, 0, self_qb4 ? &none : &pf_self);
-    }
-    const WeightPrefetch* pf_out = self_qb4 ? &pf_self : nullptr;
-    // S6: the output projection and ao . (Wo diag(gamma_cross) Wq_e) in ONE launch -- same A operand; the second problem
-    // adds the half the QKV launch left in `qp` and stores the UN-NORMALISED queries of all modules, [BT, n_cross J]
-    auto attn_out_folded = [&](const auto& epi1, int M1) {
-      if constexpr (NP == 2) {
-        TileShape t1 = pick_tile<NP, TK_TALL>(M1, D, 0, true, J);
-        const TileShape t2 = {kNarrowTile, nq % 96 == 0 ? 96 : kNarrowTile};
-        // the launch should stay within ONE round of the chip: 32 x 32 tiles that fill it by themselves (the small model:
-        // 256 blocks) leave no CU for the second problem -- 64 x 32 then (half the blocks)
-        if (t1.bm == kNarrowTile && M1 % 64 == 0 &&
-            (M1 / 32) * (D / 32) + (BT / 32) * (nq / t2.bn) > 256) t1 = {64, kNarrowTile};
-        const GemmParams p1 = gp_launch<NP>(c, KC_GEMM_ATTN_OUT, ao, J, w.self.wo, J, M1, D, J, t1.bm, pf_out);
-        const GemmParams p2 = gp_launch<NP>(c, KC_GEMM_ATTN_OUT, ao, J, w.w2_fold, J, BT, nq, J, t2.bm);
-        EpiAddStoreH16<NP> ea;
-        ea.out[0] = m->cq.p[0]; ea.out[1] = m->cq.p[NP - 1]; ea.ldc = nq; ea.addend = m->qp; ea.ld_add = nq;
-        gemm_dual<FoldOutTiles>(c, KC_GEMM_ATTN_OUT, t1, p1, epi1, t2, p2, ea);
-      }
-    };
-    // out-projection + residual; produces y for the cross-attention norm (conditional rows:
-    // plain gamma) and for the MLP norm (unconditional rows, which skip cross-attention: S4)
-    EpiResidualNorm<NP> er;
-    er.x = x; er.ldx = D; er.y[0] = y.p[0]; er.y[1] = y.p[NP - 1]; er.ssq = ssq; er.tiles = tiles;
-    er.step_ptr = m->d_step;
-    er.g_lo = cond0 ? w.ln_cross : g_tab(2 * l + 1); er.g_lo_stride = cond0 ? 0 : slots * D;
-    er.g_hi = g_tab(2 * l + 1); er.g_hi_stride = slots * D;
-    er.split_row = cond0 ? BT : 0;
-    if (dup) {   // rows [0, BT) computed once, written as both passes: y[r] for the cross-attention norm, y[r + BT] for the MLP norm
-      EpiResidualNorm<NP, true> ed;
-      ed.x = x; ed.ldx = D; ed.y[0] = y.p[0]; ed.y[1] = y.p[NP - 1]; ed.ssq = ssq; ed.tiles = tiles; ed.step_ptr = m->d_step;
-      ed.g_lo = er.g_lo; ed.g_lo_stride = er.g_lo_stride; ed.g_hi = er.g_hi; ed.g_hi_stride = er.g_hi_stride;
-      ed.split_row = 0; ed.dup_rows = BT;
-      if (fold) attn_out_folded(ed, BT);
-      else gemm<NP, TK_TALL>(c, KC_GEMM_ATTN_OUT, ao, J, w.self.wo, J, BT, D, J, ed, 0, pf_out);
-    } else if (fold) {
-      EpiResidualNorm<NP> ef = er;
-      ef.g_lo = nullptr; ef.g_lo_stride = 0;   // the conditional rows' y = x1 (.) gamma_cross has no reader any more
-      attn_out_folded(ef, M);
-    } else
-    gemm<NP, TK_TALL>(c, KC_GEMM_ATTN_OUT, ao, J, w.self.wo, J, M, D, J, er, 0, pf_out);
-    // (ii) cross-attention block, conditional rows only (S4) (network.py:196-235)
-    if (cond0) {
-      // every module projects its queries from the SAME normed input (network.py:196-198), so all query
-      // projections run before the first output projection rewrites y
-      const size_t loff = (size_t)l * m->Bmax * m->S_pad * J;
-      for (int e = 0; e < m->n_cross && !fold; ++e) {
-        const Planes& cq = e == 0 ? m->cq : m->cq2;
-        EpiStoreH16<NP> es;
-        es.out[0] = cq.p[0]; es.out[1] = cq.p[NP - 1]; es.ldc = J;
-        es.rsc = rowscale(nullptr, 0);
-        const WeightPrefetch pf = prefetch_of<NP>(m, w.wo_cross[e], D, J);
-        gemm<NP, TK_SQUARE>(c, KC_GEMM_CROSS_Q, y, D, w.wq_cross[e], D, BT, J, D, es, 0, &pf);
-      }
-      bool mlp_in_on_cross_out = false;
-      for (int e = 0; e < m->n_cross; ++e) {
-        const size_t r0 = (size_t)m->key_off[e];
-        const h16_t* kc[2] = {m->kc.p[0] + loff + r0 * J, m->kc.p[NP - 1] + loff + r0 * J};
-        Planes vt;
-        vt.p[0] = m->vtc.p[0] + loff + r0;
-        vt.p[1] = NP == 2 ? m->vtc.p[1] + loff + r0 : nullptr;
-        const int region = cross_region(m, e), ks = cross_split(m, batch, e);
-        // MLP-in's weights ride on the last module's attention launch -- unless that runs 16 compute waves per block
-        // (128-row blocks at batch: no room for a prefetch wave); its output projection carries them then
-        const bool qb4 = attention_query_blocks(m->H * (T / 64) * ks * batch, T, NP) == 4;
-        const bool warm_mlp_in = e + 1 == m->n_cross && !qb4;
-        if (e + 1 == m->n_cross && qb4) mlp_in_on_cross_out = true;
-        const WeightPrefetch pf = warm_mlp_in ? prefetch_of<NP>(m, w.mlp.wi, 2 * F, D) : WeightPrefetch();
-        Planes qe = e == 0 ? m->cq : m->cq2;   // folded: module e's columns of the stacked, un-normalised queries
-        if (fold) { qe.p[0] = m->cq.p[0] + (size_t)e * J; qe.p[1] = NP == 2 ? m->cq.p[1] + (size_t)e * J : nullptr; }
-        attention<NP>(c, KC_ATTN_CROSS, qe, fold ? nq : J, kc, J, (size_t)m->S_pad * J, region, vt, m->S_pad,
-                      (size_t)J * m->S_pad, e == 0 ? ao : m->ao2, J, m->d_nkeys_cross + (size_t)e * m->Bmax, T, m->H,
-                      batch, ks, region, &pf, -1, fold ? ssq : nullptr);
-      }
-      // y = x + sum_e zero_if_masked(MHA_e(...)) (network.py:199-216 / 217-235): residual adds one after the
-      // other; the last one also writes the folded-norm inputs of the MLP block
-      for (int e = 0; e < m->n_cross; ++e) {
-        EpiResidualNorm<NP> ec = er;
-        const bool last_mod = e + 1 == m->n_cross;
-        ec.g_lo = last_mod ? g_tab(2 * l + 1) : nullptr; ec.g_lo_stride = last_mod ? slots * D : 0;
-        ec.g_hi = nullptr; ec.g_hi_stride = 0;
-        ec.split_row = BT;
-        const WeightPrefetch pf_in = (last_mod && mlp_in_on_cross_out) ? prefetch_of<NP>(m, w.mlp.wi, 2 * F, D) : WeightPrefetch();
-        gemm<NP, TK_SQUARE>(c, KC_GEMM_CROSS_OUT, e == 0 ? ao : m->ao2, J, w.wo_cross[e], J, BT, D, J, ec, 0, &pf_in);
-      }
-    }
-    // (iii) MLP block (network.py:241-256)
-    EpiGeglu<NP> eg;
-    eg.out[0] = gb.p[0]; eg.out[1] = gb.p[NP - 1]; eg.ldc = F;
-    eg.rsc = rowscale(m->d_bw_mlp + (size_t)l * 2 * F, m->Ld * 2 * F);
-    EpiResidualNorm<NP> eo = er;
-    eo.g_lo = eo.g_hi = last_layer ? m->dec_final_ln : g_tab(2 * (l + 1));  // decoder_norm has no FiLM
-    eo.g_lo_stride = eo.g_hi_stride = last_layer ? 0 : slots * D;
-    eo.split_row = 0;
-    {
-      const WeightPrefetch pf_out = prefetch_of<NP>(m, w.mlp.wo, D, F);
-      gemm<NP, TK_MLP_IN>(c, KC_GEMM_MLP_IN, y, D, w.mlp.wi, D, M, 2 * F, D, eg, 0, &pf_out);
-      // S6: the next layer's folded query projection reads x (.) gamma_cross of the conditional rows from this epilogue
-      // (and its stacked Wq sits right behind Wq|Wk|Wv: one prefetch target)
-      const bool fold_next = !last_layer && fold_cross_q<NP>(m, batch, P, cond0, false);
-      WeightPrefetch pf_qkv = last_layer ? WeightPrefetch() : prefetch_of<NP>(m, m->dec[l + 1].self.wqkv, 3 * J + (fold_next ? nq : 0), D);
-      if (fold_next) {
-        if constexpr (NP == 2)   // (the fold exists in the two-plane modes only: no single-plane Y2 kernels)
-          gemm<NP, TK_TALL>(c, KC_GEMM_MLP_OUT, gb, F, w.mlp.wo, F, M, D, F, with_y2<NP>(eo, m->xg, m->dec[l + 1].ln_cross, BT), 0, &pf_qkv);
-      } else {
-        gemm<NP, TK_TALL>(c, KC_GEMM_MLP_OUT, gb, F, w.mlp.wo, F, M, D, F, eo, 0, &pf_qkv);
-      }
+  const DecLayerW& w = m->dec[l];
+  const StepPlan::SelfBlock& sb = p.of(l);
+  const int D = m->D, J = m->J, T = m->T, BT = p.batch * T;
+  const int nq = m->n_cross * J;              // the modules' queries, stacked
+  // fused q|k|v projection (network.py:181-189 via layers.py:262-264) on the folded-norm planes y
+  const EpiQKV<NP> eq = epi_qkv<NP>(m->qk, m->vt, 2 * J, T, J, dec_row_scale(m, m->d_bw_self + (size_t)l * 3 * J, m->Ld * 3 * J));
+  const WeightPrefetch pf_wo = prefetch_of<NP>(m, w.self.wo, sb.fold ? D + nq : D, J);   // (folded: + W2, right behind Wo)
+  if constexpr (NP == 2) {
+    if (sb.fold) {   // + (x0 (.) gamma_cross) . Wq on the launch's idle CUs, left in float32 for the attention-out launch
+      const GemmParams p1 = gp_launch<NP>(c, KC_GEMM_QKV, m->y, D, w.self.wqkv, D, sb.Ms, 3 * J, D, sb.qkv.bm, pf_wo);
+      const GemmParams p2 = gp_launch<NP>(c, KC_GEMM_QKV, m->xg, D, w.wq_fold, D, BT, nq, D, sb.qkv.bm);
+      gemm_dual<FoldQkvTiles>(c, KC_GEMM_QKV, sb.qkv, p1, eq, sb.qkv, p2, epi_store_f32(m->qp, nq));
     }
   }
-  // decoder_norm + spec_out_dense (network.py:445-456).  The reference keeps this
-  // projection in float32 "for stability": its output eps enters x0 = sqrt(1+e^-l)(z - s eps)
-  // with a gain of up to 22026 at the first steps, and with 2^-16 products the short-chain
-  // parity tests show 40x more clip-boundary outliers.  Parity mode therefore runs it on the
-  // exact-fp32 MFMA; the plain bf16 mode uses the folded bf16 GEMM like its other layers.
+  if (!sb.fold) gemm<NP, TK_QKV>(c, KC_GEMM_QKV, m->y, D, w.self.wqkv, D, sb.Ms, 3 * J, D, eq, eq.v_start, pf_wo);
+  const WeightPrefetch pf_next = sb.warms == WARM_MLP_IN ? mlp_in_weights<NP>(m, l)
+                               : sb.warms == WARM_CROSS_OUT ? prefetch_of<NP>(m, w.wo_cross[0], D, J)
+                                                            : prefetch_of<NP>(m, w.wq_cross[0], J, D);
+  const AttnKV kv = {planes_at<NP>(m->qk, J), 2 * J, (size_t)T * 2 * J, T, m->vt, T, (size_t)J * T, 0, m->d_nkeys_self};
+  attention<NP>(c, KC_ATTN_SELF, m->qk, 2 * J, kv, m->ao, J, T, m->H, sb.Ps * p.batch, 1,
+                sb.warm_on_out ? WeightPrefetch() : pf_next, sb.qb4);
+  const WeightPrefetch pf_out = sb.warm_on_out ? pf_next : WeightPrefetch();
+  // out-projection + residual; produces y for the cross-attention norm (conditional rows: plain gamma) and for the
+  // MLP norm (unconditional rows, which skip cross-attention: S4)
+  auto out_proj = [&](const auto& epi) {
+    if constexpr (NP == 2) {
+      if (sb.fold) {
+        // S6: the output projection and ao . (Wo diag(gamma_cross) Wq_e) in ONE launch -- same A operand; the second problem
+        // adds the half the QKV launch left in `qp` and stores the UN-NORMALISED queries of all modules, [BT, n_cross J]
+        const GemmParams p1 = gp_launch<NP>(c, KC_GEMM_ATTN_OUT, m->ao, J, w.self.wo, J, sb.Ms, D, J, sb.out.bm, pf_out);
+        const GemmParams p2 = gp_launch<NP>(c, KC_GEMM_ATTN_OUT, m->ao, J, w.w2_fold, J, BT, nq, J, sb.out2.bm);
+        EpiAddStoreH16<NP> ea;
+        out_pair<NP>(ea.out, m->cq); ea.ldc = nq; ea.addend = m->qp; ea.ld_add = nq;
+        return gemm_dual<FoldOutTiles>(c, KC_GEMM_ATTN_OUT, sb.out, p1, epi, sb.out2, p2, ea);
+      }
+    }
+    gemm<NP, TK_TALL>(c, KC_GEMM_ATTN_OUT, m->ao, J, w.self.wo, J, sb.Ms, D, J, epi, 0, pf_out);
+  };
+  const Gain g_mlp = g_tab(m, 2 * l + 1);
+  EpiResidualNorm<NP> er = dec_residual<NP>(m, p.cond0 ? Gain{w.ln_cross, 0} : g_mlp, g_mlp, p.cond0 ? BT : 0);
+  if (sb.dup) {   // rows [0, BT) computed once, written as both passes: y[r] for the cross-attention norm, y[r + BT] for the MLP norm
+    EpiResidualNorm<NP, true> ed = residual_form<true, false>(er);
+    ed.split_row = 0; ed.dup_rows = BT;
+    out_proj(ed);
+  } else {
+    if (sb.fold) { er.g_lo = nullptr; er.g_lo_stride = 0; }   // the conditional rows' y = x1 (.) gamma_cross has no reader any more
+    out_proj(er);
+  }
+}
+
+// (ii) cross-attention block, conditional rows only (S4) (network.py:196-235)
+template <int NP>
+void cross_attention_block(Ctx& c, const StepPlan& p, int l) {
+  msd_model* m = c.m;
+  const DecLayerW& w = m->dec[l];
+  const bool fold = p.of(l).fold;
+  const int D = m->D, J = m->J, T = m->T, BT = p.batch * T, nq = m->n_cross * J;
+  const Planes* const cq[2] = {&m->cq, &m->cq2};
+  const Planes* const ao[2] = {&m->ao, &m->ao2};
+  // every module projects its queries from the SAME normed input (network.py:196-198), so all query
+  // projections run before the first output projection rewrites y
+  for (int e = 0; e < m->n_cross && !fold; ++e)
+    gemm<NP, TK_SQUARE>(c, KC_GEMM_CROSS_Q, m->y, D, w.wq_cross[e], D, BT, J, D, epi_out<EpiStoreH16, NP>(*cq[e], J, dec_row_scale(m)), 0,
+                        prefetch_of<NP>(m, w.wo_cross[e], D, J));
+  const size_t loff = (size_t)l * m->Bmax * m->S_pad * J;
+  for (int e = 0; e < m->n_cross; ++e) {
+    const size_t r0 = (size_t)m->key_off[e];
+    const int region = cross_region(m, e);
+    const AttnKV kv = {planes_at<NP>(m->kc, loff + r0 * J), J, (size_t)m->S_pad * J, region,
+                       planes_at<NP>(m->vtc, loff + r0), m->S_pad, (size_t)J * m->S_pad, region, m->d_nkeys_cross + (size_t)e * m->Bmax};
+    const bool warm_mlp_in = e + 1 == m->n_cross && !p.mlp_in_on_cross_out;
+    // folded: module e's columns of the stacked, un-normalised queries
+    attention<NP>(c, KC_ATTN_CROSS, fold ? planes_at<NP>(m->cq, (size_t)e * J) : *cq[e], fold ? nq : J, kv, *ao[e], J, T, m->H,
+                  p.batch, p.ks[e], warm_mlp_in ? mlp_in_weights<NP>(m, l) : WeightPrefetch(), true, -1, fold ? m->ssq : nullptr);
+  }
+  // y = x + sum_e zero_if_masked(MHA_e(...)) (network.py:199-216 / 217-235): residual adds one after the
+  // other; the last one also writes the folded-norm inputs of the MLP block
+  for (int e = 0; e < m->n_cross; ++e) {
+    const bool last_mod = e + 1 == m->n_cross;
+    const EpiResidualNorm<NP> ec = dec_residual<NP>(m, last_mod ? g_tab(m, 2 * l + 1) : Gain(), Gain(), BT);
+    gemm<NP, TK_SQUARE>(c, KC_GEMM_CROSS_OUT, *ao[e], J, w.wo_cross[e], J, BT, D, J, ec, 0,
+                        last_mod && p.mlp_in_on_cross_out ? mlp_in_weights<NP>(m, l) : WeightPrefetch());
+  }
+}
+
+// (iii) MLP block (network.py:241-256)
+template <int NP>
+void mlp_block(Ctx& c, const StepPlan& p, int l) {
+  msd_model* m = c.m;
+  const DecLayerW& w = m->dec[l];
+  const int D = m->D, J = m->J, F = m->F, BT = p.batch * m->T, M = p.P * BT;
+  const bool last_layer = (l + 1 == m->Ld);
+  gemm<NP, TK_MLP_IN>(c, KC_GEMM_MLP_IN, m->y, D, w.mlp.wi, D, M, 2 * F, D,
+                      epi_out<EpiGeglu, NP>(m->g, F, dec_row_scale(m, m->d_bw_mlp + (size_t)l * 2 * F, m->Ld * 2 * F)), 0,
+                      prefetch_of<NP>(m, w.mlp.wo, D, F));
+  const Gain g_next = last_layer ? Gain{m->dec_final_ln, 0} : g_tab(m, 2 * (l + 1));   // decoder_norm has no FiLM
+  const EpiResidualNorm<NP> eo = dec_residual<NP>(m, g_next, g_next, 0);
+  // S6: the next layer's folded query projection reads x (.) gamma_cross of the conditional rows from this epilogue
+  // (and its stacked Wq sits right behind Wq|Wk|Wv: one prefetch target)
+  const bool fold_next = !last_layer && p.self[1].fold;
+  const WeightPrefetch pf_qkv = last_layer ? WeightPrefetch()
+                                           : prefetch_of<NP>(m, m->dec[l + 1].self.wqkv, 3 * J + (fold_next ? m->n_cross * J : 0), D);
+  if constexpr (NP == 2) {   // (the fold exists in the two-plane modes only: no single-plane Y2 kernels)
+    if (fold_next) {
+      EpiResidualNorm<NP, false, true> e2 = residual_form<false, true>(eo);
+      out_pair<NP>(e2.y2, m->xg); e2.g2 = m->dec[l + 1].ln_cross; e2.y2_rows = BT;
+      return gemm<NP, TK_TALL>(c, KC_GEMM_MLP_OUT, m->g, F, w.mlp.wo, F, M, D, F, e2, 0, pf_qkv);
+    }
+  }
+  gemm<NP, TK_TALL>(c, KC_GEMM_MLP_OUT, m->g, F, w.mlp.wo, F, M, D, F, eo, 0, pf_qkv);
+}
+
+// decoder_norm + spec_out_dense (network.py:445-456).  The reference keeps this
+// projection in float32 "for stability": its output eps enters x0 = sqrt(1+e^-l)(z - s eps)
+// with a gain of up to 22026 at the first steps, and with 2^-16 products the short-chain
+// parity tests show 40x more clip-boundary outliers.  Parity mode therefore runs it on the
+// exact-fp32 MFMA; the plain bf16 mode uses the folded bf16 GEMM like its other layers.
+template <int NP>
+void final_projection(Ctx& c, const StepPlan& p) {
+  msd_model* m = c.m;
+  const int D = m->D, M = p.P * p.batch * m->T;
   if (NP == 2) {
     FinalProjParams fp;
-    fp.x = x; fp.wg = m->w_out_g; fp.ssq = ssq; fp.out = eps;
-    fp.M = M; fp.N = m->ND; fp.K = D; fp.tiles = tiles; fp.inv_d = 1.0f / (float)D;
+    fp.x = m->x; fp.wg = m->w_out_g; fp.ssq = m->ssq; fp.out = m->eps;
+    fp.M = M; fp.N = m->ND; fp.K = D; fp.tiles = D / kNarrowTile; fp.inv_d = 1.0f / (float)D;
     c.begin(KC_FINAL_PROJ);
     hipLaunchKernelGGL(final_proj_f32_kernel<1>, dim3(m->ND / 32, M / 16), dim3(64 * kFinalProjWaves), 0, c.s, fp);
     c.end(KC_FINAL_PROJ);
   } else {
-    EpiStoreF32 ef;
-    ef.out = eps; ef.ldc = m->ND; ef.rsc = rowscale(nullptr, 0);
-    gemm<NP, TK_NARROW>(c, KC_FINAL_PROJ, y, D, m->w_out_p, D, M, m->ND, D, ef);
+    gemm<NP, TK_NARROW>(c, KC_FINAL_PROJ, m->y, D, m->w_out_p, D, M, m->ND, D, epi_store_f32(m->eps, m->ND, dec_row_scale(m)));
   }
 }
 
 template <int NP>
-void in_proj(Ctx& c, int batch, int P, bool publish_step = false, bool fold0 = false) {   // P: passes whose rows are written (dedup0: 1); fold0: layer 0 folds its cross-attention query projection (S6)
+void decoder_layers(Ctx& c, const StepPlan& p) {
+  for (int l = 0; l < c.m->Ld; ++l) {
+    self_attention_block<NP>(c, p, l);
+    if (p.cond0) cross_attention_block<NP>(c, p, l);
+    mlp_block<NP>(c, p, l);
+  }
+  final_projection<NP>(c, p);
+}
+
+// Decoder input (gemm_h16.h EpiInProj): x and the folded-norm inputs of layer 0's self norm (table slot 0) for the passes
+// layer 0's self-attention block reads (S5: one), + x (.) gamma_cross when layer 0 folds its query projection (S6)
+template <int NP>
+void in_proj(Ctx& c, const StepPlan& p, bool publish_step = false) {
   msd_model* m = c.m;
-  const int BT = batch * m->T;
+  const StepPlan::SelfBlock& s0 = p.self[0];
+  const int BT = p.batch * m->T;
   EpiInProj<NP> ei;
-  ei.x = m->x; ei.ldx = m->D; ei.pos = m->dec_pos; ei.T = m->T; ei.pass_rows = BT; ei.passes = P;
-  ei.y[0] = m->y.p[0]; ei.y[1] = m->y.p[NP - 1]; ei.ssq = m->ssq; ei.tiles = m->D / kNarrowTile;
-  ei.g = m->d_g; ei.g_stride = 2 * m->Ld * m->D; ei.step_ptr = m->d_step;   // slot 0 = layer 0 self norm
+  ei.x = m->x; ei.ldx = m->D; ei.pos = m->dec_pos; ei.T = m->T; ei.pass_rows = BT; ei.passes = s0.Ps;
+  out_pair<NP>(ei.y, m->y); ei.ssq = m->ssq; ei.tiles = m->D / kNarrowTile;
+  ei.g = m->d_g; ei.g_stride = 2 * m->Ld * m->D; ei.step_ptr = m->d_step;
   ei.step_copy = publish_step ? m->d_step : nullptr;
-  if (fold0) { ei.y2[0] = m->xg.p[0]; ei.y2[1] = m->xg.p[NP - 1]; ei.g2 = m->dec[0].ln_cross; }
-  WeightPrefetch pf = prefetch_of<NP>(m, m->dec[0].self.wqkv, 3 * m->J + (fold0 ? m->n_cross * m->J : 0), m->D);
-  gemm<NP, TK_NARROW>(c, KC_IN_PROJ, m->zp, m->ND, m->w_in_p, m->ND, BT, m->D, m->ND, ei, 0, &pf);
+  if (s0.fold) { out_pair<NP>(ei.y2, m->xg); ei.g2 = m->dec[0].ln_cross; }
+  gemm<NP, TK_NARROW>(c, KC_IN_PROJ, m->zp, m->ND, m->w_in_p, m->ND, BT, m->D, m->ND, ei, 0,
+                      prefetch_of<NP>(m, m->dec[0].self.wqkv, 3 * m->J + (s0.fold ? m->n_cross * m->J : 0), m->D));
+}
+
+// one decoder evaluation: P passes from z's planes to eps
+void decoder_eval(Ctx& c, const StepPlan& p, bool publish_step) {
+  if (c.m->NP == 2) { in_proj<2>(c, p, publish_step); decoder_layers<2>(c, p); }
+  else { in_proj<1>(c, p, publish_step); decoder_layers<1>(c, p); }
 }
 
 // z (fp32) -> bf16 planes, after z was written from outside the sampler kernel
-void split_z(msd_model* m, int64_t n, hipStream_t s) {
-  hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, m->z, m->zp.p[0],
-                     m->NP == 2 ? m->zp.p[1] : (h16_t*)nullptr, n, m->d_sat, (unsigned)KC_SAMPLER + 1u);
-}
+void split_z(msd_model* m, int64_t n, hipStream_t s) { split(m->z, m->zp, n, s, m->d_sat, (unsigned)KC_SAMPLER + 1u); }
 
-template <int NP>
-void enqueue_step(Ctx& c, int batch) {
+// one DDPM step of the CFG sampler: the decoder on plan_cfg_step's plan, then the sampler update
+void enqueue_step(Ctx& c, const StepPlan& p) {
   msd_model* m = c.m;
-  const int P = m->passes;
-  // S5: a CFG step computes layer 0's self-attention block once for both passes
-  const bool dedup0 = P == 2 && m->dedup_layer0;
-  in_proj<NP>(c, batch, dedup0 ? 1 : P, /*publish_step=*/true, fold_cross_q<NP>(m, batch, P, true, dedup0));
-  decoder_layers<NP>(c, batch, P, true, dedup0);
+  decoder_eval(c, p, /*publish_step=*/true);
   SamplerParams sp;
   sp.eps = m->eps; sp.z = m->z; sp.noise_slot = m->d_noise_slot; sp.coef = m->d_coef; sp.rng_key = m->d_rng_key;
-  sp.step_ptr = m->d_step; sp.n = batch * m->T * m->ND; sp.passes = P;
+  sp.step_ptr = m->d_step; sp.n = p.batch * m->T * m->ND; sp.passes = p.P;
   sp.cond_wt = m->cfg.cfg_weight; sp.clip_x0 = m->cfg.clip_x0;
   sp.ddim = m->cfg.sampler == MSD_SAMPLER_DDIM;
   sp.model_output = m->cfg.model_output;
@@ -1353,14 +1431,6 @@ void enqueue_step(Ctx& c, int batch) {
   sp.step_from_slot1 = 1;
   launch_sampler_step(sp, c.s);
   c.end(KC_SAMPLER);
-}
-
-void set_func_attrs() {
-  // opt in to > 64 KiB dynamic LDS once, outside any stream capture
-  (void)attention_prepare<1, 3>();
-  (void)attention_prepare<2, 2>();
-  (void)prepare_gemms<1>();
-  (void)prepare_gemms<2>();
 }
 
 
@@ -1837,13 +1907,12 @@ int msd_sample_rng(msd_model* m, int batch, int rng, uint64_t seed, uint64_t str
 
   // One graph = `graph_steps` consecutive DDPM steps (the scan index lives in device memory, so
   // the same graph serves every position); a second, single-step graph covers N mod graph_steps.
+  const StepPlan plan = plan_cfg_step(m, batch);
   auto capture = [&](int steps, hipGraphExec_t* out) -> int {
     hipGraph_t graph = nullptr;
     HIP_TRY(m, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     Ctx c{m, s};
-    for (int k = 0; k < steps; ++k) {
-      if (m->NP == 2) enqueue_step<2>(c, batch); else enqueue_step<1>(c, batch);
-    }
+    for (int k = 0; k < steps; ++k) enqueue_step(c, plan);
     hipError_t ce = hipStreamEndCapture(s, &graph);
     if (ce != hipSuccess || c.err != hipSuccess) {
       if (graph) (void)hipGraphDestroy(graph);
@@ -1854,16 +1923,14 @@ int msd_sample_rng(msd_model* m, int batch, int rng, uint64_t seed, uint64_t str
     if (ie != hipSuccess) { *out = nullptr; return fail(m, MSD_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie)); }
     return MSD_OK;
   };
-  // the graphs of this (batch, key splits) -- the splits follow the key counts msd_encode saw
-  const int ks0 = cross_split(m, batch, 0);
-  const int ks1 = m->n_cross > 1 ? cross_split(m, batch, 1) : 0;
+  // the graphs captured with this plan (msd_model::StepGraphs)
   msd_model::StepGraphs* g = nullptr;
   for (auto& e : m->graphs)
-    if (e.batch == batch && e.ks[0] == ks0 && e.ks[1] == ks1) g = &e;
+    if (memcmp(&e.plan, &plan, sizeof(plan)) == 0) g = &e;
   if (!g) {
     if (m->graphs.size() >= 8) (void)msd_reset_graph(m);   // (a handle that cycles through more shapes than that re-captures)
     msd_model::StepGraphs ng;
-    ng.batch = batch; ng.ks[0] = ks0; ng.ks[1] = ks1;
+    ng.plan = plan;
     int rc = capture(m->graph_steps, &ng.exec);
     if (rc) return rc;
     if (m->graph_steps > 1 && m->N % m->graph_steps) {
@@ -1910,8 +1977,7 @@ int msd_decoder_pass(msd_model* m, int batch, int step_index, const float* z_dev
   HIP_TRY(m, hipStreamSynchronize(s));
   split_z(m, n, s);
   Ctx c{m, s};
-  if (m->NP == 2) { in_proj<2>(c, batch, 1, false, fold_cross_q<2>(m, batch, 1, include_conditioning != 0, false)); decoder_layers<2>(c, batch, 1, include_conditioning != 0); }
-  else { in_proj<1>(c, batch, 1); decoder_layers<1>(c, batch, 1, include_conditioning != 0); }
+  decoder_eval(c, plan_step(m, batch, 1, include_conditioning != 0, false), /*publish_step=*/false);
   if (c.err != hipSuccess) return fail(m, MSD_ERR_HIP, "decoder pass failed: %s", hipGetErrorString(c.err));
   HIP_TRY(m, hipMemcpyAsync(eps_out_dev, m->eps, n * sizeof(float), hipMemcpyDeviceToDevice, s));
   return check_range(m, s, "msd_decoder_pass");   // synchronises
@@ -1967,8 +2033,7 @@ int msd_debug_read(msd_model* m, const char* buffer, float* host_out, int64_t ma
   } else {
     float* tmp = nullptr;
     HIP_TRY(m, hipMalloc(&tmp, n * sizeof(float)));
-    hipLaunchKernelGGL(merge_planes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, m->own_stream, pl->p[0],
-                       m->NP == 2 ? pl->p[1] : (const h16_t*)nullptr, tmp, n);
+    merge(*pl, tmp, n, m->own_stream);
     hipError_t e = copy_sync(m, host_out, tmp, n * sizeof(float), hipMemcpyDeviceToHost);
     (void)hipFree(tmp);
     HIP_TRY(m, e);
@@ -1998,9 +2063,8 @@ int msd_profile_steps(msd_model* m, int batch, int n_steps, const char* const** 
   for (int k = 0; k < KC_COUNT; ++k) { m->prof.ms[k] = 0; m->prof.launches[k] = 0; }
   m->prof.on = true;
   Ctx c{m, s};
-  for (int i = 0; i < n_steps; ++i) {
-    if (m->NP == 2) enqueue_step<2>(c, batch); else enqueue_step<1>(c, batch);
-  }
+  const StepPlan plan = plan_cfg_step(m, batch);
+  for (int i = 0; i < n_steps; ++i) enqueue_step(c, plan);
   m->prof.on = false;
   if (c.err != hipSuccess) { (void)hipStreamSynchronize(s); return fail(m, MSD_ERR_HIP, "profile run failed: %s", hipGetErrorString(c.err)); }
   if (int rc2 = check_range(m, s, "msd_profile_steps")) return rc2;   // synchronises; the timed steps ran with the flag armed
@@ -2055,9 +2119,6 @@ int op_planes(int precision) {
   if (precision < MSD_PREC_F16 || precision > MSD_PREC_BF16X3 || bf != (MSD_PLANE_BF16 != 0)) return -1;
   return (precision == MSD_PREC_F16X3 || precision == MSD_PREC_BF16X3) ? 2 : 1;
 }
-void split(const float* in, h16_t* hi, h16_t* lo, int64_t n, hipStream_t s, unsigned* sat = nullptr) {
-  hipLaunchKernelGGL(split_planes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, hi, lo, n, sat, 1u);
-}
 }  // namespace
 }  // extern "C++"
 
@@ -2076,13 +2137,13 @@ int msd_op_gemm_h16(int precision, const float* a_dev, const float* w_dev, float
     w.p[i] = sc.get<h16_t>((size_t)N * K);
     if (!a.p[i] || !w.p[i]) return MSD_ERR_HIP;
   }
-  split(a_dev, a.p[0], NP == 2 ? a.p[1] : nullptr, (int64_t)M * K, s, fl.sat());
+  split(a_dev, a, (int64_t)M * K, s, fl.sat());
   dim3 grid((K + 63) / 64, N), block(64);
   hipLaunchKernelGGL(pack_wt_kernel, grid, block, 0, s, w_dev, K, N, w.p[0],
                      NP == 2 ? w.p[1] : (h16_t*)nullptr, 0, 0, 0, fl.absmax());
   hipError_t e;
-  if (NP == 2) e = launch_gemm_h16_dma<2, 64, 64, 3>(gp<2>(a, K, w, K, M, N, K), EpiStoreF32{c_dev, N}, s);
-  else e = launch_gemm_h16_dma<1, 64, 64, 3>(gp<1>(a, K, w, K, M, N, K), EpiStoreF32{c_dev, N}, s);
+  if (NP == 2) e = launch_gemm_h16_dma<2, 64, 64, 3>(gp<2>(a, K, w, K, M, N, K), epi_store_f32(c_dev, N), s);
+  else e = launch_gemm_h16_dma<1, 64, 64, 3>(gp<1>(a, K, w, K, M, N, K), epi_store_f32(c_dev, N), s);
   if (e != hipSuccess) return MSD_ERR_HIP;
   return fl.finish(s);
 }
@@ -2150,8 +2211,8 @@ int msd_op_attention_ex(int precision, int qp, int ksplit, int merge_in_launch, 
   }
   if (!d_nk || !vt32) return MSD_ERR_HIP;
   (void)hipMemcpyAsync(d_nk, &n_keys_valid, sizeof(int), hipMemcpyHostToDevice, s);
-  split(q_dev, q.p[0], NP == 2 ? q.p[1] : nullptr, (int64_t)n_q * J, s, fl.sat());
-  split(k_dev, k.p[0], NP == 2 ? k.p[1] : nullptr, (int64_t)n_keys * J, s, fl.sat());
+  split(q_dev, q, (int64_t)n_q * J, s, fl.sat());
+  split(k_dev, k, (int64_t)n_keys * J, s, fl.sat());
   // V -> V^T with the per-16 key permutation, via the GEMM epilogue's own rule (host copy)
   std::vector<float> vh((size_t)n_keys * J), vth((size_t)J * n_keys);
   if (hipMemcpy(vh.data(), v_dev, vh.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return MSD_ERR_HIP;
@@ -2161,7 +2222,7 @@ int msd_op_attention_ex(int precision, int qp, int ksplit, int merge_in_launch, 
     for (int j = 0; j < J; ++j) vth[(size_t)j * n_keys + kp] = vh[(size_t)key * J + j];
   }
   if (hipMemcpy(vt32, vth.data(), vth.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return MSD_ERR_HIP;
-  split(vt32, vt.p[0], NP == 2 ? vt.p[1] : nullptr, (int64_t)J * n_keys, s, fl.sat());
+  split(vt32, vt, (int64_t)J * n_keys, s, fl.sat());
   AttnParams p;
   fl.arm(p);
   p.qp = qp;
@@ -2190,8 +2251,7 @@ int msd_op_attention_ex(int precision, int qp, int ksplit, int merge_in_launch, 
   for (int r = 0; r < repeats && e == hipSuccess; ++r)   // back to back: the counters must be zero again after every launch
     e = NP == 2 ? launch_attention<2>(p, heads, 1, s) : launch_attention<1>(p, heads, 1, s);
   if (e != hipSuccess) return MSD_ERR_HIP;
-  hipLaunchKernelGGL(merge_planes_kernel, dim3((unsigned)(((int64_t)n_q * J + 255) / 256)), dim3(256), 0, s,
-                     o.p[0], NP == 2 ? o.p[1] : (const h16_t*)nullptr, o_dev, (int64_t)n_q * J);
+  merge(o, o_dev, (int64_t)n_q * J, s);
   return fl.finish(s);
 }
 
@@ -2200,27 +2260,22 @@ int msd_op_attention_ex(int precision, int qp, int ksplit, int merge_in_launch, 
 extern "C++" {
 namespace {
 // W fp32 [K, N] (reference layout) -> packed W^T planes [N, K]
+bool new_planes(Scratch& sc, size_t n, Planes* out) {   // two zeroed planes of n elements
+  for (h16_t*& pl : out->p) pl = sc.get<h16_t>(n);
+  return out->p[0] && out->p[1];
+}
 bool pack_planes(Scratch& sc, const float* w_dev, int K, int N, int mode, int dst_row0, Planes* out, int rows,
                  hipStream_t s, const OpFlags& fl) {
-  if (!out->p[0]) {
-    out->p[0] = sc.get<h16_t>((size_t)rows * K);
-    out->p[1] = sc.get<h16_t>((size_t)rows * K);
-    if (!out->p[0] || !out->p[1]) return false;
-  }
+  if (!out->p[0] && !new_planes(sc, (size_t)rows * K, out)) return false;
   dim3 grid((K + 63) / 64, N), block(64);
   hipLaunchKernelGGL(pack_wt_kernel, grid, block, 0, s, w_dev, K, N, out->p[0], out->p[1], dst_row0, mode, 0,
                      fl.absmax());
   return hipGetLastError() == hipSuccess;
 }
 bool split_new(Scratch& sc, const float* in, int64_t n, Planes* out, hipStream_t s, const OpFlags& fl) {
-  out->p[0] = sc.get<h16_t>((size_t)n);
-  out->p[1] = sc.get<h16_t>((size_t)n);
-  if (!out->p[0] || !out->p[1]) return false;
-  split(in, out->p[0], out->p[1], n, s, fl.sat());
+  if (!new_planes(sc, (size_t)n, out)) return false;
+  split(in, *out, n, s, fl.sat());
   return true;
-}
-void merge(const Planes& pl, float* out, int64_t n, hipStream_t s) {
-  hipLaunchKernelGGL(merge_planes_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, pl.p[0], pl.p[1], out, n);
 }
 }  // namespace
 }  // extern "C++"
@@ -2285,14 +2340,13 @@ int msd_op_residual_norm_gemm(int folded, const float* x_in_dev, const float* a_
   if (!split_new(sc, a_dev, (int64_t)M * K, &a, s, fl) || !pack_planes(sc, w1_dev, K, D, 0, 0, &w1, D, s, fl) ||
       !pack_planes(sc, w2_dev, D, N, 0, 0, &w2, N, s, fl))
     return MSD_ERR_HIP;
-  y.p[0] = sc.get<h16_t>((size_t)M * D); y.p[1] = sc.get<h16_t>((size_t)M * D);
   const int tiles = D / kNarrowTile;
   float* ssq = sc.get<float>((size_t)M * tiles);
   float* film = sc.get<float>((size_t)2 * D);   // one-step, one-slot table: scale | bias
   float* g = sc.get<float>((size_t)D);
   float* bw = sc.get<float>((size_t)N);
   int* step = sc.get<int>(2);
-  if (!y.p[0] || !y.p[1] || !ssq || !film || !g || !bw || !step) return MSD_ERR_HIP;
+  if (!new_planes(sc, (size_t)M * D, &y) || !ssq || !film || !g || !bw || !step) return MSD_ERR_HIP;
   if (hipMemcpyAsync(x_out_dev, x_in_dev, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
     return MSD_ERR_HIP;
   if (film_scale_dev) {
@@ -2305,9 +2359,7 @@ int msd_op_residual_norm_gemm(int folded, const float* x_in_dev, const float* a_
     GemmF32Params bp;   // bias . W2 : one row
     bp.A = film + D; bp.B = w2_dev; bp.lda = D; bp.ldb = N; bp.M = 1; bp.N = N; bp.K = D;
     e = launch_gemm_f32(bp, EpiF32Store{bw, N}, s);
-    EpiResidualNorm<2> er;
-    er.x = x_out_dev; er.ldx = D; er.y[0] = y.p[0]; er.y[1] = y.p[1]; er.ssq = ssq; er.tiles = tiles;
-    er.step_ptr = step; er.g_lo = g; er.g_lo_stride = 0; er.g_hi = g; er.g_hi_stride = 0; er.split_row = M / 2;
+    const EpiResidualNorm<2> er = epi_residual_norm<2>(x_out_dev, D, y, ssq, step, Gain{g, 0}, Gain{g, 0}, M / 2);
     GemmParams p1 = gp<2>(a, K, w1, K, M, D, K);
     p1.xcd_rows = 2; p1.xcd_walk_n = 1;
     fl.arm(p1);
@@ -2317,10 +2369,7 @@ int msd_op_residual_norm_gemm(int folded, const float* x_in_dev, const float* a_
       if (D % kWide48 || M % 32) return MSD_ERR_INVALID_ARGUMENT;
       if (e == hipSuccess) e = launch_gemm_h16_dma<2, 32, kWide48, 4>(p1, er, s);
     } else if (e == hipSuccess) e = launch_gemm_h16_dma<2, 32, 32, 4>(p1, er, s);
-    EpiStoreF32 ef;
-    ef.out = h_out_dev; ef.ldc = N;
-    ef.rsc.ssq = ssq; ef.rsc.tiles = tiles; ef.rsc.inv_d = 1.0f / (float)D; ef.rsc.bias = bw;
-    ef.rsc.bias_step_stride = 0; ef.rsc.step_ptr = step;
+    const EpiStoreF32 ef = epi_store_f32(h_out_dev, N, row_scale(ssq, tiles, step, bw, 0));
     if (e == hipSuccess) e = launch_gemm_h16_dma<2, 64, 64, 3>(gp<2>(y, D, w2, D, M, N, D), ef, s);
   } else {
     e = launch_gemm_h16_dma<2, 32, 32, 4>(gp<2>(a, K, w1, K, M, D, K), EpiResidual{x_out_dev, D}, s);
@@ -2329,7 +2378,7 @@ int msd_op_residual_norm_gemm(int folded, const float* x_in_dev, const float* a_
     np.film_slots = 1; np.film_slot = 0; np.rows = M; np.D = D; np.out[0] = y.p[0]; np.out[1] = y.p[1]; np.out_f32 = nullptr;
     fl.arm(np);
     hipLaunchKernelGGL((rmsnorm_film_kernel<1, 4>), dim3((M + 3) / 4), dim3(256), 0, s, np);
-    if (e == hipSuccess) e = launch_gemm_h16_dma<2, 64, 64, 3>(gp<2>(y, D, w2, D, M, N, D), EpiStoreF32{h_out_dev, N}, s);
+    if (e == hipSuccess) e = launch_gemm_h16_dma<2, 64, 64, 3>(gp<2>(y, D, w2, D, M, N, D), epi_store_f32(h_out_dev, N), s);
   }
   if (e != hipSuccess || hipGetLastError() != hipSuccess) return MSD_ERR_HIP;
   if (const int rc = fl.finish(s)) return rc;
@@ -2349,10 +2398,8 @@ int msd_op_geglu(const float* a_dev, const float* wi0_dev, const float* wi1_dev,
   if (!split_new(sc, a_dev, (int64_t)M * K, &a, s, fl) || !pack_planes(sc, wi0_dev, K, F, 1, 0, &wi, 2 * F, s, fl) ||
       !pack_planes(sc, wi1_dev, K, F, 2, 0, &wi, 2 * F, s, fl))
     return MSD_ERR_HIP;
-  g.p[0] = sc.get<h16_t>((size_t)M * F); g.p[1] = sc.get<h16_t>((size_t)M * F);
-  if (!g.p[0] || !g.p[1]) return MSD_ERR_HIP;
-  EpiGeglu<2> eg;
-  eg.out[0] = g.p[0]; eg.out[1] = g.p[1]; eg.ldc = F;
+  if (!new_planes(sc, (size_t)M * F, &g)) return MSD_ERR_HIP;
+  const EpiGeglu<2> eg = epi_out<EpiGeglu, 2>(g, F);
   GemmParams pg = gp<2>(a, K, wi, K, M, 2 * F, K);
   fl.arm(pg);
   hipError_t e = launch_gemm_h16_dma<2, 64, 128, 3>(pg, eg, s);
@@ -2376,13 +2423,9 @@ int msd_op_qkv(const float* a_dev, const float* wq_dev, const float* wk_dev, con
   if (!split_new(sc, a_dev, (int64_t)M * K, &a, s, fl) || !pack_planes(sc, wq_dev, K, J, 0, 0, &w, 3 * J, s, fl) ||
       !pack_planes(sc, wk_dev, K, J, 0, J, &w, 3 * J, s, fl) || !pack_planes(sc, wv_dev, K, J, 0, 2 * J, &w, 3 * J, s, fl))
     return MSD_ERR_HIP;
-  qk.p[0] = sc.get<h16_t>((size_t)M * 2 * J); qk.p[1] = sc.get<h16_t>((size_t)M * 2 * J);
-  vt.p[0] = sc.get<h16_t>((size_t)M * J); vt.p[1] = sc.get<h16_t>((size_t)M * J);
   float* f32 = sc.get<float>((size_t)M * 2 * J);
-  if (!qk.p[0] || !qk.p[1] || !vt.p[0] || !vt.p[1] || !f32) return MSD_ERR_HIP;
-  EpiQKV<2> eq;
-  eq.qk[0] = qk.p[0]; eq.qk[1] = qk.p[1]; eq.vt[0] = vt.p[0]; eq.vt[1] = vt.p[1];
-  eq.ld_qk = 2 * J; eq.v_start = 2 * J; eq.seg_len = seg_len; eq.vt_ld = seg_len; eq.vt_rows = J;
+  if (!new_planes(sc, (size_t)M * 2 * J, &qk) || !new_planes(sc, (size_t)M * J, &vt) || !f32) return MSD_ERR_HIP;
+  const EpiQKV<2> eq = epi_qkv<2>(qk, vt, 2 * J, seg_len, J);
   hipError_t e;
   GemmParams pq = gp<2>(a, K, w, K, M, 3 * J, K);
   fl.arm(pq);
@@ -2431,12 +2474,9 @@ int msd_op_final_proj(const float* x_dev, const float* gamma_dev, const float* w
   float* wg = sc.get<float>((size_t)D * n);
   int* step = sc.get<int>(2);
   Planes za, zw;   // zero operands of the zero-update residual GEMM
-  for (int i = 0; i < 2; ++i) { za.p[i] = sc.get<h16_t>((size_t)M * 64); zw.p[i] = sc.get<h16_t>((size_t)D * 64); }
-  if (!x || !ssq || !wg || !step || !za.p[1] || !zw.p[1]) return MSD_ERR_HIP;
+  if (!x || !ssq || !wg || !step || !new_planes(sc, (size_t)M * 64, &za) || !new_planes(sc, (size_t)D * 64, &zw)) return MSD_ERR_HIP;
   if (hipMemcpyAsync(x, x_dev, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) return MSD_ERR_HIP;
-  EpiResidualNorm<2> er;
-  er.x = x; er.ldx = D; er.y[0] = nullptr; er.y[1] = nullptr; er.ssq = ssq; er.tiles = tiles; er.step_ptr = step;
-  er.g_lo = nullptr; er.g_lo_stride = 0; er.g_hi = nullptr; er.g_hi_stride = 0; er.split_row = 0;
+  const EpiResidualNorm<2> er = epi_residual_norm<2>(x, D, Planes(), ssq, step, Gain(), Gain(), 0);
   hipError_t e = launch_gemm_h16_dma<2, 32, 32, 4>(gp<2>(za, 64, zw, 64, M, D, 64), er, s);
   if (e != hipSuccess) return MSD_ERR_HIP;
   hipLaunchKernelGGL(scale_rows_kernel, dim3((D * n + 255) / 256), dim3(256), 0, s, w_dev, gamma_dev, wg, D, n);

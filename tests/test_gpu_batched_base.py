@@ -5,7 +5,7 @@ songs per call.  Afterwards the handle's `eps` debug buffer holds the raw model 
 (conditional rows first: sampler_step_kernel reads eps[idx] and eps[n + idx]); every song's two passes are held to
 the float64 oracle (3e-4 max-rel: the bar tests/test_ref_golden.py holds the one-song base pass to) and to the same
 song run alone on the same library (float32 rounding).  By the host's launch rules (msd_api.hip pick_tile,
-cross_split, fold_cross_q; attention.h attention_query_blocks) the batch sizes reach:
+cross_split, plan_step; attention.h attention_query_blocks) the batch sizes reach:
   B = 2   M = 1024  the folded cross-attention query projection on a CFG step (its upper limit), narrow tiles
   B = 3   M = 1536  fold off, narrow tiles, 128-row attention blocks for the cross- (key split 2) and the
                     self-attention of layers >= 1 (both passes in one launch)

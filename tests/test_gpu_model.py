@@ -610,7 +610,7 @@ def test_folded_cross_query_projection_is_the_same_function(preset, style, nb):
   (library default) and off must agree to float32 rounding AND both must sit on the float64 oracle like every other
   pass (2e-4 max-rel: tests above); a CFG segment of a few steps must stay in the float32 class.  Both cross-attention
   styles (one and two modules), the duplicating layer 0 (CFG), 1 - 3 songs.  The fold takes launches of up to 1024
-  decoder rows (msd_api.hip fold_cross_q): every single pass here folds (M = nb T <= 768), a CFG step only up to 2 songs
+  decoder rows (msd_api.hip plan_step): every single pass here folds (M = nb T <= 768), a CFG step only up to 2 songs
   at base (M = 2 nb T: 1024 at 2 songs; at 3, M = 1536, both handles run the unfolded order and the segment comparison
   is of that order with itself).  Asserted per case: the folded handle's single conditional pass writes the `qp` buffer
   (the QKV launch's half of the folded queries; zero in a fresh handle), and a CFG step launches no cross-attention
