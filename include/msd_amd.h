@@ -42,7 +42,8 @@ extern "C" {
 #endif
 
 #define MSD_AMD_ABI_VERSION 7   /* 7: msd_sample_rng, msd_fill_normal_threefry, msd_op_threefry (the reference's Threefry draws on the
-                                      device); msd_config unchanged.
+                                      device); msd_config unchanged.  Appended to ABI 7 (no version bump): the msd_vocoder_*
+                                      entry points (device STFT pair, Audio2Mel, Griffin-Lim).
                                    6: cross_merge_in_launch, cross_q_fold, mlp_in_persistent appended to msd_config.
                                    5: dedup_layer0, cross_key_split, keep_raw_weights, kv_touch_ahead appended to msd_config.
                                    4: every caller-selectable knob is a msd_config field (attn_q_planes / attn_p_planes
@@ -391,6 +392,55 @@ int msd_op_final_proj(const float* x_dev, const float* gamma_dev, const float* w
  * (the float stages over all 2^23 mantissas: stages 1 - 3); stage 0 then is MSD_ERR_INVALID_ARGUMENT.  Does not synchronise. */
 int msd_op_threefry(int stage, uint64_t seed, int64_t fold, const uint32_t* bits_in_dev, float* out_dev, int64_t n,
                     void* stream);
+
+/* ---- (appended to ABI 7) Device vocoder: the codec's STFT pair, Audio2Mel and a Griffin-Lim mel -> audio stage ----
+ * NOT the reference's decoder: audio_codecs.py:249-264 runs SoundStream, a learned vocoder whose TF-Hub artifact is
+ * not available; that stays "not built".  This is a documented stand-in -- fast Griffin-Lim (phase reconstruction with
+ * momentum) over the codec's own STFT geometry -- so that a result can be listened to and a recording can be encoded
+ * as context on the device.  It claims no parity with SoundStream.
+ * Geometry (audio_codecs.MelGAN, :204-218): frame 640, hop 320, FFT 1024 -> 513 bins, periodic Hann window,
+ * pad_end framing (frame k = samples [320k, 320k + 640) of the zero-extended signal), F = ceil(n_samples / 320)
+ * frames, 128 mel bins, log-mel = log(clip(., 1e-5, 1e8)).  Specification: stft / istft / mel_to_linear /
+ * griffin_lim of the package's audio_codecs.py (float64 NumPy).  All arithmetic is float32 (exact-fp32 MFMA GEMMs;
+ * the plane format of the library build does not enter).
+ * A handle owns its DFT / mel tables and work buffers, which grow on demand to the largest batch * n_frames seen;
+ * one handle <-> one device <-> one caller thread at a time.  Every call enqueues on `stream` and SYNCHRONISES it
+ * before returning, like the msd_op_* entry points.  Null pointers and zero or negative sizes give
+ * MSD_ERR_INVALID_ARGUMENT without touching a device. */
+typedef struct msd_vocoder msd_vocoder; /* opaque */
+
+/* On the CURRENT HIP device.  mel_basis_host float [513, 128] (linear_to_mel_weight_matrix(128, 513, 16000, 0, 8000));
+ * mel_inverse_host float [128, 513], its pseudo-inverse (taken in float64 by the caller).  On failure *out may hold a
+ * handle whose msd_vocoder_last_error has the message; destroy it. */
+int msd_vocoder_create(const float* mel_basis_host, const float* mel_inverse_host, msd_vocoder** out);
+void msd_vocoder_destroy(msd_vocoder* v);
+const char* msd_vocoder_last_error(const msd_vocoder* v);
+
+/* tf.signal.stft(pad_end=True): audio_dev float [batch, n_samples] -> spec_out_dev float [batch, F, 2, 513], real
+ * parts then imaginary parts of each frame. */
+int msd_vocoder_stft(msd_vocoder* v, int batch, int64_t n_samples, const float* audio_dev, float* spec_out_dev,
+                     void* stream);
+/* Inverse: per frame the inverse real DFT (the imaginary parts of the DC and Nyquist bins are ignored), its first 640
+ * samples times the Hann window, overlap-added, divided by max(sum of squared windows, 1e-3), cut to F * 320:
+ * spec_dev float [batch, n_frames, 2, 513] -> audio_out_dev float [batch, n_frames * 320].  istft(stft(x)) = x except
+ * on the first ~40 samples, where the window vanishes. */
+int msd_vocoder_istft(msd_vocoder* v, int batch, int n_frames, const float* spec_dev, float* audio_out_dev,
+                      void* stream);
+/* Audio2Mel (audio_codecs.py:107-143, MelGAN.encode :226-247): logmel_out_dev float [batch, F, 128] =
+ * log(clip(|stft| . mel_basis, 1e-5, 1e8)). */
+int msd_vocoder_encode(msd_vocoder* v, int batch, int64_t n_samples, const float* audio_dev, float* logmel_out_dev,
+                       void* stream);
+/* Griffin-Lim: mag = max(exp(logmel) . mel_inverse, 0); X = mag . phase; n_iters times { x = istft(X); Y = stft(x);
+ * U = Y - momentum / (1 + momentum) . Y_prev (Y_prev = 0 at first); X = mag . U / |U|, (1, 0) where U = 0 }; one final
+ * istft.  n_iters >= 0, momentum >= 0 (0.99: Perraudin et al.'s fast form; 0: the classic iteration).
+ *   logmel_dev     float [batch, n_frames, 128]
+ *   init_phase_dev float [batch, n_frames, 2, 513] (cos then sin of each frame's phases, used as given), or NULL: the
+ *                  phase of bin (b, f, k) is then the direction of the pair (d[b][f][0][k], d[b][f][1][k]) of
+ *                  d = msd_fill_normal(seed, stream_id = 0x766F63, subseq = 0, ..., batch * n_frames * 2 * 513),
+ *                  normalised to the unit circle -- uniform phases, reproducible from `seed`
+ *   audio_out_dev  float [batch, n_frames * 320] */
+int msd_vocoder_decode(msd_vocoder* v, int batch, int n_frames, const float* logmel_dev, int n_iters, float momentum,
+                       uint64_t seed, const float* init_phase_dev, float* audio_out_dev, void* stream);
 
 #ifdef __cplusplus
 }

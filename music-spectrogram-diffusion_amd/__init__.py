@@ -17,7 +17,8 @@ from . import sharding
 from . import frontend
 from . import checkpoints
 from . import jax_random
+from . import vocoder
 from .inference import InferenceModel, parse_training_gin_file
 
 __all__ = ['config', 'synthetic', 'audio_codecs', 'gin_lite', 'native', 'inference',
-           'sharding', 'frontend', 'checkpoints', 'jax_random', 'InferenceModel', 'parse_training_gin_file']
+           'sharding', 'frontend', 'checkpoints', 'jax_random', 'vocoder', 'InferenceModel', 'parse_training_gin_file']

@@ -10,6 +10,10 @@ published definitions of tf.signal.stft(pad_end=True), hann_window(periodic) and
 linear_to_mel_weight_matrix (HTK mel scale); parity with TensorFlow is UNPINNED (no TF, no
 reference vectors) -- tests/test_audio_encode.py pins it against a direct DFT and the closed-form
 filter bank.  ``decode`` (TF-Hub SoundStream, audio_codecs.py:249-264) is row N2 -- not built.
+
+``stft`` / ``istft`` / ``mel_to_linear`` / ``griffin_lim`` (float64) are the SPECIFICATION of the device vocoder
+(csrc/vocoder.h, vocoder.py: the STFT pair, Audio2Mel and a Griffin-Lim mel -> audio stand-in for SoundStream), as
+jax_random.py is for the Threefry draws; the product path does not call them.
 """
 from __future__ import annotations
 
@@ -130,6 +134,94 @@ def linear_to_mel_weight_matrix(num_mel_bins: int, num_spectrogram_bins: int, sa
   lower, center, upper = edges[:-2][None], edges[1:-1][None], edges[2:][None]
   w = np.maximum(0.0, np.minimum((bins_mel - lower) / (center - lower), (upper - bins_mel) / (upper - center)))
   return np.concatenate([np.zeros((1, num_mel_bins)), w], 0).astype(np.float32)
+
+
+# ---- specification of the device vocoder (float64; csrc/vocoder.h computes the same in float32) --------------------
+FRAME_LENGTH, FRAME_STEP, FFT_LENGTH = 640, 320, 1024   # MelGAN's STFT geometry (audio_codecs.py:204-218)
+
+
+def _hann64(n: int) -> np.ndarray:
+  return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n) / n)
+
+
+def stft(signals, frame_length: int = FRAME_LENGTH, frame_step: int = FRAME_STEP,
+         fft_length: int = FFT_LENGTH) -> np.ndarray:
+  """tf.signal.stft(signals, ..., hann_window, pad_end=True) in float64: the complex form of ``stft_magnitude``.
+  signals [B, n] -> complex128 [B, ceil(n / step), fft_length // 2 + 1]."""
+  signals = np.asarray(signals, np.float64)
+  if signals.ndim == 1:
+    signals = signals[None]
+  b, n = signals.shape
+  n_frames = -(-n // frame_step)
+  padded = np.zeros((b, (n_frames - 1) * frame_step + frame_length), np.float64)
+  padded[:, :n] = signals
+  idx = np.arange(frame_length)[None, :] + frame_step * np.arange(n_frames)[:, None]
+  return np.fft.rfft(padded[:, idx] * _hann64(frame_length), n=fft_length, axis=-1)
+
+
+def istft(spec, n_frames=None, floor: float = 1e-3, frame_length: int = FRAME_LENGTH, frame_step: int = FRAME_STEP,
+          fft_length: int = FFT_LENGTH) -> np.ndarray:
+  """Inverse of ``stft``: the inverse real DFT of each frame, truncated to frame_length samples, times the Hann
+  window, overlap-added into (F - 1) * step + frame_length samples, divided by max(sum of squared windows, floor),
+  cut to F * step.  spec complex [B, F, bins] -> float64 [B, F * step].  The first samples divide by a vanishing
+  window (the floor bounds the gain there): istft(stft(x)) == x from sample ~40 on."""
+  spec = np.asarray(spec, np.complex128)
+  if spec.ndim == 2:
+    spec = spec[None]
+  f = spec.shape[1] if n_frames is None else int(n_frames)
+  spec = spec[:, :f]
+  w = _hann64(frame_length)
+  frames = np.fft.irfft(spec, n=fft_length, axis=-1)[..., :frame_length] * w
+  total = (f - 1) * frame_step + frame_length
+  out = np.zeros((spec.shape[0], total), np.float64)
+  norm = np.zeros(total, np.float64)
+  for k in range(f):
+    out[:, k * frame_step:k * frame_step + frame_length] += frames[:, k]
+    norm[k * frame_step:k * frame_step + frame_length] += w * w
+  return (out / np.maximum(norm, floor))[:, :f * frame_step]
+
+
+def mel_pseudo_inverse(mel_basis) -> np.ndarray:
+  """pinv of the [bins, mels] mel weight matrix, taken in float64 -> [mels, bins]."""
+  return np.linalg.pinv(np.asarray(mel_basis, np.float64))
+
+
+def mel_to_linear(logmel, mel_basis=None) -> np.ndarray:
+  """log-mel [.., 128] -> linear-frequency magnitudes [.., 513]: max(exp(logmel) @ pinv(mel_basis), 0)."""
+  if mel_basis is None:
+    mel_basis = linear_to_mel_weight_matrix(128, FFT_LENGTH // 2 + 1, 16000, 0.0, 8000.0)
+  return np.maximum(np.exp(np.asarray(logmel, np.float64)) @ mel_pseudo_inverse(mel_basis), 0.0)
+
+
+def griffin_lim(mag, n_iters: int = 32, momentum: float = 0.99, init_phase=None) -> np.ndarray:
+  """Fast Griffin-Lim (Perraudin, Balazs, Sondergaard 2013) over ``stft`` / ``istft``.
+  mag [B, F, 513]; init_phase = (cos, sin), two arrays [B, F, 513] (None: zero phase).
+    X = mag * phase;  n_iters times: x = istft(X); Y = stft(x); U = Y - momentum / (1 + momentum) * Y_prev
+    (Y_prev = 0 at first); phase = U / |U|, (1, 0) where |U| == 0; X = mag * phase;  finally x = istft(X).
+  Returns float64 [B, F * 320]."""
+  mag = np.asarray(mag, np.float64)
+  if mag.ndim == 2:
+    mag = mag[None]
+  f = mag.shape[1]
+  if init_phase is None:
+    phase = np.ones(mag.shape, np.complex128)
+  else:
+    phase = np.asarray(init_phase[0], np.float64) + 1j * np.asarray(init_phase[1], np.float64)
+  alpha = momentum / (1.0 + momentum)
+  prev = np.zeros(mag.shape, np.complex128)
+  for _ in range(int(n_iters)):
+    y = stft(istft(mag * phase, f))
+    u = y - alpha * prev
+    prev = y
+    a = np.abs(u)
+    phase = np.where(a > 0, u / np.where(a > 0, a, 1.0), 1.0)
+  return istft(mag * phase, f)
+
+
+def spectral_convergence(audio, mag) -> float:
+  """|| |stft(audio)| - mag ||_F / || mag ||_F: how far a waveform's own magnitudes are from the target's."""
+  mag = np.asarray(mag, np.float64)
+  return float(np.linalg.norm(np.abs(stft(audio)) - mag.reshape((-1,) + mag.shape[-2:])) / np.linalg.norm(mag))
 
 
 def get_codec(name: str) -> AudioCodec:

@@ -27,7 +27,7 @@ LIBS = {'f16': (LIB, []), 'bf16': (os.path.join(CSRC, 'libmsd_amd_bf16.so'), ['-
 EXP_SRC = os.path.join(EXP, 'src_r04')   # round 4's sources with the experiments still inside
 EXP_LIBS = {'exp': (LIB_EXP, ['-DMSD_EXPERIMENTS=1'])}
 SOURCES = ['msd_api.hip']
-HEADERS = ['common.h', 'phase_stamps.h', 'gemm_h16.h', 'gemm_f32.h', 'attention.h', 'elementwise.h',
+HEADERS = ['common.h', 'phase_stamps.h', 'gemm_h16.h', 'gemm_f32.h', 'attention.h', 'elementwise.h', 'vocoder.h',
            os.path.join('..', '..', 'include', 'msd_amd.h')]
 EXP_HEADERS = ['chain.h', 'gemm_h16_exp.h', 'gemm_splitk_exchange.inc', 'gemm_h16_pair.h', 'gemm_h16_wide.h', 'gemm_h16_ls.h']
 
@@ -65,11 +65,15 @@ def check_prefetch_registers(listing: str) -> str:
 
 
 # kernels that must not spill: elementwise launches on the step's critical path (the sampler once went through scratch
-# memory, csrc/elementwise.h) and the Threefry fill
-NO_SCRATCH_KERNELS = ('sampler_step_kernel', 'threefry_normal_kernel')
+# memory, csrc/elementwise.h) and the Threefry fill ...
+NO_SCRATCH_STEP_KERNELS = ('sampler_step_kernel', 'threefry_normal_kernel')
+# ... and the vocoder's elementwise kernels (csrc/vocoder.h: two of the four launches of a Griffin-Lim iteration)
+NO_SCRATCH_VOCODER_KERNELS = ('voc_pad_signal_kernel', 'voc_exp_kernel', 'voc_load_spec_kernel', 'voc_ola_kernel',
+                              'voc_phase_kernel', 'voc_magnitude_kernel')
+NO_SCRATCH_KERNELS = NO_SCRATCH_STEP_KERNELS + NO_SCRATCH_VOCODER_KERNELS   # what build() checks in every product listing
 
 
-def check_no_scratch(listing: str, kernels=NO_SCRATCH_KERNELS) -> str:
+def check_no_scratch(listing: str, kernels=NO_SCRATCH_STEP_KERNELS) -> str:
   """Every instance of `kernels` in the device listing must report a private segment (scratch) of 0 bytes and no
   dynamic stack; each name must be present at least once.  An instance that spills fails the build."""
   import re
@@ -129,7 +133,7 @@ def build(force: bool = False, verbose: bool = True, experiments: bool = False) 
         if verbose:
           print('[build_native] prefetch registers:', verdict, flush=True)
         if src == CSRC:   # (the experiments library is built from frozen sources that have no Threefry kernel)
-          verdict = check_no_scratch(l)
+          verdict = check_no_scratch(l, NO_SCRATCH_KERNELS)
           if verbose:
             print('[build_native] scratch:', verdict, flush=True)
       shutil.copyfile(out, lib + '.tmp')

@@ -19,6 +19,7 @@
 #include "elementwise.h"
 #include "gemm_h16.h"
 #include "gemm_f32.h"
+#include "vocoder.h"
 
 using namespace msd;
 
@@ -2486,6 +2487,143 @@ int msd_op_final_proj(const float* x_dev, const float* gamma_dev, const float* w
   hipLaunchKernelGGL(final_proj_f32_kernel<1>, dim3(n / 32, M / 16), dim3(64 * kFinalProjWaves), 0, s, fp);
   if (hipGetLastError() != hipSuccess) return MSD_ERR_HIP;
   return hipStreamSynchronize(s) == hipSuccess ? MSD_OK : MSD_ERR_HIP;
+}
+
+// ---- device vocoder (vocoder.h): STFT pair, Audio2Mel, fast Griffin-Lim -------------------------------------------
+extern "C++" {
+namespace {
+int vfail(msd_vocoder* v, int code, const char* fmt, ...) {
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof(buf), fmt, ap);
+  va_end(ap);
+  v->err = buf;
+  return code;
+}
+constexpr int64_t kVocMaxRows = 1 << 20;   // spectrum rows per call (the elementwise kernels index in 32 bits)
+inline bool voc_shape_ok(int batch, int64_t frames) { return batch > 0 && frames > 0 && (int64_t)batch * (frames + 1) <= kVocMaxRows; }
+// first launch error of a call (a launch wrapper's own hipGetLastError clears the runtime's copy)
+struct VocErr {
+  hipError_t e = hipSuccess;
+  bool operator()(hipError_t x) { if (e == hipSuccess) e = x; return x == hipSuccess; }
+};
+inline int voc_finish(msd_vocoder* v, VocErr& err, hipStream_t s, const char* what) {
+  err(hipGetLastError());
+  if (err.e == hipSuccess) err(hipStreamSynchronize(s));
+  if (err.e != hipSuccess) return vfail(v, MSD_ERR_HIP, "%s: %s", what, hipGetErrorString(err.e));
+  return MSD_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+const char* msd_vocoder_last_error(const msd_vocoder* v) { return v ? v->err.c_str() : "null vocoder"; }
+
+int msd_vocoder_create(const float* mel_basis_host, const float* mel_inverse_host, msd_vocoder** out) {
+  if (!mel_basis_host || !mel_inverse_host || !out) return MSD_ERR_INVALID_ARGUMENT;
+  msd_vocoder* v = new msd_vocoder();
+  *out = v;   // kept alive on failure so that the caller can read the message
+  std::vector<float> fwd, inv, inv_norm;
+  voc_host_tables(fwd, inv, inv_norm);
+  std::vector<float> mel((size_t)kVocHalf * kVocMel, 0.f), mel_inv((size_t)kVocMel * kVocMelInvN, 0.f);
+  memcpy(mel.data(), mel_basis_host, (size_t)kVocBins * kVocMel * sizeof(float));
+  for (int r = 0; r < kVocMel; ++r)
+    memcpy(&mel_inv[(size_t)r * kVocMelInvN], mel_inverse_host + (size_t)r * kVocBins, kVocBins * sizeof(float));
+  struct { float** dst; const std::vector<float>* src; } up[] = {
+      {&v->fwd, &fwd}, {&v->inv, &inv}, {&v->inv_norm, &inv_norm}, {&v->mel, &mel}, {&v->mel_inv, &mel_inv}};
+  for (auto& u : up) {
+    const size_t bytes = u.src->size() * sizeof(float);
+    if (hipMalloc(reinterpret_cast<void**>(u.dst), bytes) != hipSuccess ||
+        hipMemcpy(*u.dst, u.src->data(), bytes, hipMemcpyHostToDevice) != hipSuccess)
+      return vfail(v, MSD_ERR_HIP, "msd_vocoder_create: %s", hipGetErrorString(hipGetLastError()));
+  }
+  return MSD_OK;
+}
+
+void msd_vocoder_destroy(msd_vocoder* v) {
+  if (!v) return;
+  voc_free_work(v);
+  for (float* p : {v->fwd, v->inv, v->inv_norm, v->mel, v->mel_inv})
+    if (p) (void)hipFree(p);
+  delete v;
+}
+
+int msd_vocoder_stft(msd_vocoder* v, int batch, int64_t n_samples, const float* audio_dev, float* spec_out_dev, void* stream) {
+  if (!v || !audio_dev || !spec_out_dev || n_samples <= 0) return MSD_ERR_INVALID_ARGUMENT;
+  const int64_t frames = (n_samples + kVocHop - 1) / kVocHop;
+  if (!voc_shape_ok(batch, frames)) return vfail(v, MSD_ERR_INVALID_ARGUMENT, "msd_vocoder_stft: batch %d x %lld samples", batch, (long long)n_samples);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int F = (int)frames, rows = batch * (F + 1);
+  if (!voc_reserve(v, rows, s)) return vfail(v, MSD_ERR_HIP, "msd_vocoder_stft: cannot allocate %d rows", rows);
+  VocErr err;
+  voc_pad(v, batch, (int)n_samples, F, audio_dev, s);
+  err(voc_forward(v, rows, EpiVocSpecOut{spec_out_dev, F}, s));
+  return voc_finish(v, err, s, "msd_vocoder_stft");
+}
+
+int msd_vocoder_istft(msd_vocoder* v, int batch, int n_frames, const float* spec_dev, float* audio_out_dev, void* stream) {
+  if (!v || !spec_dev || !audio_out_dev) return MSD_ERR_INVALID_ARGUMENT;
+  if (!voc_shape_ok(batch, n_frames)) return vfail(v, MSD_ERR_INVALID_ARGUMENT, "msd_vocoder_istft: batch %d x %d frames", batch, n_frames);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int F = n_frames, rows = batch * (F + 1);
+  if (!voc_reserve(v, rows, s)) return vfail(v, MSD_ERR_HIP, "msd_vocoder_istft: cannot allocate %d rows", rows);
+  hipLaunchKernelGGL(voc_load_spec_kernel, voc_grid_rows(rows), dim3(256), 0, s, spec_dev, (const float*)nullptr, v->w[VB_X], F, rows, 0);
+  VocErr err;
+  err(voc_inverse(v, batch, F, audio_out_dev, false, s));
+  return voc_finish(v, err, s, "msd_vocoder_istft");
+}
+
+int msd_vocoder_encode(msd_vocoder* v, int batch, int64_t n_samples, const float* audio_dev, float* logmel_out_dev, void* stream) {
+  if (!v || !audio_dev || !logmel_out_dev || n_samples <= 0) return MSD_ERR_INVALID_ARGUMENT;
+  const int64_t frames = (n_samples + kVocHop - 1) / kVocHop;
+  if (!voc_shape_ok(batch, frames)) return vfail(v, MSD_ERR_INVALID_ARGUMENT, "msd_vocoder_encode: batch %d x %lld samples", batch, (long long)n_samples);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int F = (int)frames, rows = batch * (F + 1);
+  if (!voc_reserve(v, rows, s)) return vfail(v, MSD_ERR_HIP, "msd_vocoder_encode: cannot allocate %d rows", rows);
+  VocErr err;
+  voc_pad(v, batch, (int)n_samples, F, audio_dev, s);
+  err(voc_forward(v, rows, EpiF32Store{v->w[VB_Y0], kVocSpec}, s));
+  hipLaunchKernelGGL(voc_magnitude_kernel, voc_grid_rows(rows - 1), dim3(256), 0, s, v->w[VB_Y0], v->w[VB_MAG], rows - 1);
+  err(launch_gemm_f32(voc_gemm(v->w[VB_MAG], kVocHalf, v->mel, kVocMel, rows - 1, kVocMel, kVocHalf), EpiVocLogMel{logmel_out_dev, F}, s));
+  return voc_finish(v, err, s, "msd_vocoder_encode");
+}
+
+int msd_vocoder_decode(msd_vocoder* v, int batch, int n_frames, const float* logmel_dev, int n_iters, float momentum,
+                       uint64_t seed, const float* init_phase_dev, float* audio_out_dev, void* stream) {
+  if (!v || !logmel_dev || !audio_out_dev || n_iters < 0) return MSD_ERR_INVALID_ARGUMENT;
+  if (!voc_shape_ok(batch, n_frames)) return vfail(v, MSD_ERR_INVALID_ARGUMENT, "msd_vocoder_decode: batch %d x %d frames", batch, n_frames);
+  if (!(momentum >= 0.f && momentum < 1e6f)) return vfail(v, MSD_ERR_INVALID_ARGUMENT, "msd_vocoder_decode: momentum %g", (double)momentum);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int F = n_frames, rows = batch * (F + 1);
+  if (!voc_reserve(v, rows, s)) return vfail(v, MSD_ERR_HIP, "msd_vocoder_decode: cannot allocate %d rows", rows);
+  // target magnitudes: max(exp(log-mel) . pinv(mel basis), 0); the straddling rows and pad columns stay zero
+  const int64_t n_mel = (int64_t)batch * F * kVocMel;
+  VocErr err;
+  err(hipMemsetAsync(v->w[VB_MAG], 0, (size_t)rows * kVocHalf * sizeof(float), s));
+  hipLaunchKernelGGL(voc_exp_kernel, dim3((unsigned)((n_mel / 4 + 255) / 256)), dim3(256), 0, s, logmel_dev, v->w[VB_LIN], n_mel / 4);
+  err(launch_gemm_f32(voc_gemm(v->w[VB_LIN], kVocMel, v->mel_inv, kVocMelInvN, batch * F, kVocMelInvN, kVocMel),
+                      EpiVocClampMag{v->w[VB_MAG], F}, s));
+  // X = mag . phase; Y_prev = 0 (a grown or reused buffer must not leak an earlier call's spectrum into the momentum)
+  const float* phase = init_phase_dev;
+  if (!phase) {
+    if (msd_fill_normal(seed, 0x766F63ull, 0u, v->w[VB_DRAWS], (int64_t)batch * F * 2 * kVocBins, stream) != MSD_OK)
+      return vfail(v, MSD_ERR_HIP, "msd_vocoder_decode: phase draw failed");
+    phase = v->w[VB_DRAWS];
+  }
+  hipLaunchKernelGGL(voc_load_spec_kernel, voc_grid_rows(rows), dim3(256), 0, s, phase, (const float*)v->w[VB_MAG], v->w[VB_X], F, rows,
+                     init_phase_dev ? 0 : 1);
+  int cur = 0;
+  err(hipMemsetAsync(v->w[VB_Y1], 0, (size_t)rows * kVocSpec * sizeof(float), s));
+  const float alpha = momentum / (1.0f + momentum);
+  for (int it = 0; it < n_iters; ++it) {
+    if (!err(voc_inverse(v, batch, F, v->w[VB_AUDIO], true, s))) break;
+    if (!err(voc_forward(v, rows, EpiF32Store{v->w[VB_Y0 + cur], kVocSpec}, s))) break;
+    hipLaunchKernelGGL(voc_phase_kernel, voc_grid_rows(rows - 1), dim3(256), 0, s, (const float*)v->w[VB_Y0 + cur],
+                       (const float*)v->w[VB_Y0 + (cur ^ 1)], (const float*)v->w[VB_MAG], v->w[VB_X], rows - 1, alpha);
+    cur ^= 1;
+  }
+  if (err.e == hipSuccess) err(voc_inverse(v, batch, F, audio_out_dev, false, s));
+  return voc_finish(v, err, s, "msd_vocoder_decode");
 }
 
 }  // extern "C"

@@ -302,6 +302,7 @@ class InferenceModel(object):
     self._native: Optional[native.NativeModel] = None
     self._step = 0
     self._stream = None
+    self._vocoder = None
     self.last_timing: Dict[str, float] = {}
 
   # -- shapes / types (inference.py:113-157) -------------------------------------
@@ -360,6 +361,15 @@ class InferenceModel(object):
   def params(self) -> Dict[str, np.ndarray]:
     self._get_native()
     return self._params_np
+
+  @property
+  def vocoder(self):
+    """The device vocoder of this model's codec (vocoder.GriffinLimVocoder: Audio2Mel, and Griffin-Lim as the stand-in
+    for the SoundStream decoder that is not built); created on first use, one per model."""
+    if self._vocoder is None:
+      from . import vocoder as vocoder_lib
+      self._vocoder = vocoder_lib.GriffinLimVocoder(self.audio_codec, device=self.device.index)
+    return self._vocoder
 
   # -- predict (inference.py:200-203) -----------------------------------------------
   def predict(self, batch: Mapping[str, Any], seed: int = 0, segment: int = 0,
@@ -525,14 +535,23 @@ class InferenceModel(object):
                                    segment_frames=self.targets_length, inputs_length=self.inputs_length)
     return tokenizer.note_sequence_to_model_inputs(ns, cfg, on_too_long=on_too_long)
 
-  def synthesize_note_sequence(self, ns, seed: int = 0, **kw):
+  def synthesize_note_sequence(self, ns, seed: int = 0, audio: bool = False, vocoder_iters: int = 32, **kw):
     """Notes -> mel frames of the whole song, float32 [1, K * targets_length, n_dims] (the tail past
-    ns.total_time is the padding of the last segment).  kw: predict_sequence options."""
-    return self.predict_sequence(self.tokenize_note_sequence(ns), seed=seed, **kw)
+    ns.total_time is the padding of the last segment).  kw: predict_sequence options.
+    audio=True: returns (mel, audio) -- audio float32 [1, frames * hop_size] from `vocoder_iters` Griffin-Lim
+    iterations on the device (self.vocoder: a stand-in, not the reference's SoundStream); with return_timing
+    (mel, audio, timing)."""
+    res = self.predict_sequence(self.tokenize_note_sequence(ns), seed=seed, **kw)
+    if not audio:
+      return res
+    mel, rest = (res[0], tuple(res[1:])) if isinstance(res, tuple) else (res, ())
+    wav = self.vocoder.decode(mel, n_iters=vocoder_iters, seed=seed, return_torch=bool(kw.get('return_torch')))
+    return (mel, wav) + rest
 
   def synthesize_midi(self, path: str, seed: int = 0, **kw):
     """Standard MIDI File -> mel frames (the reference's notebooks read MIDI with
-    note_seq.midi_file_to_note_sequence; frontend/midi_io.py restates that reader)."""
+    note_seq.midi_file_to_note_sequence; frontend/midi_io.py restates that reader).  audio=True: (mel, audio), see
+    synthesize_note_sequence."""
     from .frontend import midi_io
     return self.synthesize_note_sequence(midi_io.midi_file_to_note_sequence(path), seed=seed, **kw)
 

@@ -56,7 +56,10 @@ EXPORTED_SYMBOLS = (
     'msd_encode', 'msd_sample', 'msd_reset_graph', 'msd_decoder_pass', 'msd_fill_normal', 'msd_get_schedule',
     'msd_debug_read', 'msd_profile_steps', 'msd_op_gemm_h16', 'msd_op_gemm_bf16', 'msd_op_gemm_f32',
     'msd_op_attention', 'msd_op_attention_qp', 'msd_op_attention_split', 'msd_op_attention_ex', 'msd_op_sampler_step', 'msd_op_residual_norm_gemm', 'msd_op_geglu',
-    'msd_op_qkv', 'msd_op_final_proj', 'msd_sample_rng', 'msd_fill_normal_threefry', 'msd_op_threefry')
+    'msd_op_qkv', 'msd_op_final_proj', 'msd_sample_rng', 'msd_fill_normal_threefry', 'msd_op_threefry',
+    # (appended to ABI 7) the device vocoder
+    'msd_vocoder_create', 'msd_vocoder_destroy', 'msd_vocoder_last_error', 'msd_vocoder_stft', 'msd_vocoder_istft',
+    'msd_vocoder_encode', 'msd_vocoder_decode')
 
 
 class NativeLibraryError(RuntimeError):
@@ -188,9 +191,19 @@ def load(planes: str = 'f16') -> ctypes.CDLL:
   lib.msd_op_geglu.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
   lib.msd_op_qkv.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
   lib.msd_op_final_proj.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
+  if 'msd_vocoder_create' in present:   # (appended to ABI 7: an older library under MSD_AMD_LIB has none of them)
+    lib.msd_vocoder_create.argtypes = [vp, vp, c.POINTER(vp)]
+    lib.msd_vocoder_destroy.argtypes = [vp]
+    lib.msd_vocoder_destroy.restype = None
+    lib.msd_vocoder_last_error.argtypes = [vp]
+    lib.msd_vocoder_last_error.restype = c.c_char_p
+    lib.msd_vocoder_stft.argtypes = [vp, i32, i64, vp, vp, vp]
+    lib.msd_vocoder_istft.argtypes = [vp, i32, i32, vp, vp, vp]
+    lib.msd_vocoder_encode.argtypes = [vp, i32, i64, vp, vp, vp]
+    lib.msd_vocoder_decode.argtypes = [vp, i32, i32, vp, i32, c.c_float, u64, vp, vp, vp]
   for name in present:
     fn = getattr(lib, name)
-    if name not in ('msd_version', 'msd_last_error', 'msd_destroy'):
+    if name not in ('msd_version', 'msd_last_error', 'msd_destroy', 'msd_vocoder_last_error', 'msd_vocoder_destroy'):
       fn.restype = i32
   _libs[planes] = lib
   return lib

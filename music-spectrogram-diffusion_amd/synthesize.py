@@ -5,6 +5,11 @@ beam/evaluation.py:161-223) on the MI355X path.
   python -m msd_amd.synthesize song.mid --checkpoint /path/to/base_with_context/checkpoint_500000 \\
       --out song_mel.npy [--preset base_with_context] [--gin-file train.gin --gin-bindings ...]
       [--seed 0] [--rng threefry|jax] [--num-steps 1000] [--dry-run]
+      [--wav song.wav [--vocoder-iters 32]] [--context-audio earlier.wav]
+
+--wav writes 16-bit PCM mono at 16 kHz from the device vocoder: Griffin-Lim over the codec's STFT, a stand-in for the
+reference's SoundStream decoder (which is not built).  --context-audio continues a recording: its last 256 frames are
+encoded on the device and given to the first segment as context.
 
 --dry-run tokenises only (no GPU): prints the segment / token statistics the synthesis would see."""
 from __future__ import annotations
@@ -37,6 +42,10 @@ def main(argv=None) -> int:
                        "of switching to 'bf16x3' and repeating the segment (the default: a real checkpoint's residual "
                        "stream may have outlier channels; the reference is float32 and never fails on them)")
   ap.add_argument('--out', default=None, help='.npy file for the mel frames [frames, 128]')
+  ap.add_argument('--wav', default=None, help='write the audio as 16-bit PCM mono (Griffin-Lim on the device; not SoundStream)')
+  ap.add_argument('--vocoder-iters', type=int, default=32, help='Griffin-Lim iterations of --wav')
+  ap.add_argument('--context-audio', default=None,
+                  help='16 kHz PCM .wav whose last context-length frames are encoded on the device as the first segment\'s context')
   ap.add_argument('--on-too-long', choices=['error', 'truncate'], default='error')
   ap.add_argument('--dry-run', action='store_true')
   args = ap.parse_args(argv)
@@ -59,7 +68,15 @@ def main(argv=None) -> int:
   if args.dry_run:
     return 0
   model = msd_amd.InferenceModel(args.checkpoint, spec, precision=args.precision, range_fallback=args.range_fallback)
-  mel, timing = model.predict_sequence(segments, seed=args.seed, rng=args.rng, return_timing=True)
+  init_context = None
+  if args.context_audio:
+    if model.targets_context_length is None:
+      ap.error('--context-audio needs a model with context')
+    from msd_amd import vocoder
+    init_context = context_from_audio(model, vocoder.read_wav(args.context_audio, model.audio_codec.sample_rate))
+  mel, timing = model.predict_sequence(segments, seed=args.seed, rng=args.rng, return_timing=True, init_context=init_context,
+                                       return_torch=True)
+  mel_dev, mel = mel, mel.cpu().numpy()
   frames = int(np.ceil(ns.total_time * cfg.frame_rate))
   mel = mel[0, :max(frames, 1)]
   print('synthesised %d mel frames; %.3f s per %.2f s segment (x%.2f realtime)'
@@ -68,7 +85,30 @@ def main(argv=None) -> int:
         file=sys.stderr)
   if args.out:
     np.save(args.out, mel)
+  if args.wav:
+    from msd_amd import vocoder
+    t0 = time.perf_counter()
+    audio = model.vocoder.decode(mel_dev[:, :mel.shape[0]], n_iters=args.vocoder_iters, seed=args.seed)
+    gain = vocoder.write_wav(args.wav, audio[0], model.audio_codec.sample_rate)
+    print('wrote %s: %d samples, %d Griffin-Lim iterations in %.3f s%s'
+          % (args.wav, audio.shape[1], args.vocoder_iters, time.perf_counter() - t0,
+             '' if gain == 1.0 else ' (peak-normalised, gain %.3f)' % gain), file=sys.stderr)
   return 0
+
+
+def context_from_audio(model, samples):
+  """The last targets_context_length frames of a recording as predict_sequence(init_context=): log-mel [1, C, 128] made on
+  the device (model.vocoder.encode); a shorter recording is padded in front with the codec's pad value."""
+  c_len, hop = model.targets_context_length, model.audio_codec.hop_size
+  samples = np.asarray(samples, np.float32).reshape(-1)
+  if samples.size == 0:
+    raise ValueError('the context recording is empty')
+  whole = samples[:samples.size // hop * hop] if samples.size >= hop else samples   # whole frames, so that none is half silence
+  mel = model.vocoder.encode(whole[None, -c_len * hop:], return_torch=True)
+  if mel.shape[1] < c_len:
+    pad = mel.new_full((1, c_len - mel.shape[1], mel.shape[2]), model.audio_codec.pad_value)
+    mel = model._torch.cat([pad, mel], dim=1)
+  return mel[:, -c_len:]
 
 
 if __name__ == '__main__':
