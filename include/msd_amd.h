@@ -43,7 +43,8 @@ extern "C" {
 
 #define MSD_AMD_ABI_VERSION 7   /* 7: msd_sample_rng, msd_fill_normal_threefry, msd_op_threefry (the reference's Threefry draws on the
                                       device); msd_config unchanged.  Appended to ABI 7 (no version bump): the msd_vocoder_*
-                                      entry points (device STFT pair, Audio2Mel, Griffin-Lim).
+                                      entry points (device STFT pair, Audio2Mel, Griffin-Lim); msd_sample_rows (one
+                                      generator key per row of a batched call).
                                    6: cross_merge_in_launch, cross_q_fold, mlp_in_persistent appended to msd_config.
                                    5: dedup_layer0, cross_key_split, keep_raw_weights, kv_touch_ahead appended to msd_config.
                                    4: every caller-selectable knob is a msd_config field (attn_q_planes / attn_p_planes
@@ -264,11 +265,29 @@ enum { MSD_RNG_PHILOX = 0, MSD_RNG_THREEFRY = 1 };
  * MSD_RNG_THREEFRY: init_z = normal(PRNGKey(seed), [batch,T,n]), step i = normal(fold_in(PRNGKey(seed), i), [batch,T,n])
  * (inference.py:203, diffusion_utils.py:389-390,462), drawn inside the sampler kernel; the values are those
  * msd_fill_normal_threefry(seed, -1 / i, ..., batch*T*n) writes, bit for bit.  One draw covers the WHOLE [batch,T,n] array, as
- * in the reference: row b of a batched call is not the draw of a one-row call.  stream_id is ignored, as the reference
+ * in the reference: row b of a batched call is not the draw of a one-row call (msd_sample_rows keys every row on its
+ * own).  stream_id is ignored, as the reference
  * ignores the segment (beam/evaluation.py:209-210).  An unknown rng is MSD_ERR_INVALID_ARGUMENT.  A DDIM sampler
  * uses init_z only.  The step graphs are shared by both generators (the kind lives in device memory). */
 int msd_sample_rng(msd_model* m, int batch, int rng, uint64_t seed, uint64_t stream_id,
                    const float* init_z_dev, const float* noise_dev, float* out_dev, void* stream);
+
+/* (appended to ABI 7) msd_sample_rng with one generator key PER ROW: row b of the call draws, bit for bit, what the
+ * ONE-row call msd_sample_rng(m, 1, rng, seeds[b], stream_ids[b], NULL, NULL, ...) draws, whatever the other rows are
+ * -- independent segments (and songs) share one call and keep their own noise.  With R = T * n_dims elements per row:
+ *   MSD_RNG_PHILOX    init_z row b = msd_fill_normal(seeds[b], stream_ids[b], 0, ..., R); step i's noise of row b is what the
+ *                     three-argument form msd_fill_normal(seeds[b], stream_ids[b], 1 + i, ..., R) writes: counter block
+ *                     e / 4 of element e INSIDE the row, sub-sequence 1 + i
+ *   MSD_RNG_THREEFRY  init_z row b = normal(PRNGKey(seeds[b]), [1,T,n]) = msd_fill_normal_threefry(seeds[b], -1, ..., R);
+ *                     step i = normal(fold_in(PRNGKey(seeds[b]), i), [1,T,n]) = msd_fill_normal_threefry(seeds[b], i, ..., R)
+ *   seeds      host uint64 [batch]; NULL is MSD_ERR_INVALID_ARGUMENT
+ *   stream_ids host uint64 [batch] (the segment of each row), or NULL = zeros (MSD_RNG_THREEFRY ignores it)
+ * init_z_dev / noise_dev, when given, take precedence exactly as in msd_sample_rng; every other argument, check and
+ * status is msd_sample_rng's.  The keys travel in device memory beside the generator kind: the step graphs captured by
+ * msd_sample / msd_sample_rng serve this call too and nothing is re-captured.  Rows must be a whole number of 1024
+ * elements (R % 1024 == 0, true of every shipped configuration); otherwise MSD_ERR_UNSUPPORTED. */
+int msd_sample_rows(msd_model* m, int batch, int rng, const uint64_t* seeds, const uint64_t* stream_ids,
+                    const float* init_z_dev, const float* noise_dev, float* out_dev, void* stream);
 
 /* Drop the captured hipGraph of the DDPM step; the next msd_sample captures it again. */
 int msd_reset_graph(msd_model* m);

@@ -251,21 +251,27 @@ enum { kCoefLogsnrT = 0, kCoefLogsnrS, kCoefX0Scale, kCoefX0Eps, kCoefMeanZ, kCo
        kCoefMLogsnr, kCoefMX0Scale, kCoefMX0Eps, kCoefMEpsScale, kCoefMEpsX0, kCoefMAlpha, kCoefMSigma,
        kCoefPad0, kCoefPad1, kCoefCount };
 enum { kOutEps = 0, kOutX0 = 1, kOutV = 2 };   // = msd_model_output
-// words of SamplerParams::rng_key: 0..3 the Philox key and stream, then the generator kind (= MSD_RNG_*) and the
-// Threefry key PRNGKey(seed)
-enum { kRngKind = 4, kRngTfKey0 = 5, kRngTfKey1 = 6, kRngWords = 8 };
+// words of one row of SamplerParams::rng_key: 0..3 the Philox key and stream, then the generator kind (= MSD_RNG_*), the
+// Threefry key PRNGKey(seed) and the mode of the draw: 0 = one draw over the whole [batch, T, n] array under row 0's key
+// (every row of the table holds that key then), 1 = every row of the array is a draw of its own under its table row
+enum { kRngKind = 4, kRngTfKey0 = 5, kRngTfKey1 = 6, kRngPerRow = 7, kRngWords = 8 };
+enum { kRngRowBlock = 1024 };   // elements per block of sampler_step_kernel: a row of a per-row draw is a whole number of them
 enum { kRngPhilox = 0, kRngThreefry = 1 };
 
 struct SamplerParams {
   const float* eps;     // [passes][n] decoder outputs (pass 0 = conditional)
   float* z;             // [n] in/out
   const float* const* noise_slot;  // device slot holding the [N][n] per-step draws pointer; a NULL pointer there = draw here
-  const uint32_t* rng_key = nullptr;   // kRngWords device words, ALWAYS read (set at every launch): {seed_lo, seed_hi, stream_lo, stream_hi} of the in-kernel draw (round 6):
+  const uint32_t* rng_key = nullptr;   // [rows][kRngWords] device words, this block's row ALWAYS read (set at every launch): {seed_lo, seed_hi, stream_lo, stream_hi} of the in-kernel draw (round 6):
                                        // step i's noise = sub-sequence 1 + i of the caller's Philox stream, element block =
                                        // this thread -- exactly the row philox_normal_kernel used to write for it (the
                                        // [N][n] buffer: 131 MB x songs at base, a hipMalloc inside msd_sample)
                                        // followed by {generator kind, PRNGKey(seed) word 0, word 1} (kRng*): the kind lives in
                                        // device memory so that ONE captured graph serves both generators
+                                       // and {per-row mode} (kRngPerRow): block x reads table row x / row_blocks, so the same
+                                       // graph serves the whole-array draw (all rows equal) and the per-row one
+  int row_blocks = 1 << 30;            // blocks of kRngRowBlock elements per [T, n] row of z = per row of the key table; the
+                                       // default keeps every block on table row 0 (a one-row table, no per-row draw)
   const float* coef;    // [N][kCoefCount]
   int* step_ptr;        // scan index i (device); see step_from_slot1
   int step_from_slot1 = 0;
@@ -336,8 +342,12 @@ __global__ void __launch_bounds__(256) sampler_step_kernel(SamplerParams p) {
   // tests below are vector compares whose outcome is the same in every lane.  This is the form that was measured.
   typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
   const float* noise = *p.noise_slot;
-  u32x4 rk0 = reinterpret_cast<const u32x4*>(p.rng_key)[0], rk1 = reinterpret_cast<const u32x4*>(p.rng_key)[1];
-  static_assert(kRngKind == 4 && kRngTfKey0 == 5 && kRngTfKey1 == 6, "rk1 = {kind, Threefry key, pad}");
+  // The key row of this block's row of z: its address comes from the block index alone, so the per-row keys are one
+  // more address computation in front of the same two loads, not a load behind a load.
+  const uint32_t row = blockIdx.x / (uint32_t)p.row_blocks;
+  const u32x4* rkp = reinterpret_cast<const u32x4*>(p.rng_key + (size_t)row * kRngWords);
+  u32x4 rk0 = rkp[0], rk1 = rkp[1];
+  static_assert(kRngKind == 4 && kRngTfKey0 == 5 && kRngTfKey1 == 6 && kRngPerRow == 7, "rk1 = {kind, Threefry key, mode}");
   asm volatile("" : "+v"(noise), "+v"(rk0), "+v"(rk1));
   const int idx = (blockIdx.x * 256 + threadIdx.x) * 4;
   if (idx < p.n) {
@@ -354,18 +364,24 @@ __global__ void __launch_bounds__(256) sampler_step_kernel(SamplerParams p) {
 #pragma unroll
     for (int k = 0; k < 5; ++k) cr[k] = reinterpret_cast<const f32x4*>(p.coef + (size_t)i * kCoefCount)[k];
     if (!p.ddim && i != 0) {
+      // per-row mode (the same in every lane): the draw covers this row's R = row_blocks * kRngRowBlock elements and e is
+      // the element inside the row -- what a one-row call under this row's key draws; else the whole array, e = idx
+      const bool per_row = rk1[3] != 0u;
+      const uint32_t e = per_row ? (uint32_t)idx - row * (uint32_t)p.row_blocks * kRngRowBlock : (uint32_t)idx;
+      const uint32_t span = per_row ? (uint32_t)p.row_blocks * kRngRowBlock : (uint32_t)p.n;
       if (noise != nullptr) {   // (the same in every lane)
         nz = *reinterpret_cast<const f32x4*>(noise + (size_t)i * p.n + idx);
       } else if (rk1[0] == kRngThreefry) {   // (the same in every lane) the reference's generator: this thread's four
-        // elements of normal(fold_in(PRNGKey(seed), i), [batch, T, n]); the folded key is the same for every thread
+        // elements of normal(fold_in(PRNGKey(seed), i), [batch, T, n]) ([1, T, n] per row); the folded key is the same
+        // for every thread of the draw
         uint32_t f0 = 0u, f1 = (uint32_t)i;
         threefry2x32(rk1[1], rk1[2], f0, f1);
-        const uint32_t half = (uint32_t)p.n >> 1;   // p.n % 4 == 0: no zero pad
+        const uint32_t half = span >> 1;   // span % 4 == 0: no zero pad
 #pragma unroll
-        for (int k = 0; k < 4; ++k) nz[k] = threefry_normal_at(f0, f1, (uint32_t)(idx + k), half);
-      } else {   // no buffer: this thread's four draws of sub-sequence 1 + i (idx / 4 = the counter block)
+        for (int k = 0; k < 4; ++k) nz[k] = threefry_normal_at(f0, f1, e + (uint32_t)k, half);
+      } else {   // no buffer: this thread's four draws of sub-sequence 1 + i (e / 4 = the counter block)
         float d[4];
-        philox_normal4((uint32_t)(idx >> 2), 1u + (uint32_t)i, rk0[0], rk0[1], rk0[2], rk0[3], d);
+        philox_normal4(e >> 2, 1u + (uint32_t)i, rk0[0], rk0[1], rk0[2], rk0[3], d);
         nz = f32x4{d[0], d[1], d[2], d[3]};
       }
     }

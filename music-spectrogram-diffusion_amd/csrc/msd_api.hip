@@ -177,7 +177,8 @@ struct msd_model {
   float* eps = nullptr;
   float* z = nullptr;
   const float** d_noise_slot = nullptr;
-  uint32_t* d_rng_key = nullptr;       // {seed_lo, seed_hi, stream_lo, stream_hi, generator kind, PRNGKey(seed) words} of the current msd_sample (elementwise.h SamplerParams::rng_key, kRng*)
+  uint32_t* d_rng_key = nullptr;       // [Bmax] rows of {seed_lo, seed_hi, stream_lo, stream_hi, generator kind, PRNGKey(seed) words, per-row mode} of the current msd_sample: one row per row of z (elementwise.h SamplerParams::rng_key, kRng*)
+  std::vector<uint32_t> h_rng_key;     // host staging of the rows just uploaded
   int* d_step = nullptr;       // [2]
   int* d_nkeys_self = nullptr; // [passes*Bmax] = T
   int* d_nkeys_cross = nullptr;// [n_cross][Bmax] valid keys per key region and song
@@ -1422,6 +1423,7 @@ void enqueue_step(Ctx& c, const StepPlan& p) {
   SamplerParams sp;
   sp.eps = m->eps; sp.z = m->z; sp.noise_slot = m->d_noise_slot; sp.coef = m->d_coef; sp.rng_key = m->d_rng_key;
   sp.step_ptr = m->d_step; sp.n = p.batch * m->T * m->ND; sp.passes = p.P;
+  if (m->T * m->ND % kRngRowBlock == 0) sp.row_blocks = m->T * m->ND / kRngRowBlock;   // (else: table row 0 only, msd_sample_rows refuses)
   sp.cond_wt = m->cfg.cfg_weight; sp.clip_x0 = m->cfg.clip_x0;
   sp.ddim = m->cfg.sampler == MSD_SAMPLER_DDIM;
   sp.model_output = m->cfg.model_output;
@@ -1581,7 +1583,7 @@ int msd_create(const msd_config* cfg, msd_model** out) {
   TRY(dalloc(m, &m->eps, Mmax * m->ND));
   TRY(dalloc(m, &m->z, (size_t)m->Bmax * T * m->ND));
   TRY(dalloc(m, &m->d_noise_slot, 1));
-  TRY(dalloc(m, &m->d_rng_key, kRngWords));
+  TRY(dalloc(m, &m->d_rng_key, (size_t)m->Bmax * kRngWords));
   TRY(dalloc(m, &m->d_step, 2));
   TRY(dalloc(m, &m->d_absmax, 1));
   TRY(dalloc(m, &m->d_sat, 1));
@@ -1848,13 +1850,35 @@ int msd_op_threefry(int stage, uint64_t seed, int64_t fold, const uint32_t* bits
   return threefry_fill(stage, seed, fold, bits_in_dev, out_dev, n, static_cast<hipStream_t>(stream));
 }
 
-// the words the sampler kernel's own draw reads (SamplerParams::rng_key): EVERY place that launches the step with a
-// NULL noise slot writes all of them, the generator kind included
-static void fill_rng_key(uint32_t (&key)[kRngWords], int rng, uint64_t seed, uint64_t stream_id) {
+// the words the sampler kernel's own draw reads (one row of SamplerParams::rng_key): EVERY place that launches the step
+// with a NULL noise slot writes all of them for every row of z, the generator kind and the mode included
+static void fill_rng_key(uint32_t* key, int rng, uint64_t seed, uint64_t stream_id, bool per_row) {
   const uint32_t k[kRngWords] = {(uint32_t)seed, (uint32_t)(seed >> 32), (uint32_t)stream_id, (uint32_t)(stream_id >> 32),
-                                 (uint32_t)rng, (uint32_t)(seed >> 32), (uint32_t)seed, 0u};
+                                 (uint32_t)rng, (uint32_t)(seed >> 32), (uint32_t)seed, per_row ? 1u : 0u};
   memcpy(key, k, sizeof(k));
 }
+
+// The generator keys of one sampling call: ONE (seed, stream_id) for a draw over the whole [batch, T, n] array
+// (msd_sample, msd_sample_rng), or one per row (msd_sample_rows; stream_ids may be NULL = zeros).
+struct SampleKeys {
+  uint64_t seed = 0, stream_id = 0;
+  const uint64_t* seeds = nullptr;
+  const uint64_t* stream_ids = nullptr;
+  bool per_row() const { return seeds != nullptr; }
+  uint64_t seed_of(int b) const { return seeds ? seeds[b] : seed; }
+  uint64_t stream_of(int b) const { return seeds ? (stream_ids ? stream_ids[b] : 0) : stream_id; }
+};
+
+// the key table of a call over `batch` rows of z (whole-array draw: every row holds the one key)
+static hipError_t upload_rng_keys(msd_model* m, int batch, int rng, const SampleKeys& keys, hipStream_t s) {
+  m->h_rng_key.resize((size_t)batch * kRngWords);   // a member: the copy below may still read it when this returns
+  for (int b = 0; b < batch; ++b)
+    fill_rng_key(&m->h_rng_key[(size_t)b * kRngWords], rng, keys.seed_of(b), keys.stream_of(b), keys.per_row());
+  return hipMemcpyAsync(m->d_rng_key, m->h_rng_key.data(), m->h_rng_key.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s);
+}
+
+static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys, const float* init_z_dev,
+                       const float* noise_dev, float* out_dev, void* stream);
 
 int msd_sample(msd_model* m, int batch, uint64_t seed, uint64_t stream_id, const float* init_z_dev,
                const float* noise_dev, float* out_dev, void* stream) {
@@ -1863,11 +1887,30 @@ int msd_sample(msd_model* m, int batch, uint64_t seed, uint64_t stream_id, const
 
 int msd_sample_rng(msd_model* m, int batch, int rng, uint64_t seed, uint64_t stream_id, const float* init_z_dev,
                    const float* noise_dev, float* out_dev, void* stream) {
+  SampleKeys keys;
+  keys.seed = seed; keys.stream_id = stream_id;
+  return sample_body(m, batch, rng, keys, init_z_dev, noise_dev, out_dev, stream);
+}
+
+int msd_sample_rows(msd_model* m, int batch, int rng, const uint64_t* seeds, const uint64_t* stream_ids,
+                    const float* init_z_dev, const float* noise_dev, float* out_dev, void* stream) {
+  if (!m) return MSD_ERR_INVALID_ARGUMENT;
+  if (!seeds) return fail(m, MSD_ERR_INVALID_ARGUMENT, "seeds is null");
+  SampleKeys keys;
+  keys.seeds = seeds; keys.stream_ids = stream_ids;
+  return sample_body(m, batch, rng, keys, init_z_dev, noise_dev, out_dev, stream);
+}
+
+static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys, const float* init_z_dev,
+                       const float* noise_dev, float* out_dev, void* stream) {
   if (!m) return MSD_ERR_INVALID_ARGUMENT;
   if (rng != MSD_RNG_PHILOX && rng != MSD_RNG_THREEFRY) return fail(m, MSD_ERR_INVALID_ARGUMENT, "unknown rng %d", rng);
   if (!m->encoded) return fail(m, MSD_ERR_BAD_STATE, "msd_encode has not run");
   if (batch != m->encoded_batch) return fail(m, MSD_ERR_INVALID_ARGUMENT, "batch %d != encoded batch %d", batch, m->encoded_batch);
   if (!out_dev) return fail(m, MSD_ERR_INVALID_ARGUMENT, "out is null");
+  const int64_t row_n = (int64_t)m->T * m->ND;
+  if (keys.per_row() && row_n % kRngRowBlock)   // a block of the sampler launch would straddle two rows' keys
+    return fail(m, MSD_ERR_UNSUPPORTED, "per-row keys need targets_length * n_dims %% %d == 0 (got %lld)", (int)kRngRowBlock, (long long)row_n);
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool null_stream = (s == nullptr);
   if (null_stream) {
@@ -1883,9 +1926,15 @@ int msd_sample_rng(msd_model* m, int batch, int rng, uint64_t seed, uint64_t str
   if (init_z_dev) {
     HIP_TRY(m, hipMemcpyAsync(m->z, init_z_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
   } else {
-    int rc = rng == MSD_RNG_THREEFRY ? msd_fill_normal_threefry(seed, -1, m->z, n, s)   // normal(PRNGKey(seed), [batch, T, n])
-                                     : msd_fill_normal(seed, stream_id, 0, m->z, n, s);
-    if (rc) return fail(m, rc, "init_z fill failed");
+    // one fill over the whole array, or -- per-row keys -- one per row over its T * n elements under its own key
+    const int fills = keys.per_row() ? batch : 1;
+    const int64_t fill_n = keys.per_row() ? row_n : n;
+    for (int b = 0; b < fills; ++b) {
+      float* zb = m->z + b * fill_n;
+      int rc = rng == MSD_RNG_THREEFRY ? msd_fill_normal_threefry(keys.seed_of(b), -1, zb, fill_n, s)   // normal(PRNGKey(seed), [batch | 1, T, n])
+                                       : msd_fill_normal(keys.seed_of(b), keys.stream_of(b), 0, zb, fill_n, s);
+      if (rc) return fail(m, rc, "init_z fill failed");
+    }
   }
   split_z(m, n, s);
   // Step noise: the caller's buffer, or -- noise_dev == NULL -- drawn INSIDE sampler_step_kernel (round 6): step i's draw is
@@ -1894,10 +1943,10 @@ int msd_sample_rng(msd_model* m, int batch, int rng, uint64_t seed, uint64_t str
   // function, same counters: bit-identical to the buffered form (tests/test_gpu_model.py).  The slot holds NULL then.
   // MSD_RNG_THREEFRY: step i's draw is normal(fold_in(PRNGKey(seed), i), [batch, T, n]) instead, what
   // msd_fill_normal_threefry(seed, i, ...) writes; the kind travels in device memory, so the captured graphs below serve both.
+  // Per-row keys: row b of z draws under row b of the key table what a ONE-row call (seed_b, stream_b) draws; the mode
+  // is a word of that table too, so the same graphs serve it.
   const float* noise = noise_dev;
-  uint32_t key[kRngWords];
-  fill_rng_key(key, rng, seed, stream_id);
-  HIP_TRY(m, hipMemcpyAsync(m->d_rng_key, key, sizeof(key), hipMemcpyHostToDevice, s));
+  HIP_TRY(m, upload_rng_keys(m, batch, rng, keys, s));
   // arrival counters of the in-launch merge: zero between launches by construction (the reducer resets its own); once
   // per call in case an aborted launch left a count behind
   HIP_TRY(m, hipMemsetAsync(m->att_tickets, 0, (size_t)m->att_ticket_count * sizeof(int), s));
@@ -2054,9 +2103,9 @@ int msd_profile_steps(msd_model* m, int batch, int n_steps, const char* const** 
   if (rc) return rc;
   split_z(m, n, s);
   const float* noise = nullptr;   // the sampler kernel draws the steps' noise itself (Philox stream (1, 0): elementwise.h)
-  uint32_t key[kRngWords];
-  fill_rng_key(key, kRngPhilox, 1, 0);
-  HIP_TRY(m, hipMemcpyAsync(m->d_rng_key, key, sizeof(key), hipMemcpyHostToDevice, s));
+  SampleKeys keys;
+  keys.seed = 1;
+  HIP_TRY(m, upload_rng_keys(m, batch, kRngPhilox, keys, s));
   HIP_TRY(m, hipMemcpyAsync(m->d_noise_slot, &noise, sizeof(float*), hipMemcpyHostToDevice, s));
   const int start[2] = {m->N - 1, m->N - 1};
   HIP_TRY(m, hipMemcpyAsync(m->d_step, start, sizeof(start), hipMemcpyHostToDevice, s));
@@ -2299,7 +2348,7 @@ int msd_op_sampler_step(const msd_config* cfg, int step_index, const float* z_de
   float* noise = sc.get<float>((size_t)n);   // one step's draw (zeros) when the caller gives none
   const float** slot = sc.get<const float*>(1);
   int* step = sc.get<int>(2);
-  uint32_t* key = sc.get<uint32_t>(kRngWords);   // the kernel fetches the words of its own draw up front, used or not
+  uint32_t* key = sc.get<uint32_t>(kRngWords);   // the kernel fetches the words of its own draw up front, used or not (table row 0: SamplerParams::row_blocks' default)
   if (!coef || !eps || !noise || !slot || !step || !key) return MSD_ERR_HIP;
   // the kernel indexes noise as base + i * n: hand it base = draw - i * n
   const float* base = (noise_dev ? noise_dev : noise) - (size_t)step_index * n;

@@ -372,13 +372,19 @@ class InferenceModel(object):
     return self._vocoder
 
   # -- predict (inference.py:200-203) -----------------------------------------------
-  def predict(self, batch: Mapping[str, Any], seed: int = 0, segment: int = 0,
+  def predict(self, batch: Mapping[str, Any], seed: Union[int, Sequence[int]] = 0,
+              segment: Union[int, Sequence[int]] = 0,
               init_z=None, noise=None, return_torch: bool = False, rng: Optional[str] = None):
     """Predict one batch of 256-frame segments.
 
     batch: the model features of inference.py:113-136 (NumPy arrays or torch
       tensors); ``decoder_target_tokens`` is used for its shape only.
-    seed / segment: key of the Philox generator (replaces PRNGKey(seed)).
+    seed / segment: key of the Philox generator (replaces PRNGKey(seed)).  Scalars key ONE draw over the whole
+      [B,T,n] array (row b of a batched call is then not the draw of any one-row call).  Either may be a sequence of
+      B integers (a scalar beside it is broadcast): every row is keyed by its own (seed[b], segment[b]) and draws,
+      bit for bit, what the one-row call predict(row b, seed=seed[b], segment=segment[b]) draws -- independent
+      segments share one call (msd_sample_rows; predict_sequence(batch_segments=) drives it).  In the 'threefry' and
+      'jax' modes row b draws what the reference draws for PRNGKey(seed[b]) and a batch of one.
     init_z [B,T,n] / noise [N,B,T,n]: explicit draws (the parity contract).
     rng: None = the model's default (InferenceModel(rng=), 'philox' unless given).
       'philox': the library's device generator, one stream per segment.
@@ -442,8 +448,11 @@ class InferenceModel(object):
       nm.encode(b, tokens, ctx, mask, stream=s)
       t1 = time.perf_counter()
       out = torch.empty((b, t, n), dtype=torch.float32, device=dev)
+      per_row = not (np.isscalar(seed) and np.isscalar(segment))
+      if per_row:
+        seed, segment = native.row_keys(b, seed, segment)
       if rng == 'jax' and init_z is None and noise is None:
-        init_z, noise = self._jax_noise(seed, b)
+        init_z, noise = self._jax_noise_rows(seed) if per_row else self._jax_noise(seed, b)
       elif rng not in RNG_MODES:
         raise ValueError('rng must be one of %s: %r' % (RNG_MODES, rng))
       z0 = None if init_z is None else _to_device(torch, init_z, dev, torch.float32)
@@ -475,11 +484,24 @@ class InferenceModel(object):
       self._jax_noise_key = key
     return self._jax_noise_val
 
+  def _jax_noise_rows(self, seeds: Sequence[int]):
+    """(init_z [B,T,n], noise [N,B,T,n]) whose row b is the one-row host draw of seeds[b]: one draw per distinct seed."""
+    from . import jax_random
+    torch = self._torch
+    t, n = self.targets_length, self.audio_codec.n_dims
+    steps = self.spec.diffusion.sampler.schedule.num_steps
+    drawn = {}
+    for sd in seeds:
+      if sd not in drawn:
+        z, nz = jax_random.reference_noise(sd, (1, t, n), steps)
+        drawn[sd] = (torch.as_tensor(z).to(self.device), torch.as_tensor(nz).to(self.device))
+    return (torch.cat([drawn[sd][0] for sd in seeds], dim=0), torch.cat([drawn[sd][1] for sd in seeds], dim=1))
+
   # -- InferSong.process segment loop (beam/evaluation.py:161-223) ---------------------
   def predict_sequence(self, segments_tokens: Sequence[np.ndarray], seed: int = 0,
                        always_mask_context: bool = False, init_context: Optional[np.ndarray] = None,
                        first_segment_index: int = 0, return_timing: bool = False, rng: Optional[str] = None,
-                       return_torch: bool = False):
+                       return_torch: bool = False, batch_segments: int = 1):
     """Synthesize a whole song: segments of int32 [inputs_length] (or [1, L]).
 
     Segment 0 runs with context zeros + mask 0 (beam/evaluation.py:195-198);
@@ -490,7 +512,18 @@ class InferenceModel(object):
     Returns float32 [1, T*K, n] (NumPy; with ``return_torch`` the device tensor, so that the
     hand-off message never leaves the GPU); with ``return_timing`` also a dict with the
     reference's own metric (evaluation.py:217-220,244-250).
+
+    ``batch_segments`` = B > 1 sends consecutive groups of B segments (the last group smaller) through ONE predict
+    each, row j keyed (seed, first_segment_index + its index): the noise, and so the result up to the rounding of a
+    batched launch, is what the loop gives that segment.  Only where the segments are independent of each other: a
+    model without context (models/diffusion/models.py:167-199), or ``always_mask_context`` (the context is zeros with
+    mask 0 then: a masked context contributes nothing, whatever its values).  Anything else, B > batch_size, or
+    ``init_context`` with B > 1 is a ValueError.  The timing is group seconds / group rows, averaged over all groups
+    but the first (the loop leaves out its first segment the same way).
     """
+    if batch_segments != 1:
+      return self._predict_sequence_batched(segments_tokens, seed, always_mask_context, init_context,
+                                            first_segment_index, return_timing, rng, return_torch, batch_segments)
     torch = self._torch
     n = self.audio_codec.n_dims
     c_len = self.targets_context_length
@@ -520,10 +553,56 @@ class InferenceModel(object):
       full = full.cpu().numpy()
     if not return_timing:
       return full
+    return full, self._sequence_timing(seconds)
+
+  def _sequence_timing(self, seconds: Sequence[float]) -> Dict[str, float]:
     seconds_per_chunk = self.targets_length * (self.audio_codec.hop_size / self.audio_codec.sample_rate)
     per_chunk = float(np.mean(seconds)) if seconds else float('nan')
-    return full, {'prediction_seconds_per_chunk': per_chunk,
-                  'predictions_seconds_per_audio_second': per_chunk / seconds_per_chunk}
+    return {'prediction_seconds_per_chunk': per_chunk,
+            'predictions_seconds_per_audio_second': per_chunk / seconds_per_chunk}
+
+  def check_batch_segments(self, batch_segments: int, always_mask_context: bool = False, init_context=None):
+    """ValueError unless predict_sequence(batch_segments=) may run with these options (no device needed)."""
+    if int(batch_segments) != batch_segments or batch_segments < 1:
+      raise ValueError('batch_segments must be a positive integer: %r' % (batch_segments,))
+    if batch_segments == 1:
+      return
+    if self.targets_context_length is not None and not always_mask_context:
+      raise ValueError('batch_segments=%d needs independent segments: this model conditions every segment on the '
+                       'previous prediction; pass always_mask_context=True or use a model without context'
+                       % batch_segments)
+    if batch_segments > self.batch_size:
+      raise ValueError('batch_segments=%d exceeds batch_size %d' % (batch_segments, self.batch_size))
+    if init_context is not None:
+      raise ValueError('init_context cannot be combined with batch_segments > 1 (every row runs with a masked context)')
+
+  def _predict_sequence_batched(self, segments_tokens, seed, always_mask_context, init_context, first_segment_index,
+                                return_timing, rng, return_torch, batch_segments):
+    self.check_batch_segments(batch_segments, always_mask_context, init_context)
+    torch = self._torch
+    n = self.audio_codec.n_dims
+    c_len = self.targets_context_length
+    segs = [np.asarray(t, np.int32).reshape(1, -1) for t in segments_tokens]
+    outs, seconds = [], []
+    for g0 in range(0, len(segs), batch_segments):
+      rows = segs[g0:g0 + batch_segments]
+      b = len(rows)
+      batch = {'encoder_input_tokens': np.concatenate(rows, axis=0)}
+      if c_len is not None:
+        batch['encoder_continuous_inputs'] = torch.zeros((b, c_len, n), dtype=torch.float32, device=self.device)
+        batch['encoder_continuous_mask'] = np.zeros((b, c_len), np.int32)
+      tick = time.perf_counter()
+      out, _ = self.predict(batch, seed=seed, segment=[first_segment_index + g0 + j for j in range(b)],
+                            return_torch=True, rng=rng)
+      if g0 != 0:
+        seconds.append((time.perf_counter() - tick) / b)
+      outs.append(out[:b].reshape(1, -1, n))
+    full = torch.cat(outs, dim=1)
+    if not return_torch:
+      full = full.cpu().numpy()
+    if not return_timing:
+      return full
+    return full, self._sequence_timing(seconds)
 
 
   # ---- MIDI in (SURVEY 8(f) N1) -----------------------------------------------------

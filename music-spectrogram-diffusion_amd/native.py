@@ -59,7 +59,9 @@ EXPORTED_SYMBOLS = (
     'msd_op_qkv', 'msd_op_final_proj', 'msd_sample_rng', 'msd_fill_normal_threefry', 'msd_op_threefry',
     # (appended to ABI 7) the device vocoder
     'msd_vocoder_create', 'msd_vocoder_destroy', 'msd_vocoder_last_error', 'msd_vocoder_stft', 'msd_vocoder_istft',
-    'msd_vocoder_encode', 'msd_vocoder_decode')
+    'msd_vocoder_encode', 'msd_vocoder_decode',
+    # (appended to ABI 7) one generator key per row of a batched call
+    'msd_sample_rows')
 
 
 class NativeLibraryError(RuntimeError):
@@ -167,6 +169,8 @@ def load(planes: str = 'f16') -> ctypes.CDLL:
   lib.msd_fill_normal.argtypes = [u64, u64, u32, vp, i64, vp]
   if 'msd_sample_rng' in present:
     lib.msd_sample_rng.argtypes = [vp, i32, i32, u64, u64, vp, vp, vp, vp]
+  if 'msd_sample_rows' in present:   # (appended to ABI 7)
+    lib.msd_sample_rows.argtypes = [vp, i32, i32, c.POINTER(u64), c.POINTER(u64), vp, vp, vp, vp]
   if 'msd_fill_normal_threefry' in present:
     lib.msd_fill_normal_threefry.argtypes = [u64, i64, vp, i64, vp]
   if 'msd_op_threefry' in present:
@@ -308,10 +312,18 @@ class NativeModel:
   def sample(self, batch: int, out, seed: int = 0, stream_id: int = 0, init_z=None,
              noise=None, stream: int = 0, rng: str = 'philox'):
     """rng: the generator of the draws that are not given -- 'philox' (the library's own, keyed by seed and stream_id)
-    or 'threefry' (the reference's jax.random draws for PRNGKey(seed), made on the device; stream_id is ignored)."""
+    or 'threefry' (the reference's jax.random draws for PRNGKey(seed), made on the device; stream_id is ignored).
+
+    seed / stream_id may be sequences of `batch` integers (a scalar beside a sequence is broadcast): every row then
+    has a key of its own and draws what the one-row call (seed[b], stream_id[b]) draws (msd_sample_rows).  Scalars
+    key ONE draw over the whole [batch, T, n] array, as before."""
     if rng not in RNGS:
       raise ValueError('rng must be one of %s: %r' % (sorted(RNGS), rng))
-    if rng == 'philox':   # (the entry point every ABI has: an older library under MSD_AMD_LIB still runs)
+    if not (np.isscalar(seed) and np.isscalar(stream_id)):
+      seeds, stream_ids = row_keys(batch, seed, stream_id)
+      rc = self.lib.msd_sample_rows(self.handle, batch, RNGS[rng], (ctypes.c_uint64 * batch)(*seeds),
+                                    (ctypes.c_uint64 * batch)(*stream_ids), _ptr(init_z), _ptr(noise), _ptr(out), stream)
+    elif rng == 'philox':   # (the entry point every ABI has: an older library under MSD_AMD_LIB still runs)
       rc = self.lib.msd_sample(self.handle, batch, seed, stream_id, _ptr(init_z), _ptr(noise), _ptr(out), stream)
     else:
       rc = self.lib.msd_sample_rng(self.handle, batch, RNGS[rng], seed, stream_id, _ptr(init_z), _ptr(noise),
@@ -360,6 +372,17 @@ class NativeModel:
       out[names[i].decode()] = (float(ms[i]), int(launches[i]))
       i += 1
     return out
+
+
+def row_keys(batch: int, seed, stream_id) -> Tuple[List[int], List[int]]:
+  """(seeds, stream_ids) of a call with per-row keys: each argument a sequence of `batch` integers, or a scalar that
+  is broadcast to every row."""
+  def rows(v, what):
+    v = [int(v)] * batch if np.isscalar(v) else [int(x) for x in v]
+    if len(v) != batch:
+      raise ValueError('%s has %d entries for a batch of %d' % (what, len(v), batch))
+    return v
+  return rows(seed, 'seed'), rows(stream_id, 'stream_id')
 
 
 def fill_normal(out, seed: int, stream_id: int, subseq: int, stream: int = 0):

@@ -5,11 +5,15 @@ beam/evaluation.py:161-223) on the MI355X path.
   python -m msd_amd.synthesize song.mid --checkpoint /path/to/base_with_context/checkpoint_500000 \\
       --out song_mel.npy [--preset base_with_context] [--gin-file train.gin --gin-bindings ...]
       [--seed 0] [--rng threefry|jax] [--num-steps 1000] [--dry-run]
+      [--batch-segments B [--always-mask-context]]
       [--wav song.wav [--vocoder-iters 32]] [--context-audio earlier.wav]
 
 --wav writes 16-bit PCM mono at 16 kHz from the device vocoder: Griffin-Lim over the codec's STFT, a stand-in for the
 reference's SoundStream decoder (which is not built).  --context-audio continues a recording: its last 256 frames are
 encoded on the device and given to the first segment as context.
+
+--batch-segments B sends B segments through every sampling call, each with the noise the one-by-one loop gives it; the
+segments must be independent of each other: a preset without context, or --always-mask-context.
 
 --dry-run tokenises only (no GPU): prints the segment / token statistics the synthesis would see."""
 from __future__ import annotations
@@ -46,6 +50,11 @@ def main(argv=None) -> int:
   ap.add_argument('--vocoder-iters', type=int, default=32, help='Griffin-Lim iterations of --wav')
   ap.add_argument('--context-audio', default=None,
                   help='16 kHz PCM .wav whose last context-length frames are encoded on the device as the first segment\'s context')
+  ap.add_argument('--batch-segments', type=int, default=1,
+                  help='segments per sampling call (the model is built with batch_size=B); needs independent segments: '
+                       'a preset without context, or --always-mask-context')
+  ap.add_argument('--always-mask-context', action='store_true',
+                  help='no segment sees the previous prediction (beam/evaluation.py:66-68)')
   ap.add_argument('--on-too-long', choices=['error', 'truncate'], default='error')
   ap.add_argument('--dry-run', action='store_true')
   args = ap.parse_args(argv)
@@ -67,7 +76,12 @@ def main(argv=None) -> int:
            float(np.mean(n_tok)), max(n_tok), t_tok), file=sys.stderr)
   if args.dry_run:
     return 0
-  model = msd_amd.InferenceModel(args.checkpoint, spec, precision=args.precision, range_fallback=args.range_fallback)
+  model = msd_amd.InferenceModel(args.checkpoint, spec, batch_size=max(args.batch_segments, 1), precision=args.precision,
+                                 range_fallback=args.range_fallback)
+  try:   # (before any sampling, and before the context recording is read)
+    model.check_batch_segments(args.batch_segments, args.always_mask_context, args.context_audio)
+  except ValueError as e:
+    ap.error(str(e))
   init_context = None
   if args.context_audio:
     if model.targets_context_length is None:
@@ -75,7 +89,8 @@ def main(argv=None) -> int:
     from msd_amd import vocoder
     init_context = context_from_audio(model, vocoder.read_wav(args.context_audio, model.audio_codec.sample_rate))
   mel, timing = model.predict_sequence(segments, seed=args.seed, rng=args.rng, return_timing=True, init_context=init_context,
-                                       return_torch=True)
+                                       return_torch=True, always_mask_context=args.always_mask_context,
+                                       batch_segments=args.batch_segments)
   mel_dev, mel = mel, mel.cpu().numpy()
   frames = int(np.ceil(ns.total_time * cfg.frame_rate))
   mel = mel[0, :max(frames, 1)]
