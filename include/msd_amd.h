@@ -44,7 +44,8 @@ extern "C" {
 #define MSD_AMD_ABI_VERSION 7   /* 7: msd_sample_rng, msd_fill_normal_threefry, msd_op_threefry (the reference's Threefry draws on the
                                       device); msd_config unchanged.  Appended to ABI 7 (no version bump): the msd_vocoder_*
                                       entry points (device STFT pair, Audio2Mel, Griffin-Lim); msd_sample_rows (one
-                                      generator key per row of a batched call).
+                                      generator key per row of a batched call); msd_sample_keep and
+                                      msd_op_sampler_step_keep (known frames in the sampler).
                                    6: cross_merge_in_launch, cross_q_fold, mlp_in_persistent appended to msd_config.
                                    5: dedup_layer0, cross_key_split, keep_raw_weights, kv_touch_ahead appended to msd_config.
                                    4: every caller-selectable knob is a msd_config field (attn_q_planes / attn_p_planes
@@ -289,6 +290,27 @@ int msd_sample_rng(msd_model* m, int batch, int rng, uint64_t seed, uint64_t str
 int msd_sample_rows(msd_model* m, int batch, int rng, const uint64_t* seeds, const uint64_t* stream_ids,
                     const float* init_z_dev, const float* noise_dev, float* out_dev, void* stream);
 
+/* (appended to ABI 7) Sampling with KNOWN frames: regenerate part of a segment and keep the rest (x0-replacement).
+ *   known_dev  float [batch,T,n] mel units (device): the frames to keep; the values of the other frames are not used
+ *   keep_mask  int32 [batch,T], host or device: non-zero = frame t of row b is known.  Per frame only.
+ * The known mel is brought to model units as the context is (scale_features(clip=True)): xk.  In EVERY scan step, after
+ * the CFG combine and after the clip_x0 branch, the kept elements get
+ *     pred_x0 := xk     pred_eps := predict_eps_from_x0(z_t, xk, logsnr_t)
+ * and the ordinary ddpm_step / ddim_step runs: they follow the posterior q(z_s | z_t, x0 = xk), carry the noise level of
+ * their step (the free frames see them through self-attention at that level) and arrive at xk at scan index 0.  init_z
+ * and every noise draw are what the call without a mask makes; no resampling jumps (RePaint) are made.  out_dev gets the
+ * CALLER's values on kept frames, bit for bit (also values outside the codec's range, which xk clips), and the sampled
+ * mel on the others.  An all-zero mask gives msd_sample_rng's / msd_sample_rows' result bit for bit.
+ *   per_row = 0: ONE draw over the whole array under (seeds[0], stream_ids[0]) -- msd_sample_rng's keying
+ *   per_row != 0: msd_sample_rows' keying, seeds / stream_ids host uint64 [batch]
+ *   stream_ids may be NULL (zeros); seeds, known_dev or keep_mask NULL is MSD_ERR_INVALID_ARGUMENT
+ * Every other argument, check and status is theirs; n_dims % 4 != 0 is MSD_ERR_UNSUPPORTED.  The scaled mel and the flags
+ * live in buffers the handle owns (allocated by the first such call); the step graphs of this form are captured and
+ * cached beside the plain ones, by (step plan, keep): plain calls before and after replay their own graphs unchanged. */
+int msd_sample_keep(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
+                    const float* init_z_dev, const float* noise_dev, const float* known_dev, const int32_t* keep_mask,
+                    float* out_dev, void* stream);
+
 /* Drop the captured hipGraph of the DDPM step; the next msd_sample captures it again. */
 int msd_reset_graph(msd_model* m);
 
@@ -376,6 +398,15 @@ int msd_op_attention_ex(int precision, int qp, int ksplit, int merge_in_launch, 
 int msd_op_sampler_step(const msd_config* cfg, int step_index, const float* z_dev,
                         const float* out_cond_dev, const float* out_uncond_dev,
                         const float* noise_dev, float* z_out_dev, int64_t n, void* stream);
+
+/* (appended to ABI 7) msd_op_sampler_step with known frames (msd_sample_keep's update): element e belongs to frame
+ * e / n_dims; where keep_mask_dev[frame] != 0, pred_x0 := known_scaled_dev[e] (MODEL units, [-1, 1]) and pred_eps follows
+ * from it, after the CFG combine and the clip; the other elements are msd_op_sampler_step's, bit for bit.
+ *   known_scaled_dev float [n]; keep_mask_dev int32 [n / n_dims] (device); n_dims % 4 == 0, n % n_dims == 0 */
+int msd_op_sampler_step_keep(const msd_config* cfg, int step_index, const float* z_dev,
+                             const float* out_cond_dev, const float* out_uncond_dev,
+                             const float* noise_dev, const float* known_scaled_dev, const int32_t* keep_mask_dev,
+                             int n_dims, float* z_out_dev, int64_t n, void* stream);
 
 /* x_out = x_in + a.w1 ; h_out = (RMSNorm(x_out; gamma) (.) (film_scale+1) + film_bias) . w2
  * (layers.py:632-666 + the Dense that follows).  folded=1: the decoder's folded-norm epilogues

@@ -286,6 +286,15 @@ struct SamplerParams {
   unsigned sat_tag = 1;
 };
 
+// The keep form's arguments (msd_sample_keep): frames of the target that are KNOWN.  A struct of its own, so that the
+// plain instances' argument block stays at its 120 bytes -- two of the 64-byte lines warm_kernargs counts in, one 128-byte
+// cache line -- and their code is what it was; the keep form's 144 bytes take a third 64-byte line.
+struct SamplerKeepParams : SamplerParams {
+  const float* xk = nullptr;     // [n] the known mel in model units (scale_clip_kernel of the caller's mel)
+  const int32_t* keep = nullptr; // [n / n_dims] per frame: non-zero = its n_dims elements are known
+  int n_dims = 0;                // elements per frame, % 4 == 0: a thread's four elements lie in one frame
+};
+
 // model output -> (eps, x0) at the TRAIN schedule's log-SNR (diffusion_utils.py:288-322)
 template <int mode>
 __device__ __forceinline__ void convert_model_output(const float (&c)[kCoefCount], float z, float o,
@@ -327,11 +336,76 @@ __device__ __forceinline__ float sampler_update(const SamplerParams& p, const fl
   return (i == 0) ? x0 : zs;
 }
 
+// The update with KNOWN frames (msd_sample_keep): sampler_update plus x0-replacement.  On a kept element (kf, xk = its
+// known value in model units), after the CFG combine and the clip: pred_x0 := xk, pred_eps := predict_eps_from_x0(z_t, xk,
+// logsnr_t) -- the clip branch's expression -- and the ordinary step: the element follows the posterior
+// q(z_s | z_t, x0 = xk) and arrives at xk at i == 0.
+//
+// Why this is a second text and not a branch inside sampler_update: a zero keep mask has to give the plain form's BITS,
+// and which products the compiler fuses into which sums is its own choice per compilation -- with the replacement as an
+// `if constexpr` inside the one function the DDPM line came out as fma(std, nz, a z + b x0) in the plain instances and as
+// fma(b, x0, a z) + std nz in the keep instances (measured on the MI355X: 26 % of the free elements off by an ulp or
+// more), and routing both through shared helpers moved the plain instances' code.  So sampler_update stays the text it
+// was -- its instances are instruction for instruction what they were before there was a keep form -- and this function
+// WRITES OUT the operations that text compiles to, with contraction off: every difference of a product fused
+// (fma(-a, b, c)), the CFG combine as two rounded products and a sum, the DDPM line as fma(std, nz, (a z) + (b x0)), the
+// DDIM line as fma(sigma, eps, alpha x0); v mode: alpha z - sigma v with both products rounded in the conditional pass
+// and the second fused in the unconditional one (that pass reuses the first product).  tests/test_gpu_keep_frames.py
+// holds the two together bit for bit on thirteen combinations of the branches (OP_CASES there); should a compiler choose otherwise for sampler_update, those
+// tests fail and this function follows it.
+template <int mode>
+__device__ __forceinline__ void convert_model_output_pinned(const float (&c)[kCoefCount], float z, float o,
+                                                            float& eps, float& x0, bool uncond) {
+#pragma clang fp contract(off)
+  if constexpr (mode == kOutEps) {
+    eps = o;
+    x0 = c[kCoefMX0Scale] * fmaf(-o, c[kCoefMX0Eps], z);
+  } else if constexpr (mode == kOutX0) {
+    x0 = o;
+    eps = c[kCoefMEpsScale] * fmaf(-o, c[kCoefMEpsX0], z);
+  } else {
+    const float az = c[kCoefMAlpha] * z;
+    x0 = uncond ? fmaf(-o, c[kCoefMSigma], az) : az - c[kCoefMSigma] * o;
+    eps = c[kCoefMEpsScale] * fmaf(-x0, c[kCoefMEpsX0], z);
+  }
+}
+
+template <int MODE>
+__device__ __forceinline__ float sampler_update_keep(const SamplerParams& p, const float (&c)[kCoefCount], int i, float z,
+                                                     float o_c, float o_u, float nz, float xk, bool kf) {
+#pragma clang fp contract(off)
+  float eps, x0;
+  convert_model_output_pinned<MODE>(c, z, o_c, eps, x0, /*uncond=*/false);
+  if (p.passes == 2) {
+    float eps_u, x0_u;
+    convert_model_output_pinned<MODE>(c, z, o_u, eps_u, x0_u, /*uncond=*/true);
+    eps = p.cond_wt * eps + (1.0f - p.cond_wt) * eps_u;
+    x0 = c[kCoefX0Scale] * fmaf(-eps, c[kCoefX0Eps], z);
+  }
+  if (p.clip_x0) {
+    x0 = x0 < -1.0f ? -1.0f : (x0 > 1.0f ? 1.0f : x0);   // (jnp.clip semantics, as in sampler_update)
+    eps = c[kCoefEpsScale] * fmaf(-x0, c[kCoefEpsX0], z);
+  }
+  if (kf) {
+    x0 = xk;
+    eps = c[kCoefEpsScale] * fmaf(-xk, c[kCoefEpsX0], z);
+  }
+  float zs;
+  if (p.ddim) zs = fmaf(c[kCoefSigmaS], eps, c[kCoefAlphaS] * x0);
+  else zs = fmaf(c[kCoefStd], nz, c[kCoefMeanZ] * z + c[kCoefMeanX0] * x0);
+  return (i == 0) ? x0 : zs;
+}
+
 // MODE = p.model_output as a compile-time constant: with the run-time switch the conversions' two results travelled
 // through scratch memory and a maze of scalar branches (885 lines of ISA for an elementwise kernel)
-template <int MODE>
-__global__ void __launch_bounds__(256) sampler_step_kernel(SamplerParams p) {
-  warm_kernargs<kernarg_lines<SamplerParams>()>();
+// P = SamplerKeepParams: the keep form -- the frame flag and the known values are loaded with z / eps and handed to
+// sampler_update_keep.  One kernel for both, the difference under `if constexpr`: the plain instances' code is what it
+// was when there was no other form.
+template <int MODE, class P = SamplerParams>
+__global__ void __launch_bounds__(256) sampler_step_kernel(P p) {
+  constexpr bool KEEP = std::is_same<P, SamplerKeepParams>::value;
+  static_assert(KEEP || std::is_same<P, SamplerParams>::value, "SamplerParams or SamplerKeepParams");
+  warm_kernargs<kernarg_lines<P>()>();
   // step_from_slot1: the step's first kernel (in_proj) copied the index to slot 1 and nobody else
   // reads slot 0 any more in this step, so this launch may decrement slot 0 itself
   const int i = p.step_from_slot1 ? p.step_ptr[1] : p.step_ptr[0];
@@ -359,6 +433,12 @@ __global__ void __launch_bounds__(256) sampler_step_kernel(SamplerParams p) {
     const f32x4 ec = *reinterpret_cast<const f32x4*>(p.eps + idx);
     f32x4 eu = {0.f, 0.f, 0.f, 0.f}, nz = {0.f, 0.f, 0.f, 0.f};
     if (p.passes == 2) eu = *reinterpret_cast<const f32x4*>(p.eps + p.n + idx);
+    f32x4 xk = {0.f, 0.f, 0.f, 0.f};
+    int kf = 0;
+    if constexpr (KEEP) {
+      xk = *reinterpret_cast<const f32x4*>(p.xk + idx);
+      kf = p.keep[(uint32_t)idx / (uint32_t)p.n_dims];
+    }
     static_assert(kCoefCount == 20, "five 16-byte loads per row");
     f32x4 cr[5];
 #pragma unroll
@@ -390,7 +470,10 @@ __global__ void __launch_bounds__(256) sampler_step_kernel(SamplerParams p) {
     for (int k = 0; k < kCoefCount; ++k) c[k] = cr[k >> 2][k & 3];
     f32x4 out;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) out[k] = sampler_update<MODE>(p, c, i, zz[k], ec[k], eu[k], nz[k]);
+    for (int k = 0; k < 4; ++k) {
+      if constexpr (KEEP) out[k] = sampler_update_keep<MODE>(p, c, i, zz[k], ec[k], eu[k], nz[k], xk[k], kf != 0);
+      else out[k] = sampler_update<MODE>(p, c, i, zz[k], ec[k], eu[k], nz[k]);
+    }
     *reinterpret_cast<f32x4*>(p.z + idx) = out;
     if (p.z_hi) {
       uint32_t h[2], l[2];
@@ -417,6 +500,10 @@ inline void launch_sampler_step(const SamplerParams& sp, hipStream_t s) {
   else if (sp.model_output == kOutV) hipLaunchKernelGGL(sampler_step_kernel<kOutV>, grid, block, 0, s, sp);
   else hipLaunchKernelGGL(sampler_step_kernel<kOutEps>, grid, block, 0, s, sp);
 }
+// the keep form's launches: keep_frames_tail.h, which msd_api.hip includes last (the reason is written there)
+void launch_sampler_step(const SamplerKeepParams& sp, hipStream_t s);
+void launch_unscale_keep(const float* x0, const float* known, const int32_t* keep, float* out, int n, int n_dims, float fmin,
+                         float fmax, hipStream_t s);
 
 // g[step][slot][k] = gamma[k] * (film_scale[step][slot][k] + 1): the column multiplier of a
 // FiLM-modulated RMSNorm, tabulated for every step (folded-norm GEMM epilogues, gemm_h16.h)

@@ -179,6 +179,10 @@ struct msd_model {
   const float** d_noise_slot = nullptr;
   uint32_t* d_rng_key = nullptr;       // [Bmax] rows of {seed_lo, seed_hi, stream_lo, stream_hi, generator kind, PRNGKey(seed) words, per-row mode} of the current msd_sample: one row per row of z (elementwise.h SamplerParams::rng_key, kRng*)
   std::vector<uint32_t> h_rng_key;     // host staging of the rows just uploaded
+  // msd_sample_keep: the known mel in model units [Bmax][T][n] and its frame flags [Bmax][T]; allocated by the first
+  // keep call (outside stream capture) and owned by the handle, so the captured keep graphs hold stable addresses
+  float* keep_xk = nullptr;
+  int32_t* keep_flags = nullptr;
   int* d_step = nullptr;       // [2]
   int* d_nkeys_self = nullptr; // [passes*Bmax] = T
   int* d_nkeys_cross = nullptr;// [n_cross][Bmax] valid keys per key region and song
@@ -198,7 +202,9 @@ struct msd_model {
   // plan of a CFG step is a function of the handle's constants, the batch and the key counts msd_encode saw (they choose
   // the cross-attention's key splits, cross_split), and the launch sequence of a step is a function of the handle's
   // constants and the plan: equal plans, same graph.
-  struct StepGraphs { StepPlan plan; hipGraphExec_t exec = nullptr, exec1 = nullptr; };
+  // `keep`: the graphs of msd_sample_keep launch the sampler's keep form (other kernel, other arguments), so a set is
+  // looked up by (plan, keep) and a plain call never replays a keep graph, nor the other way round.
+  struct StepGraphs { StepPlan plan; bool keep = false; hipGraphExec_t exec = nullptr, exec1 = nullptr; };
   std::vector<StepGraphs> graphs;
   int graph_steps = 8;              // DDPM steps per graph launch (msd_config.graph_steps; 1 -> 4 -> 10: 1.2000 -> 1.1963 -> 1.1955 ms/step)
   bool prefetch = true;        // producers warm the next GEMM's weights (msd_config.weight_prefetch; default: by model size)
@@ -1417,10 +1423,11 @@ void decoder_eval(Ctx& c, const StepPlan& p, bool publish_step) {
 void split_z(msd_model* m, int64_t n, hipStream_t s) { split(m->z, m->zp, n, s, m->d_sat, (unsigned)KC_SAMPLER + 1u); }
 
 // one DDPM step of the CFG sampler: the decoder on plan_cfg_step's plan, then the sampler update
-void enqueue_step(Ctx& c, const StepPlan& p) {
+// keep: the sampler's keep form on the handle's known-frame buffers (msd_sample_keep)
+void enqueue_step(Ctx& c, const StepPlan& p, bool keep = false) {
   msd_model* m = c.m;
   decoder_eval(c, p, /*publish_step=*/true);
-  SamplerParams sp;
+  SamplerKeepParams sp;
   sp.eps = m->eps; sp.z = m->z; sp.noise_slot = m->d_noise_slot; sp.coef = m->d_coef; sp.rng_key = m->d_rng_key;
   sp.step_ptr = m->d_step; sp.n = p.batch * m->T * m->ND; sp.passes = p.P;
   if (m->T * m->ND % kRngRowBlock == 0) sp.row_blocks = m->T * m->ND / kRngRowBlock;   // (else: table row 0 only, msd_sample_rows refuses)
@@ -1432,7 +1439,12 @@ void enqueue_step(Ctx& c, const StepPlan& p) {
   sp.sat = m->d_sat; sp.sat_tag = (unsigned)KC_SAMPLER + 1u;
   c.begin(KC_SAMPLER);
   sp.step_from_slot1 = 1;
-  launch_sampler_step(sp, c.s);
+  if (keep) {
+    sp.xk = m->keep_xk; sp.keep = m->keep_flags; sp.n_dims = m->ND;
+    launch_sampler_step(sp, c.s);
+  } else {
+    launch_sampler_step(static_cast<const SamplerParams&>(sp), c.s);
+  }
   c.end(KC_SAMPLER);
 }
 
@@ -1877,8 +1889,14 @@ static hipError_t upload_rng_keys(msd_model* m, int batch, int rng, const Sample
   return hipMemcpyAsync(m->d_rng_key, m->h_rng_key.data(), m->h_rng_key.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s);
 }
 
+// The known frames of msd_sample_keep: the caller's mel [batch, T, n] (device) and frame flags [batch, T] (host or device)
+struct KeepFrames {
+  const float* known_dev = nullptr;
+  const int32_t* mask = nullptr;
+};
+
 static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys, const float* init_z_dev,
-                       const float* noise_dev, float* out_dev, void* stream);
+                       const float* noise_dev, float* out_dev, void* stream, const KeepFrames* keep = nullptr);
 
 int msd_sample(msd_model* m, int batch, uint64_t seed, uint64_t stream_id, const float* init_z_dev,
                const float* noise_dev, float* out_dev, void* stream) {
@@ -1901,8 +1919,22 @@ int msd_sample_rows(msd_model* m, int batch, int rng, const uint64_t* seeds, con
   return sample_body(m, batch, rng, keys, init_z_dev, noise_dev, out_dev, stream);
 }
 
+int msd_sample_keep(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
+                    const float* init_z_dev, const float* noise_dev, const float* known_dev, const int32_t* keep_mask,
+                    float* out_dev, void* stream) {
+  if (!m) return MSD_ERR_INVALID_ARGUMENT;
+  if (!seeds) return fail(m, MSD_ERR_INVALID_ARGUMENT, "seeds is null");
+  if (!known_dev || !keep_mask) return fail(m, MSD_ERR_INVALID_ARGUMENT, "known mel or keep mask is null");
+  SampleKeys keys;
+  if (per_row) { keys.seeds = seeds; keys.stream_ids = stream_ids; }
+  else { keys.seed = seeds[0]; keys.stream_id = stream_ids ? stream_ids[0] : 0; }
+  KeepFrames keep;
+  keep.known_dev = known_dev; keep.mask = keep_mask;
+  return sample_body(m, batch, rng, keys, init_z_dev, noise_dev, out_dev, stream, &keep);
+}
+
 static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys, const float* init_z_dev,
-                       const float* noise_dev, float* out_dev, void* stream) {
+                       const float* noise_dev, float* out_dev, void* stream, const KeepFrames* keep) {
   if (!m) return MSD_ERR_INVALID_ARGUMENT;
   if (rng != MSD_RNG_PHILOX && rng != MSD_RNG_THREEFRY) return fail(m, MSD_ERR_INVALID_ARGUMENT, "unknown rng %d", rng);
   if (!m->encoded) return fail(m, MSD_ERR_BAD_STATE, "msd_encode has not run");
@@ -1911,6 +1943,14 @@ static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys,
   const int64_t row_n = (int64_t)m->T * m->ND;
   if (keys.per_row() && row_n % kRngRowBlock)   // a block of the sampler launch would straddle two rows' keys
     return fail(m, MSD_ERR_UNSUPPORTED, "per-row keys need targets_length * n_dims %% %d == 0 (got %lld)", (int)kRngRowBlock, (long long)row_n);
+  if (keep && m->ND % 4)   // a thread of the sampler holds four consecutive elements and ONE frame flag
+    return fail(m, MSD_ERR_UNSUPPORTED, "kept frames need n_dims %% 4 == 0 (got %d)", m->ND);
+  // first keep call of the handle (nothing is being captured here); each buffer on its own, so that a call after a failed
+  // allocation tries again for the one that is missing
+  if (keep && !m->keep_xk)
+    if (int rc = dalloc(m, &m->keep_xk, (size_t)m->Bmax * row_n)) return rc;
+  if (keep && !m->keep_flags)
+    if (int rc = dalloc(m, &m->keep_flags, (size_t)m->Bmax * m->T)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool null_stream = (s == nullptr);
   if (null_stream) {
@@ -1937,6 +1977,13 @@ static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys,
     }
   }
   split_z(m, n, s);
+  if (keep) {
+    // the known mel enters the chain as the context does: scale_features(clip=True); init_z and the draws are untouched
+    hipLaunchKernelGGL(scale_clip_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, keep->known_dev, m->keep_xk,
+                       (int)n, m->cfg.feature_min, m->cfg.feature_max);
+    HIP_TRY(m, hipGetLastError());
+    HIP_TRY(m, hipMemcpyAsync(m->keep_flags, keep->mask, (size_t)batch * m->T * sizeof(int32_t), hipMemcpyDefault, s));
+  }
   // Step noise: the caller's buffer, or -- noise_dev == NULL -- drawn INSIDE sampler_step_kernel (round 6): step i's draw is
   // sub-sequence 1 + i of the (seed, stream_id) Philox stream, the row philox_normal_kernel used to write into an
   // [N][n] buffer up front (131 MB x songs at base, with a hipMalloc in here on the first call of a batch size).  Same
@@ -1962,7 +2009,7 @@ static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys,
     hipGraph_t graph = nullptr;
     HIP_TRY(m, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     Ctx c{m, s};
-    for (int k = 0; k < steps; ++k) enqueue_step(c, plan);
+    for (int k = 0; k < steps; ++k) enqueue_step(c, plan, keep != nullptr);
     hipError_t ce = hipStreamEndCapture(s, &graph);
     if (ce != hipSuccess || c.err != hipSuccess) {
       if (graph) (void)hipGraphDestroy(graph);
@@ -1976,11 +2023,12 @@ static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys,
   // the graphs captured with this plan (msd_model::StepGraphs)
   msd_model::StepGraphs* g = nullptr;
   for (auto& e : m->graphs)
-    if (memcmp(&e.plan, &plan, sizeof(plan)) == 0) g = &e;
+    if (e.keep == (keep != nullptr) && memcmp(&e.plan, &plan, sizeof(plan)) == 0) g = &e;
   if (!g) {
     if (m->graphs.size() >= 8) (void)msd_reset_graph(m);   // (a handle that cycles through more shapes than that re-captures)
     msd_model::StepGraphs ng;
     ng.plan = plan;
+    ng.keep = keep != nullptr;
     int rc = capture(m->graph_steps, &ng.exec);
     if (rc) return rc;
     if (m->graph_steps > 1 && m->N % m->graph_steps) {
@@ -1993,8 +2041,11 @@ static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys,
   for (int i = 0; i < m->N / m->graph_steps; ++i) HIP_TRY(m, hipGraphLaunch(g->exec, s));
   for (int i = 0; i < m->N % m->graph_steps; ++i)
     HIP_TRY(m, hipGraphLaunch(m->graph_steps > 1 ? g->exec1 : g->exec, s));
-  hipLaunchKernelGGL(unscale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, m->z, out_dev,
-                     (int)n, m->cfg.feature_min, m->cfg.feature_max);
+  if (keep)   // kept frames: the caller's own values, not a round trip through model units
+    launch_unscale_keep(m->z, keep->known_dev, m->keep_flags, out_dev, (int)n, m->ND, m->cfg.feature_min, m->cfg.feature_max, s);
+  else
+    hipLaunchKernelGGL(unscale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, m->z, out_dev,
+                       (int)n, m->cfg.feature_min, m->cfg.feature_max);
   HIP_TRY(m, hipGetLastError());
   // The call ends with ONE stream synchronisation (tens of microseconds against a ~1 s segment): behind it the
   // half-plane range flag is read, so that a bad run fails THIS call.
@@ -2330,9 +2381,10 @@ bool split_new(Scratch& sc, const float* in, int64_t n, Planes* out, hipStream_t
 }  // namespace
 }  // extern "C++"
 
-int msd_op_sampler_step(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
-                        const float* out_uncond_dev, const float* noise_dev, float* z_out_dev, int64_t n,
-                        void* stream) {
+// one launch of the sampler update on the caller's arrays; known_scaled_dev != NULL: the keep form
+static int op_sampler_step(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
+                           const float* out_uncond_dev, const float* noise_dev, const float* known_scaled_dev,
+                           const int32_t* keep_mask_dev, int n_dims, float* z_out_dev, int64_t n, void* stream) {
   if (!cfg || cfg->struct_size != (int32_t)sizeof(msd_config) || !z_dev || !out_cond_dev || !z_out_dev ||
       n <= 0 || n % 4 || step_index < 0 || step_index >= cfg->num_steps)
     return MSD_ERR_INVALID_ARGUMENT;
@@ -2361,14 +2413,35 @@ int msd_op_sampler_step(const msd_config* cfg, int step_index, const float* z_de
       hipMemcpyAsync(step, st, sizeof(st), hipMemcpyHostToDevice, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
     return MSD_ERR_HIP;
-  SamplerParams sp;
+  SamplerKeepParams sp;
   sp.eps = eps; sp.z = z_out_dev; sp.noise_slot = slot; sp.coef = coef; sp.step_ptr = step; sp.rng_key = key;
   sp.n = (int)n; sp.passes = passes; sp.cond_wt = cfg->cfg_weight; sp.clip_x0 = cfg->clip_x0;
   sp.ddim = cfg->sampler == MSD_SAMPLER_DDIM; sp.model_output = cfg->model_output;
   sp.z_hi = nullptr; sp.z_lo = nullptr; sp.step_from_slot1 = 1;
-  launch_sampler_step(sp, s);
+  if (known_scaled_dev) {
+    sp.xk = known_scaled_dev; sp.keep = keep_mask_dev; sp.n_dims = n_dims;
+    launch_sampler_step(sp, s);
+  } else {
+    launch_sampler_step(static_cast<const SamplerParams&>(sp), s);
+  }
   if (hipGetLastError() != hipSuccess) return MSD_ERR_HIP;
   return hipStreamSynchronize(s) == hipSuccess ? MSD_OK : MSD_ERR_HIP;
+}
+
+int msd_op_sampler_step(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
+                        const float* out_uncond_dev, const float* noise_dev, float* z_out_dev, int64_t n,
+                        void* stream) {
+  return op_sampler_step(cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, noise_dev, nullptr, nullptr, 0, z_out_dev,
+                         n, stream);
+}
+
+int msd_op_sampler_step_keep(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
+                             const float* out_uncond_dev, const float* noise_dev, const float* known_scaled_dev,
+                             const int32_t* keep_mask_dev, int n_dims, float* z_out_dev, int64_t n, void* stream) {
+  if (!known_scaled_dev || !keep_mask_dev || n_dims <= 0 || n_dims % 4 || n <= 0 || n % n_dims)
+    return MSD_ERR_INVALID_ARGUMENT;
+  return op_sampler_step(cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, noise_dev, known_scaled_dev, keep_mask_dev,
+                         n_dims, z_out_dev, n, stream);
 }
 
 // x_out = x_in + a . w1 ;  h_out = (RMSNorm(x_out; gamma) (.) (film_scale + 1) + film_bias) . w2
@@ -2676,3 +2749,5 @@ int msd_vocoder_decode(msd_vocoder* v, int batch, int n_frames, const float* log
 }
 
 }  // extern "C"
+
+#include "keep_frames_tail.h"   // last on purpose: see the file

@@ -208,6 +208,44 @@ def _load_checkpoint(path, spec: config_lib.ModelSpec) -> Tuple[Dict[str, np.nda
 RNG_MODES = ('philox', 'threefry', 'jax')
 
 
+def plan_region(n_frames: int, segment_frames: int, start: int, stop: int):
+  """The segments a regenerated region [start, stop) of a song of n_frames touches: [(segment, mask_row)], in order;
+  mask_row int32 [segment_frames], 1 = the frame lies outside the region and is KEPT.  No device needed.  The song must
+  be whole segments and 0 <= start < stop <= n_frames, all integers: anything else is a ValueError."""
+  vals = (n_frames, segment_frames, start, stop)
+  if any(isinstance(v, bool) or int(v) != v for v in vals):
+    raise ValueError('frame counts must be integers: %r' % (vals,))
+  n_frames, segment_frames, start, stop = (int(v) for v in vals)
+  if segment_frames <= 0 or n_frames <= 0 or n_frames % segment_frames:
+    raise ValueError('the song (%d frames) is not a whole number of %d-frame segments' % (n_frames, segment_frames))
+  if not 0 <= start < stop <= n_frames:
+    raise ValueError('region [%d, %d) must be non-empty and inside the song\'s %d frames' % (start, stop, n_frames))
+  plan = []
+  for k in range(start // segment_frames, (stop - 1) // segment_frames + 1):
+    lo, hi = max(start - k * segment_frames, 0), min(stop - k * segment_frames, segment_frames)
+    row = np.ones((segment_frames,), np.int32)
+    row[lo:hi] = 0
+    plan.append((k, row))
+  return plan
+
+
+def check_keep(keep, keep_mask, b: int, t: int, n: int):
+  """The known-frame arguments of predict: both or neither; keep [b, t, n], keep_mask [b, t] bool or integer.
+  Returns (keep, flags) with flags a contiguous int32 NumPy array of zeros and ones, or (None, None)."""
+  if keep is None and keep_mask is None:
+    return None, None
+  if keep is None or keep_mask is None:
+    raise ValueError('keep and keep_mask go together: one was given without the other')
+  if tuple(np.shape(keep)) != (b, t, n):
+    raise ValueError('keep must be [batch, %d, %d] = %r: got %r' % (t, n, (b, t, n), tuple(np.shape(keep))))
+  flags = _to_numpy(keep_mask)
+  if flags.dtype.kind not in 'biu':
+    raise ValueError('keep_mask must be bool or integer: %s' % flags.dtype)
+  if flags.shape != (b, t):
+    raise ValueError('keep_mask must be [batch, %d] = %r: got %r' % (t, (b, t), flags.shape))
+  return keep, np.ascontiguousarray(flags != 0, dtype=np.int32)
+
+
 class InferenceModel(object):
   """Wrapper of the HIP synthesizer with the reference's InferenceModel API."""
 
@@ -374,7 +412,8 @@ class InferenceModel(object):
   # -- predict (inference.py:200-203) -----------------------------------------------
   def predict(self, batch: Mapping[str, Any], seed: Union[int, Sequence[int]] = 0,
               segment: Union[int, Sequence[int]] = 0,
-              init_z=None, noise=None, return_torch: bool = False, rng: Optional[str] = None):
+              init_z=None, noise=None, return_torch: bool = False, rng: Optional[str] = None,
+              keep=None, keep_mask=None):
     """Predict one batch of 256-frame segments.
 
     batch: the model features of inference.py:113-136 (NumPy arrays or torch
@@ -396,12 +435,21 @@ class InferenceModel(object):
       the rounding of log1p: <= 3 ulp on about one value in a hundred).
       Like the reference (beam/evaluation.py:209 calls predict(batch) with the default seed for EVERY segment),
       `segment` does not enter the key in the 'threefry' and 'jax' modes.
+    keep [B,T,n] (mel units; NumPy or a device tensor) / keep_mask [B,T] (bool or int, non-zero = known): frames of the
+      target that are KNOWN.  They come back exactly as given -- values outside the codec's range included -- and
+      the other frames are sampled so that they fit them: in every step the kept elements' x0 is replaced by the
+      known value (x0-replacement inside the sampler kernel, msd_sample_keep), so they carry the step's noise
+      level and the free frames see them through self-attention.  The draws are those of the call without a mask
+      (an all-zero mask changes nothing, bit for bit); every seed / segment / rng / init_z / noise form works.
+      One without the other, or a wrong shape, is a ValueError.
     Returns (decodes float32 [B,T,n] in mel units, scores float32 [B] zeros).
     """
+    keep, keep_mask = check_keep(keep, keep_mask, np.shape(batch['encoder_input_tokens'])[0], self.targets_length,
+                                 self.audio_codec.n_dims)
     if rng is None:
       rng = self.rng
     try:
-      return self._predict_once(batch, seed, segment, init_z, noise, return_torch, rng)
+      return self._predict_once(batch, seed, segment, init_z, noise, return_torch, rng, keep, keep_mask)
     except native.RangeError:
       if not (self.range_fallback and self.precision in ('f16x3', 'f16')):
         raise
@@ -413,9 +461,9 @@ class InferenceModel(object):
       if self._native is not None:
         self._native.close()
       self._native = None
-      return self._predict_once(batch, seed, segment, init_z, noise, return_torch, rng)
+      return self._predict_once(batch, seed, segment, init_z, noise, return_torch, rng, keep, keep_mask)
 
-  def _predict_once(self, batch, seed, segment, init_z, noise, return_torch, rng):
+  def _predict_once(self, batch, seed, segment, init_z, noise, return_torch, rng, keep=None, keep_mask=None):
     torch = self._torch
     nm = self._get_native()
     dev = self.device
@@ -462,8 +510,9 @@ class InferenceModel(object):
       if nz is not None and tuple(nz.shape) != (self.spec.diffusion.sampler.schedule.num_steps, b, t, n):
         raise ValueError('noise must be [num_steps, batch, %d, %d]' % (t, n))
       # explicit draws keep precedence in every mode; 'jax' has none left to generate
+      known = None if keep is None else _to_device(torch, keep, dev, torch.float32)
       nm.sample(b, out, seed=seed, stream_id=segment, init_z=z0, noise=nz, stream=s,
-                rng='threefry' if rng == 'threefry' else 'philox')
+                rng='threefry' if rng == 'threefry' else 'philox', keep=known, keep_mask=keep_mask)
       self._stream.synchronize()
     t2 = time.perf_counter()
     self.last_timing = {'encode_s': t1 - t0, 'sample_s': t2 - t1, 'total_s': t2 - t0}
@@ -554,6 +603,42 @@ class InferenceModel(object):
     if not return_timing:
       return full
     return full, self._sequence_timing(seconds)
+
+  def regenerate(self, song, segments_tokens: Sequence[np.ndarray], start_frame: int, stop_frame: int, seed: int = 0,
+                 always_mask_context: bool = False, rng: Optional[str] = None, return_torch: bool = False):
+    """Sample the frames [start_frame, stop_frame) of a song again and keep the rest.
+
+    song float32 [1, K * T, n] (mel units; NumPy or a device tensor), K == len(segments_tokens), the tokens of ALL its
+    segments (after a MIDI edit: the edited ones).  Only the segments that overlap the region are sampled (plan_region),
+    in order, each keyed (seed, segment index) as predict_sequence keys it and each keeping its frames outside the
+    region (predict(keep=, keep_mask=)).  The context of segment k is segment k - 1 of the song AS IT STANDS --
+    regenerated if the region touched it, the original otherwise --; segment 0 and ``always_mask_context`` run with
+    zeros and mask 0, as in predict_sequence.  Segments behind the region are not run again: the region's last frames
+    are sampled with the frames that follow them in their own segment known, and the next segment keeps the context
+    it was made with.  Returns the new song [1, K * T, n] (NumPy; ``return_torch``: the device tensor); every frame
+    outside the region is the input's, bit for bit."""
+    torch = self._torch
+    t, n = self.targets_length, self.audio_codec.n_dims
+    c_len = self.targets_context_length
+    if len(np.shape(song)) != 3 or np.shape(song)[0] != 1 or np.shape(song)[2] != n:
+      raise ValueError('song must be [1, frames, %d]: got %r' % (n, tuple(np.shape(song))))
+    plan = plan_region(np.shape(song)[1], t, start_frame, stop_frame)
+    if np.shape(song)[1] != t * len(segments_tokens):
+      raise ValueError('song has %d segments of %d frames but %d segments of tokens were given'
+                       % (np.shape(song)[1] // t, t, len(segments_tokens)))
+    new = _to_device(torch, song, self.device, torch.float32).clone()
+    for k, row in plan:
+      batch = {'encoder_input_tokens': np.asarray(segments_tokens[k], np.int32).reshape(1, -1)}
+      if c_len is not None:
+        no_ctx = always_mask_context or k == 0
+        batch['encoder_continuous_inputs'] = (torch.zeros((1, c_len, n), dtype=torch.float32, device=self.device)
+                                              if no_ctx else new[:, (k - 1) * t:k * t].clone())
+        batch['encoder_continuous_mask'] = (np.zeros if no_ctx else np.ones)((1, c_len), np.int32)
+      out, _ = self.predict(batch, seed=seed, segment=k, return_torch=True, rng=rng,
+                            keep=new[:, k * t:(k + 1) * t].clone(), keep_mask=row[None])
+      free = torch.as_tensor(row == 0, device=self.device)
+      new[0, k * t:(k + 1) * t][free] = out[0].to(self.device)[free]   # (the kept frames of `out` are the song's already)
+    return new if return_torch else new.cpu().numpy()
 
   def _sequence_timing(self, seconds: Sequence[float]) -> Dict[str, float]:
     seconds_per_chunk = self.targets_length * (self.audio_codec.hop_size / self.audio_codec.sample_rate)

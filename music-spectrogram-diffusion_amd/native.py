@@ -61,7 +61,9 @@ EXPORTED_SYMBOLS = (
     'msd_vocoder_create', 'msd_vocoder_destroy', 'msd_vocoder_last_error', 'msd_vocoder_stft', 'msd_vocoder_istft',
     'msd_vocoder_encode', 'msd_vocoder_decode',
     # (appended to ABI 7) one generator key per row of a batched call
-    'msd_sample_rows')
+    'msd_sample_rows',
+    # (appended to ABI 7) known frames in the sampler
+    'msd_sample_keep', 'msd_op_sampler_step_keep')
 
 
 class NativeLibraryError(RuntimeError):
@@ -171,6 +173,9 @@ def load(planes: str = 'f16') -> ctypes.CDLL:
     lib.msd_sample_rng.argtypes = [vp, i32, i32, u64, u64, vp, vp, vp, vp]
   if 'msd_sample_rows' in present:   # (appended to ABI 7)
     lib.msd_sample_rows.argtypes = [vp, i32, i32, c.POINTER(u64), c.POINTER(u64), vp, vp, vp, vp]
+  if 'msd_sample_keep' in present:   # (appended to ABI 7)
+    lib.msd_sample_keep.argtypes = [vp, i32, i32, i32, c.POINTER(u64), c.POINTER(u64), vp, vp, vp, vp, vp, vp]
+    lib.msd_op_sampler_step_keep.argtypes = [c.POINTER(MsdConfig), i32, vp, vp, vp, vp, vp, vp, i32, vp, i64, vp]
   if 'msd_fill_normal_threefry' in present:
     lib.msd_fill_normal_threefry.argtypes = [u64, i64, vp, i64, vp]
   if 'msd_op_threefry' in present:
@@ -310,15 +315,29 @@ class NativeModel:
            'msd_encode')
 
   def sample(self, batch: int, out, seed: int = 0, stream_id: int = 0, init_z=None,
-             noise=None, stream: int = 0, rng: str = 'philox'):
+             noise=None, stream: int = 0, rng: str = 'philox', keep=None, keep_mask=None):
     """rng: the generator of the draws that are not given -- 'philox' (the library's own, keyed by seed and stream_id)
     or 'threefry' (the reference's jax.random draws for PRNGKey(seed), made on the device; stream_id is ignored).
 
     seed / stream_id may be sequences of `batch` integers (a scalar beside a sequence is broadcast): every row then
     has a key of its own and draws what the one-row call (seed[b], stream_id[b]) draws (msd_sample_rows).  Scalars
-    key ONE draw over the whole [batch, T, n] array, as before."""
+    key ONE draw over the whole [batch, T, n] array, as before.
+
+    keep (float32 device tensor [batch, T, n], mel units) / keep_mask (int32 [batch, T], NumPy or device; non-zero = the
+    frame is known): the kept frames come back as given and the others are sampled around them (msd_sample_keep); both
+    or neither.  The keys and the draws are those of the call without them."""
     if rng not in RNGS:
       raise ValueError('rng must be one of %s: %r' % (sorted(RNGS), rng))
+    if (keep is None) != (keep_mask is None):
+      raise ValueError('keep and keep_mask go together')
+    if keep is not None:
+      per_row = not (np.isscalar(seed) and np.isscalar(stream_id))
+      seeds, stream_ids = row_keys(batch if per_row else 1, seed, stream_id)
+      rc = self.lib.msd_sample_keep(self.handle, batch, RNGS[rng], int(per_row), (ctypes.c_uint64 * len(seeds))(*seeds),
+                                    (ctypes.c_uint64 * len(seeds))(*stream_ids), _ptr(init_z), _ptr(noise), _ptr(keep),
+                                    _ptr(keep_mask), _ptr(out), stream)
+      _check(self.lib, self.handle, rc, 'msd_sample_keep')
+      return
     if not (np.isscalar(seed) and np.isscalar(stream_id)):
       seeds, stream_ids = row_keys(batch, seed, stream_id)
       rc = self.lib.msd_sample_rows(self.handle, batch, RNGS[rng], (ctypes.c_uint64 * batch)(*seeds),
@@ -486,6 +505,20 @@ def op_sampler_step(cfg: MsdConfig, step_index: int, z, out_cond, out_uncond, no
   cfg.struct_size = ABI_STRUCT_SIZES[getattr(lib, '_msd_abi', None) or ABI_VERSION]
   _op_check(lib.msd_op_sampler_step(ctypes.byref(cfg), step_index, _ptr(z), _ptr(out_cond), _ptr(out_uncond),
                                     _ptr(noise), _ptr(z_out), z.numel(), stream), 'msd_op_sampler_step')
+
+
+def op_sampler_step_keep(cfg: MsdConfig, step_index: int, z, out_cond, out_uncond, noise, known_scaled, keep_mask,
+                         z_out, stream: int = 0):
+  """op_sampler_step with known frames (msd_op_sampler_step_keep): known_scaled float32 [..., frames, n_dims] in model
+  units, keep_mask int32 device tensor with one flag per frame."""
+  lib = load()
+  cfg.struct_size = ABI_STRUCT_SIZES[getattr(lib, '_msd_abi', None) or ABI_VERSION]
+  n_dims = int(known_scaled.shape[-1])
+  if known_scaled.numel() != z.numel() or keep_mask.numel() * n_dims != z.numel():
+    raise ValueError('known_scaled must have z\'s element count and keep_mask one flag per frame of %d' % n_dims)
+  _op_check(lib.msd_op_sampler_step_keep(ctypes.byref(cfg), step_index, _ptr(z), _ptr(out_cond), _ptr(out_uncond),
+                                         _ptr(noise), _ptr(known_scaled), _ptr(keep_mask), n_dims, _ptr(z_out), z.numel(),
+                                         stream), 'msd_op_sampler_step_keep')
 
 
 def op_residual_norm_gemm(folded: bool, x_in, a, w1, gamma, film_scale, film_bias, w2, x_out, h_out,

@@ -7,6 +7,7 @@ beam/evaluation.py:161-223) on the MI355X path.
       [--seed 0] [--rng threefry|jax] [--num-steps 1000] [--dry-run]
       [--batch-segments B [--always-mask-context]]
       [--wav song.wav [--vocoder-iters 32]] [--context-audio earlier.wav]
+      [--regenerate START:STOP (--edit-mel old_mel.npy | --edit-audio old.wav)]
 
 --wav writes 16-bit PCM mono at 16 kHz from the device vocoder: Griffin-Lim over the codec's STFT, a stand-in for the
 reference's SoundStream decoder (which is not built).  --context-audio continues a recording: its last 256 frames are
@@ -15,7 +16,13 @@ encoded on the device and given to the first segment as context.
 --batch-segments B sends B segments through every sampling call, each with the noise the one-by-one loop gives it; the
 segments must be independent of each other: a preset without context, or --always-mask-context.
 
---dry-run tokenises only (no GPU): prints the segment / token statistics the synthesis would see."""
+--regenerate START:STOP (seconds, rounded outward to whole frames) changes part of a song: the old rendering comes from
+--edit-mel (the .npy a previous --out wrote) or --edit-audio (a recording, encoded on the device), the MIDI file is the
+song as it should be now, and only the segments the region touches are sampled again, each keeping its frames outside
+the region; every frame outside the region stays what it was.  --out / --wav write the edited song.
+
+--dry-run tokenises only (no GPU): prints the segment / token statistics the synthesis would see, and with --regenerate
+the plan: the segments touched and the frames each keeps."""
 from __future__ import annotations
 
 import argparse
@@ -55,9 +62,23 @@ def main(argv=None) -> int:
                        'a preset without context, or --always-mask-context')
   ap.add_argument('--always-mask-context', action='store_true',
                   help='no segment sees the previous prediction (beam/evaluation.py:66-68)')
+  ap.add_argument('--regenerate', default=None, metavar='START:STOP',
+                  help='sample this region of the song again (seconds, rounded outward to frames) and keep the rest of '
+                       '--edit-mel / --edit-audio')
+  ap.add_argument('--edit-mel', default=None, metavar='OLD.npy', help='the old rendering as mel frames [frames, 128]')
+  ap.add_argument('--edit-audio', default=None, metavar='OLD.wav',
+                  help='the old rendering as a 16 kHz PCM recording (encoded on the device)')
   ap.add_argument('--on-too-long', choices=['error', 'truncate'], default='error')
   ap.add_argument('--dry-run', action='store_true')
   args = ap.parse_args(argv)
+  if args.regenerate and not (args.edit_mel or args.edit_audio):
+    ap.error('--regenerate needs the old rendering: --edit-mel OLD.npy or --edit-audio OLD.wav')
+  if args.edit_mel and args.edit_audio:
+    ap.error('--edit-mel and --edit-audio are two sources of the same thing: give one')
+  if (args.edit_mel or args.edit_audio) and not args.regenerate:
+    ap.error('--edit-mel / --edit-audio need the region to change: --regenerate START:STOP')
+  if args.regenerate and (args.batch_segments != 1 or args.context_audio):
+    ap.error('--regenerate samples its segments one by one with the song as context: no --batch-segments / --context-audio')
 
   import msd_amd
   from msd_amd.frontend import midi_io, tokenizer
@@ -74,6 +95,36 @@ def main(argv=None) -> int:
   print('%s: %d notes, %.2f s -> %d segments of %d frames; tokens per segment min/mean/max %d/%.0f/%d (%.3f s)'
         % (args.midi, len(ns.notes), ns.total_time, len(segments), cfg.segment_frames, min(n_tok),
            float(np.mean(n_tok)), max(n_tok), t_tok), file=sys.stderr)
+  edit = None
+  if args.regenerate:
+    # everything about the edit that needs no device: the region in frames, the old rendering's length, the plan
+    from msd_amd import audio_codecs, inference, vocoder
+    codec = audio_codecs.get_codec(spec.audio_codec)
+    song_frames = len(segments) * cfg.segment_frames
+    try:
+      start, stop = region_frames(args.regenerate, codec.sample_rate / codec.hop_size)
+      if args.edit_mel:
+        old = np.load(args.edit_mel)
+        old = old[0] if old.ndim == 3 and old.shape[0] == 1 else old
+        if old.ndim != 2 or old.shape[1] != codec.n_dims:
+          raise ValueError('%s must hold mel frames [frames, %d]: got %r' % (args.edit_mel, codec.n_dims, old.shape))
+        old_frames = old.shape[0]
+      else:
+        old = vocoder.read_wav(args.edit_audio, codec.sample_rate)
+        old_frames = -(-old.size // codec.hop_size)
+      if old_frames > song_frames:
+        raise ValueError('the old rendering has %d frames, the MIDI file only %d (%d segments)'
+                         % (old_frames, song_frames, len(segments)))
+      plan = inference.plan_region(song_frames, cfg.segment_frames, start, stop)
+    except ValueError as e:
+      ap.error(str(e))
+    print('regenerate frames [%d, %d) of %d (%.3f s .. %.3f s): %d of %d segments'
+          % (start, stop, song_frames, start / cfg.frame_rate, stop / cfg.frame_rate, len(plan), len(segments)))
+    for k, row in plan:
+      free = np.nonzero(row == 0)[0]
+      print('  segment %d: frames [%d, %d) sampled again, %d of %d kept'
+            % (k, free[0], free[-1] + 1, int(row.sum()), row.size))
+    edit = (old, start, stop)
   if args.dry_run:
     return 0
   model = msd_amd.InferenceModel(args.checkpoint, spec, batch_size=max(args.batch_segments, 1), precision=args.precision,
@@ -82,6 +133,8 @@ def main(argv=None) -> int:
     model.check_batch_segments(args.batch_segments, args.always_mask_context, args.context_audio)
   except ValueError as e:
     ap.error(str(e))
+  if edit is not None:
+    return _regenerate(args, model, segments, edit, ns, cfg)
   init_context = None
   if args.context_audio:
     if model.targets_context_length is None:
@@ -98,6 +151,12 @@ def main(argv=None) -> int:
         % (mel.shape[0], timing['prediction_seconds_per_chunk'], cfg.segment_frames / cfg.frame_rate,
            1.0 / timing['predictions_seconds_per_audio_second'] if timing['predictions_seconds_per_audio_second'] == timing['predictions_seconds_per_audio_second'] else float('nan')),
         file=sys.stderr)
+  _write_outputs(args, model, mel_dev, mel)
+  return 0
+
+
+def _write_outputs(args, model, mel_dev, mel):
+  """--out / --wav of the song `mel` [frames, 128] (`mel_dev`: the device tensor [1, >= frames, 128] it was cut from)."""
   if args.out:
     np.save(args.out, mel)
   if args.wav:
@@ -108,6 +167,44 @@ def main(argv=None) -> int:
     print('wrote %s: %d samples, %d Griffin-Lim iterations in %.3f s%s'
           % (args.wav, audio.shape[1], args.vocoder_iters, time.perf_counter() - t0,
              '' if gain == 1.0 else ' (peak-normalised, gain %.3f)' % gain), file=sys.stderr)
+
+
+def region_frames(text: str, frame_rate: float):
+  """'START:STOP' in seconds -> (start_frame, stop_frame), rounded OUTWARD to whole frames of 1 / frame_rate seconds
+  (a time that is a whole frame up to 1e-6 frames is that frame)."""
+  try:
+    a, b = (float(v) for v in text.split(':'))
+  except ValueError:
+    raise ValueError('--regenerate wants START:STOP in seconds: %r' % (text,))
+  if not 0.0 <= a < b:
+    raise ValueError('--regenerate wants 0 <= START < STOP: %r' % (text,))
+  return int(np.floor(round(a * frame_rate, 6))), int(np.ceil(round(b * frame_rate, 6)))
+
+
+def pad_to_segments(mel, n_frames: int, pad_value: float):
+  """mel [1, frames, n] (device tensor) padded at its end with the codec's pad value to n_frames."""
+  if mel.shape[1] >= n_frames:
+    return mel[:, :n_frames]
+  pad = mel.new_full((1, n_frames - mel.shape[1], mel.shape[2]), pad_value)
+  import torch
+  return torch.cat([mel, pad], dim=1)
+
+
+def _regenerate(args, model, segments, edit, ns, cfg) -> int:
+  old, start, stop = edit
+  torch = model._torch
+  if args.edit_mel:
+    song = torch.as_tensor(np.ascontiguousarray(old, np.float32)).to(model.device)[None]
+  else:   # the recording's frames, made on the device as a context recording's are (context_from_audio)
+    song = model.vocoder.encode(np.asarray(old, np.float32)[None], return_torch=True)
+  song = pad_to_segments(song, len(segments) * cfg.segment_frames, model.audio_codec.pad_value)
+  t0 = time.perf_counter()
+  mel_dev = model.regenerate(song, segments, start, stop, seed=args.seed, always_mask_context=args.always_mask_context,
+                             rng=args.rng, return_torch=True)
+  frames = int(np.ceil(ns.total_time * cfg.frame_rate))
+  mel = mel_dev.cpu().numpy()[0, :max(frames, 1)]
+  print('regenerated frames [%d, %d) of %d in %.3f s' % (start, stop, mel.shape[0], time.perf_counter() - t0), file=sys.stderr)
+  _write_outputs(args, model, mel_dev, mel)
   return 0
 
 
