@@ -45,7 +45,8 @@ extern "C" {
                                       device); msd_config unchanged.  Appended to ABI 7 (no version bump): the msd_vocoder_*
                                       entry points (device STFT pair, Audio2Mel, Griffin-Lim); msd_sample_rows (one
                                       generator key per row of a batched call); msd_sample_keep and
-                                      msd_op_sampler_step_keep (known frames in the sampler).
+                                      msd_op_sampler_step_keep (known frames in the sampler); msd_op_gemm_site and
+                                      msd_op_gemm_site_tiles, msd_op_gemm_site_name (one GEMM launch site at a time, for the tests).
                                    6: cross_merge_in_launch, cross_q_fold, mlp_in_persistent appended to msd_config.
                                    5: dedup_layer0, cross_key_split, keep_raw_weights, kv_touch_ahead appended to msd_config.
                                    4: every caller-selectable knob is a msd_config field (attn_q_planes / attn_p_planes
@@ -491,6 +492,84 @@ int msd_vocoder_encode(msd_vocoder* v, int batch, int64_t n_samples, const float
  *   audio_out_dev  float [batch, n_frames * 320] */
 int msd_vocoder_decode(msd_vocoder* v, int batch, int n_frames, const float* logmel_dev, int n_iters, float momentum,
                        uint64_t seed, const float* init_phase_dev, float* audio_out_dev, void* stream);
+
+/* ---- (appended to ABI 7) One GEMM launch site of the decoder at a time (tests/test_gpu_gemm_sites.py) ----
+ * Runs ONE launch site of the step (GemmSites / DualSites of csrc/msd_api.hip) on the caller's float32 operands through
+ * the product's own dispatch: pick_tile, gp_launch / set_xcd_grid, the range flag, gemm_t's persistent switch and the
+ * prefetch-wave choice are the decoder's.  Context: the entry builds a MINIMAL context of its own (no handle is passed and
+ * no model is needed): the plane count of `precision`, a range flag, the device's CU count.
+ * `site` is the position in GemmSites<planes> (0 .. 9, and 10 in the two-plane modes), then DualSites (11 .. 13):
+ *    0 QKV             out[m][n] = q | k | v = [rstd .] (a . w) [+ bias]; n = 3 j, V^T un-permuted on the host
+ *    1 MLP-in          out[m][n/2] = gelu_tanh(h0) . h1, h = [rstd .] (a . (w | w_gate)) [+ bias], bias = [steps][b0 | b1]
+ *    2 residual (square kind)   3 residual (tall kind)        x[m][n] += a . w
+ *    4 residual + norm inputs (tall)   5 its DUP form (tall)   6 (square)   10 its Y2 form (tall, two planes only)
+ *                      x += a . w; ssq_out[row][n/32] partial sums of squares (spare slots zero); y = x (.) g, g_lo for
+ *                      rows < split_row and g_hi from there, rows of a null gain are not written; DUP: every row also at
+ *                      row + dup_rows (g_lo for the first copy, g_hi for the second; buffers hold dup_rows + m rows);
+ *                      Y2: rows < y2_rows also y2 = x (.) g2
+ *    7 store, 16-bit planes (square)   8 store, float32 (narrow)      out[m][n] = [rstd .] (a . w) [+ bias]
+ *    9 in-projection   x[p][m] = a . w + pos[m % seg_len] for p < passes; y = x (.) g_lo(step); ssq_out; optional
+ *                      y2 = x (.) g2 of the first pass; step_copy = the word the epilogue publishes (the scan index)
+ *   11 dual, folded QKV: problem 1 as site 0, problem 2 out2[m2][n2] = a2 . w2 (float32)
+ *   12 dual, folded attention-out: problem 1 as site 4, problem 2 out2 = a2 . w2 + addend2 (16-bit planes)   13: as site 5
+ * rstd[m] = 1 / sqrt(sum_t ssq[m][t] / k + 1e-6) over the caller's [m][k/32] partial sums (k <= 1024); null ssq: no row
+ * scale (and then no bias).  bias / g_lo / g_hi are tables of `steps` rows of n floats, read at row `step`.
+ * Results that the product keeps as 16-bit planes come back merged to float32; such buffers start as NaN inside the
+ * entry, so what the epilogue did not store comes back NaN.  float32 results (x, ssq_out, out of site 8, out2 of site 11)
+ * are the caller's buffers as the kernel left them.
+ * force_bm / force_bn (dual sites: also force_bm2 / force_bn2, required there -- the step plan, not pick_tile, names a dual
+ * launch's tiles): 0 = pick_tile decides; a shape outside the site's table is MSD_ERR_INVALID_ARGUMENT, as are sizes the
+ * tile that runs does not divide.  Errors otherwise as the other msd_op_* entries: MSD_ERR_UNSUPPORTED for a precision of
+ * the other build and for weights beyond the half planes' range, MSD_ERR_RANGE for activations beyond it.  Synchronises. */
+typedef struct msd_gemm_site_args {
+  int32_t struct_size;       /* sizeof(msd_gemm_site_args) */
+  int32_t precision;         /* msd_precision */
+  int32_t site;
+  int32_t m, n, k;
+  int32_t step, steps;       /* scan index the step-indexed rows are read at; rows of those tables */
+  int32_t force_bm, force_bn;
+  int32_t persistent;        /* MLP-in: 0 = the product's switch (on), 2 = off (msd_config.mlp_in_persistent) */
+  int32_t resident_blocks;   /* MLP-in, persistent form: 0 = the product's (one per CU), else a multiple of 8 */
+  int32_t seg_len;           /* QKV: rows per V^T segment (m % seg_len == 0, seg_len % 16 == 0); in-projection: rows of pos */
+  int32_t split_row, dup_rows, y2_rows, passes;
+  int32_t m2, n2, k2, force_bm2, force_bn2;   /* dual sites: the second problem */
+  int32_t prefetch_rows, prefetch_k;          /* shape of the prefetch target: two planes of [rows][k] 16-bit elements */
+  /* out: what ran */
+  int32_t ran_bm, ran_bn, ran_ns, ran_xcd_rows, ran_persistent, ran_dual, ran_prefetch;
+  int32_t ran_bm2, ran_bn2, ran_ns2, ran_xcd_rows2;
+  int32_t step_copy;
+  /* operands (device, float32) */
+  const float* a;            /* [m][k] */
+  const float* w;            /* [k][n] (MLP-in: wi_0 [k][n/2]) */
+  const float* w_gate;       /* MLP-in: wi_1 [k][n/2] */
+  const float* ssq;
+  const float* bias;
+  const float* g_lo;
+  const float* g_hi;
+  const float* g2;           /* [n] */
+  const float* pos;          /* [seg_len][n] */
+  const float* a2;           /* [m2][k2] */
+  const float* w2;           /* [k2][n2] */
+  const float* addend2;      /* [m2][n2] */
+  const void* prefetch;      /* optional weight-shaped buffer a prefetch wave touches (two-plane modes); never written */
+  /* results (device, float32) */
+  float* x;
+  float* out;
+  float* y;
+  float* y2;
+  float* ssq_out;
+  float* out2;
+} msd_gemm_site_args;
+int msd_op_gemm_site(msd_gemm_site_args* args, void* stream);
+
+/* The index-th tile (BM x BN, ring depth NS) of `site`'s table for `precision`, read from the tile table itself; bm, bn
+ * and ns point to TWO ints each: [0] the tile (dual sites: the first problem's), [1] the second problem's tile of a dual
+ * site's pair, 0 otherwise.  MSD_ERR_INVALID_ARGUMENT past the last tile or the last site. */
+int msd_op_gemm_site_tiles(int precision, int site, int index, int32_t* bm, int32_t* bn, int32_t* ns);
+/* The name of launch site `site` for `precision`, derived from the site's type (tile kind and epilogue) -- "qkv", "mlp_in",
+ * "residual_square", "residual_tall", "resnorm_tall", "resnorm_tall_dup", "resnorm_square", "store_h16", "store_f32",
+ * "in_proj", "resnorm_tall_y2", "dual_qkv", "dual_out", "dual_out_dup" -- or NULL past the last site. */
+const char* msd_op_gemm_site_name(int precision, int site);
 
 #ifdef __cplusplus
 }

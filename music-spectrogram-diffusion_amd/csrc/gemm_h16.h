@@ -1330,6 +1330,14 @@ inline hipError_t gemm_h16_dma_prepare() {
   return e;
 }
 
+// does this launch run the kernel's PF = 1 twin (a prefetch wave)?  The single-plane modes and the epilogues that never
+// carry a target have none.  (host only)
+template <int NP, class Epi>
+inline bool gemm_carries_prefetch(const GemmParams& p) {
+  if constexpr (NP == 2 && epi_may_prefetch<Epi>::value) return prefetch_kind(p.pf) >= 1;   // product: the first target only
+  else return false;
+}
+
 template <int NP, int BM, int BN, int NS, class Epi>
 inline hipError_t launch_gemm_h16_dma(const GemmParams& p_in, const Epi& epi, hipStream_t stream) {
   constexpr int smem = gemm_h16_dma_smem<NP, BM, BN, NS, Epi>();
@@ -1342,9 +1350,8 @@ inline hipError_t launch_gemm_h16_dma(const GemmParams& p_in, const Epi& epi, hi
   // one kernel instantiation per number of prefetch targets (single path: see prefetch_weights)
 #define MSD_LAUNCH_PF(PF_) \
   hipLaunchKernelGGL((gemm_h16_dma_kernel<NP, BM, BN, NS, Epi, PF_>), dim3(grid), dim3(256 + pf_threads(PF_)), smem, stream, p, epi)
-  const int npf = NP == 2 ? prefetch_kind(p.pf) : 0;
   if constexpr (NP == 2 && epi_may_prefetch<Epi>::value) {
-    if (npf >= 1) MSD_LAUNCH_PF(1);   // product: the first target only
+    if (gemm_carries_prefetch<NP, Epi>(p)) MSD_LAUNCH_PF(1);
     else MSD_LAUNCH_PF(0);
   } else {
     MSD_LAUNCH_PF(0);

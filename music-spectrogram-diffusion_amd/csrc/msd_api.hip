@@ -576,11 +576,18 @@ using DualSites = List<DualSite<FoldQkvTiles, EpiQKV<2>, EpiStoreF32>,
 template <int NP, class T, class Epi>
 constexpr bool kHasPersistentForm = NP == 2 && std::is_same<T, BigMlpInTile>::value && std::is_same<Epi, EpiGeglu<2>>::value;
 
+// does gemm_t run tile T's persistent form for this launch?  (host only; msd_op_gemm_site reports it from here too)
+template <int NP, class T, class Epi>
+bool runs_persistent(const msd_model* m, const GemmParams& p, const Epi& epi) {
+  if constexpr (kHasPersistentForm<NP, T, Epi>) return m->persist_mlp_in && epi.rsc.ssq && epi.rsc.bias && p.K >= 2 * kGemmBK;
+  else return false;
+}
+
 template <int NP, class T, class Epi>
 void gemm_t(Ctx& c, int kc, const GemmParams& p, const Epi& epi) {
   c.begin(kc);
   if constexpr (kHasPersistentForm<NP, T, Epi>) {
-    if (c.m->persist_mlp_in && epi.rsc.ssq && epi.rsc.bias && p.K >= 2 * kGemmBK) {
+    if (runs_persistent<NP, T, Epi>(c.m, p, epi)) {
       c.latch(launch_gemm_h16_geglu_persist<NP, T::BM, T::BN, T::NS>(p, epi, (c.m->cus > 0 ? c.m->cus : 256) / 8 * 8, c.s));
       return c.end(kc);
     }
@@ -2746,6 +2753,433 @@ int msd_vocoder_decode(msd_vocoder* v, int batch, int n_frames, const float* log
   }
   if (err.e == hipSuccess) err(voc_inverse(v, batch, F, audio_out_dev, false, s));
   return voc_finish(v, err, s, "msd_vocoder_decode");
+}
+
+// ---- one GEMM launch site at a time, through the product's dispatcher (tests/test_gpu_gemm_sites.py) ----------------
+// Behind every other entry point on purpose: every kernel instance this code can reach is first named by set_func_attrs,
+// so the device code of the library is what it was without it (compare the device listings when this changes).
+extern "C++" {
+namespace {
+struct TileInfo { int bm = 0, bn = 0, ns = 0; };
+template <class... T> std::vector<TileInfo> tiles_of(List<T...>) { return {TileInfo{T::BM, T::BN, T::NS}...}; }
+template <class... P> std::vector<TileInfo> first_tiles_of(List<P...>) { return {TileInfo{P::P1::BM, P::P1::BN, P::P1::NS}...}; }
+template <class... P> std::vector<TileInfo> second_tiles_of(List<P...>) { return {TileInfo{P::P2::BM, P::P2::BN, P::P2::NS}...}; }
+const TileInfo* find_tile(const std::vector<TileInfo>& v, TileShape t) {
+  for (const TileInfo& x : v)
+    if (x.bm == t.bm && x.bn == t.bn) return &x;
+  return nullptr;
+}
+template <int NP, class Epi, class... T>
+bool persistent_on(List<T...>, TileShape t, const msd_model* m, const GemmParams& p, const Epi& epi) {
+  return ((T::is(t) && runs_persistent<NP, T, Epi>(m, p, epi)) || ...);
+}
+// the launch sites by name, from their types (msd_op_gemm_site_name)
+template <int TK, int NP> const char* site_name(Site<TK, EpiQKV<NP>>) { return "qkv"; }
+template <int TK, int NP> const char* site_name(Site<TK, EpiGeglu<NP>>) { return "mlp_in"; }
+template <int TK> const char* site_name(Site<TK, EpiResidual>) { return TK == TK_TALL ? "residual_tall" : "residual_square"; }
+template <int TK, int NP, bool DUP, bool Y2> const char* site_name(Site<TK, EpiResidualNorm<NP, DUP, Y2>>) {
+  return TK == TK_TALL ? (DUP ? "resnorm_tall_dup" : (Y2 ? "resnorm_tall_y2" : "resnorm_tall")) : "resnorm_square";
+}
+template <int TK, int NP> const char* site_name(Site<TK, EpiStoreH16<NP>>) { return "store_h16"; }
+template <int TK> const char* site_name(Site<TK, EpiStoreF32>) { return "store_f32"; }
+template <int TK, int NP> const char* site_name(Site<TK, EpiInProj<NP>>) { return "in_proj"; }
+template <class Pairs> const char* site_name(DualSite<Pairs, EpiQKV<2>, EpiStoreF32>) { return "dual_qkv"; }
+template <class Pairs, bool DUP> const char* site_name(DualSite<Pairs, EpiResidualNorm<2, DUP>, EpiAddStoreH16<2>>) {
+  return DUP ? "dual_out_dup" : "dual_out";
+}
+
+// f(S{}) for the index-th entry of a list of (empty) site types; false: no such entry
+template <class F, class... S>
+bool visit_at(List<S...>, int index, F&& f) {
+  int i = 0;
+  return ((i++ == index ? (f(S{}), true) : false) || ...);
+}
+template <class... S> constexpr int list_size(List<S...>) { return (int)sizeof...(S); }
+
+template <int NP> struct SiteTiles {
+  std::vector<TileInfo> first, second;   // second: dual sites only
+  template <int TK, class Epi> void operator()(Site<TK, Epi>) { first = tiles_of(TileTable<NP, TK, Epi>{}); }
+  template <class Pairs, class E1, class E2> void operator()(DualSite<Pairs, E1, E2>) {
+    first = first_tiles_of(Pairs{});
+    second = second_tiles_of(Pairs{});
+  }
+};
+
+// One site launch.  Its context is a MINIMAL one of its own: an msd_model of which Ctx, gp_launch, gemm_t and
+// weights_target read the plane count, the range flag, the CU count and the persistent / prefetch switches; it has no
+// weights, tables or buffers.
+template <int NP>
+struct SiteRun {
+  msd_gemm_site_args* g;
+  msd_model ctx_model;
+  Ctx c;
+  Scratch sc;
+  OpFlags fl;
+  hipStream_t s;
+  int* step = nullptr;
+  int rc = MSD_OK;
+
+  SiteRun(msd_gemm_site_args* g_, hipStream_t s_) : g(g_), c{&ctx_model, s_}, s(s_) { ctx_model.NP = NP; }
+
+  bool ok(hipError_t e) {
+    if (e != hipSuccess && rc == MSD_OK) rc = MSD_ERR_HIP;
+    return e == hipSuccess;
+  }
+  bool bad() { rc = MSD_ERR_INVALID_ARGUMENT; return false; }
+
+  // zeroed planes (one when NP == 1: p[1] stays null, the operand convention); `nan`: every element a NaN instead
+  bool planes(size_t n, Planes* out, bool nan = false) {
+    for (int i = 0; i < NP; ++i) {
+      out->p[i] = sc.get<h16_t>(n);
+      if (!out->p[i]) { rc = MSD_ERR_HIP; return false; }
+      if (nan && !ok(hipMemsetAsync(out->p[i], 0xFF, n * sizeof(h16_t), s))) return false;
+    }
+    return true;
+  }
+  bool operand(const float* in, size_t n, Planes* out) {
+    if (!planes(n, out)) return false;
+    split(in, *out, (int64_t)n, s, fl.sat());
+    return true;
+  }
+  bool weight(const float* w, int K, int N, int mode, int row0, Planes* out, int rows) {
+    if (!out->p[0] && !planes((size_t)rows * K, out)) return false;
+    if (!pack_planes(sc, w, K, N, mode, row0, out, rows, s, fl)) { rc = MSD_ERR_HIP; return false; }
+    return true;
+  }
+  void back(const Planes& pl, float* out, size_t n) { merge(pl, out, (int64_t)n, s); }
+
+  bool init() {
+    if (!fl.init(sc)) { rc = MSD_ERR_HIP; return false; }
+    step = sc.get<int>(2);
+    if (!step) { rc = MSD_ERR_HIP; return false; }
+    const int st[2] = {g->step, -1};
+    if (!ok(hipMemcpyAsync(step, st, sizeof(st), hipMemcpyHostToDevice, s)) || !ok(hipStreamSynchronize(s))) return false;
+    ctx_model.d_sat = fl.sat();
+    ctx_model.persist_mlp_in = g->persistent != 2;
+    ctx_model.prefetch = true;
+    int dev = 0, cus = 0;
+    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
+      ctx_model.cus = cus;
+    if (g->resident_blocks > 0) ctx_model.cus = g->resident_blocks;
+    return true;
+  }
+  int finish() {
+    int st[2] = {0, 0};
+    if (!ok(hipGetLastError()) || !ok(hipMemcpyAsync(st, step, sizeof(st), hipMemcpyDeviceToHost, s))) return rc;
+    const int frc = fl.finish(s);   // synchronises
+    g->step_copy = st[1];
+    return frc;
+  }
+  // folded-norm row scale of a consumer site: rstd from the caller's [M][K / 32] partial sums, + the step-indexed bias row
+  bool row_scale_of(int K, const float* bias, int N, RowScale* out) {
+    *out = RowScale();
+    if (!g->ssq) return bias ? bad() : true;
+    if (K / kNarrowTile > kAuxMaxTiles) return bad();
+    *out = row_scale(g->ssq, K / kNarrowTile, step, bias, bias ? N : 0);
+    return true;
+  }
+  WeightPrefetch pf_target() {
+    WeightPrefetch pf;
+    if (!g->prefetch) return pf;
+    Planes w;
+    w.p[0] = static_cast<h16_t*>(const_cast<void*>(g->prefetch));
+    w.p[1] = w.p[0] + (size_t)g->prefetch_rows * g->prefetch_k;
+    pf = prefetch_of<NP>(&ctx_model, w, g->prefetch_rows, g->prefetch_k);
+    return pf;
+  }
+  bool common_ok(int M, int N, int K, const float* a, const float* w) {
+    if (M <= 0 || N <= 0 || K <= 0 || K % kGemmBK || !a || !w) return bad();
+    if (g->prefetch && (g->prefetch_rows <= 0 || g->prefetch_k <= 0 || g->prefetch_k % kGemmBK || g->prefetch_k > 4096)) return bad();
+    if (g->resident_blocks < 0 || g->resident_blocks % 8) return bad();
+    return true;
+  }
+
+  // The launch of a single site: the product's gemm<NP, TK, Epi> when no tile is forced; gemm_on on the forced tile, with
+  // gemm's own launch parameters, otherwise.  Reported: the table's entry of that shape, or its last one (the fall-back).
+  template <int TK, class Epi>
+  bool launch(int kc, const Planes& a, const Planes& w, int M, int N, int K, const Epi& epi, int align) {
+    using Tab = TileTable<NP, TK, Epi>;
+    const std::vector<TileInfo> tiles = tiles_of(Tab{});
+    TileShape t = {g->force_bm, g->force_bn};
+    const bool forced = t.bm != 0 || t.bn != 0;
+    if (!forced) t = pick_tile<NP, TK>(M, N, align, epi_takes_48<Epi>::value, K);
+    const TileInfo* ti = find_tile(tiles, t);
+    if (!ti) {
+      if (forced) return bad();
+      ti = &tiles.back();
+    }
+    if (M % ti->bm || M % t.bm || N % ti->bn || align % ti->bn) return bad();
+    const WeightPrefetch pf = pf_target();
+    GemmParams probe;
+    set_xcd_grid(probe, M, t.bm);
+    g->ran_bm = ti->bm; g->ran_bn = ti->bn; g->ran_ns = ti->ns; g->ran_xcd_rows = probe.xcd_rows;
+    const GemmParams lp = gp_launch<NP>(c, kc, a, K, w, K, M, N, K, t.bm, pf);
+    // both reports come from the predicates the launch itself uses (gemm_t, launch_gemm_h16_dma / _geglu_persist)
+    g->ran_persistent = persistent_on<NP, Epi>(Tab{}, TileShape{ti->bm, ti->bn}, &ctx_model, lp, epi);
+    g->ran_prefetch = g->ran_persistent ? prefetch_kind(lp.pf) >= 1 : gemm_carries_prefetch<NP, Epi>(lp);
+    if (forced) gemm_on<NP>(Tab{}, t, c, kc, lp, epi);
+    else gemm<NP, TK>(c, kc, a, K, w, K, M, N, K, epi, align, pf);
+    return ok(c.err);
+  }
+  template <class Pairs, class E1, class E2>
+  bool launch_dual(int kc, const Planes& a1, const Planes& w1, int M1, int N1, int K1, const E1& e1, int align1,
+                   const Planes& a2, const Planes& w2, int M2, int N2, int K2, const E2& e2) {
+    const std::vector<TileInfo> t1s = first_tiles_of(Pairs{}), t2s = second_tiles_of(Pairs{});
+    const TileShape t1 = {g->force_bm, g->force_bn}, t2 = {g->force_bm2, g->force_bn2};
+    const TileInfo *i1 = nullptr, *i2 = nullptr;
+    for (size_t i = 0; i < t1s.size() && !i1; ++i)
+      if (t1s[i].bm == t1.bm && t1s[i].bn == t1.bn && t2s[i].bm == t2.bm && t2s[i].bn == t2.bn) { i1 = &t1s[i]; i2 = &t2s[i]; }
+    if (!i1) return bad();   // the step plan names both tiles of a dual launch: there is nothing to pick here
+    if (M1 % t1.bm || N1 % t1.bn || align1 % t1.bn || M2 % t2.bm || N2 % t2.bn) return bad();
+    const WeightPrefetch pf = pf_target();
+    const GemmParams p1 = gp_launch<NP>(c, kc, a1, K1, w1, K1, M1, N1, K1, t1.bm, pf);
+    const GemmParams p2 = gp_launch<NP>(c, kc, a2, K2, w2, K2, M2, N2, K2, t2.bm);
+    g->ran_bm = i1->bm; g->ran_bn = i1->bn; g->ran_ns = i1->ns; g->ran_xcd_rows = p1.xcd_rows;
+    g->ran_bm2 = i2->bm; g->ran_bn2 = i2->bn; g->ran_ns2 = i2->ns; g->ran_xcd_rows2 = p2.xcd_rows;
+    g->ran_dual = 1;
+    g->ran_prefetch = prefetch_kind(p1.pf) >= 1;   // (launch_gemm_h16_dual's own test)
+    gemm_dual<Pairs>(c, kc, t1, p1, e1, t2, p2, e2);
+    return ok(c.err);
+  }
+
+  // ---- operands and results of each epilogue ----
+  struct QkvIo { Planes a, w, qk, vt; int J = 0; };
+  bool qkv_prepare(QkvIo* io, EpiQKV<NP>* e) {
+    const int M = g->m, N = g->n, K = g->k, J = N / 3;
+    if (!common_ok(M, N, K, g->a, g->w) || N % 3 || J % 16 || !g->out || g->seg_len <= 0 || g->seg_len % 16 || M % g->seg_len)
+      return bad();
+    RowScale rs;
+    if (!row_scale_of(K, g->bias, N, &rs)) return false;
+    io->J = J;
+    if (!operand(g->a, (size_t)M * K, &io->a) || !weight(g->w, K, N, 0, 0, &io->w, N) ||
+        !planes((size_t)M * 2 * J, &io->qk, true) || !planes((size_t)M * J, &io->vt, true))
+      return false;
+    *e = epi_qkv<NP>(io->qk, io->vt, 2 * J, g->seg_len, J, rs);
+    return true;
+  }
+  // q | k row-major and V^T[seg][j][perm(key)] (msd_op_qkv's host-side un-permutation) -> out [M][3J] = q | k | v
+  bool qkv_collect(const QkvIo& io) {
+    const int M = g->m, J = io.J, L = g->seg_len;
+    float* f32 = sc.get<float>((size_t)M * 2 * J);
+    if (!f32) { rc = MSD_ERR_HIP; return false; }
+    std::vector<float> h((size_t)M * 2 * J), o((size_t)M * 3 * J);
+    back(io.qk, f32, (size_t)M * 2 * J);
+    if (!ok(hipMemcpyAsync(h.data(), f32, h.size() * sizeof(float), hipMemcpyDeviceToHost, s)) || !ok(hipStreamSynchronize(s)))
+      return false;
+    for (int m = 0; m < M; ++m)
+      memcpy(&o[(size_t)m * 3 * J], &h[(size_t)m * 2 * J], (size_t)2 * J * sizeof(float));
+    back(io.vt, f32, (size_t)M * J);
+    if (!ok(hipMemcpyAsync(h.data(), f32, (size_t)M * J * sizeof(float), hipMemcpyDeviceToHost, s)) || !ok(hipStreamSynchronize(s)))
+      return false;
+    for (int m = 0; m < M; ++m) {
+      const int seg = m / L, key = m % L, o16 = key & 15;
+      const int kp = (key & ~15) + 8 * ((o16 >> 2) & 1) + (o16 & 3) + 4 * (o16 >> 3);
+      for (int j = 0; j < J; ++j) o[(size_t)m * 3 * J + 2 * J + j] = h[((size_t)seg * J + j) * L + kp];
+    }
+    return ok(hipMemcpyAsync(g->out, o.data(), o.size() * sizeof(float), hipMemcpyHostToDevice, s)) && ok(hipStreamSynchronize(s));
+  }
+
+  struct ResNormIo { Planes a, w, y, y2; int rows = 0; };
+  template <bool DUP, bool Y2>
+  bool resnorm_prepare(ResNormIo* io, EpiResidualNorm<NP, DUP, Y2>* e) {
+    const int M = g->m, N = g->n, K = g->k;
+    if (!common_ok(M, N, K, g->a, g->w) || N % kNarrowTile || !g->x || !g->y || !g->ssq_out || g->split_row < 0) return bad();
+    if (DUP && (g->dup_rows < M || !g->g_lo || !g->g_hi)) return bad();   // (the duplicating form reads both gain rows)
+    if (Y2 && (!g->y2 || !g->g2 || g->y2_rows < 0 || g->y2_rows > M)) return bad();
+    io->rows = DUP ? g->dup_rows + M : M;
+    if (!operand(g->a, (size_t)M * K, &io->a) || !weight(g->w, K, N, 0, 0, &io->w, N) ||
+        !planes((size_t)io->rows * N, &io->y, true))
+      return false;
+    const EpiResidualNorm<NP> base = epi_residual_norm<NP>(g->x, N, io->y, g->ssq_out, step, Gain{g->g_lo, g->g_lo ? N : 0},
+                                                           Gain{g->g_hi, g->g_hi ? N : 0}, g->split_row);
+    *e = residual_form<DUP, Y2>(base);
+    if (DUP) { e->split_row = 0; e->dup_rows = g->dup_rows; }
+    if constexpr (Y2) {
+      if (!planes((size_t)M * N, &io->y2, true)) return false;
+      out_pair<NP>(e->y2, io->y2); e->g2 = g->g2; e->y2_rows = g->y2_rows;
+    }
+    return true;
+  }
+  bool resnorm_collect(const ResNormIo& io, bool y2) {
+    back(io.y, g->y, (size_t)io.rows * g->n);
+    if (y2) back(io.y2, g->y2, (size_t)g->m * g->n);
+    return true;
+  }
+
+  // ---- the sites ----
+  template <int TK> void run(Site<TK, EpiQKV<NP>>) {
+    QkvIo io;
+    EpiQKV<NP> e;
+    if (qkv_prepare(&io, &e) && launch<TK>(KC_GEMM_QKV, io.a, io.w, g->m, g->n, g->k, e, e.v_start)) qkv_collect(io);
+  }
+  template <int TK> void run(Site<TK, EpiGeglu<NP>>) {
+    const int M = g->m, N = g->n, K = g->k, F = N / 2;
+    if (!common_ok(M, N, K, g->a, g->w) || N % 32 || !g->w_gate || !g->out) return (void)bad();
+    Planes a, wi, o;
+    const float* bias = nullptr;
+    if (g->bias) {   // natural order [steps][wi_0 columns | wi_1 columns] -> the packed column order of the weights
+      if (g->steps <= 0) return (void)bad();
+      std::vector<float> h((size_t)g->steps * N), p((size_t)g->steps * N);
+      float* d = sc.get<float>(p.size());
+      if (!d || !ok(hipMemcpyAsync(h.data(), g->bias, h.size() * sizeof(float), hipMemcpyDeviceToHost, s)) || !ok(hipStreamSynchronize(s)))
+        return (void)(rc = rc ? rc : MSD_ERR_HIP);
+      for (int r = 0; r < g->steps; ++r)
+        for (int j = 0; j < F; ++j) {
+          p[(size_t)r * N + (j / 16) * 32 + j % 16] = h[(size_t)r * N + j];
+          p[(size_t)r * N + (j / 16) * 32 + 16 + j % 16] = h[(size_t)r * N + F + j];
+        }
+      if (!ok(hipMemcpyAsync(d, p.data(), p.size() * sizeof(float), hipMemcpyHostToDevice, s)) || !ok(hipStreamSynchronize(s))) return;
+      bias = d;
+    }
+    RowScale rs;
+    if (!row_scale_of(K, bias, N, &rs)) return;
+    if (!operand(g->a, (size_t)M * K, &a) || !weight(g->w, K, F, 1, 0, &wi, N) || !weight(g->w_gate, K, F, 2, 0, &wi, N) ||
+        !planes((size_t)M * F, &o, true))
+      return;
+    if (launch<TK>(KC_GEMM_MLP_IN, a, wi, M, N, K, epi_out<EpiGeglu, NP>(o, F, rs), 0)) back(o, g->out, (size_t)M * F);
+  }
+  template <int TK> void run(Site<TK, EpiResidual>) {
+    const int M = g->m, N = g->n, K = g->k;
+    if (!common_ok(M, N, K, g->a, g->w) || !g->x) return (void)bad();
+    Planes a, w;
+    if (!operand(g->a, (size_t)M * K, &a) || !weight(g->w, K, N, 0, 0, &w, N)) return;
+    launch<TK>(KC_GEMM_MLP_OUT, a, w, M, N, K, EpiResidual{g->x, N}, 0);
+  }
+  template <int TK, bool DUP, bool Y2> void run(Site<TK, EpiResidualNorm<NP, DUP, Y2>>) {
+    ResNormIo io;
+    EpiResidualNorm<NP, DUP, Y2> e;
+    if (resnorm_prepare<DUP, Y2>(&io, &e) && launch<TK>(KC_GEMM_ATTN_OUT, io.a, io.w, g->m, g->n, g->k, e, 0)) resnorm_collect(io, Y2);
+  }
+  template <int TK> void run(Site<TK, EpiStoreH16<NP>>) {
+    const int M = g->m, N = g->n, K = g->k;
+    if (!common_ok(M, N, K, g->a, g->w) || !g->out) return (void)bad();
+    RowScale rs;
+    Planes a, w, o;
+    if (!row_scale_of(K, g->bias, N, &rs) || !operand(g->a, (size_t)M * K, &a) || !weight(g->w, K, N, 0, 0, &w, N) ||
+        !planes((size_t)M * N, &o, true))
+      return;
+    if (launch<TK>(KC_GEMM_CROSS_Q, a, w, M, N, K, epi_out<EpiStoreH16, NP>(o, N, rs), 0)) back(o, g->out, (size_t)M * N);
+  }
+  template <int TK> void run(Site<TK, EpiStoreF32>) {
+    const int M = g->m, N = g->n, K = g->k;
+    if (!common_ok(M, N, K, g->a, g->w) || !g->out) return (void)bad();
+    RowScale rs;
+    Planes a, w;
+    if (!row_scale_of(K, g->bias, N, &rs) || !operand(g->a, (size_t)M * K, &a) || !weight(g->w, K, N, 0, 0, &w, N)) return;
+    launch<TK>(KC_FINAL_PROJ, a, w, M, N, K, epi_store_f32(g->out, N, rs), 0);
+  }
+  template <int TK> void run(Site<TK, EpiInProj<NP>>) {
+    const int M = g->m, N = g->n, K = g->k, P = g->passes;
+    if (!common_ok(M, N, K, g->a, g->w) || N % kNarrowTile || !g->pos || !g->g_lo || !g->x || !g->y || !g->ssq_out ||
+        g->seg_len <= 0 || P < 1 || P > 2 || (g->g2 != nullptr) != (g->y2 != nullptr))
+      return (void)bad();
+    Planes a, w, y, y2;
+    if (!operand(g->a, (size_t)M * K, &a) || !weight(g->w, K, N, 0, 0, &w, N) || !planes((size_t)P * M * N, &y, true)) return;
+    EpiInProj<NP> ei;
+    ei.x = g->x; ei.ldx = N; ei.pos = g->pos; ei.T = g->seg_len; ei.pass_rows = M; ei.passes = P;
+    out_pair<NP>(ei.y, y); ei.ssq = g->ssq_out; ei.tiles = N / kNarrowTile;
+    ei.g = g->g_lo; ei.g_stride = N; ei.step_ptr = step; ei.step_copy = step;
+    if (g->g2) {
+      if (!planes((size_t)M * N, &y2, true)) return;
+      out_pair<NP>(ei.y2, y2); ei.g2 = g->g2;
+    }
+    if (!launch<TK>(KC_IN_PROJ, a, w, M, N, K, ei, 0)) return;
+    back(y, g->y, (size_t)P * M * N);
+    if (g->g2) back(y2, g->y2, (size_t)M * N);
+  }
+  // dual sites (two-plane modes): problem 1 as its single site, problem 2 from a2 / w2 (/ addend2) into out2
+  bool second_operands(Planes* a2, Planes* w2) {
+    if (g->m2 <= 0 || g->n2 <= 0 || g->k2 <= 0 || g->k2 % kGemmBK || !g->a2 || !g->w2 || !g->out2) return bad();
+    return operand(g->a2, (size_t)g->m2 * g->k2, a2) && weight(g->w2, g->k2, g->n2, 0, 0, w2, g->n2);
+  }
+  template <class Pairs> void run(DualSite<Pairs, EpiQKV<2>, EpiStoreF32>) {
+    if constexpr (NP == 2) {
+      QkvIo io;
+      EpiQKV<NP> e;
+      Planes a2, w2;
+      if (!qkv_prepare(&io, &e) || !second_operands(&a2, &w2)) return;
+      if (launch_dual<Pairs>(KC_GEMM_QKV, io.a, io.w, g->m, g->n, g->k, e, e.v_start, a2, w2, g->m2, g->n2, g->k2,
+                             epi_store_f32(g->out2, g->n2)))
+        qkv_collect(io);
+    }
+  }
+  template <class Pairs, bool DUP> void run(DualSite<Pairs, EpiResidualNorm<2, DUP>, EpiAddStoreH16<2>>) {
+    if constexpr (NP == 2) {
+      ResNormIo io;
+      EpiResidualNorm<NP, DUP> e;
+      Planes a2, w2, o2;
+      if (!resnorm_prepare<DUP, false>(&io, &e) || !second_operands(&a2, &w2) || !g->addend2) return (void)(rc = rc ? rc : MSD_ERR_INVALID_ARGUMENT);
+      if (!planes((size_t)g->m2 * g->n2, &o2, true)) return;
+      EpiAddStoreH16<NP> ea;
+      out_pair<NP>(ea.out, o2); ea.ldc = g->n2; ea.addend = g->addend2; ea.ld_add = g->n2;
+      if (!launch_dual<Pairs>(KC_GEMM_ATTN_OUT, io.a, io.w, g->m, g->n, g->k, e, 0, a2, w2, g->m2, g->n2, g->k2, ea)) return;
+      resnorm_collect(io, false);
+      back(o2, g->out2, (size_t)g->m2 * g->n2);
+    }
+  }
+};
+
+template <int NP>
+int run_gemm_site(msd_gemm_site_args* g, hipStream_t s) {
+  SiteRun<NP> r(g, s);
+  if (!r.init()) return r.rc;
+  bool found = visit_at(GemmSites<NP>{}, g->site, [&](auto site) { r.run(site); });
+  if constexpr (NP == 2) {
+    if (!found) found = visit_at(DualSites{}, g->site - list_size(GemmSites<NP>{}), [&](auto site) { r.run(site); });
+  }
+  if (!found) return MSD_ERR_INVALID_ARGUMENT;
+  const int frc = r.finish();
+  return r.rc ? r.rc : frc;
+}
+template <int NP>
+bool gemm_site_tiles(int site, SiteTiles<NP>* t) {
+  bool found = visit_at(GemmSites<NP>{}, site, *t);
+  if constexpr (NP == 2) {
+    if (!found) found = visit_at(DualSites{}, site - list_size(GemmSites<NP>{}), *t);
+  }
+  return found;
+}
+}  // namespace
+}  // extern "C++"
+
+int msd_op_gemm_site(msd_gemm_site_args* args, void* stream) {
+  if (!args || args->struct_size != (int32_t)sizeof(msd_gemm_site_args) || args->site < 0 || args->step < 0 ||
+      args->steps <= 0 || args->step >= args->steps)
+    return MSD_ERR_INVALID_ARGUMENT;
+  const int NP = op_planes(args->precision);
+  if (NP < 0) return MSD_ERR_UNSUPPORTED;
+  args->ran_bm = args->ran_bn = args->ran_ns = args->ran_xcd_rows = args->ran_persistent = args->ran_dual = 0;
+  args->ran_prefetch = args->ran_bm2 = args->ran_bn2 = args->ran_ns2 = args->ran_xcd_rows2 = 0;
+  args->step_copy = -1;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return NP == 2 ? run_gemm_site<2>(args, s) : run_gemm_site<1>(args, s);
+}
+
+const char* msd_op_gemm_site_name(int precision, int site) {
+  const int NP = op_planes(precision);
+  const char* name = nullptr;
+  auto f = [&](auto s) { name = site_name(s); };
+  if (NP == 2) {
+    if (!visit_at(GemmSites<2>{}, site, f)) visit_at(DualSites{}, site - list_size(GemmSites<2>{}), f);
+  } else if (NP == 1) {
+    visit_at(GemmSites<1>{}, site, f);
+  }
+  return name;
+}
+
+int msd_op_gemm_site_tiles(int precision, int site, int index, int32_t* bm, int32_t* bn, int32_t* ns) {
+  if (!bm || !bn || !ns || site < 0 || index < 0) return MSD_ERR_INVALID_ARGUMENT;
+  const int NP = op_planes(precision);
+  if (NP < 0) return MSD_ERR_UNSUPPORTED;
+  std::vector<TileInfo> first, second;
+  bool found;
+  if (NP == 2) { SiteTiles<2> t; found = gemm_site_tiles<2>(site, &t); first = t.first; second = t.second; }
+  else { SiteTiles<1> t; found = gemm_site_tiles<1>(site, &t); first = t.first; second = t.second; }
+  if (!found || index >= (int)first.size()) return MSD_ERR_INVALID_ARGUMENT;
+  bm[0] = first[index].bm; bn[0] = first[index].bn; ns[0] = first[index].ns;
+  bm[1] = bn[1] = ns[1] = 0;
+  if (!second.empty()) { bm[1] = second[index].bm; bn[1] = second[index].bn; ns[1] = second[index].ns; }
+  return MSD_OK;
 }
 
 }  // extern "C"

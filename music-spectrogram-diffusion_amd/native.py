@@ -63,7 +63,9 @@ EXPORTED_SYMBOLS = (
     # (appended to ABI 7) one generator key per row of a batched call
     'msd_sample_rows',
     # (appended to ABI 7) known frames in the sampler
-    'msd_sample_keep', 'msd_op_sampler_step_keep')
+    'msd_sample_keep', 'msd_op_sampler_step_keep',
+    # (appended to ABI 7) one GEMM launch site at a time
+    'msd_op_gemm_site', 'msd_op_gemm_site_tiles', 'msd_op_gemm_site_name')
 
 
 class NativeLibraryError(RuntimeError):
@@ -102,6 +104,25 @@ class MsdConfig(ctypes.Structure):
       ('kv_touch_ahead', ctypes.c_int32),
       ('cross_merge_in_launch', ctypes.c_int32), ('cross_q_fold', ctypes.c_int32),
       ('mlp_in_persistent', ctypes.c_int32)]
+
+
+class GemmSiteArgs(ctypes.Structure):
+  """msd_gemm_site_args of include/msd_amd.h, field for field."""
+  _INTS = ('struct_size', 'precision', 'site', 'm', 'n', 'k', 'step', 'steps', 'force_bm', 'force_bn', 'persistent',
+           'resident_blocks', 'seg_len', 'split_row', 'dup_rows', 'y2_rows', 'passes', 'm2', 'n2', 'k2', 'force_bm2',
+           'force_bn2', 'prefetch_rows', 'prefetch_k',
+           'ran_bm', 'ran_bn', 'ran_ns', 'ran_xcd_rows', 'ran_persistent', 'ran_dual', 'ran_prefetch',
+           'ran_bm2', 'ran_bn2', 'ran_ns2', 'ran_xcd_rows2', 'step_copy')
+  _PTRS = ('a', 'w', 'w_gate', 'ssq', 'bias', 'g_lo', 'g_hi', 'g2', 'pos', 'a2', 'w2', 'addend2', 'prefetch',
+           'x', 'out', 'y', 'y2', 'ssq_out', 'out2')
+  _fields_ = [(n, ctypes.c_int32) for n in _INTS] + [(n, ctypes.c_void_p) for n in _PTRS]
+
+
+# launch sites of msd_op_gemm_site: positions in GemmSites / DualSites of csrc/msd_api.hip (include/msd_amd.h).  The
+# library names its sites from their types (gemm_site_names); tests/test_gpu_gemm_sites.py holds this table against it.
+GEMM_SITES = {'qkv': 0, 'mlp_in': 1, 'residual_square': 2, 'residual_tall': 3, 'resnorm_tall': 4, 'resnorm_tall_dup': 5,
+              'resnorm_square': 6, 'store_h16': 7, 'store_f32': 8, 'in_proj': 9, 'resnorm_tall_y2': 10,
+              'dual_qkv': 11, 'dual_out': 12, 'dual_out_dup': 13}
 
 
 # msd_config only ever grows at its end, so an OLDER library can be driven by passing it the struct size it knows
@@ -210,14 +231,21 @@ def load(planes: str = 'f16') -> ctypes.CDLL:
     lib.msd_vocoder_istft.argtypes = [vp, i32, i32, vp, vp, vp]
     lib.msd_vocoder_encode.argtypes = [vp, i32, i64, vp, vp, vp]
     lib.msd_vocoder_decode.argtypes = [vp, i32, i32, vp, i32, c.c_float, u64, vp, vp, vp]
+  if 'msd_op_gemm_site' in present:   # (appended to ABI 7)
+    lib.msd_op_gemm_site.argtypes = [c.POINTER(GemmSiteArgs), vp]
+    lib.msd_op_gemm_site_tiles.argtypes = [i32, i32, i32, c.POINTER(c.c_int32), c.POINTER(c.c_int32), c.POINTER(c.c_int32)]
+    lib.msd_op_gemm_site_name.argtypes = [i32, i32]
+    lib.msd_op_gemm_site_name.restype = c.c_char_p
   for name in present:
     fn = getattr(lib, name)
-    if name not in ('msd_version', 'msd_last_error', 'msd_destroy', 'msd_vocoder_last_error', 'msd_vocoder_destroy'):
+    if name not in ('msd_version', 'msd_last_error', 'msd_destroy', 'msd_vocoder_last_error', 'msd_vocoder_destroy',
+                    'msd_op_gemm_site_name'):
       fn.restype = i32
   _libs[planes] = lib
   return lib
 
 
+MSD_ERR_INVALID_ARGUMENT = 1   # msd_status of include/msd_amd.h
 _EXC = {1: ValueError, 2: KeyError, 3: ValueError, 4: RuntimeError, 5: RuntimeError,
         6: NotImplementedError, 7: RangeError}
 
@@ -549,3 +577,51 @@ def op_final_proj(x, gamma, w, out, stream: int = 0):
   m, d = x.shape
   _op_check(lib.msd_op_final_proj(_ptr(x), _ptr(gamma), _ptr(w), _ptr(out), m, d, w.shape[1], stream),
             'msd_op_final_proj')
+
+
+def gemm_site_tiles(precision: str, site) -> List[Tuple[int, ...]]:
+  """The tiles of a launch site, from the library's tile table (msd_op_gemm_site_tiles): (bm, bn, ns) per tile; for a
+  dual site (bm, bn, ns, bm2, bn2, ns2) per tile pair.  A site the precision does not have gives an empty list."""
+  lib = load(plane_format(precision))
+  site = GEMM_SITES.get(site, site)
+  out = []
+  bm, bn, ns = (ctypes.c_int32 * 2)(), (ctypes.c_int32 * 2)(), (ctypes.c_int32 * 2)()
+  while True:
+    rc = lib.msd_op_gemm_site_tiles(PRECISIONS[precision], site, len(out), bm, bn, ns)
+    if rc == MSD_ERR_INVALID_ARGUMENT:   # past the last tile (or the last site)
+      return out
+    _op_check(rc, 'msd_op_gemm_site_tiles')
+    out.append((bm[0], bn[0], ns[0]) + ((bm[1], bn[1], ns[1]) if bm[1] else ()))
+
+
+def gemm_site_names(precision: str) -> List[str]:
+  """The launch sites of `precision` in the library's order, named by the library from their types."""
+  lib = load(plane_format(precision))
+  out = []
+  while True:
+    name = lib.msd_op_gemm_site_name(PRECISIONS[precision], len(out))
+    if not name:
+      return out
+    out.append(name.decode())
+
+
+def op_gemm_site(precision: str, site, stream: int = 0, planes: Optional[str] = None, **fields) -> Dict[str, int]:
+  """One launch site of the decoder through the product's dispatcher (msd_op_gemm_site).  `fields`: the members of
+  msd_gemm_site_args by name -- integers, and float32 device tensors for the pointers (kept alive by the caller).
+  Returns the ran_* out-fields and step_copy.  `planes` names the library build to call when it is not the one
+  `precision` belongs to (which that build answers with MSD_ERR_UNSUPPORTED)."""
+  lib = load(planes or plane_format(precision))
+  args = GemmSiteArgs()
+  args.struct_size = ctypes.sizeof(GemmSiteArgs)
+  args.precision = PRECISIONS[precision]
+  args.site = GEMM_SITES.get(site, site)
+  args.steps = 1
+  for name, value in fields.items():
+    if name in GemmSiteArgs._PTRS:
+      setattr(args, name, _ptr(value))
+    elif name in GemmSiteArgs._INTS and not name.startswith('ran_'):
+      setattr(args, name, int(value))
+    else:
+      raise TypeError('msd_gemm_site_args has no input field %r' % name)
+  _op_check(lib.msd_op_gemm_site(ctypes.byref(args), stream), 'msd_op_gemm_site')
+  return {n: getattr(args, n) for n in GemmSiteArgs._INTS if n.startswith('ran_') or n == 'step_copy'}

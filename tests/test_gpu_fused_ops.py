@@ -170,7 +170,7 @@ def test_folded_norm_film_vs_oracle_and_unfolded(env, film, m, k, d, n):
     h = h * (sc.astype(np.float64) + 1.0) + bi.astype(np.float64)
   h_ref = h @ w2.astype(np.float64)
   res = {}
-  # (folded = 2, the split-K producer, exists in the experiments build only: tests/test_gpu_experiments.py; the
+  # (folded = 2, the split-K producer, exists in the experiments build only: tests/frozen/gpu_experiments_r04.py; the
   # product library answers MSD_ERR_UNSUPPORTED)
   with pytest.raises(NotImplementedError):
     native.op_residual_norm_gemm(2, _dev(torch, x_in), _dev(torch, a), _dev(torch, w1), _dev(torch, gamma), None, None,

@@ -263,7 +263,7 @@ def test_batched_songs_use_big_tiles_and_match_oracle():
   """16 songs per handle: M = 2*16*64 = 2048 rows -> the 128-row GEMM tiles of the batched
   path (msd_api.hip big_m_threshold).  emb 192 / 3 heads / mlp 256 make every N a multiple of the
   96/128-column tiles so all big instantiations run; checked per song against the oracle.
-  (The rejected alternative tiles of the experiments build run the same test: tests/test_gpu_experiments.py.)"""
+  (The rejected alternative tiles of the experiments build run the same test: tests/frozen/gpu_experiments_r04.py.)"""
   import dataclasses
   base = msd_amd.config.preset('tiny_context', num_steps=4)
   spec = dataclasses.replace(base, t5=dataclasses.replace(base.t5, emb_dim=192, num_heads=3))
