@@ -22,7 +22,7 @@
  *     other: several may be created, loaded and run concurrently from different threads, also on ONE device (the
  *     library's own synchronous copies use a non-blocking stream of the handle, never the legacy stream).  This
  *     covers every msd_* entry point that takes a handle; the stand-alone msd_op_* building blocks (unit-test entry
- *     points: they allocate, clear and copy scratch through the legacy stream) are NOT part of that guarantee -- do
+ *     points, csrc/standalone_ops.h: they allocate, clear and copy scratch through the legacy stream) are NOT part of that guarantee -- do
  *     not call them while another thread captures or runs a model.
  *   - `stream` is a hipStream_t passed as void* (NULL = the default stream); all
  *     device work is enqueued on it; calls return without synchronising unless
@@ -494,7 +494,7 @@ int msd_vocoder_decode(msd_vocoder* v, int batch, int n_frames, const float* log
                        uint64_t seed, const float* init_phase_dev, float* audio_out_dev, void* stream);
 
 /* ---- (appended to ABI 7) One GEMM launch site of the decoder at a time (tests/test_gpu_gemm_sites.py) ----
- * Runs ONE launch site of the step (GemmSites / DualSites of csrc/msd_api.hip) on the caller's float32 operands through
+ * Runs ONE launch site of the step (GemmSites / DualSites of csrc/msd_api.hip; the entry: csrc/standalone_ops.h SiteRun) on the caller's float32 operands through
  * the product's own dispatch: pick_tile, gp_launch / set_xcd_grid, the range flag, gemm_t's persistent switch and the
  * prefetch-wave choice are the decoder's.  Context: the entry builds a MINIMAL context of its own (no handle is passed and
  * no model is needed): the plane count of `precision`, a range flag, the device's CU count.

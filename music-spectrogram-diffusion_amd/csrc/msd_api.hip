@@ -1863,12 +1863,6 @@ int msd_fill_normal_threefry(uint64_t seed, int64_t fold, float* out_dev, int64_
   return threefry_fill(2, seed, fold, nullptr, out_dev, n, static_cast<hipStream_t>(stream));
 }
 
-int msd_op_threefry(int stage, uint64_t seed, int64_t fold, const uint32_t* bits_in_dev, float* out_dev, int64_t n,
-                    void* stream) {
-  if (bits_in_dev && stage == 0) return MSD_ERR_INVALID_ARGUMENT;
-  return threefry_fill(stage, seed, fold, bits_in_dev, out_dev, n, static_cast<hipStream_t>(stream));
-}
-
 // the words the sampler kernel's own draw reads (one row of SamplerParams::rng_key): EVERY place that launches the step
 // with a NULL noise slot writes all of them for every row of z, the generator kind and the mode included
 static void fill_rng_key(uint32_t* key, int rng, uint64_t seed, uint64_t stream_id, bool per_row) {
@@ -2184,439 +2178,11 @@ int msd_profile_steps(msd_model* m, int batch, int n_steps, const char* const** 
   return MSD_OK;
 }
 
-// ---- standalone ops -----------------------------------------------------------------
-extern "C++" {
-namespace {
-struct Scratch {
-  std::vector<void*> p;
-  ~Scratch() { for (void* q : p) (void)hipFree(q); }
-  template <class Tp> Tp* get(size_t n) {
-    void* q = nullptr;
-    if (hipMalloc(&q, n * sizeof(Tp) + 16) != hipSuccess) return nullptr;
-    (void)hipMemset(q, 0, n * sizeof(Tp) + 16);
-    (void)hipStreamSynchronize(nullptr);   // the ops run on the caller's (possibly non-blocking) stream
-    p.push_back(q);
-    return static_cast<Tp*>(q);
-  }
-};
-// Range bookkeeping of a stand-alone op: device words [0] = bits of the largest packed |w| (pack_wt_kernel),
-// [1] = the activation range flag (common.h RangeCheck).  The ops fail like the model does: weights beyond the
-// half-plane range -> MSD_ERR_UNSUPPORTED (msd_finalize_weights), activations beyond it -> MSD_ERR_RANGE.
-struct OpFlags {
-  unsigned* d = nullptr;
-  bool init(Scratch& sc) { d = sc.get<unsigned>(2); return d != nullptr; }
-  unsigned* absmax() const { return d; }
-  unsigned* sat() const { return d + 1; }
-  template <class P> void arm(P& p) const { p.sat = sat(); p.sat_tag = 1; }
-  int finish(hipStream_t s) const {   // synchronises
-    unsigned h[2] = {0, 0};
-    if (hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-      return MSD_ERR_HIP;
-    if (kPlaneSaturates) {
-      float top;
-      memcpy(&top, &h[0], sizeof(top));
-      if (!(top < kPlaneMax / kWScale)) return MSD_ERR_UNSUPPORTED;
-      if (h[1]) return MSD_ERR_RANGE;
-    }
-    return MSD_OK;
-  }
-};
-// planes per operand of an op's `precision` argument; -1: not a precision of THIS build's plane format
-int op_planes(int precision) {
-  const bool bf = precision == MSD_PREC_BF16 || precision == MSD_PREC_BF16X3;
-  if (precision < MSD_PREC_F16 || precision > MSD_PREC_BF16X3 || bf != (MSD_PLANE_BF16 != 0)) return -1;
-  return (precision == MSD_PREC_F16X3 || precision == MSD_PREC_BF16X3) ? 2 : 1;
-}
-}  // namespace
-}  // extern "C++"
+}  // extern "C"
 
-int msd_op_gemm_h16(int precision, const float* a_dev, const float* w_dev, float* c_dev, int M,
-                    int N, int K, void* stream) {
-  if (M % 64 || N % 64 || K % 64 || M <= 0 || N <= 0 || K <= 0) return MSD_ERR_INVALID_ARGUMENT;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int NP = op_planes(precision);
-  if (NP < 0) return MSD_ERR_UNSUPPORTED;
-  Scratch sc;
-  OpFlags fl;
-  if (!fl.init(sc)) return MSD_ERR_HIP;
-  Planes a, w;
-  for (int i = 0; i < NP; ++i) {
-    a.p[i] = sc.get<h16_t>((size_t)M * K);
-    w.p[i] = sc.get<h16_t>((size_t)N * K);
-    if (!a.p[i] || !w.p[i]) return MSD_ERR_HIP;
-  }
-  split(a_dev, a, (int64_t)M * K, s, fl.sat());
-  dim3 grid((K + 63) / 64, N), block(64);
-  hipLaunchKernelGGL(pack_wt_kernel, grid, block, 0, s, w_dev, K, N, w.p[0],
-                     NP == 2 ? w.p[1] : (h16_t*)nullptr, 0, 0, 0, fl.absmax());
-  hipError_t e;
-  if (NP == 2) e = launch_gemm_h16_dma<2, 64, 64, 3>(gp<2>(a, K, w, K, M, N, K), epi_store_f32(c_dev, N), s);
-  else e = launch_gemm_h16_dma<1, 64, 64, 3>(gp<1>(a, K, w, K, M, N, K), epi_store_f32(c_dev, N), s);
-  if (e != hipSuccess) return MSD_ERR_HIP;
-  return fl.finish(s);
-}
+#include "standalone_ops.h"   // the msd_op_* unit-test entry points; belongs to this file alone (see the file)
 
-/* ABI <= 2 name of msd_op_gemm_h16 (the planes were bfloat16 then); kept so that old bindings keep linking */
-int msd_op_gemm_bf16(int precision, const float* a_dev, const float* w_dev, float* c_dev, int M,
-                     int N, int K, void* stream) {
-  return msd_op_gemm_h16(precision, a_dev, w_dev, c_dev, M, N, K, stream);
-}
-
-int msd_op_gemm_f32(const float* a_dev, const float* w_dev, float* c_dev, int M, int N, int K,
-                    void* stream) {
-  if (N % 64 || K % 16 || M <= 0) return MSD_ERR_INVALID_ARGUMENT;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  GemmF32Params p;
-  p.A = a_dev; p.B = w_dev; p.lda = K; p.ldb = N; p.M = M; p.N = N; p.K = K;
-  if (launch_gemm_f32(p, EpiF32Store{c_dev, N}, s) != hipSuccess) return MSD_ERR_HIP;
-  return hipStreamSynchronize(s) == hipSuccess ? MSD_OK : MSD_ERR_HIP;
-}
-
-int msd_op_attention(int precision, const float* q_dev, const float* k_dev, const float* v_dev,
-                     float* o_dev, int n_q, int n_keys, int n_keys_valid, int heads, void* stream) {
-  return msd_op_attention_qp(precision, 0, q_dev, k_dev, v_dev, o_dev, n_q, n_keys, n_keys_valid, heads, stream);
-}
-
-int msd_op_attention_qp(int precision, int qp, const float* q_dev, const float* k_dev, const float* v_dev,
-                        float* o_dev, int n_q, int n_keys, int n_keys_valid, int heads, void* stream) {
-  // (long key axes exercise the key-split path + the merge LAUNCH: a split of 3 runs as 2)
-  return msd_op_attention_split(precision, qp, n_keys >= 512 ? 3 : 1, 0, 1, q_dev, k_dev, v_dev, o_dev, n_q, n_keys, n_keys_valid,
-                                heads, stream);
-}
-
-int msd_op_attention_split(int precision, int qp, int ksplit, int merge_in_launch, int repeats, const float* q_dev,
-                           const float* k_dev, const float* v_dev, float* o_dev, int n_q, int n_keys, int n_keys_valid,
-                           int heads, void* stream) {
-  return msd_op_attention_ex(precision, qp, ksplit, merge_in_launch, repeats, 0, nullptr, 0, q_dev, k_dev, v_dev, o_dev, n_q,
-                             n_keys, n_keys_valid, heads, stream);
-}
-
-int msd_op_attention_ex(int precision, int qp, int ksplit, int merge_in_launch, int repeats, int allow_qb4,
-                        const float* q_ssq_dev, int q_tiles, const float* q_dev, const float* k_dev, const float* v_dev,
-                        float* o_dev, int n_q, int n_keys, int n_keys_valid, int heads, void* stream) {
-  if (qp < 0 || qp > 3 || ksplit < 1 || ksplit > 8 || repeats < 1 || repeats > 1000) return MSD_ERR_INVALID_ARGUMENT;
-  if (n_q % 64 || n_keys % 32 || n_q <= 0 || n_keys <= 0 || heads <= 0 || n_keys_valid < 0 ||
-      n_keys_valid > n_keys)
-    return MSD_ERR_INVALID_ARGUMENT;
-  if (q_ssq_dev != nullptr && (q_tiles <= 0 || q_tiles > kAuxMaxTiles || q_tiles % 4)) return MSD_ERR_INVALID_ARGUMENT;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const int NP = op_planes(precision);
-  if (NP < 0) return MSD_ERR_UNSUPPORTED;
-  if (q_ssq_dev != nullptr && NP != 2) return MSD_ERR_UNSUPPORTED;   // (un-normalised queries: two-plane kernels only)
-  const int J = heads * kHeadDim;
-  Scratch sc;
-  OpFlags fl;
-  if (!fl.init(sc)) return MSD_ERR_HIP;
-  Planes q, k, vt, o;
-  int* d_nk = sc.get<int>(1);
-  float* vt32 = sc.get<float>((size_t)J * n_keys);
-  for (int i = 0; i < NP; ++i) {
-    q.p[i] = sc.get<h16_t>((size_t)n_q * J);
-    k.p[i] = sc.get<h16_t>((size_t)n_keys * J);
-    vt.p[i] = sc.get<h16_t>((size_t)J * n_keys);
-    o.p[i] = sc.get<h16_t>((size_t)n_q * J);
-    if (!q.p[i] || !k.p[i] || !vt.p[i] || !o.p[i]) return MSD_ERR_HIP;
-  }
-  if (!d_nk || !vt32) return MSD_ERR_HIP;
-  (void)hipMemcpyAsync(d_nk, &n_keys_valid, sizeof(int), hipMemcpyHostToDevice, s);
-  split(q_dev, q, (int64_t)n_q * J, s, fl.sat());
-  split(k_dev, k, (int64_t)n_keys * J, s, fl.sat());
-  // V -> V^T with the per-16 key permutation, via the GEMM epilogue's own rule (host copy)
-  std::vector<float> vh((size_t)n_keys * J), vth((size_t)J * n_keys);
-  if (hipMemcpy(vh.data(), v_dev, vh.size() * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) return MSD_ERR_HIP;
-  for (int key = 0; key < n_keys; ++key) {
-    const int o16 = key & 15;
-    const int kp = (key & ~15) + 8 * ((o16 >> 2) & 1) + (o16 & 3) + 4 * (o16 >> 3);
-    for (int j = 0; j < J; ++j) vth[(size_t)j * n_keys + kp] = vh[(size_t)key * J + j];
-  }
-  if (hipMemcpy(vt32, vth.data(), vth.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return MSD_ERR_HIP;
-  split(vt32, vt, (int64_t)J * n_keys, s, fl.sat());
-  AttnParams p;
-  fl.arm(p);
-  p.qp = qp;
-  p.allow_qb4 = allow_qb4 != 0;
-  if (q_ssq_dev != nullptr) { p.q_ssq = q_ssq_dev; p.q_tiles = q_tiles; p.q_inv_d = 1.0f / (float)(kNarrowTile * q_tiles); }
-  for (int i = 0; i < 2; ++i) {
-    const int j = i < NP ? i : 0;
-    p.q[i] = q.p[j]; p.k[i] = k.p[j]; p.vt[i] = vt.p[j]; p.o[i] = o.p[j];
-  }
-  p.n_keys = d_nk; p.ldq = J; p.ldk = J; p.ldo = J; p.vt_ld = n_keys; p.q_rows_per_seg = n_q;
-  p.k_seg_stride = 0; p.vt_seg_stride = 0; p.k_rows = n_keys;
-  p.ksplit = 1; p.part_o = nullptr; p.part_ml = nullptr; p.total_rows = n_q;
-  float *po = nullptr, *pml = nullptr;
-  if (ksplit > 1) {
-    p.ksplit = ksplit;
-    po = sc.get<float>((size_t)ksplit * n_q * J);
-    pml = sc.get<float>((size_t)ksplit * n_q * heads * 2);
-    if (!po || !pml) return MSD_ERR_HIP;
-    p.part_o = po; p.part_ml = pml;
-    if (merge_in_launch) {   // attention.h attention_inlaunch_merge: one (zeroed) arrival counter per (query block, head)
-      p.tickets = sc.get<int>((size_t)(n_q / 32) * heads);
-      if (!p.tickets) return MSD_ERR_HIP;
-    }
-  }
-  hipError_t e = hipSuccess;
-  for (int r = 0; r < repeats && e == hipSuccess; ++r)   // back to back: the counters must be zero again after every launch
-    e = NP == 2 ? launch_attention<2>(p, heads, 1, s) : launch_attention<1>(p, heads, 1, s);
-  if (e != hipSuccess) return MSD_ERR_HIP;
-  merge(o, o_dev, (int64_t)n_q * J, s);
-  return fl.finish(s);
-}
-
-
-// ---- standalone ops of the FUSED pieces (each has its own parity test, tests/test_gpu_fused_ops.py) ---
-extern "C++" {
-namespace {
-// W fp32 [K, N] (reference layout) -> packed W^T planes [N, K]
-bool new_planes(Scratch& sc, size_t n, Planes* out) {   // two zeroed planes of n elements
-  for (h16_t*& pl : out->p) pl = sc.get<h16_t>(n);
-  return out->p[0] && out->p[1];
-}
-bool pack_planes(Scratch& sc, const float* w_dev, int K, int N, int mode, int dst_row0, Planes* out, int rows,
-                 hipStream_t s, const OpFlags& fl) {
-  if (!out->p[0] && !new_planes(sc, (size_t)rows * K, out)) return false;
-  dim3 grid((K + 63) / 64, N), block(64);
-  hipLaunchKernelGGL(pack_wt_kernel, grid, block, 0, s, w_dev, K, N, out->p[0], out->p[1], dst_row0, mode, 0,
-                     fl.absmax());
-  return hipGetLastError() == hipSuccess;
-}
-bool split_new(Scratch& sc, const float* in, int64_t n, Planes* out, hipStream_t s, const OpFlags& fl) {
-  if (!new_planes(sc, (size_t)n, out)) return false;
-  split(in, *out, n, s, fl.sat());
-  return true;
-}
-}  // namespace
-}  // extern "C++"
-
-// one launch of the sampler update on the caller's arrays; known_scaled_dev != NULL: the keep form
-static int op_sampler_step(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
-                           const float* out_uncond_dev, const float* noise_dev, const float* known_scaled_dev,
-                           const int32_t* keep_mask_dev, int n_dims, float* z_out_dev, int64_t n, void* stream) {
-  if (!cfg || cfg->struct_size != (int32_t)sizeof(msd_config) || !z_dev || !out_cond_dev || !z_out_dev ||
-      n <= 0 || n % 4 || step_index < 0 || step_index >= cfg->num_steps)
-    return MSD_ERR_INVALID_ARGUMENT;
-  const int passes = cfg->cfg_weight != 1.0f ? 2 : 1;
-  if (passes == 2 && !out_uncond_dev) return MSD_ERR_INVALID_ARGUMENT;
-  std::vector<float> rows;
-  std::string why;
-  if (!build_coef_rows(*cfg, &rows, &why)) return MSD_ERR_INVALID_ARGUMENT;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  Scratch sc;
-  float* coef = sc.get<float>(rows.size());
-  float* eps = sc.get<float>((size_t)passes * n);
-  float* noise = sc.get<float>((size_t)n);   // one step's draw (zeros) when the caller gives none
-  const float** slot = sc.get<const float*>(1);
-  int* step = sc.get<int>(2);
-  uint32_t* key = sc.get<uint32_t>(kRngWords);   // the kernel fetches the words of its own draw up front, used or not (table row 0: SamplerParams::row_blocks' default)
-  if (!coef || !eps || !noise || !slot || !step || !key) return MSD_ERR_HIP;
-  // the kernel indexes noise as base + i * n: hand it base = draw - i * n
-  const float* base = (noise_dev ? noise_dev : noise) - (size_t)step_index * n;
-  const int st[2] = {step_index, step_index};
-  if (hipMemcpyAsync(coef, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(eps, out_cond_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-      (passes == 2 && hipMemcpyAsync(eps + n, out_uncond_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) ||
-      hipMemcpyAsync(z_out_dev, z_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(slot, &base, sizeof(base), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(step, st, sizeof(st), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess)
-    return MSD_ERR_HIP;
-  SamplerKeepParams sp;
-  sp.eps = eps; sp.z = z_out_dev; sp.noise_slot = slot; sp.coef = coef; sp.step_ptr = step; sp.rng_key = key;
-  sp.n = (int)n; sp.passes = passes; sp.cond_wt = cfg->cfg_weight; sp.clip_x0 = cfg->clip_x0;
-  sp.ddim = cfg->sampler == MSD_SAMPLER_DDIM; sp.model_output = cfg->model_output;
-  sp.z_hi = nullptr; sp.z_lo = nullptr; sp.step_from_slot1 = 1;
-  if (known_scaled_dev) {
-    sp.xk = known_scaled_dev; sp.keep = keep_mask_dev; sp.n_dims = n_dims;
-    launch_sampler_step(sp, s);
-  } else {
-    launch_sampler_step(static_cast<const SamplerParams&>(sp), s);
-  }
-  if (hipGetLastError() != hipSuccess) return MSD_ERR_HIP;
-  return hipStreamSynchronize(s) == hipSuccess ? MSD_OK : MSD_ERR_HIP;
-}
-
-int msd_op_sampler_step(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
-                        const float* out_uncond_dev, const float* noise_dev, float* z_out_dev, int64_t n,
-                        void* stream) {
-  return op_sampler_step(cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, noise_dev, nullptr, nullptr, 0, z_out_dev,
-                         n, stream);
-}
-
-int msd_op_sampler_step_keep(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
-                             const float* out_uncond_dev, const float* noise_dev, const float* known_scaled_dev,
-                             const int32_t* keep_mask_dev, int n_dims, float* z_out_dev, int64_t n, void* stream) {
-  if (!known_scaled_dev || !keep_mask_dev || n_dims <= 0 || n_dims % 4 || n <= 0 || n % n_dims)
-    return MSD_ERR_INVALID_ARGUMENT;
-  return op_sampler_step(cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, noise_dev, known_scaled_dev, keep_mask_dev,
-                         n_dims, z_out_dev, n, stream);
-}
-
-// x_out = x_in + a . w1 ;  h_out = (RMSNorm(x_out; gamma) (.) (film_scale + 1) + film_bias) . w2
-// folded != 0: the product's path -- EpiResidualNorm (y = x (.) g planes + partial sums of squares)
-// then a consumer GEMM whose epilogue applies rstd and the tabulated bias.W2;
-// folded == 0: residual GEMM, rmsnorm_film_kernel, plain GEMM.
-int msd_op_residual_norm_gemm(int folded, const float* x_in_dev, const float* a_dev, const float* w1_dev,
-                              const float* gamma_dev, const float* film_scale_dev, const float* film_bias_dev,
-                              const float* w2_dev, float* x_out_dev, float* h_out_dev, int M, int K, int D, int N,
-                              void* stream) {
-  if (M % 64 || K % 64 || D % 64 || N % 64 || M <= 0 || D > 1024 || !x_in_dev || !a_dev || !w1_dev || !gamma_dev ||
-      !w2_dev || !x_out_dev || !h_out_dev || (!film_scale_dev) != (!film_bias_dev))
-    return MSD_ERR_INVALID_ARGUMENT;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  Scratch sc;
-  OpFlags fl;
-  if (!fl.init(sc)) return MSD_ERR_HIP;
-  Planes a, w1, w2, y;
-  if (!split_new(sc, a_dev, (int64_t)M * K, &a, s, fl) || !pack_planes(sc, w1_dev, K, D, 0, 0, &w1, D, s, fl) ||
-      !pack_planes(sc, w2_dev, D, N, 0, 0, &w2, N, s, fl))
-    return MSD_ERR_HIP;
-  const int tiles = D / kNarrowTile;
-  float* ssq = sc.get<float>((size_t)M * tiles);
-  float* film = sc.get<float>((size_t)2 * D);   // one-step, one-slot table: scale | bias
-  float* g = sc.get<float>((size_t)D);
-  float* bw = sc.get<float>((size_t)N);
-  int* step = sc.get<int>(2);
-  if (!new_planes(sc, (size_t)M * D, &y) || !ssq || !film || !g || !bw || !step) return MSD_ERR_HIP;
-  if (hipMemcpyAsync(x_out_dev, x_in_dev, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess)
-    return MSD_ERR_HIP;
-  if (film_scale_dev) {
-    (void)hipMemcpyAsync(film, film_scale_dev, D * sizeof(float), hipMemcpyDeviceToDevice, s);
-    (void)hipMemcpyAsync(film + D, film_bias_dev, D * sizeof(float), hipMemcpyDeviceToDevice, s);
-  }
-  hipError_t e = hipSuccess;
-  if (folded) {
-    hipLaunchKernelGGL(build_g_kernel, dim3((D + 255) / 256), dim3(256), 0, s, film, gamma_dev, g, 1, 1, 0, D);
-    GemmF32Params bp;   // bias . W2 : one row
-    bp.A = film + D; bp.B = w2_dev; bp.lda = D; bp.ldb = N; bp.M = 1; bp.N = N; bp.K = D;
-    e = launch_gemm_f32(bp, EpiF32Store{bw, N}, s);
-    const EpiResidualNorm<2> er = epi_residual_norm<2>(x_out_dev, D, y, ssq, step, Gain{g, 0}, Gain{g, 0}, M / 2);
-    GemmParams p1 = gp<2>(a, K, w1, K, M, D, K);
-    p1.xcd_rows = 2; p1.xcd_walk_n = 1;
-    fl.arm(p1);
-    if (folded == 2) {   // (was: the split-K producer of the frozen experiments build, tools/ubench/exp -- not in the product)
-      return MSD_ERR_UNSUPPORTED;
-    } else if (folded == 3) {   // the producer on 32 x 48 tiles (one partial sum per row and tile + zeroed spare slots)
-      if (D % kWide48 || M % 32) return MSD_ERR_INVALID_ARGUMENT;
-      if (e == hipSuccess) e = launch_gemm_h16_dma<2, 32, kWide48, 4>(p1, er, s);
-    } else if (e == hipSuccess) e = launch_gemm_h16_dma<2, 32, 32, 4>(p1, er, s);
-    const EpiStoreF32 ef = epi_store_f32(h_out_dev, N, row_scale(ssq, tiles, step, bw, 0));
-    if (e == hipSuccess) e = launch_gemm_h16_dma<2, 64, 64, 3>(gp<2>(y, D, w2, D, M, N, D), ef, s);
-  } else {
-    e = launch_gemm_h16_dma<2, 32, 32, 4>(gp<2>(a, K, w1, K, M, D, K), EpiResidual{x_out_dev, D}, s);
-    NormParams np;
-    np.x = x_out_dev; np.gamma = gamma_dev; np.film = film_scale_dev ? film : nullptr; np.step_ptr = step;
-    np.film_slots = 1; np.film_slot = 0; np.rows = M; np.D = D; np.out[0] = y.p[0]; np.out[1] = y.p[1]; np.out_f32 = nullptr;
-    fl.arm(np);
-    hipLaunchKernelGGL((rmsnorm_film_kernel<1, 4>), dim3((M + 3) / 4), dim3(256), 0, s, np);
-    if (e == hipSuccess) e = launch_gemm_h16_dma<2, 64, 64, 3>(gp<2>(y, D, w2, D, M, N, D), epi_store_f32(h_out_dev, N), s);
-  }
-  if (e != hipSuccess || hipGetLastError() != hipSuccess) return MSD_ERR_HIP;
-  if (const int rc = fl.finish(s)) return rc;
-  return MSD_OK;
-}
-
-// out[M, F] = gelu_tanh(a . wi0) * (a . wi1)   (layers.py:483-497): interleaved wi_0/wi_1 packing + EpiGeglu,
-// on the 64 x 128 tile the decoder uses
-int msd_op_geglu(const float* a_dev, const float* wi0_dev, const float* wi1_dev, float* out_dev, int M, int K, int F,
-                 void* stream) {
-  if (M % 64 || K % 64 || F % 64 || M <= 0 || !a_dev || !wi0_dev || !wi1_dev || !out_dev) return MSD_ERR_INVALID_ARGUMENT;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  Scratch sc;
-  OpFlags fl;
-  if (!fl.init(sc)) return MSD_ERR_HIP;
-  Planes a, wi, g;
-  if (!split_new(sc, a_dev, (int64_t)M * K, &a, s, fl) || !pack_planes(sc, wi0_dev, K, F, 1, 0, &wi, 2 * F, s, fl) ||
-      !pack_planes(sc, wi1_dev, K, F, 2, 0, &wi, 2 * F, s, fl))
-    return MSD_ERR_HIP;
-  if (!new_planes(sc, (size_t)M * F, &g)) return MSD_ERR_HIP;
-  const EpiGeglu<2> eg = epi_out<EpiGeglu, 2>(g, F);
-  GemmParams pg = gp<2>(a, K, wi, K, M, 2 * F, K);
-  fl.arm(pg);
-  hipError_t e = launch_gemm_h16_dma<2, 64, 128, 3>(pg, eg, s);
-  if (e != hipSuccess) return MSD_ERR_HIP;
-  merge(g, out_dev, (int64_t)M * F, s);
-  return fl.finish(s);
-}
-
-// Fused q|k|v projection with the attention kernel's operand layouts (EpiQKV): q, k row-major, V^T per
-// segment with the per-16 key permutation; returned un-permuted as q, k, v [M, J].
-int msd_op_qkv(const float* a_dev, const float* wq_dev, const float* wk_dev, const float* wv_dev, float* q_out_dev,
-               float* k_out_dev, float* v_out_dev, int M, int K, int J, int seg_len, void* stream) {
-  if (M % 64 || K % 64 || J % 64 || M <= 0 || seg_len <= 0 || seg_len % 64 || M % seg_len || !a_dev || !wq_dev ||
-      !wk_dev || !wv_dev || !q_out_dev || !k_out_dev || !v_out_dev)
-    return MSD_ERR_INVALID_ARGUMENT;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  Scratch sc;
-  OpFlags fl;
-  if (!fl.init(sc)) return MSD_ERR_HIP;
-  Planes a, w, qk, vt;
-  if (!split_new(sc, a_dev, (int64_t)M * K, &a, s, fl) || !pack_planes(sc, wq_dev, K, J, 0, 0, &w, 3 * J, s, fl) ||
-      !pack_planes(sc, wk_dev, K, J, 0, J, &w, 3 * J, s, fl) || !pack_planes(sc, wv_dev, K, J, 0, 2 * J, &w, 3 * J, s, fl))
-    return MSD_ERR_HIP;
-  float* f32 = sc.get<float>((size_t)M * 2 * J);
-  if (!new_planes(sc, (size_t)M * 2 * J, &qk) || !new_planes(sc, (size_t)M * J, &vt) || !f32) return MSD_ERR_HIP;
-  const EpiQKV<2> eq = epi_qkv<2>(qk, vt, 2 * J, seg_len, J);
-  hipError_t e;
-  GemmParams pq = gp<2>(a, K, w, K, M, 3 * J, K);
-  fl.arm(pq);
-  if ((3 * J) % 96 == 0 && (2 * J) % 96 == 0) e = launch_gemm_h16_dma<2, 64, 96, 3>(pq, eq, s);
-  else e = launch_gemm_h16_dma<2, 64, 64, 3>(pq, eq, s);
-  if (e != hipSuccess) return MSD_ERR_HIP;
-  if (const int rc = fl.finish(s)) return rc;
-  std::vector<float> h((size_t)M * 2 * J), qh((size_t)M * J), kh((size_t)M * J), vh((size_t)M * J);
-  merge(qk, f32, (int64_t)M * 2 * J, s);
-  if (hipMemcpyAsync(h.data(), f32, h.size() * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess)
-    return MSD_ERR_HIP;
-  for (int m = 0; m < M; ++m)
-    for (int j = 0; j < J; ++j) {
-      qh[(size_t)m * J + j] = h[(size_t)m * 2 * J + j];
-      kh[(size_t)m * J + j] = h[(size_t)m * 2 * J + J + j];
-    }
-  merge(vt, f32, (int64_t)M * J, s);
-  if (hipMemcpyAsync(h.data(), f32, (size_t)M * J * sizeof(float), hipMemcpyDeviceToHost, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess)
-    return MSD_ERR_HIP;
-  for (int m = 0; m < M; ++m) {   // V^T[seg][j][perm(key)] -> v[m][j]
-    const int seg = m / seg_len, key = m % seg_len, o16 = key & 15;
-    const int kp = (key & ~15) + 8 * ((o16 >> 2) & 1) + (o16 & 3) + 4 * (o16 >> 3);
-    for (int j = 0; j < J; ++j) vh[(size_t)m * J + j] = h[((size_t)seg * J + j) * seg_len + kp];
-  }
-  if (hipMemcpy(q_out_dev, qh.data(), qh.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(k_out_dev, kh.data(), kh.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-      hipMemcpy(v_out_dev, vh.data(), vh.size() * sizeof(float), hipMemcpyHostToDevice) != hipSuccess)
-    return MSD_ERR_HIP;
-  return MSD_OK;
-}
-
-// out[M, n] = RMSNorm(x; gamma) . w in exact fp32 (network.py:445-456): final_proj_f32_kernel with the
-// decoder_norm folded in (w pre-multiplied by gamma, rstd from the partial sums of squares that the
-// residual epilogue of the last MLP writes -- produced here by the same epilogue with a zero update)
-int msd_op_final_proj(const float* x_dev, const float* gamma_dev, const float* w_dev, float* out_dev, int M, int D,
-                      int n, void* stream) {
-  if (M % 64 || D % 64 || n % 32 || M <= 0 || D > 1024 || !x_dev || !gamma_dev || !w_dev || !out_dev)
-    return MSD_ERR_INVALID_ARGUMENT;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  Scratch sc;
-  const int tiles = D / kNarrowTile;
-  float* x = sc.get<float>((size_t)M * D);
-  float* ssq = sc.get<float>((size_t)M * tiles);
-  float* wg = sc.get<float>((size_t)D * n);
-  int* step = sc.get<int>(2);
-  Planes za, zw;   // zero operands of the zero-update residual GEMM
-  if (!x || !ssq || !wg || !step || !new_planes(sc, (size_t)M * 64, &za) || !new_planes(sc, (size_t)D * 64, &zw)) return MSD_ERR_HIP;
-  if (hipMemcpyAsync(x, x_dev, (size_t)M * D * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) return MSD_ERR_HIP;
-  const EpiResidualNorm<2> er = epi_residual_norm<2>(x, D, Planes(), ssq, step, Gain(), Gain(), 0);
-  hipError_t e = launch_gemm_h16_dma<2, 32, 32, 4>(gp<2>(za, 64, zw, 64, M, D, 64), er, s);
-  if (e != hipSuccess) return MSD_ERR_HIP;
-  hipLaunchKernelGGL(scale_rows_kernel, dim3((D * n + 255) / 256), dim3(256), 0, s, w_dev, gamma_dev, wg, D, n);
-  FinalProjParams fp;
-  fp.x = x; fp.wg = wg; fp.ssq = ssq; fp.out = out_dev; fp.M = M; fp.N = n; fp.K = D; fp.tiles = tiles;
-  fp.inv_d = 1.0f / (float)D;
-  hipLaunchKernelGGL(final_proj_f32_kernel<1>, dim3(n / 32, M / 16), dim3(64 * kFinalProjWaves), 0, s, fp);
-  if (hipGetLastError() != hipSuccess) return MSD_ERR_HIP;
-  return hipStreamSynchronize(s) == hipSuccess ? MSD_OK : MSD_ERR_HIP;
-}
+extern "C" {
 
 // ---- device vocoder (vocoder.h): STFT pair, Audio2Mel, fast Griffin-Lim -------------------------------------------
 extern "C++" {
@@ -2753,433 +2319,6 @@ int msd_vocoder_decode(msd_vocoder* v, int batch, int n_frames, const float* log
   }
   if (err.e == hipSuccess) err(voc_inverse(v, batch, F, audio_out_dev, false, s));
   return voc_finish(v, err, s, "msd_vocoder_decode");
-}
-
-// ---- one GEMM launch site at a time, through the product's dispatcher (tests/test_gpu_gemm_sites.py) ----------------
-// Behind every other entry point on purpose: every kernel instance this code can reach is first named by set_func_attrs,
-// so the device code of the library is what it was without it (compare the device listings when this changes).
-extern "C++" {
-namespace {
-struct TileInfo { int bm = 0, bn = 0, ns = 0; };
-template <class... T> std::vector<TileInfo> tiles_of(List<T...>) { return {TileInfo{T::BM, T::BN, T::NS}...}; }
-template <class... P> std::vector<TileInfo> first_tiles_of(List<P...>) { return {TileInfo{P::P1::BM, P::P1::BN, P::P1::NS}...}; }
-template <class... P> std::vector<TileInfo> second_tiles_of(List<P...>) { return {TileInfo{P::P2::BM, P::P2::BN, P::P2::NS}...}; }
-const TileInfo* find_tile(const std::vector<TileInfo>& v, TileShape t) {
-  for (const TileInfo& x : v)
-    if (x.bm == t.bm && x.bn == t.bn) return &x;
-  return nullptr;
-}
-template <int NP, class Epi, class... T>
-bool persistent_on(List<T...>, TileShape t, const msd_model* m, const GemmParams& p, const Epi& epi) {
-  return ((T::is(t) && runs_persistent<NP, T, Epi>(m, p, epi)) || ...);
-}
-// the launch sites by name, from their types (msd_op_gemm_site_name)
-template <int TK, int NP> const char* site_name(Site<TK, EpiQKV<NP>>) { return "qkv"; }
-template <int TK, int NP> const char* site_name(Site<TK, EpiGeglu<NP>>) { return "mlp_in"; }
-template <int TK> const char* site_name(Site<TK, EpiResidual>) { return TK == TK_TALL ? "residual_tall" : "residual_square"; }
-template <int TK, int NP, bool DUP, bool Y2> const char* site_name(Site<TK, EpiResidualNorm<NP, DUP, Y2>>) {
-  return TK == TK_TALL ? (DUP ? "resnorm_tall_dup" : (Y2 ? "resnorm_tall_y2" : "resnorm_tall")) : "resnorm_square";
-}
-template <int TK, int NP> const char* site_name(Site<TK, EpiStoreH16<NP>>) { return "store_h16"; }
-template <int TK> const char* site_name(Site<TK, EpiStoreF32>) { return "store_f32"; }
-template <int TK, int NP> const char* site_name(Site<TK, EpiInProj<NP>>) { return "in_proj"; }
-template <class Pairs> const char* site_name(DualSite<Pairs, EpiQKV<2>, EpiStoreF32>) { return "dual_qkv"; }
-template <class Pairs, bool DUP> const char* site_name(DualSite<Pairs, EpiResidualNorm<2, DUP>, EpiAddStoreH16<2>>) {
-  return DUP ? "dual_out_dup" : "dual_out";
-}
-
-// f(S{}) for the index-th entry of a list of (empty) site types; false: no such entry
-template <class F, class... S>
-bool visit_at(List<S...>, int index, F&& f) {
-  int i = 0;
-  return ((i++ == index ? (f(S{}), true) : false) || ...);
-}
-template <class... S> constexpr int list_size(List<S...>) { return (int)sizeof...(S); }
-
-template <int NP> struct SiteTiles {
-  std::vector<TileInfo> first, second;   // second: dual sites only
-  template <int TK, class Epi> void operator()(Site<TK, Epi>) { first = tiles_of(TileTable<NP, TK, Epi>{}); }
-  template <class Pairs, class E1, class E2> void operator()(DualSite<Pairs, E1, E2>) {
-    first = first_tiles_of(Pairs{});
-    second = second_tiles_of(Pairs{});
-  }
-};
-
-// One site launch.  Its context is a MINIMAL one of its own: an msd_model of which Ctx, gp_launch, gemm_t and
-// weights_target read the plane count, the range flag, the CU count and the persistent / prefetch switches; it has no
-// weights, tables or buffers.
-template <int NP>
-struct SiteRun {
-  msd_gemm_site_args* g;
-  msd_model ctx_model;
-  Ctx c;
-  Scratch sc;
-  OpFlags fl;
-  hipStream_t s;
-  int* step = nullptr;
-  int rc = MSD_OK;
-
-  SiteRun(msd_gemm_site_args* g_, hipStream_t s_) : g(g_), c{&ctx_model, s_}, s(s_) { ctx_model.NP = NP; }
-
-  bool ok(hipError_t e) {
-    if (e != hipSuccess && rc == MSD_OK) rc = MSD_ERR_HIP;
-    return e == hipSuccess;
-  }
-  bool bad() { rc = MSD_ERR_INVALID_ARGUMENT; return false; }
-
-  // zeroed planes (one when NP == 1: p[1] stays null, the operand convention); `nan`: every element a NaN instead
-  bool planes(size_t n, Planes* out, bool nan = false) {
-    for (int i = 0; i < NP; ++i) {
-      out->p[i] = sc.get<h16_t>(n);
-      if (!out->p[i]) { rc = MSD_ERR_HIP; return false; }
-      if (nan && !ok(hipMemsetAsync(out->p[i], 0xFF, n * sizeof(h16_t), s))) return false;
-    }
-    return true;
-  }
-  bool operand(const float* in, size_t n, Planes* out) {
-    if (!planes(n, out)) return false;
-    split(in, *out, (int64_t)n, s, fl.sat());
-    return true;
-  }
-  bool weight(const float* w, int K, int N, int mode, int row0, Planes* out, int rows) {
-    if (!out->p[0] && !planes((size_t)rows * K, out)) return false;
-    if (!pack_planes(sc, w, K, N, mode, row0, out, rows, s, fl)) { rc = MSD_ERR_HIP; return false; }
-    return true;
-  }
-  void back(const Planes& pl, float* out, size_t n) { merge(pl, out, (int64_t)n, s); }
-
-  bool init() {
-    if (!fl.init(sc)) { rc = MSD_ERR_HIP; return false; }
-    step = sc.get<int>(2);
-    if (!step) { rc = MSD_ERR_HIP; return false; }
-    const int st[2] = {g->step, -1};
-    if (!ok(hipMemcpyAsync(step, st, sizeof(st), hipMemcpyHostToDevice, s)) || !ok(hipStreamSynchronize(s))) return false;
-    ctx_model.d_sat = fl.sat();
-    ctx_model.persist_mlp_in = g->persistent != 2;
-    ctx_model.prefetch = true;
-    int dev = 0, cus = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess)
-      ctx_model.cus = cus;
-    if (g->resident_blocks > 0) ctx_model.cus = g->resident_blocks;
-    return true;
-  }
-  int finish() {
-    int st[2] = {0, 0};
-    if (!ok(hipGetLastError()) || !ok(hipMemcpyAsync(st, step, sizeof(st), hipMemcpyDeviceToHost, s))) return rc;
-    const int frc = fl.finish(s);   // synchronises
-    g->step_copy = st[1];
-    return frc;
-  }
-  // folded-norm row scale of a consumer site: rstd from the caller's [M][K / 32] partial sums, + the step-indexed bias row
-  bool row_scale_of(int K, const float* bias, int N, RowScale* out) {
-    *out = RowScale();
-    if (!g->ssq) return bias ? bad() : true;
-    if (K / kNarrowTile > kAuxMaxTiles) return bad();
-    *out = row_scale(g->ssq, K / kNarrowTile, step, bias, bias ? N : 0);
-    return true;
-  }
-  WeightPrefetch pf_target() {
-    WeightPrefetch pf;
-    if (!g->prefetch) return pf;
-    Planes w;
-    w.p[0] = static_cast<h16_t*>(const_cast<void*>(g->prefetch));
-    w.p[1] = w.p[0] + (size_t)g->prefetch_rows * g->prefetch_k;
-    pf = prefetch_of<NP>(&ctx_model, w, g->prefetch_rows, g->prefetch_k);
-    return pf;
-  }
-  bool common_ok(int M, int N, int K, const float* a, const float* w) {
-    if (M <= 0 || N <= 0 || K <= 0 || K % kGemmBK || !a || !w) return bad();
-    if (g->prefetch && (g->prefetch_rows <= 0 || g->prefetch_k <= 0 || g->prefetch_k % kGemmBK || g->prefetch_k > 4096)) return bad();
-    if (g->resident_blocks < 0 || g->resident_blocks % 8) return bad();
-    return true;
-  }
-
-  // The launch of a single site: the product's gemm<NP, TK, Epi> when no tile is forced; gemm_on on the forced tile, with
-  // gemm's own launch parameters, otherwise.  Reported: the table's entry of that shape, or its last one (the fall-back).
-  template <int TK, class Epi>
-  bool launch(int kc, const Planes& a, const Planes& w, int M, int N, int K, const Epi& epi, int align) {
-    using Tab = TileTable<NP, TK, Epi>;
-    const std::vector<TileInfo> tiles = tiles_of(Tab{});
-    TileShape t = {g->force_bm, g->force_bn};
-    const bool forced = t.bm != 0 || t.bn != 0;
-    if (!forced) t = pick_tile<NP, TK>(M, N, align, epi_takes_48<Epi>::value, K);
-    const TileInfo* ti = find_tile(tiles, t);
-    if (!ti) {
-      if (forced) return bad();
-      ti = &tiles.back();
-    }
-    if (M % ti->bm || M % t.bm || N % ti->bn || align % ti->bn) return bad();
-    const WeightPrefetch pf = pf_target();
-    GemmParams probe;
-    set_xcd_grid(probe, M, t.bm);
-    g->ran_bm = ti->bm; g->ran_bn = ti->bn; g->ran_ns = ti->ns; g->ran_xcd_rows = probe.xcd_rows;
-    const GemmParams lp = gp_launch<NP>(c, kc, a, K, w, K, M, N, K, t.bm, pf);
-    // both reports come from the predicates the launch itself uses (gemm_t, launch_gemm_h16_dma / _geglu_persist)
-    g->ran_persistent = persistent_on<NP, Epi>(Tab{}, TileShape{ti->bm, ti->bn}, &ctx_model, lp, epi);
-    g->ran_prefetch = g->ran_persistent ? prefetch_kind(lp.pf) >= 1 : gemm_carries_prefetch<NP, Epi>(lp);
-    if (forced) gemm_on<NP>(Tab{}, t, c, kc, lp, epi);
-    else gemm<NP, TK>(c, kc, a, K, w, K, M, N, K, epi, align, pf);
-    return ok(c.err);
-  }
-  template <class Pairs, class E1, class E2>
-  bool launch_dual(int kc, const Planes& a1, const Planes& w1, int M1, int N1, int K1, const E1& e1, int align1,
-                   const Planes& a2, const Planes& w2, int M2, int N2, int K2, const E2& e2) {
-    const std::vector<TileInfo> t1s = first_tiles_of(Pairs{}), t2s = second_tiles_of(Pairs{});
-    const TileShape t1 = {g->force_bm, g->force_bn}, t2 = {g->force_bm2, g->force_bn2};
-    const TileInfo *i1 = nullptr, *i2 = nullptr;
-    for (size_t i = 0; i < t1s.size() && !i1; ++i)
-      if (t1s[i].bm == t1.bm && t1s[i].bn == t1.bn && t2s[i].bm == t2.bm && t2s[i].bn == t2.bn) { i1 = &t1s[i]; i2 = &t2s[i]; }
-    if (!i1) return bad();   // the step plan names both tiles of a dual launch: there is nothing to pick here
-    if (M1 % t1.bm || N1 % t1.bn || align1 % t1.bn || M2 % t2.bm || N2 % t2.bn) return bad();
-    const WeightPrefetch pf = pf_target();
-    const GemmParams p1 = gp_launch<NP>(c, kc, a1, K1, w1, K1, M1, N1, K1, t1.bm, pf);
-    const GemmParams p2 = gp_launch<NP>(c, kc, a2, K2, w2, K2, M2, N2, K2, t2.bm);
-    g->ran_bm = i1->bm; g->ran_bn = i1->bn; g->ran_ns = i1->ns; g->ran_xcd_rows = p1.xcd_rows;
-    g->ran_bm2 = i2->bm; g->ran_bn2 = i2->bn; g->ran_ns2 = i2->ns; g->ran_xcd_rows2 = p2.xcd_rows;
-    g->ran_dual = 1;
-    g->ran_prefetch = prefetch_kind(p1.pf) >= 1;   // (launch_gemm_h16_dual's own test)
-    gemm_dual<Pairs>(c, kc, t1, p1, e1, t2, p2, e2);
-    return ok(c.err);
-  }
-
-  // ---- operands and results of each epilogue ----
-  struct QkvIo { Planes a, w, qk, vt; int J = 0; };
-  bool qkv_prepare(QkvIo* io, EpiQKV<NP>* e) {
-    const int M = g->m, N = g->n, K = g->k, J = N / 3;
-    if (!common_ok(M, N, K, g->a, g->w) || N % 3 || J % 16 || !g->out || g->seg_len <= 0 || g->seg_len % 16 || M % g->seg_len)
-      return bad();
-    RowScale rs;
-    if (!row_scale_of(K, g->bias, N, &rs)) return false;
-    io->J = J;
-    if (!operand(g->a, (size_t)M * K, &io->a) || !weight(g->w, K, N, 0, 0, &io->w, N) ||
-        !planes((size_t)M * 2 * J, &io->qk, true) || !planes((size_t)M * J, &io->vt, true))
-      return false;
-    *e = epi_qkv<NP>(io->qk, io->vt, 2 * J, g->seg_len, J, rs);
-    return true;
-  }
-  // q | k row-major and V^T[seg][j][perm(key)] (msd_op_qkv's host-side un-permutation) -> out [M][3J] = q | k | v
-  bool qkv_collect(const QkvIo& io) {
-    const int M = g->m, J = io.J, L = g->seg_len;
-    float* f32 = sc.get<float>((size_t)M * 2 * J);
-    if (!f32) { rc = MSD_ERR_HIP; return false; }
-    std::vector<float> h((size_t)M * 2 * J), o((size_t)M * 3 * J);
-    back(io.qk, f32, (size_t)M * 2 * J);
-    if (!ok(hipMemcpyAsync(h.data(), f32, h.size() * sizeof(float), hipMemcpyDeviceToHost, s)) || !ok(hipStreamSynchronize(s)))
-      return false;
-    for (int m = 0; m < M; ++m)
-      memcpy(&o[(size_t)m * 3 * J], &h[(size_t)m * 2 * J], (size_t)2 * J * sizeof(float));
-    back(io.vt, f32, (size_t)M * J);
-    if (!ok(hipMemcpyAsync(h.data(), f32, (size_t)M * J * sizeof(float), hipMemcpyDeviceToHost, s)) || !ok(hipStreamSynchronize(s)))
-      return false;
-    for (int m = 0; m < M; ++m) {
-      const int seg = m / L, key = m % L, o16 = key & 15;
-      const int kp = (key & ~15) + 8 * ((o16 >> 2) & 1) + (o16 & 3) + 4 * (o16 >> 3);
-      for (int j = 0; j < J; ++j) o[(size_t)m * 3 * J + 2 * J + j] = h[((size_t)seg * J + j) * L + kp];
-    }
-    return ok(hipMemcpyAsync(g->out, o.data(), o.size() * sizeof(float), hipMemcpyHostToDevice, s)) && ok(hipStreamSynchronize(s));
-  }
-
-  struct ResNormIo { Planes a, w, y, y2; int rows = 0; };
-  template <bool DUP, bool Y2>
-  bool resnorm_prepare(ResNormIo* io, EpiResidualNorm<NP, DUP, Y2>* e) {
-    const int M = g->m, N = g->n, K = g->k;
-    if (!common_ok(M, N, K, g->a, g->w) || N % kNarrowTile || !g->x || !g->y || !g->ssq_out || g->split_row < 0) return bad();
-    if (DUP && (g->dup_rows < M || !g->g_lo || !g->g_hi)) return bad();   // (the duplicating form reads both gain rows)
-    if (Y2 && (!g->y2 || !g->g2 || g->y2_rows < 0 || g->y2_rows > M)) return bad();
-    io->rows = DUP ? g->dup_rows + M : M;
-    if (!operand(g->a, (size_t)M * K, &io->a) || !weight(g->w, K, N, 0, 0, &io->w, N) ||
-        !planes((size_t)io->rows * N, &io->y, true))
-      return false;
-    const EpiResidualNorm<NP> base = epi_residual_norm<NP>(g->x, N, io->y, g->ssq_out, step, Gain{g->g_lo, g->g_lo ? N : 0},
-                                                           Gain{g->g_hi, g->g_hi ? N : 0}, g->split_row);
-    *e = residual_form<DUP, Y2>(base);
-    if (DUP) { e->split_row = 0; e->dup_rows = g->dup_rows; }
-    if constexpr (Y2) {
-      if (!planes((size_t)M * N, &io->y2, true)) return false;
-      out_pair<NP>(e->y2, io->y2); e->g2 = g->g2; e->y2_rows = g->y2_rows;
-    }
-    return true;
-  }
-  bool resnorm_collect(const ResNormIo& io, bool y2) {
-    back(io.y, g->y, (size_t)io.rows * g->n);
-    if (y2) back(io.y2, g->y2, (size_t)g->m * g->n);
-    return true;
-  }
-
-  // ---- the sites ----
-  template <int TK> void run(Site<TK, EpiQKV<NP>>) {
-    QkvIo io;
-    EpiQKV<NP> e;
-    if (qkv_prepare(&io, &e) && launch<TK>(KC_GEMM_QKV, io.a, io.w, g->m, g->n, g->k, e, e.v_start)) qkv_collect(io);
-  }
-  template <int TK> void run(Site<TK, EpiGeglu<NP>>) {
-    const int M = g->m, N = g->n, K = g->k, F = N / 2;
-    if (!common_ok(M, N, K, g->a, g->w) || N % 32 || !g->w_gate || !g->out) return (void)bad();
-    Planes a, wi, o;
-    const float* bias = nullptr;
-    if (g->bias) {   // natural order [steps][wi_0 columns | wi_1 columns] -> the packed column order of the weights
-      if (g->steps <= 0) return (void)bad();
-      std::vector<float> h((size_t)g->steps * N), p((size_t)g->steps * N);
-      float* d = sc.get<float>(p.size());
-      if (!d || !ok(hipMemcpyAsync(h.data(), g->bias, h.size() * sizeof(float), hipMemcpyDeviceToHost, s)) || !ok(hipStreamSynchronize(s)))
-        return (void)(rc = rc ? rc : MSD_ERR_HIP);
-      for (int r = 0; r < g->steps; ++r)
-        for (int j = 0; j < F; ++j) {
-          p[(size_t)r * N + (j / 16) * 32 + j % 16] = h[(size_t)r * N + j];
-          p[(size_t)r * N + (j / 16) * 32 + 16 + j % 16] = h[(size_t)r * N + F + j];
-        }
-      if (!ok(hipMemcpyAsync(d, p.data(), p.size() * sizeof(float), hipMemcpyHostToDevice, s)) || !ok(hipStreamSynchronize(s))) return;
-      bias = d;
-    }
-    RowScale rs;
-    if (!row_scale_of(K, bias, N, &rs)) return;
-    if (!operand(g->a, (size_t)M * K, &a) || !weight(g->w, K, F, 1, 0, &wi, N) || !weight(g->w_gate, K, F, 2, 0, &wi, N) ||
-        !planes((size_t)M * F, &o, true))
-      return;
-    if (launch<TK>(KC_GEMM_MLP_IN, a, wi, M, N, K, epi_out<EpiGeglu, NP>(o, F, rs), 0)) back(o, g->out, (size_t)M * F);
-  }
-  template <int TK> void run(Site<TK, EpiResidual>) {
-    const int M = g->m, N = g->n, K = g->k;
-    if (!common_ok(M, N, K, g->a, g->w) || !g->x) return (void)bad();
-    Planes a, w;
-    if (!operand(g->a, (size_t)M * K, &a) || !weight(g->w, K, N, 0, 0, &w, N)) return;
-    launch<TK>(KC_GEMM_MLP_OUT, a, w, M, N, K, EpiResidual{g->x, N}, 0);
-  }
-  template <int TK, bool DUP, bool Y2> void run(Site<TK, EpiResidualNorm<NP, DUP, Y2>>) {
-    ResNormIo io;
-    EpiResidualNorm<NP, DUP, Y2> e;
-    if (resnorm_prepare<DUP, Y2>(&io, &e) && launch<TK>(KC_GEMM_ATTN_OUT, io.a, io.w, g->m, g->n, g->k, e, 0)) resnorm_collect(io, Y2);
-  }
-  template <int TK> void run(Site<TK, EpiStoreH16<NP>>) {
-    const int M = g->m, N = g->n, K = g->k;
-    if (!common_ok(M, N, K, g->a, g->w) || !g->out) return (void)bad();
-    RowScale rs;
-    Planes a, w, o;
-    if (!row_scale_of(K, g->bias, N, &rs) || !operand(g->a, (size_t)M * K, &a) || !weight(g->w, K, N, 0, 0, &w, N) ||
-        !planes((size_t)M * N, &o, true))
-      return;
-    if (launch<TK>(KC_GEMM_CROSS_Q, a, w, M, N, K, epi_out<EpiStoreH16, NP>(o, N, rs), 0)) back(o, g->out, (size_t)M * N);
-  }
-  template <int TK> void run(Site<TK, EpiStoreF32>) {
-    const int M = g->m, N = g->n, K = g->k;
-    if (!common_ok(M, N, K, g->a, g->w) || !g->out) return (void)bad();
-    RowScale rs;
-    Planes a, w;
-    if (!row_scale_of(K, g->bias, N, &rs) || !operand(g->a, (size_t)M * K, &a) || !weight(g->w, K, N, 0, 0, &w, N)) return;
-    launch<TK>(KC_FINAL_PROJ, a, w, M, N, K, epi_store_f32(g->out, N, rs), 0);
-  }
-  template <int TK> void run(Site<TK, EpiInProj<NP>>) {
-    const int M = g->m, N = g->n, K = g->k, P = g->passes;
-    if (!common_ok(M, N, K, g->a, g->w) || N % kNarrowTile || !g->pos || !g->g_lo || !g->x || !g->y || !g->ssq_out ||
-        g->seg_len <= 0 || P < 1 || P > 2 || (g->g2 != nullptr) != (g->y2 != nullptr))
-      return (void)bad();
-    Planes a, w, y, y2;
-    if (!operand(g->a, (size_t)M * K, &a) || !weight(g->w, K, N, 0, 0, &w, N) || !planes((size_t)P * M * N, &y, true)) return;
-    EpiInProj<NP> ei;
-    ei.x = g->x; ei.ldx = N; ei.pos = g->pos; ei.T = g->seg_len; ei.pass_rows = M; ei.passes = P;
-    out_pair<NP>(ei.y, y); ei.ssq = g->ssq_out; ei.tiles = N / kNarrowTile;
-    ei.g = g->g_lo; ei.g_stride = N; ei.step_ptr = step; ei.step_copy = step;
-    if (g->g2) {
-      if (!planes((size_t)M * N, &y2, true)) return;
-      out_pair<NP>(ei.y2, y2); ei.g2 = g->g2;
-    }
-    if (!launch<TK>(KC_IN_PROJ, a, w, M, N, K, ei, 0)) return;
-    back(y, g->y, (size_t)P * M * N);
-    if (g->g2) back(y2, g->y2, (size_t)M * N);
-  }
-  // dual sites (two-plane modes): problem 1 as its single site, problem 2 from a2 / w2 (/ addend2) into out2
-  bool second_operands(Planes* a2, Planes* w2) {
-    if (g->m2 <= 0 || g->n2 <= 0 || g->k2 <= 0 || g->k2 % kGemmBK || !g->a2 || !g->w2 || !g->out2) return bad();
-    return operand(g->a2, (size_t)g->m2 * g->k2, a2) && weight(g->w2, g->k2, g->n2, 0, 0, w2, g->n2);
-  }
-  template <class Pairs> void run(DualSite<Pairs, EpiQKV<2>, EpiStoreF32>) {
-    if constexpr (NP == 2) {
-      QkvIo io;
-      EpiQKV<NP> e;
-      Planes a2, w2;
-      if (!qkv_prepare(&io, &e) || !second_operands(&a2, &w2)) return;
-      if (launch_dual<Pairs>(KC_GEMM_QKV, io.a, io.w, g->m, g->n, g->k, e, e.v_start, a2, w2, g->m2, g->n2, g->k2,
-                             epi_store_f32(g->out2, g->n2)))
-        qkv_collect(io);
-    }
-  }
-  template <class Pairs, bool DUP> void run(DualSite<Pairs, EpiResidualNorm<2, DUP>, EpiAddStoreH16<2>>) {
-    if constexpr (NP == 2) {
-      ResNormIo io;
-      EpiResidualNorm<NP, DUP> e;
-      Planes a2, w2, o2;
-      if (!resnorm_prepare<DUP, false>(&io, &e) || !second_operands(&a2, &w2) || !g->addend2) return (void)(rc = rc ? rc : MSD_ERR_INVALID_ARGUMENT);
-      if (!planes((size_t)g->m2 * g->n2, &o2, true)) return;
-      EpiAddStoreH16<NP> ea;
-      out_pair<NP>(ea.out, o2); ea.ldc = g->n2; ea.addend = g->addend2; ea.ld_add = g->n2;
-      if (!launch_dual<Pairs>(KC_GEMM_ATTN_OUT, io.a, io.w, g->m, g->n, g->k, e, 0, a2, w2, g->m2, g->n2, g->k2, ea)) return;
-      resnorm_collect(io, false);
-      back(o2, g->out2, (size_t)g->m2 * g->n2);
-    }
-  }
-};
-
-template <int NP>
-int run_gemm_site(msd_gemm_site_args* g, hipStream_t s) {
-  SiteRun<NP> r(g, s);
-  if (!r.init()) return r.rc;
-  bool found = visit_at(GemmSites<NP>{}, g->site, [&](auto site) { r.run(site); });
-  if constexpr (NP == 2) {
-    if (!found) found = visit_at(DualSites{}, g->site - list_size(GemmSites<NP>{}), [&](auto site) { r.run(site); });
-  }
-  if (!found) return MSD_ERR_INVALID_ARGUMENT;
-  const int frc = r.finish();
-  return r.rc ? r.rc : frc;
-}
-template <int NP>
-bool gemm_site_tiles(int site, SiteTiles<NP>* t) {
-  bool found = visit_at(GemmSites<NP>{}, site, *t);
-  if constexpr (NP == 2) {
-    if (!found) found = visit_at(DualSites{}, site - list_size(GemmSites<NP>{}), *t);
-  }
-  return found;
-}
-}  // namespace
-}  // extern "C++"
-
-int msd_op_gemm_site(msd_gemm_site_args* args, void* stream) {
-  if (!args || args->struct_size != (int32_t)sizeof(msd_gemm_site_args) || args->site < 0 || args->step < 0 ||
-      args->steps <= 0 || args->step >= args->steps)
-    return MSD_ERR_INVALID_ARGUMENT;
-  const int NP = op_planes(args->precision);
-  if (NP < 0) return MSD_ERR_UNSUPPORTED;
-  args->ran_bm = args->ran_bn = args->ran_ns = args->ran_xcd_rows = args->ran_persistent = args->ran_dual = 0;
-  args->ran_prefetch = args->ran_bm2 = args->ran_bn2 = args->ran_ns2 = args->ran_xcd_rows2 = 0;
-  args->step_copy = -1;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  return NP == 2 ? run_gemm_site<2>(args, s) : run_gemm_site<1>(args, s);
-}
-
-const char* msd_op_gemm_site_name(int precision, int site) {
-  const int NP = op_planes(precision);
-  const char* name = nullptr;
-  auto f = [&](auto s) { name = site_name(s); };
-  if (NP == 2) {
-    if (!visit_at(GemmSites<2>{}, site, f)) visit_at(DualSites{}, site - list_size(GemmSites<2>{}), f);
-  } else if (NP == 1) {
-    visit_at(GemmSites<1>{}, site, f);
-  }
-  return name;
-}
-
-int msd_op_gemm_site_tiles(int precision, int site, int index, int32_t* bm, int32_t* bn, int32_t* ns) {
-  if (!bm || !bn || !ns || site < 0 || index < 0) return MSD_ERR_INVALID_ARGUMENT;
-  const int NP = op_planes(precision);
-  if (NP < 0) return MSD_ERR_UNSUPPORTED;
-  std::vector<TileInfo> first, second;
-  bool found;
-  if (NP == 2) { SiteTiles<2> t; found = gemm_site_tiles<2>(site, &t); first = t.first; second = t.second; }
-  else { SiteTiles<1> t; found = gemm_site_tiles<1>(site, &t); first = t.first; second = t.second; }
-  if (!found || index >= (int)first.size()) return MSD_ERR_INVALID_ARGUMENT;
-  bm[0] = first[index].bm; bn[0] = first[index].bn; ns[0] = first[index].ns;
-  bm[1] = bn[1] = ns[1] = 0;
-  if (!second.empty()) { bm[1] = second[index].bm; bn[1] = second[index].bn; ns[1] = second[index].ns; }
-  return MSD_OK;
 }
 
 }  // extern "C"

@@ -8,6 +8,7 @@ These are the pieces that carry the tricky algebra and that whole-decoder tests 
   * EpiGeglu (interleaved wi_0/wi_1, v_exp/v_rcp GELU)  vs oracle/ops.py gelu_tanh (layers.py:483-497)
   * EpiQKV (q|k row-major, V^T with the per-16 key permutation)  vs a float64 matmul
   * final_proj_f32_kernel (decoder_norm folded, exact fp32)      vs oracle rms_layer_norm + matmul
+  * op_geglu / op_qkv                                            vs the launch sites they run (op_gemm_site), bit for bit
 """
 import dataclasses
 
@@ -256,6 +257,39 @@ def test_qkv_layouts_vs_matmul(env, m, k, j, seg):
   wv[0, :] = 1.0
   native.op_qkv(_dev(torch, a2), _dev(torch, ws[0]), _dev(torch, ws[1]), _dev(torch, wv), *outs, seg)
   np.testing.assert_array_equal(outs[2].cpu().numpy(), np.repeat(np.arange(m, dtype=np.float32)[:, None], j, 1))
+
+
+# --------------------------------------------------------------------------------------------------
+# op_geglu / op_qkv ARE the launch sites mlp_in / qkv on a forced tile: the same bits
+# --------------------------------------------------------------------------------------------------
+def test_geglu_is_site_mlp_in(env):
+  torch, native = env
+  m, k, f = 64, 64, 64
+  rng = np.random.default_rng(7)
+  a = _dev(torch, rng.standard_normal((m, k)))
+  wi0, wi1 = (_dev(torch, rng.standard_normal((k, f)) / np.sqrt(k)) for _ in range(2))
+  out, ref = (torch.full((m, f), np.nan, dtype=torch.float32, device='cuda') for _ in range(2))
+  native.op_geglu(a, wi0, wi1, out)
+  ran = native.op_gemm_site('f16x3', 'mlp_in', m=m, n=2 * f, k=k, a=a, w=wi0, w_gate=wi1, out=ref, force_bm=64, force_bn=128)
+  assert (ran['ran_bm'], ran['ran_bn']) == (64, 128)
+  np.testing.assert_array_equal(out.cpu().numpy().view(np.uint32), ref.cpu().numpy().view(np.uint32))
+
+
+# the smallest shapes that reach both of op_qkv's tiles, with a V^T segment boundary on the 64-row tile's edge
+@pytest.mark.parametrize('m,k,j,seg,bn', [(64, 64, 64, 64, 64), (64, 64, 192, 64, 96)])
+def test_qkv_is_site_qkv(env, m, k, j, seg, bn):
+  torch, native = env
+  rng = np.random.default_rng(j)
+  a = _dev(torch, rng.standard_normal((m, k)))
+  ws = [_dev(torch, rng.standard_normal((k, j)) / np.sqrt(k)) for _ in range(3)]
+  outs = [torch.full((m, j), np.nan, dtype=torch.float32, device='cuda') for _ in range(3)]
+  native.op_qkv(a, *ws, *outs, seg)
+  ref = torch.full((m, 3 * j), np.nan, dtype=torch.float32, device='cuda')
+  ran = native.op_gemm_site('f16x3', 'qkv', m=m, n=3 * j, k=k, a=a, w=torch.cat(ws, dim=1).contiguous(), out=ref, seg_len=seg,
+                            force_bm=64, force_bn=bn)
+  assert (ran['ran_bm'], ran['ran_bn']) == (64, bn)
+  got = np.concatenate([o.cpu().numpy() for o in outs], axis=1)
+  np.testing.assert_array_equal(got.view(np.uint32), ref.cpu().numpy().view(np.uint32))
 
 
 # --------------------------------------------------------------------------------------------------
