@@ -46,7 +46,9 @@ extern "C" {
                                       entry points (device STFT pair, Audio2Mel, Griffin-Lim); msd_sample_rows (one
                                       generator key per row of a batched call); msd_sample_keep and
                                       msd_op_sampler_step_keep (known frames in the sampler); msd_op_gemm_site and
-                                      msd_op_gemm_site_tiles, msd_op_gemm_site_name (one GEMM launch site at a time, for the tests).
+                                      msd_op_gemm_site_tiles, msd_op_gemm_site_name (one GEMM launch site at a time, for the tests);
+                                      msd_sample_edit, msd_op_sampler_step_release and msd_op_diffuse_to_step (edit strength:
+                                      per-frame release words and a part-way start of the sampler).
                                    6: cross_merge_in_launch, cross_q_fold, mlp_in_persistent appended to msd_config.
                                    5: dedup_layer0, cross_key_split, keep_raw_weights, kv_touch_ahead appended to msd_config.
                                    4: every caller-selectable knob is a msd_config field (attn_q_planes / attn_p_planes
@@ -312,6 +314,30 @@ int msd_sample_keep(msd_model* m, int batch, int rng, int per_row, const uint64_
                     const float* init_z_dev, const float* noise_dev, const float* known_dev, const int32_t* keep_mask,
                     float* out_dev, void* stream);
 
+/* (appended to ABI 7) Edit strength: msd_sample_keep with a RELEASE SCHEDULE per frame and a start part-way down the scan.
+ *   release    HOST int32 [batch,T], one word v per frame, 0 <= v <= num_steps:
+ *                v == 0   the frame is free at every step (msd_sample_keep's flag 0)
+ *                v >= 1   the frame is known (x0-replacement, as above) at scan indices i >= v - 1 and free below: the
+ *                         sampler has the last f = v - 1 steps to move it.  v == 1: known throughout (flag 1); it alone
+ *                         comes back as the caller's values -- a released frame returns what the scan made of it
+ *   start_step the scan index of the first step that runs, in [-1, num_steps - 1]; the call runs start_step + 1 steps
+ *                start_step == num_steps - 1   z starts as init_z.  With words in {0, 1} this IS msd_sample_keep, bit for bit
+ *                0 <= start_step < num_steps - 1   z starts as a direct sample of q(z_t | x0 = xk) at the start index
+ *                         (the reference's diffusion_forward, diffusion_utils.py:109-117):
+ *                             z = fmaf(sigma, eps, alpha * xk),  alpha = sqrt(sigmoid(logsnr_t)), sigma = sqrt(sigmoid(-logsnr_t))
+ *                         of the SAMPLER schedule's logsnr_t of that index (float32 table value; alpha, sigma computed in double
+ *                         and rounded once); eps = the call's own initial draw: init_z_dev if given, else what msd_sample_rng /
+ *                         msd_sample_rows would have started from.  Every frame must be known at every skipped step:
+ *                         1 <= v <= start_step + 2
+ *                start_step == -1   only with every word 1: no step runs, out_dev = known_dev
+ * Violations, and a NULL known_dev / release / seeds, are MSD_ERR_INVALID_ARGUMENT with a message.  The steps' noise is
+ * indexed by scan index exactly as in the full call (noise_dev stays [num_steps][batch,T,n]).  Rows share start_step; a row
+ * that should move less is held by its words.  start_step + 1 steps = whole step graphs of msd_sample_keep's set plus
+ * single-step launches; the single-step graph is captured on first need.  Everything else is msd_sample_keep's. */
+int msd_sample_edit(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
+                    const float* init_z_dev, const float* noise_dev, const float* known_dev, const int32_t* release,
+                    int start_step, float* out_dev, void* stream);
+
 /* Drop the captured hipGraph of the DDPM step; the next msd_sample captures it again. */
 int msd_reset_graph(msd_model* m);
 
@@ -408,6 +434,21 @@ int msd_op_sampler_step_keep(const msd_config* cfg, int step_index, const float*
                              const float* out_cond_dev, const float* out_uncond_dev,
                              const float* noise_dev, const float* known_scaled_dev, const int32_t* keep_mask_dev,
                              int n_dims, float* z_out_dev, int64_t n, void* stream);
+
+/* (appended to ABI 7) msd_op_sampler_step_keep with release words (msd_sample_edit's update): frame f is known in this
+ * step iff release_dev[f] >= 1 and step_index >= release_dev[f] - 1; its elements are then msd_op_sampler_step_keep's
+ * with flag 1, all others msd_op_sampler_step's, bit for bit.  At step_index 0 only words == 1 return known_scaled_dev. */
+int msd_op_sampler_step_release(const msd_config* cfg, int step_index, const float* z_dev,
+                                const float* out_cond_dev, const float* out_uncond_dev,
+                                const float* noise_dev, const float* known_scaled_dev, const int32_t* release_dev,
+                                int n_dims, float* z_out_dev, int64_t n, void* stream);
+
+/* (appended to ABI 7) The part-way start of msd_sample_edit on its own: xk = scale_features(clip=True) of mel_dev
+ * (cfg->feature_min / feature_max) and z = fmaf(sigma, eps, alpha * xk) at step_index's noise level (see msd_sample_edit).
+ *   mel_dev, eps_dev float [n] in; z_out_dev, xk_out_dev float [n] out; z_planes_out_dev float [n]: z's operand planes of
+ *   cfg->precision merged back to float32; n % 4 == 0.  Uses cfg->{num_steps, sampler_schedule*, feature_*, precision}. */
+int msd_op_diffuse_to_step(const msd_config* cfg, int step_index, const float* mel_dev, const float* eps_dev,
+                           float* z_out_dev, float* z_planes_out_dev, float* xk_out_dev, int64_t n, void* stream);
 
 /* x_out = x_in + a.w1 ; h_out = (RMSNorm(x_out; gamma) (.) (film_scale+1) + film_bias) . w2
  * (layers.py:632-666 + the Dense that follows).  folded=1: the decoder's folded-norm epilogues

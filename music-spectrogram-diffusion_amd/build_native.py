@@ -67,10 +67,12 @@ def check_prefetch_registers(listing: str) -> str:
 # kernels that must not spill: elementwise launches on the step's critical path (the sampler once went through scratch
 # memory, csrc/elementwise.h) and the Threefry fill ...
 NO_SCRATCH_STEP_KERNELS = ('sampler_step_kernel', 'threefry_normal_kernel')
+# ... the part-way start of msd_sample_edit (csrc/keep_frames_tail.h: one pass in front of the first step) ...
+NO_SCRATCH_EDIT_KERNELS = ('diffuse_to_step_kernel',)
 # ... and the vocoder's elementwise kernels (csrc/vocoder.h: two of the four launches of a Griffin-Lim iteration)
 NO_SCRATCH_VOCODER_KERNELS = ('voc_pad_signal_kernel', 'voc_exp_kernel', 'voc_load_spec_kernel', 'voc_ola_kernel',
                               'voc_phase_kernel', 'voc_magnitude_kernel')
-NO_SCRATCH_KERNELS = NO_SCRATCH_STEP_KERNELS + NO_SCRATCH_VOCODER_KERNELS   # what build() checks in every product listing
+NO_SCRATCH_KERNELS = NO_SCRATCH_STEP_KERNELS + NO_SCRATCH_EDIT_KERNELS + NO_SCRATCH_VOCODER_KERNELS   # what build() checks in every product listing
 
 
 def check_no_scratch(listing: str, kernels=NO_SCRATCH_STEP_KERNELS) -> str:

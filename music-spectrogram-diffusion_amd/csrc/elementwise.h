@@ -291,7 +291,8 @@ struct SamplerParams {
 // cache line -- and their code is what it was; the keep form's 144 bytes take a third 64-byte line.
 struct SamplerKeepParams : SamplerParams {
   const float* xk = nullptr;     // [n] the known mel in model units (scale_clip_kernel of the caller's mel)
-  const int32_t* keep = nullptr; // [n / n_dims] per frame: non-zero = its n_dims elements are known
+  const int32_t* keep = nullptr; // [n / n_dims] per frame, a release word v: 0 = free at every step; v >= 1 = known at scan
+                                 // indices i >= v - 1 and free below (1 = known throughout: msd_sample_keep's flag)
   int n_dims = 0;                // elements per frame, % 4 == 0: a thread's four elements lie in one frame
 };
 
@@ -437,7 +438,8 @@ __global__ void __launch_bounds__(256) sampler_step_kernel(P p) {
     int kf = 0;
     if constexpr (KEEP) {
       xk = *reinterpret_cast<const f32x4*>(p.xk + idx);
-      kf = p.keep[(uint32_t)idx / (uint32_t)p.n_dims];
+      // the frame's release word -> known in THIS step: one unsigned compare (v == 0 wraps to 2^32 - 1: never known)
+      kf = (uint32_t)p.keep[(uint32_t)idx / (uint32_t)p.n_dims] - 1u <= (uint32_t)i;
     }
     static_assert(kCoefCount == 20, "five 16-byte loads per row");
     f32x4 cr[5];
@@ -504,6 +506,25 @@ inline void launch_sampler_step(const SamplerParams& sp, hipStream_t s) {
 void launch_sampler_step(const SamplerKeepParams& sp, hipStream_t s);
 void launch_unscale_keep(const float* x0, const float* known, const int32_t* keep, float* out, int n, int n_dims, float fmin,
                          float fmax, hipStream_t s);
+
+// The part-way start of msd_sample_edit (keep_frames_tail.h): the caller's mel -> xk, and z = alpha xk + sigma eps as fp32
+// and operand planes.  eps may be z itself (a thread reads its four elements before it writes them).
+struct DiffuseParams {
+  const float* mel;     // [n] the caller's mel, mel units
+  const float* eps;     // [n] the call's initial draw
+  float* xk;            // [n] out: scale_features(clip=True) of mel
+  float* z;             // [n] out
+  h16_t* z_hi;          // out: operand planes of z (z_lo may be null: one-plane precisions)
+  h16_t* z_lo;
+  int n;                // % 4 == 0
+  float fmin, fmax;     // the codec's range
+  float alpha, sigma;   // sqrt(sigmoid(+-logsnr_t)) of the start index (host, double, rounded once)
+  unsigned* sat = nullptr;   // half-plane range flag (common.h RangeCheck)
+  unsigned sat_tag = 1;
+};
+void launch_diffuse_to_step(const DiffuseParams& dp, hipStream_t s);
+// flags[i] = flags[i] != 0: msd_sample_keep's "any non-zero flag = known throughout" as the release word 1
+void launch_normalize_flags(const int32_t* in, int32_t* out, int n, hipStream_t s);
 
 // g[step][slot][k] = gamma[k] * (film_scale[step][slot][k] + 1): the column multiplier of a
 // FiLM-modulated RMSNorm, tabulated for every step (folded-norm GEMM epilogues, gemm_h16.h)

@@ -1,5 +1,5 @@
-// The launches of the sampler's keep form (msd_sample_keep): the keep instances of sampler_step_kernel and the unscale that
-// passes the caller's mel through on kept frames.  msd_api.hip includes this file LAST: the template instances a
+// The launches of the sampler's keep form (msd_sample_keep, msd_sample_edit): the keep instances of sampler_step_kernel,
+// the unscale that passes the caller's mel through on kept frames, and the part-way start of msd_sample_edit.  msd_api.hip includes this file LAST: the template instances a
 // translation unit emits follow the order of their first use, so the keep instances land behind every kernel the
 // library had before and those move by 6.4 KB in the code object instead of by 47 KB.  Every one of them is
 // instruction for instruction what it was either way, and yet the placement alone shows on the clock: one box, three
@@ -17,11 +17,12 @@ void launch_sampler_step(const SamplerKeepParams& sp, hipStream_t s) {
   else hipLaunchKernelGGL((sampler_step_kernel<kOutEps, SamplerKeepParams>), grid, block, 0, s, sp);
 }
 
-// the same on the free frames; a kept frame (msd_sample_keep) gets the caller's own mel values, whatever they are
+// the same on the free frames; a frame known THROUGHOUT (release word 1: msd_sample_keep's kept frame) gets the caller's own
+// mel values, whatever they are.  A frame released part-way (word > 1, msd_sample_edit) was sampled: unscaled like a free one.
 __global__ void unscale_keep_kernel(const float* x0, const float* known, const int32_t* keep, float* out, int n,
                                     int n_dims, float fmin, float fmax) {
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < n) out[i] = keep[i / n_dims] ? known[i] : (x0[i] + 1.0f) / 2.0f * (fmax - fmin) + fmin;
+  if (i < n) out[i] = keep[i / n_dims] == 1 ? known[i] : (x0[i] + 1.0f) / 2.0f * (fmax - fmin) + fmin;
 }
 
 
@@ -29,5 +30,57 @@ void launch_unscale_keep(const float* x0, const float* known, const int32_t* kee
                          float fmax, hipStream_t s) {
   hipLaunchKernelGGL(unscale_keep_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, x0, known, keep, out, n, n_dims,
                      fmin, fmax);
+}
+
+// msd_sample_keep's flags -> release words: any non-zero flag = known throughout = 1
+__global__ void normalize_flags_kernel(const int32_t* in, int32_t* out, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = in[i] != 0;
+}
+
+void launch_normalize_flags(const int32_t* in, int32_t* out, int n, hipStream_t s) {
+  hipLaunchKernelGGL(normalize_flags_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, in, out, n);
+}
+
+// The part-way start of msd_sample_edit: a direct sample of q(z_t | x0 = xk) at the start index (the reference's
+// diffusion_forward, diffusion_utils.py:109-117: mean alpha x0, std sigma), in ONE pass over [B, T, n]:
+//   xk = scale_features(clip=True) of the caller's mel  -- scale_clip_kernel's expression, so its bits
+//   z  = fmaf(sigma, eps, alpha * xk)                   -- the product rounded, then one fused multiply-add; contraction off,
+//                                                          so that this line is the operation order (tests/edit_spec.py)
+// written as fp32 and as operand planes, with the range flag fed as split_z feeds it for the plain start.  eps is the call's
+// own initial draw, which the fill kernels (or the init_z copy) have just put into z: a thread reads its float4 of eps
+// before it writes its float4 of z, and no other thread touches those elements.  A float4 per lane and step of the
+// grid-stride loop; the grid is capped at eight blocks per CU.
+__global__ void __launch_bounds__(256) diffuse_to_step_kernel(DiffuseParams p) {
+#pragma clang fp contract(off)
+  RangeCheck rc;
+  const int stride = (int)gridDim.x * 1024;
+  for (int idx = ((int)blockIdx.x * 256 + (int)threadIdx.x) * 4; idx < p.n; idx += stride) {
+    const f32x4 mel = *reinterpret_cast<const f32x4*>(p.mel + idx);
+    const f32x4 ep = *reinterpret_cast<const f32x4*>(p.eps + idx);
+    f32x4 xk, z;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const float f = fminf(fmaxf(mel[k], p.fmin), p.fmax);
+      xk[k] = (f - p.fmin) / (p.fmax - p.fmin) * 2.0f + (-1.0f);
+      z[k] = fmaf(p.sigma, ep[k], p.alpha * xk[k]);
+    }
+    *reinterpret_cast<f32x4*>(p.xk + idx) = xk;
+    *reinterpret_cast<f32x4*>(p.z + idx) = z;
+    uint32_t h[2], l[2];
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+      rc.see(z[2 * k], z[2 * k + 1]);
+      split2_h16(z[2 * k], z[2 * k + 1], h[k], l[k]);
+    }
+    *reinterpret_cast<uint2*>(p.z_hi + idx) = make_uint2(h[0], h[1]);
+    if (p.z_lo) *reinterpret_cast<uint2*>(p.z_lo + idx) = make_uint2(l[0], l[1]);
+  }
+  rc.commit(p.sat, p.sat_tag);
+}
+
+void launch_diffuse_to_step(const DiffuseParams& dp, hipStream_t s) {
+  const int blocks = (dp.n / 4 + 255) / 256;
+  hipLaunchKernelGGL(diffuse_to_step_kernel, dim3((unsigned)(blocks < 2048 ? blocks : 2048)), dim3(256), 0, s, dp);
 }
 }  // namespace msd

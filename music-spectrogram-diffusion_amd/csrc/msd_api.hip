@@ -964,6 +964,14 @@ bool build_coef_rows(const msd_config& cfg, std::vector<float>* out, std::string
   return true;
 }
 
+// The part-way start's coefficients (diffuse_to_step_kernel): alpha = sqrt(sigmoid(logsnr_t)), sigma = sqrt(sigmoid(-logsnr_t))
+// of a row's sampler log-SNR, in double, rounded once
+void diffuse_coefs(float logsnr_t, float* alpha, float* sigma) {
+  const double l = (double)logsnr_t;
+  *alpha = (float)std::sqrt(1.0 / (1.0 + std::exp(-l)));
+  *sigma = (float)std::sqrt(1.0 / (1.0 + std::exp(l)));
+}
+
 int build_tables(msd_model* m, hipStream_t s) {
   const int N = m->N, D = m->D;
   {
@@ -1890,10 +1898,13 @@ static hipError_t upload_rng_keys(msd_model* m, int batch, int rng, const Sample
   return hipMemcpyAsync(m->d_rng_key, m->h_rng_key.data(), m->h_rng_key.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s);
 }
 
-// The known frames of msd_sample_keep: the caller's mel [batch, T, n] (device) and frame flags [batch, T] (host or device)
+// The known frames of msd_sample_keep: the caller's mel [batch, T, n] (device) and frame flags [batch, T] (host or device);
+// of msd_sample_edit: release words instead (host, validated by the entry point) and the scan index the call starts at
 struct KeepFrames {
   const float* known_dev = nullptr;
   const int32_t* mask = nullptr;
+  const int32_t* release = nullptr;
+  int start_step = -2;   // (msd_sample_keep: N - 1, set by sample_body)
 };
 
 static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys, const float* init_z_dev,
@@ -1934,6 +1945,34 @@ int msd_sample_keep(msd_model* m, int batch, int rng, int per_row, const uint64_
   return sample_body(m, batch, rng, keys, init_z_dev, noise_dev, out_dev, stream, &keep);
 }
 
+int msd_sample_edit(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
+                    const float* init_z_dev, const float* noise_dev, const float* known_dev, const int32_t* release,
+                    int start_step, float* out_dev, void* stream) {
+  if (!m) return MSD_ERR_INVALID_ARGUMENT;
+  if (!seeds) return fail(m, MSD_ERR_INVALID_ARGUMENT, "seeds is null");
+  if (!known_dev || !release) return fail(m, MSD_ERR_INVALID_ARGUMENT, "known mel or release words are null");
+  if (batch < 1 || batch > m->Bmax) return fail(m, MSD_ERR_INVALID_ARGUMENT, "batch %d outside [1, %d]", batch, m->Bmax);
+  const int N = m->N;
+  if (start_step < -1 || start_step > N - 1)
+    return fail(m, MSD_ERR_INVALID_ARGUMENT, "start_step %d outside [-1, %d]", start_step, N - 1);
+  // a frame must be known at every step the call skips: free below scan index v - 1 <= start_step + 1 at the most
+  const int v_lo = start_step < N - 1 ? 1 : 0, v_hi = start_step < N - 1 ? start_step + 2 : N;
+  for (int64_t k = 0; k < (int64_t)batch * m->T; ++k) {
+    const int v = release[k];
+    if (v < 0 || v > N)
+      return fail(m, MSD_ERR_INVALID_ARGUMENT, "release word %d of row %d, frame %d outside [0, %d]", v, (int)(k / m->T), (int)(k % m->T), N);
+    if (v < v_lo || v > v_hi)
+      return fail(m, MSD_ERR_INVALID_ARGUMENT, "release word %d of row %d, frame %d: a call that starts at scan index %d needs "
+                  "every frame known at the steps it skips (words in [1, %d])", v, (int)(k / m->T), (int)(k % m->T), start_step, v_hi);
+  }
+  SampleKeys keys;
+  if (per_row) { keys.seeds = seeds; keys.stream_ids = stream_ids; }
+  else { keys.seed = seeds[0]; keys.stream_id = stream_ids ? stream_ids[0] : 0; }
+  KeepFrames keep;
+  keep.known_dev = known_dev; keep.release = release; keep.start_step = start_step;
+  return sample_body(m, batch, rng, keys, init_z_dev, noise_dev, out_dev, stream, &keep);
+}
+
 static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys, const float* init_z_dev,
                        const float* noise_dev, float* out_dev, void* stream, const KeepFrames* keep) {
   if (!m) return MSD_ERR_INVALID_ARGUMENT;
@@ -1963,6 +2002,13 @@ static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys,
     s = m->own_stream;
   }
   const int64_t n = (int64_t)batch * m->T * m->ND;
+  // the scan index the call starts at: N - 1 but for msd_sample_edit
+  const int start_step = keep && keep->release ? keep->start_step : m->N - 1;
+  if (start_step < 0) {   // (msd_sample_edit: every frame known throughout) no step runs: the caller's mel
+    HIP_TRY(m, hipMemcpyAsync(out_dev, keep->known_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(m, hipStreamSynchronize(s));
+    return MSD_OK;
+  }
   if (int rc0 = arm_range(m, s)) return rc0;
   if (init_z_dev) {
     HIP_TRY(m, hipMemcpyAsync(m->z, init_z_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
@@ -1977,13 +2023,34 @@ static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys,
       if (rc) return fail(m, rc, "init_z fill failed");
     }
   }
-  split_z(m, n, s);
-  if (keep) {
-    // the known mel enters the chain as the context does: scale_features(clip=True); init_z and the draws are untouched
-    hipLaunchKernelGGL(scale_clip_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, keep->known_dev, m->keep_xk,
-                       (int)n, m->cfg.feature_min, m->cfg.feature_max);
+  if (start_step == m->N - 1) {
+    split_z(m, n, s);
+    if (keep) {
+      // the known mel enters the chain as the context does: scale_features(clip=True); init_z and the draws are untouched
+      hipLaunchKernelGGL(scale_clip_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, keep->known_dev, m->keep_xk,
+                         (int)n, m->cfg.feature_min, m->cfg.feature_max);
+      HIP_TRY(m, hipGetLastError());
+    }
+  } else {
+    // part-way start (msd_sample_edit): z holds the call's initial draw eps; one pass makes xk and z = alpha xk + sigma eps
+    // at the start index's noise level, with z's planes and the range flag (what split_z does for the plain start)
+    DiffuseParams dp;
+    dp.mel = keep->known_dev; dp.eps = m->z; dp.xk = m->keep_xk; dp.z = m->z;
+    dp.z_hi = m->zp.p[0]; dp.z_lo = m->NP == 2 ? m->zp.p[1] : nullptr;
+    dp.n = (int)n; dp.fmin = m->cfg.feature_min; dp.fmax = m->cfg.feature_max;
+    diffuse_coefs(m->h_coef[(size_t)start_step * kCoefCount + kCoefLogsnrT], &dp.alpha, &dp.sigma);
+    dp.sat = m->d_sat; dp.sat_tag = (unsigned)KC_SAMPLER + 1u;
+    launch_diffuse_to_step(dp, s);
     HIP_TRY(m, hipGetLastError());
-    HIP_TRY(m, hipMemcpyAsync(m->keep_flags, keep->mask, (size_t)batch * m->T * sizeof(int32_t), hipMemcpyDefault, s));
+  }
+  if (keep) {
+    // the frames' release words: msd_sample_edit's as given; msd_sample_keep's flags (host or device) as 0 / 1
+    HIP_TRY(m, hipMemcpyAsync(m->keep_flags, keep->release ? keep->release : keep->mask, (size_t)batch * m->T * sizeof(int32_t),
+                              hipMemcpyDefault, s));
+    if (!keep->release) {
+      launch_normalize_flags(m->keep_flags, m->keep_flags, batch * m->T, s);
+      HIP_TRY(m, hipGetLastError());
+    }
   }
   // Step noise: the caller's buffer, or -- noise_dev == NULL -- drawn INSIDE sampler_step_kernel (round 6): step i's draw is
   // sub-sequence 1 + i of the (seed, stream_id) Philox stream, the row philox_normal_kernel used to write into an
@@ -1999,7 +2066,7 @@ static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys,
   // per call in case an aborted launch left a count behind
   HIP_TRY(m, hipMemsetAsync(m->att_tickets, 0, (size_t)m->att_ticket_count * sizeof(int), s));
   HIP_TRY(m, hipMemcpyAsync(m->d_noise_slot, &noise, sizeof(float*), hipMemcpyHostToDevice, s));
-  const int start[2] = {m->N - 1, m->N - 1};
+  const int start[2] = {start_step, start_step};
   HIP_TRY(m, hipMemcpyAsync(m->d_step, start, sizeof(start), hipMemcpyHostToDevice, s));
   HIP_TRY(m, hipStreamSynchronize(s));  // host temporaries above are on the stack
 
@@ -2039,8 +2106,13 @@ static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys,
     m->graphs.push_back(ng);
     g = &m->graphs.back();
   }
-  for (int i = 0; i < m->N / m->graph_steps; ++i) HIP_TRY(m, hipGraphLaunch(g->exec, s));
-  for (int i = 0; i < m->N % m->graph_steps; ++i)
+  // the call runs start_step + 1 steps (N but for msd_sample_edit's part-way start, whose remainder may need the single-step
+  // graph on a handle whose N is a whole number of graphs: captured on first need, kept in the same entry)
+  const int steps = start_step + 1;
+  if (m->graph_steps > 1 && steps % m->graph_steps && !g->exec1)
+    if (int rc = capture(1, &g->exec1)) return rc;
+  for (int i = 0; i < steps / m->graph_steps; ++i) HIP_TRY(m, hipGraphLaunch(g->exec, s));
+  for (int i = 0; i < steps % m->graph_steps; ++i)
     HIP_TRY(m, hipGraphLaunch(m->graph_steps > 1 ? g->exec1 : g->exec, s));
   if (keep)   // kept frames: the caller's own values, not a round trip through model units
     launch_unscale_keep(m->z, keep->known_dev, m->keep_flags, out_dev, (int)n, m->ND, m->cfg.feature_min, m->cfg.feature_max, s);

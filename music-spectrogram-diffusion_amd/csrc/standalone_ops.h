@@ -1,5 +1,5 @@
 // The msd_op_* entry points: the library's building blocks one at a time, for the unit tests (tests/test_gpu_ops.py,
-// test_gpu_fused_ops.py, test_gpu_gemm_sites.py, test_gpu_keep_frames.py, test_gpu_threefry.py).  Host code only, and no
+// test_gpu_fused_ops.py, test_gpu_gemm_sites.py, test_gpu_keep_frames.py, test_gpu_edit_strength.py, test_gpu_threefry.py).  Host code only, and no
 // part of the product's paths; the file belongs to msd_api.hip alone, which includes it behind its own entry points and
 // in front of the vocoder's.
 // Every GEMM here runs through the product's dispatch (gemm / gemm_on on a site's TileTable), so its tile is an entry of
@@ -478,10 +478,11 @@ msd_gemm_site_args forced_site_args(TileShape tile, int M, int N, int K) {
   return g;
 }
 
-// one launch of the sampler update on the caller's arrays; known_scaled_dev != NULL: the keep form
+// one launch of the sampler update on the caller's arrays; known_scaled_dev != NULL: the keep form, keep_mask_dev its
+// frames' release words, or -- flags -- msd_sample_keep's flags (any non-zero = known throughout)
 int op_sampler_step(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
                     const float* out_uncond_dev, const float* noise_dev, const float* known_scaled_dev,
-                    const int32_t* keep_mask_dev, int n_dims, float* z_out_dev, int64_t n, void* stream) {
+                    const int32_t* keep_mask_dev, int n_dims, float* z_out_dev, int64_t n, void* stream, bool flags = false) {
   if (!cfg || cfg->struct_size != (int32_t)sizeof(msd_config) || !z_dev || !out_cond_dev || !z_out_dev ||
       n <= 0 || n % 4 || step_index < 0 || step_index >= cfg->num_steps)
     return MSD_ERR_INVALID_ARGUMENT;
@@ -517,6 +518,12 @@ int op_sampler_step(const msd_config* cfg, int step_index, const float* z_dev, c
   sp.z_hi = nullptr; sp.z_lo = nullptr; sp.step_from_slot1 = 1;
   if (known_scaled_dev) {
     sp.xk = known_scaled_dev; sp.keep = keep_mask_dev; sp.n_dims = n_dims;
+    if (flags) {
+      int32_t* words = kit.get<int32_t>((size_t)(n / n_dims));
+      if (!words) return MSD_ERR_HIP;
+      launch_normalize_flags(keep_mask_dev, words, (int)(n / n_dims), s);
+      sp.keep = words;
+    }
     launch_sampler_step(sp, s);
   } else {
     launch_sampler_step(static_cast<const SamplerParams&>(sp), s);
@@ -658,7 +665,41 @@ int msd_op_sampler_step_keep(const msd_config* cfg, int step_index, const float*
   if (!known_scaled_dev || !keep_mask_dev || n_dims <= 0 || n_dims % 4 || n <= 0 || n % n_dims)
     return MSD_ERR_INVALID_ARGUMENT;
   return op_sampler_step(cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, noise_dev, known_scaled_dev, keep_mask_dev,
+                         n_dims, z_out_dev, n, stream, /*flags=*/true);
+}
+
+int msd_op_sampler_step_release(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
+                                const float* out_uncond_dev, const float* noise_dev, const float* known_scaled_dev,
+                                const int32_t* release_dev, int n_dims, float* z_out_dev, int64_t n, void* stream) {
+  if (!known_scaled_dev || !release_dev || n_dims <= 0 || n_dims % 4 || n <= 0 || n % n_dims)
+    return MSD_ERR_INVALID_ARGUMENT;
+  return op_sampler_step(cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, noise_dev, known_scaled_dev, release_dev,
                          n_dims, z_out_dev, n, stream);
+}
+
+int msd_op_diffuse_to_step(const msd_config* cfg, int step_index, const float* mel_dev, const float* eps_dev,
+                           float* z_out_dev, float* z_planes_out_dev, float* xk_out_dev, int64_t n, void* stream) {
+  if (!cfg || cfg->struct_size != (int32_t)sizeof(msd_config) || !mel_dev || !eps_dev || !z_out_dev || !z_planes_out_dev ||
+      !xk_out_dev || n <= 0 || n % 4 || n > 0x7FFFFFFFll || step_index < 0 || step_index >= cfg->num_steps)
+    return MSD_ERR_INVALID_ARGUMENT;
+  const int NP = op_planes(cfg->precision);
+  if (NP < 0) return MSD_ERR_UNSUPPORTED;
+  std::vector<float> rows;
+  std::string why;
+  if (!build_coef_rows(*cfg, &rows, &why)) return MSD_ERR_INVALID_ARGUMENT;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  OpKit kit(s, NP);
+  Planes zp;
+  if (!kit.init_flags() || !kit.planes((size_t)n, &zp)) return MSD_ERR_HIP;
+  DiffuseParams dp;
+  dp.mel = mel_dev; dp.eps = eps_dev; dp.xk = xk_out_dev; dp.z = z_out_dev; dp.z_hi = zp.p[0]; dp.z_lo = zp.p[1];
+  dp.n = (int)n; dp.fmin = cfg->feature_min; dp.fmax = cfg->feature_max;
+  diffuse_coefs(rows[(size_t)step_index * kCoefCount + kCoefLogsnrT], &dp.alpha, &dp.sigma);
+  kit.arm(dp);
+  launch_diffuse_to_step(dp, s);
+  if (hipGetLastError() != hipSuccess) return MSD_ERR_HIP;
+  kit.back(zp, z_planes_out_dev, (size_t)n);
+  return kit.finish();
 }
 
 // x_out = x_in + a . w1 ;  h_out = (RMSNorm(x_out; gamma) (.) (film_scale + 1) + film_bias) . w2

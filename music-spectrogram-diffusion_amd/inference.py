@@ -229,6 +229,63 @@ def plan_region(n_frames: int, segment_frames: int, start: int, stop: int):
   return plan
 
 
+def region_strength(n_frames: int, segment_frames: int, start: int, stop: int, blend_frames: int):
+  """plan_region with a soft edge: [(segment, strength_row)], in order; strength_row float64 [segment_frames] -- 1 inside
+  the region [start, stop), 1 - d / (blend_frames + 1) at distance d = 1 .. blend_frames outside it (across segment
+  boundaries, cut off at the song's ends), 0 beyond.  Every segment the region OR the ramp touches is in the plan.
+  blend_frames = 0: plan_region's segments, strength_row == 1 - its mask row.  No device needed; the checks are
+  plan_region's, and blend_frames must be an integer >= 0."""
+  plan_region(n_frames, segment_frames, start, stop)   # (its checks)
+  if isinstance(blend_frames, bool) or int(blend_frames) != blend_frames or blend_frames < 0:
+    raise ValueError('blend_frames must be an integer >= 0: %r' % (blend_frames,))
+  n_frames, segment_frames, start, stop, blend = (int(v) for v in (n_frames, segment_frames, start, stop, blend_frames))
+  frame = np.arange(n_frames)
+  dist = np.maximum(np.maximum(start - frame, frame - (stop - 1)), 0)   # 0 inside the region
+  song = np.where(dist <= blend, 1.0 - dist / float(blend + 1), 0.0)
+  lo, hi = max(start - blend, 0), min(stop + blend, n_frames)
+  return [(k, song[k * segment_frames:(k + 1) * segment_frames].copy())
+          for k in range(lo // segment_frames, (hi - 1) // segment_frames + 1)]
+
+
+def plan_strength(strength, num_steps: int):
+  """Edit strengths -> the sampler's release schedule.  strength [B, T] floats in [0, 1]: the share of the scan during
+  which a frame is FREE -- f = floor(s * num_steps + 0.5) final steps; before them it is known (x0-replacement).  Returns
+  (words int32 [B, T], start_step): word = f + 1 for f < num_steps (1 = known throughout, returned as given) and 0 for
+  f == num_steps (free throughout); start_step = max f - 1 is the scan index the call starts at -- the steps above it
+  have every frame known and are not run (-1: nothing to sample).  Pure: no device.  NaN, a value outside [0, 1], a
+  non-float-convertible or non-2-D array, or num_steps < 1 is a ValueError."""
+  if isinstance(num_steps, bool) or int(num_steps) != num_steps or num_steps < 1:
+    raise ValueError('num_steps must be a positive integer: %r' % (num_steps,))
+  try:
+    s = np.asarray(strength, np.float64)
+  except (TypeError, ValueError) as e:
+    raise ValueError('strength must be an array of floats: %s' % e)
+  if s.ndim != 2 or s.size == 0:
+    raise ValueError('strength must be [batch, frames]: got shape %r' % (s.shape,))
+  if not (np.isfinite(s).all() and (s >= 0.0).all() and (s <= 1.0).all()):
+    raise ValueError('strength must lie in [0, 1] (no NaN)')
+  f = np.floor(s * float(num_steps) + 0.5).astype(np.int64)
+  words = np.where(f < num_steps, f + 1, 0).astype(np.int32)
+  return np.ascontiguousarray(words), int(f.max()) - 1
+
+
+def check_strength(strength, flags, b: int, t: int):
+  """predict's strength -- a scalar, [b] or [b, t] -- as float64 [b, t], with 0 on the frames `flags` (int [b, t] or None)
+  names.  A shape that is none of the three is a ValueError; the values are plan_strength's to check."""
+  try:
+    s = np.asarray(_to_numpy(strength), np.float64)
+  except (TypeError, ValueError) as e:
+    raise ValueError('strength must be a float, [batch] or [batch, %d]: %s' % (t, e))
+  if s.shape == (b,):
+    s = s[:, None]
+  elif s.shape not in ((), (b, t)):
+    raise ValueError('strength must be a scalar, [batch] = [%d] or [batch, %d]: got %r' % (b, t, s.shape))
+  s = np.broadcast_to(s, (b, t)).copy()
+  if flags is not None:
+    s[flags != 0] = 0.0
+  return s
+
+
 def check_keep(keep, keep_mask, b: int, t: int, n: int):
   """The known-frame arguments of predict: both or neither; keep [b, t, n], keep_mask [b, t] bool or integer.
   Returns (keep, flags) with flags a contiguous int32 NumPy array of zeros and ones, or (None, None)."""
@@ -413,7 +470,7 @@ class InferenceModel(object):
   def predict(self, batch: Mapping[str, Any], seed: Union[int, Sequence[int]] = 0,
               segment: Union[int, Sequence[int]] = 0,
               init_z=None, noise=None, return_torch: bool = False, rng: Optional[str] = None,
-              keep=None, keep_mask=None):
+              keep=None, keep_mask=None, strength=None):
     """Predict one batch of 256-frame segments.
 
     batch: the model features of inference.py:113-136 (NumPy arrays or torch
@@ -442,14 +499,30 @@ class InferenceModel(object):
       level and the free frames see them through self-attention.  The draws are those of the call without a mask
       (an all-zero mask changes nothing, bit for bit); every seed / segment / rng / init_z / noise form works.
       One without the other, or a wrong shape, is a ValueError.
+    strength (with keep; a float, [B] or [B,T], each in [0, 1]): how far each frame of `keep` may move -- an
+      SDEdit-style restart with a per-frame release schedule on top of the x0-replacement (plan_strength,
+      msd_sample_edit).  A frame of strength s is known while the noise is high and free for the last
+      f = round(s * N) steps; 0 returns it as given, 1 samples it from pure noise.  The call starts at scan index
+      max f - 1 from the known mel diffused to that step's noise level (with the call's own initial draw) and costs
+      max f steps, not N.  Frames named by keep_mask (optional here) get strength 0.  strength == 1 - keep_mask
+      is the keep_mask call, bit for bit.  The network was never trained on known frames; the schedule is per frame
+      (no per-bin map) and the scan makes no resampling jumps.  strength without keep is a ValueError.
     Returns (decodes float32 [B,T,n] in mel units, scores float32 [B] zeros).
     """
-    keep, keep_mask = check_keep(keep, keep_mask, np.shape(batch['encoder_input_tokens'])[0], self.targets_length,
-                                 self.audio_codec.n_dims)
+    b, t, n = np.shape(batch['encoder_input_tokens'])[0], self.targets_length, self.audio_codec.n_dims
+    edit = None   # (release words, start_step) of the edit form
+    if strength is not None:
+      if keep is None:
+        raise ValueError('strength needs keep: the mel it is a variation of')
+      keep, flags = check_keep(keep, np.zeros((b, t), np.int32) if keep_mask is None else keep_mask, b, t, n)
+      edit = plan_strength(check_strength(strength, flags, b, t), self.spec.diffusion.sampler.schedule.num_steps)
+      keep_mask = None
+    else:
+      keep, keep_mask = check_keep(keep, keep_mask, b, t, n)
     if rng is None:
       rng = self.rng
     try:
-      return self._predict_once(batch, seed, segment, init_z, noise, return_torch, rng, keep, keep_mask)
+      return self._predict_once(batch, seed, segment, init_z, noise, return_torch, rng, keep, keep_mask, edit)
     except native.RangeError:
       if not (self.range_fallback and self.precision in ('f16x3', 'f16')):
         raise
@@ -461,9 +534,9 @@ class InferenceModel(object):
       if self._native is not None:
         self._native.close()
       self._native = None
-      return self._predict_once(batch, seed, segment, init_z, noise, return_torch, rng, keep, keep_mask)
+      return self._predict_once(batch, seed, segment, init_z, noise, return_torch, rng, keep, keep_mask, edit)
 
-  def _predict_once(self, batch, seed, segment, init_z, noise, return_torch, rng, keep=None, keep_mask=None):
+  def _predict_once(self, batch, seed, segment, init_z, noise, return_torch, rng, keep=None, keep_mask=None, edit=None):
     torch = self._torch
     nm = self._get_native()
     dev = self.device
@@ -512,7 +585,8 @@ class InferenceModel(object):
       # explicit draws keep precedence in every mode; 'jax' has none left to generate
       known = None if keep is None else _to_device(torch, keep, dev, torch.float32)
       nm.sample(b, out, seed=seed, stream_id=segment, init_z=z0, noise=nz, stream=s,
-                rng='threefry' if rng == 'threefry' else 'philox', keep=known, keep_mask=keep_mask)
+                rng='threefry' if rng == 'threefry' else 'philox', keep=known, keep_mask=keep_mask,
+                release=None if edit is None else edit[0], start_step=None if edit is None else edit[1])
       self._stream.synchronize()
     t2 = time.perf_counter()
     self.last_timing = {'encode_s': t1 - t0, 'sample_s': t2 - t1, 'total_s': t2 - t0}
@@ -604,8 +678,56 @@ class InferenceModel(object):
       return full
     return full, self._sequence_timing(seconds)
 
+  def _check_song(self, song, segments_tokens):
+    t, n = self.targets_length, self.audio_codec.n_dims
+    if len(np.shape(song)) != 3 or np.shape(song)[0] != 1 or np.shape(song)[2] != n:
+      raise ValueError('song must be [1, frames, %d]: got %r' % (n, tuple(np.shape(song))))
+    if np.shape(song)[1] != t * len(segments_tokens) or not len(segments_tokens):
+      raise ValueError('song has %d frames but %d segments of tokens (%d frames each) were given'
+                       % (np.shape(song)[1], len(segments_tokens), t))
+
+  def _edit_segment(self, new, k, tokens, always_mask_context, seed, rng, **keep_kw):
+    """predict for segment k of the song `new` as it stands ([1, K * T, n] on the device): its context is segment k - 1 of
+    `new` (zeros and mask 0 for segment 0 and always_mask_context), its key (seed, k), its known mel its own frames."""
+    torch = self._torch
+    t, n, c_len = self.targets_length, self.audio_codec.n_dims, self.targets_context_length
+    batch = {'encoder_input_tokens': np.asarray(tokens, np.int32).reshape(1, -1)}
+    if c_len is not None:
+      no_ctx = always_mask_context or k == 0
+      batch['encoder_continuous_inputs'] = (torch.zeros((1, c_len, n), dtype=torch.float32, device=self.device)
+                                            if no_ctx else new[:, (k - 1) * t:k * t].clone())
+      batch['encoder_continuous_mask'] = (np.zeros if no_ctx else np.ones)((1, c_len), np.int32)
+    out, _ = self.predict(batch, seed=seed, segment=k, return_torch=True, rng=rng, keep=new[:, k * t:(k + 1) * t].clone(),
+                          **keep_kw)
+    return out.to(self.device)
+
+  def vary(self, song, segments_tokens: Sequence[np.ndarray], strength, seed: int = 0, always_mask_context: bool = False,
+           rng: Optional[str] = None, return_torch: bool = False):
+    """A variation of a rendering: the same song at a chosen distance.
+
+    song float32 [1, K * T, n] (mel units; NumPy or a device tensor), K == len(segments_tokens).  strength: a float in
+    [0, 1], or one value per frame ([K * T] or [1, K * T]).  Every segment runs through predict(keep=its old frames,
+    strength=...), keyed (seed, segment index) as predict_sequence keys it; its context is the NEW previous segment, as
+    in predict_sequence.  A segment costs round(max strength * N) steps, not N: it starts part-way down the scan from its
+    old frames diffused to that noise level.  strength 1.0 is predict_sequence, bit for bit; frames of strength 0 are
+    the input's, bit for bit.  Returns the new song [1, K * T, n] (NumPy; ``return_torch``: the device tensor)."""
+    torch = self._torch
+    t = self.targets_length
+    self._check_song(song, segments_tokens)
+    frames = np.shape(song)[1]
+    s = np.asarray(_to_numpy(strength), np.float64)
+    if s.shape not in ((), (frames,), (1, frames)):
+      raise ValueError('strength must be a float or one value per frame ([%d] or [1, %d]): got %r' % (frames, frames, s.shape))
+    s = np.broadcast_to(s.reshape(-1) if s.ndim else s, (frames,))
+    new = _to_device(torch, song, self.device, torch.float32).clone()
+    for k, toks in enumerate(segments_tokens):
+      out = self._edit_segment(new, k, toks, always_mask_context, seed, rng, strength=s[None, k * t:(k + 1) * t])
+      new[:, k * t:(k + 1) * t] = out[:1]
+    return new if return_torch else new.cpu().numpy()
+
   def regenerate(self, song, segments_tokens: Sequence[np.ndarray], start_frame: int, stop_frame: int, seed: int = 0,
-                 always_mask_context: bool = False, rng: Optional[str] = None, return_torch: bool = False):
+                 always_mask_context: bool = False, rng: Optional[str] = None, return_torch: bool = False,
+                 blend_frames: int = 0):
     """Sample the frames [start_frame, stop_frame) of a song again and keep the rest.
 
     song float32 [1, K * T, n] (mel units; NumPy or a device tensor), K == len(segments_tokens), the tokens of ALL its
@@ -616,13 +738,27 @@ class InferenceModel(object):
     zeros and mask 0, as in predict_sequence.  Segments behind the region are not run again: the region's last frames
     are sampled with the frames that follow them in their own segment known, and the next segment keeps the context
     it was made with.  Returns the new song [1, K * T, n] (NumPy; ``return_torch``: the device tensor); every frame
-    outside the region is the input's, bit for bit."""
+    outside the region is the input's, bit for bit.
+
+    blend_frames = F > 0 softens the seams: the F frames on either side of the region are released to the sampler for
+    the last part of the scan only -- strength 1 - d / (F + 1) at distance d (region_strength; predict(strength=)) --,
+    across segment boundaries; segments that only this ramp touches are sampled too.  Frames beyond the ramp, and ramp
+    frames whose share rounds to no step at all, are the input's bit for bit.  0 is the hard edge above, unchanged."""
     torch = self._torch
     t, n = self.targets_length, self.audio_codec.n_dims
     c_len = self.targets_context_length
     if len(np.shape(song)) != 3 or np.shape(song)[0] != 1 or np.shape(song)[2] != n:
       raise ValueError('song must be [1, frames, %d]: got %r' % (n, tuple(np.shape(song))))
     plan = plan_region(np.shape(song)[1], t, start_frame, stop_frame)
+    if blend_frames != 0:
+      soft = region_strength(np.shape(song)[1], t, start_frame, stop_frame, blend_frames)
+      self._check_song(song, segments_tokens)
+      new = _to_device(torch, song, self.device, torch.float32).clone()
+      for k, row in soft:
+        out = self._edit_segment(new, k, segments_tokens[k], always_mask_context, seed, rng, strength=row[None])
+        free = torch.as_tensor(row > 0.0, device=self.device)
+        new[0, k * t:(k + 1) * t][free] = out[0][free]
+      return new if return_torch else new.cpu().numpy()
     if np.shape(song)[1] != t * len(segments_tokens):
       raise ValueError('song has %d segments of %d frames but %d segments of tokens were given'
                        % (np.shape(song)[1] // t, t, len(segments_tokens)))

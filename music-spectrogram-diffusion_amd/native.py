@@ -65,7 +65,9 @@ EXPORTED_SYMBOLS = (
     # (appended to ABI 7) known frames in the sampler
     'msd_sample_keep', 'msd_op_sampler_step_keep',
     # (appended to ABI 7) one GEMM launch site at a time
-    'msd_op_gemm_site', 'msd_op_gemm_site_tiles', 'msd_op_gemm_site_name')
+    'msd_op_gemm_site', 'msd_op_gemm_site_tiles', 'msd_op_gemm_site_name',
+    # (appended to ABI 7) edit strength: per-frame release words and a part-way start of the sampler
+    'msd_sample_edit', 'msd_op_sampler_step_release', 'msd_op_diffuse_to_step')
 
 
 class NativeLibraryError(RuntimeError):
@@ -197,6 +199,10 @@ def load(planes: str = 'f16') -> ctypes.CDLL:
   if 'msd_sample_keep' in present:   # (appended to ABI 7)
     lib.msd_sample_keep.argtypes = [vp, i32, i32, i32, c.POINTER(u64), c.POINTER(u64), vp, vp, vp, vp, vp, vp]
     lib.msd_op_sampler_step_keep.argtypes = [c.POINTER(MsdConfig), i32, vp, vp, vp, vp, vp, vp, i32, vp, i64, vp]
+  if 'msd_sample_edit' in present:   # (appended to ABI 7)
+    lib.msd_sample_edit.argtypes = [vp, i32, i32, i32, c.POINTER(u64), c.POINTER(u64), vp, vp, vp, vp, i32, vp, vp]
+    lib.msd_op_sampler_step_release.argtypes = [c.POINTER(MsdConfig), i32, vp, vp, vp, vp, vp, vp, i32, vp, i64, vp]
+    lib.msd_op_diffuse_to_step.argtypes = [c.POINTER(MsdConfig), i32, vp, vp, vp, vp, vp, i64, vp]
   if 'msd_fill_normal_threefry' in present:
     lib.msd_fill_normal_threefry.argtypes = [u64, i64, vp, i64, vp]
   if 'msd_op_threefry' in present:
@@ -343,7 +349,8 @@ class NativeModel:
            'msd_encode')
 
   def sample(self, batch: int, out, seed: int = 0, stream_id: int = 0, init_z=None,
-             noise=None, stream: int = 0, rng: str = 'philox', keep=None, keep_mask=None):
+             noise=None, stream: int = 0, rng: str = 'philox', keep=None, keep_mask=None, release=None,
+             start_step: Optional[int] = None):
     """rng: the generator of the draws that are not given -- 'philox' (the library's own, keyed by seed and stream_id)
     or 'threefry' (the reference's jax.random draws for PRNGKey(seed), made on the device; stream_id is ignored).
 
@@ -353,9 +360,30 @@ class NativeModel:
 
     keep (float32 device tensor [batch, T, n], mel units) / keep_mask (int32 [batch, T], NumPy or device; non-zero = the
     frame is known): the kept frames come back as given and the others are sampled around them (msd_sample_keep); both
-    or neither.  The keys and the draws are those of the call without them."""
+    or neither.  The keys and the draws are those of the call without them.
+
+    keep with release (int32 NumPy [batch, T], the frames' release words) and start_step instead of keep_mask: the edit
+    form (msd_sample_edit) -- a frame with word v >= 1 is known at scan indices >= v - 1 and free below, 0 = free
+    throughout; the scan starts at start_step from the known mel diffused to that step (None = num_steps - 1: from
+    init_z, as ever)."""
     if rng not in RNGS:
       raise ValueError('rng must be one of %s: %r' % (sorted(RNGS), rng))
+    if release is not None:
+      if keep is None or keep_mask is not None:
+        raise ValueError('release goes with keep and without keep_mask')
+      words = np.ascontiguousarray(release, dtype=np.int32)
+      if words.size != batch * self.cfg.targets_length:
+        raise ValueError('release must hold one word per frame: [%d, %d]' % (batch, self.cfg.targets_length))
+      per_row = not (np.isscalar(seed) and np.isscalar(stream_id))
+      seeds, stream_ids = row_keys(batch if per_row else 1, seed, stream_id)
+      start = self.cfg.num_steps - 1 if start_step is None else int(start_step)
+      rc = self.lib.msd_sample_edit(self.handle, batch, RNGS[rng], int(per_row), (ctypes.c_uint64 * len(seeds))(*seeds),
+                                    (ctypes.c_uint64 * len(seeds))(*stream_ids), _ptr(init_z), _ptr(noise), _ptr(keep),
+                                    _ptr(words), start, _ptr(out), stream)
+      _check(self.lib, self.handle, rc, 'msd_sample_edit')
+      return
+    if start_step is not None:
+      raise ValueError('start_step goes with release')
     if (keep is None) != (keep_mask is None):
       raise ValueError('keep and keep_mask go together')
     if keep is not None:
@@ -547,6 +575,32 @@ def op_sampler_step_keep(cfg: MsdConfig, step_index: int, z, out_cond, out_uncon
   _op_check(lib.msd_op_sampler_step_keep(ctypes.byref(cfg), step_index, _ptr(z), _ptr(out_cond), _ptr(out_uncond),
                                          _ptr(noise), _ptr(known_scaled), _ptr(keep_mask), n_dims, _ptr(z_out), z.numel(),
                                          stream), 'msd_op_sampler_step_keep')
+
+
+def op_sampler_step_release(cfg: MsdConfig, step_index: int, z, out_cond, out_uncond, noise, known_scaled, release,
+                            z_out, stream: int = 0):
+  """op_sampler_step_keep with release words (msd_op_sampler_step_release): release int32 device tensor, one word per
+  frame -- 0 = free, v >= 1 = known at scan indices >= v - 1."""
+  lib = load()
+  cfg.struct_size = ABI_STRUCT_SIZES[getattr(lib, '_msd_abi', None) or ABI_VERSION]
+  n_dims = int(known_scaled.shape[-1])
+  if known_scaled.numel() != z.numel() or release.numel() * n_dims != z.numel():
+    raise ValueError('known_scaled must have z\'s element count and release one word per frame of %d' % n_dims)
+  _op_check(lib.msd_op_sampler_step_release(ctypes.byref(cfg), step_index, _ptr(z), _ptr(out_cond), _ptr(out_uncond),
+                                            _ptr(noise), _ptr(known_scaled), _ptr(release), n_dims, _ptr(z_out), z.numel(),
+                                            stream), 'msd_op_sampler_step_release')
+
+
+def op_diffuse_to_step(cfg: MsdConfig, step_index: int, mel, eps, z_out, z_planes_out, xk_out, stream: int = 0):
+  """The part-way start of msd_sample_edit on its own (msd_op_diffuse_to_step): mel (mel units) and eps in; z = alpha xk +
+  sigma eps at step_index's noise level, z's operand planes of cfg.precision merged back to float32, and xk =
+  scale_features(clip=True) of mel out.  float32 device tensors of equal numel (% 4 == 0)."""
+  lib = load(_PLANES_OF[cfg.precision])
+  cfg.struct_size = ABI_STRUCT_SIZES[getattr(lib, '_msd_abi', None) or ABI_VERSION]
+  if not (mel.numel() == eps.numel() == z_out.numel() == z_planes_out.numel() == xk_out.numel()):
+    raise ValueError('mel, eps and the three outputs must have the same element count')
+  _op_check(lib.msd_op_diffuse_to_step(ctypes.byref(cfg), step_index, _ptr(mel), _ptr(eps), _ptr(z_out), _ptr(z_planes_out),
+                                       _ptr(xk_out), mel.numel(), stream), 'msd_op_diffuse_to_step')
 
 
 def op_residual_norm_gemm(folded: bool, x_in, a, w1, gamma, film_scale, film_bias, w2, x_out, h_out,

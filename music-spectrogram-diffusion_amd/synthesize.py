@@ -7,7 +7,8 @@ beam/evaluation.py:161-223) on the MI355X path.
       [--seed 0] [--rng threefry|jax] [--num-steps 1000] [--dry-run]
       [--batch-segments B [--always-mask-context]]
       [--wav song.wav [--vocoder-iters 32]] [--context-audio earlier.wav]
-      [--regenerate START:STOP (--edit-mel old_mel.npy | --edit-audio old.wav)]
+      [--regenerate START:STOP [--blend FRAMES] (--edit-mel old_mel.npy | --edit-audio old.wav)]
+      [--vary STRENGTH (--edit-mel old_mel.npy | --edit-audio old.wav)]
 
 --wav writes 16-bit PCM mono at 16 kHz from the device vocoder: Griffin-Lim over the codec's STFT, a stand-in for the
 reference's SoundStream decoder (which is not built).  --context-audio continues a recording: its last 256 frames are
@@ -20,6 +21,13 @@ segments must be independent of each other: a preset without context, or --alway
 --edit-mel (the .npy a previous --out wrote) or --edit-audio (a recording, encoded on the device), the MIDI file is the
 song as it should be now, and only the segments the region touches are sampled again, each keeping its frames outside
 the region; every frame outside the region stays what it was.  --out / --wav write the edited song.
+
+--blend FRAMES softens the region's edges: the FRAMES frames on either side are released to the sampler for the last part
+of the scan only, less the farther they lie from the region (InferenceModel.regenerate(blend_frames=)).
+
+--vary STRENGTH (0 .. 1) renders a variation of the old rendering: every segment starts part-way down the scan from its old
+frames at the matching noise level and runs round(STRENGTH * steps) steps -- 1 is a fresh rendering, 0 the old one
+(InferenceModel.vary).  An SDEdit-style restart: the network was never trained on known frames.
 
 --dry-run tokenises only (no GPU): prints the segment / token statistics the synthesis would see, and with --regenerate
 the plan: the segments touched and the frames each keeps."""
@@ -65,20 +73,32 @@ def main(argv=None) -> int:
   ap.add_argument('--regenerate', default=None, metavar='START:STOP',
                   help='sample this region of the song again (seconds, rounded outward to frames) and keep the rest of '
                        '--edit-mel / --edit-audio')
+  ap.add_argument('--blend', type=int, default=0, metavar='FRAMES',
+                  help='with --regenerate: release this many frames on either side of the region part-way (soft seams)')
+  ap.add_argument('--vary', type=float, default=None, metavar='STRENGTH',
+                  help='a variation of --edit-mel / --edit-audio at this distance, 0 .. 1 (1 = a fresh rendering)')
   ap.add_argument('--edit-mel', default=None, metavar='OLD.npy', help='the old rendering as mel frames [frames, 128]')
   ap.add_argument('--edit-audio', default=None, metavar='OLD.wav',
                   help='the old rendering as a 16 kHz PCM recording (encoded on the device)')
   ap.add_argument('--on-too-long', choices=['error', 'truncate'], default='error')
   ap.add_argument('--dry-run', action='store_true')
   args = ap.parse_args(argv)
+  if args.regenerate and args.vary is not None:
+    ap.error('--regenerate and --vary are two edits: give one')
   if args.regenerate and not (args.edit_mel or args.edit_audio):
     ap.error('--regenerate needs the old rendering: --edit-mel OLD.npy or --edit-audio OLD.wav')
+  if args.vary is not None and not (args.edit_mel or args.edit_audio):
+    ap.error('--vary needs the old rendering: --edit-mel OLD.npy or --edit-audio OLD.wav')
   if args.edit_mel and args.edit_audio:
     ap.error('--edit-mel and --edit-audio are two sources of the same thing: give one')
-  if (args.edit_mel or args.edit_audio) and not args.regenerate:
-    ap.error('--edit-mel / --edit-audio need the region to change: --regenerate START:STOP')
-  if args.regenerate and (args.batch_segments != 1 or args.context_audio):
-    ap.error('--regenerate samples its segments one by one with the song as context: no --batch-segments / --context-audio')
+  if (args.edit_mel or args.edit_audio) and not (args.regenerate or args.vary is not None):
+    ap.error('--edit-mel / --edit-audio need the edit to make: --regenerate START:STOP or --vary STRENGTH')
+  if (args.regenerate or args.vary is not None) and (args.batch_segments != 1 or args.context_audio):
+    ap.error('--regenerate / --vary sample their segments one by one with the song as context: no --batch-segments / --context-audio')
+  if args.vary is not None and not 0.0 <= args.vary <= 1.0:
+    ap.error('--vary wants a strength in [0, 1]: %r' % (args.vary,))
+  if args.blend < 0 or (args.blend and not args.regenerate):
+    ap.error('--blend FRAMES (>= 0) goes with --regenerate')
 
   import msd_amd
   from msd_amd.frontend import midi_io, tokenizer
@@ -96,13 +116,13 @@ def main(argv=None) -> int:
         % (args.midi, len(ns.notes), ns.total_time, len(segments), cfg.segment_frames, min(n_tok),
            float(np.mean(n_tok)), max(n_tok), t_tok), file=sys.stderr)
   edit = None
-  if args.regenerate:
+  if args.regenerate or args.vary is not None:
     # everything about the edit that needs no device: the region in frames, the old rendering's length, the plan
     from msd_amd import audio_codecs, inference, vocoder
     codec = audio_codecs.get_codec(spec.audio_codec)
     song_frames = len(segments) * cfg.segment_frames
     try:
-      start, stop = region_frames(args.regenerate, codec.sample_rate / codec.hop_size)
+      start, stop = region_frames(args.regenerate, codec.sample_rate / codec.hop_size) if args.regenerate else (0, song_frames)
       if args.edit_mel:
         old = np.load(args.edit_mel)
         old = old[0] if old.ndim == 3 and old.shape[0] == 1 else old
@@ -116,14 +136,25 @@ def main(argv=None) -> int:
         raise ValueError('the old rendering has %d frames, the MIDI file only %d (%d segments)'
                          % (old_frames, song_frames, len(segments)))
       plan = inference.plan_region(song_frames, cfg.segment_frames, start, stop)
+      soft = inference.region_strength(song_frames, cfg.segment_frames, start, stop, args.blend) if args.blend else []
+      steps = spec.diffusion.sampler.schedule.num_steps
+      vary_steps = None if args.vary is None else inference.plan_strength([[args.vary]], steps)[1] + 1
     except ValueError as e:
       ap.error(str(e))
-    print('regenerate frames [%d, %d) of %d (%.3f s .. %.3f s): %d of %d segments'
-          % (start, stop, song_frames, start / cfg.frame_rate, stop / cfg.frame_rate, len(plan), len(segments)))
-    for k, row in plan:
-      free = np.nonzero(row == 0)[0]
-      print('  segment %d: frames [%d, %d) sampled again, %d of %d kept'
-            % (k, free[0], free[-1] + 1, int(row.sum()), row.size))
+    if args.vary is not None:
+      print('vary %d segments at strength %g: %d of %d steps each' % (len(segments), args.vary, vary_steps, steps))
+    else:
+      print('regenerate frames [%d, %d) of %d (%.3f s .. %.3f s): %d of %d segments'
+            % (start, stop, song_frames, start / cfg.frame_rate, stop / cfg.frame_rate, len(plan), len(segments)))
+      for k, row in plan:
+        free = np.nonzero(row == 0)[0]
+        print('  segment %d: frames [%d, %d) sampled again, %d of %d kept'
+              % (k, free[0], free[-1] + 1, int(row.sum()), row.size))
+      for k, row in soft:
+        words, start_step = inference.plan_strength(row[None], steps)
+        part = (words[0] > 1)
+        print('  blend %d, segment %d: %d frames released part-way, %d of %d steps'
+              % (args.blend, k, int(part.sum()), start_step + 1, steps))
     edit = (old, start, stop)
   if args.dry_run:
     return 0
@@ -199,11 +230,19 @@ def _regenerate(args, model, segments, edit, ns, cfg) -> int:
     song = model.vocoder.encode(np.asarray(old, np.float32)[None], return_torch=True)
   song = pad_to_segments(song, len(segments) * cfg.segment_frames, model.audio_codec.pad_value)
   t0 = time.perf_counter()
-  mel_dev = model.regenerate(song, segments, start, stop, seed=args.seed, always_mask_context=args.always_mask_context,
-                             rng=args.rng, return_torch=True)
+  if args.vary is not None:
+    mel_dev = model.vary(song, segments, args.vary, seed=args.seed, always_mask_context=args.always_mask_context,
+                         rng=args.rng, return_torch=True)
+  else:
+    kw = dict(blend_frames=args.blend) if args.blend else {}
+    mel_dev = model.regenerate(song, segments, start, stop, seed=args.seed, always_mask_context=args.always_mask_context,
+                               rng=args.rng, return_torch=True, **kw)
   frames = int(np.ceil(ns.total_time * cfg.frame_rate))
   mel = mel_dev.cpu().numpy()[0, :max(frames, 1)]
-  print('regenerated frames [%d, %d) of %d in %.3f s' % (start, stop, mel.shape[0], time.perf_counter() - t0), file=sys.stderr)
+  if args.vary is not None:
+    print('varied %d frames at strength %g in %.3f s' % (mel.shape[0], args.vary, time.perf_counter() - t0), file=sys.stderr)
+  else:
+    print('regenerated frames [%d, %d) of %d in %.3f s' % (start, stop, mel.shape[0], time.perf_counter() - t0), file=sys.stderr)
   _write_outputs(args, model, mel_dev, mel)
   return 0
 
