@@ -48,7 +48,9 @@ extern "C" {
                                       msd_op_sampler_step_keep (known frames in the sampler); msd_op_gemm_site and
                                       msd_op_gemm_site_tiles, msd_op_gemm_site_name (one GEMM launch site at a time, for the tests);
                                       msd_sample_edit, msd_op_sampler_step_release and msd_op_diffuse_to_step (edit strength:
-                                      per-frame release words and a part-way start of the sampler).
+                                      per-frame release words and a part-way start of the sampler);
+                                      msd_sample_steps, msd_op_sampler_step_multistep and MSD_SAMPLER_DPMPP_2M (a step
+                                      count per call and a second-order multistep sampler).
                                    6: cross_merge_in_launch, cross_q_fold, mlp_in_persistent appended to msd_config.
                                    5: dedup_layer0, cross_key_split, keep_raw_weights, kv_touch_ahead appended to msd_config.
                                    4: every caller-selectable knob is a msd_config field (attn_q_planes / attn_p_planes
@@ -94,7 +96,10 @@ typedef enum msd_precision {
 
 typedef enum msd_sampler_kind {
   MSD_SAMPLER_DDPM = 0, /* diffusion_utils.py:382-395 */
-  MSD_SAMPLER_DDIM = 1  /* diffusion_utils.py:369-379 */
+  MSD_SAMPLER_DDIM = 1, /* diffusion_utils.py:369-379 */
+  MSD_SAMPLER_DPMPP_2M = 2 /* (appended to ABI 7; not in the reference) DPM-Solver++(2M), data-prediction form: the
+                              deterministic second-order multistep solver of the ODE ddim_step solves to first order;
+                              see msd_sample_steps.  Valid in msd_config.sampler and as msd_sample_steps' argument. */
 } msd_sampler_kind;
 
 typedef enum msd_schedule_kind {
@@ -338,6 +343,37 @@ int msd_sample_edit(msd_model* m, int batch, int rng, int per_row, const uint64_
                     const float* init_z_dev, const float* noise_dev, const float* known_dev, const int32_t* release,
                     int start_step, float* out_dev, void* stream);
 
+/* (appended to ABI 7) A step count and a sampler PER CALL: preview in 50 steps, render in 1000, on one handle.
+ *   num_steps  K: 0 = the handle's N = msd_config.num_steps; else K must DIVIDE N (MSD_ERR_INVALID_ARGUMENT otherwise, with
+ *              the divisors of N in the message)
+ *   sampler    -1 = the handle's; else MSD_SAMPLER_DDPM, MSD_SAMPLER_DDIM or MSD_SAMPLER_DPMPP_2M
+ * The call runs the scan of eval_scan (diffusion_utils.py:456-476) with sampler.schedule.num_steps = K: scan indices
+ * j = K - 1 .. 0, t = (j + 1) / K, s = j / K.  Everything else is the handle's configuration: train schedule, model output,
+ * CFG weight, clip, logvar type.  For the cosine sampler schedule that IS the reference configured with K steps.  For a
+ * LINEAR sampler schedule it is not: the reference would rebuild its beta grid with K knots, whereas this call evaluates
+ * the handle's N-knot schedule function at t = (j + 1) / K and j / K (the same noise levels as the N-step call, visited
+ * more coarsely).
+ *   How: the time (j + 1) / K is the time (r + 1) / N of row r = (j + 1) N / K - 1 of the handle's step-indexed tables --
+ *   the same rational, correctly rounded, hence the same float32 -- so the time embedding's FiLM tables are read at row
+ *   offset N / K - 1 with N / K times the row stride; no table is rebuilt.  The sampler's own K coefficient rows are
+ *   built on the first call with that K and kept.  The scan index in device memory is j: the noise of step j is Philox
+ *   sub-sequence 1 + j, Threefry fold_in(key, j), or row j of noise_dev -- the draws of a handle created with
+ *   num_steps = K.
+ *   noise_dev, when given, is [K][batch,T,n].
+ * MSD_SAMPLER_DPMPP_2M, with lambda = logsnr / 2 of the sampler schedule, h = lambda_s - lambda_t, r = h_prev / h:
+ *     D   = x0_t                                    on the first step of a call
+ *     D   = (1 + 1/(2r)) x0_t - (1/(2r)) x0_prev    afterwards
+ *     z_s = (sigma_s / sigma_t) z_t - alpha_s expm1(-h) D         scan index 0 returns x0_t
+ * x0_t = the step's pred_x0 after the model-output conversion, the CFG combine and the clip.  With D = x0_t this is
+ * ddim_step; no draw is made after init_z (noise_dev is ignored).  The history lives in a buffer the handle owns.
+ * Keying (per_row, seeds, stream_ids), the stream rules, the range flag and the final synchronisation are
+ * msd_sample_keep's.  Step graphs are cached by (step plan, keep, K, sampler), eight sets at the most; K % graph_steps
+ * steps run as single-step launches.  num_steps in {0, N} with sampler in {-1, msd_config.sampler} IS msd_sample_rng /
+ * msd_sample_rows: the same path, the same cached graphs, the same bits. */
+int msd_sample_steps(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
+                     const float* init_z_dev, const float* noise_dev, int num_steps, int sampler,
+                     float* out_dev, void* stream);
+
 /* Drop the captured hipGraph of the DDPM step; the next msd_sample captures it again. */
 int msd_reset_graph(msd_model* m);
 
@@ -449,6 +485,14 @@ int msd_op_sampler_step_release(const msd_config* cfg, int step_index, const flo
  *   cfg->precision merged back to float32; n % 4 == 0.  Uses cfg->{num_steps, sampler_schedule*, feature_*, precision}. */
 int msd_op_diffuse_to_step(const msd_config* cfg, int step_index, const float* mel_dev, const float* eps_dev,
                            float* z_out_dev, float* z_planes_out_dev, float* xk_out_dev, int64_t n, void* stream);
+
+/* (appended to ABI 7) One update of MSD_SAMPLER_DPMPP_2M (msd_sample_steps) at scan index step_index of cfg->num_steps:
+ * x0_prev_inout_dev float [n] holds the previous step's pred_x0 on entry (not read when first != 0: D = x0_t) and this
+ * step's on return.  Uses cfg->{num_steps, clip_x0, cfg_weight, model_output, *_schedule*}; cfg->sampler is not read.
+ *   out_uncond_dev may be NULL iff cfg_weight == 1; n % 4 == 0. */
+int msd_op_sampler_step_multistep(const msd_config* cfg, int step_index, const float* z_dev,
+                                  const float* out_cond_dev, const float* out_uncond_dev,
+                                  float* x0_prev_inout_dev, int first, float* z_out_dev, int64_t n, void* stream);
 
 /* x_out = x_in + a.w1 ; h_out = (RMSNorm(x_out; gamma) (.) (film_scale+1) + film_bias) . w2
  * (layers.py:632-666 + the Dense that follows).  folded=1: the decoder's folded-norm epilogues

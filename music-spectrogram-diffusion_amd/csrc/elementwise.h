@@ -526,6 +526,17 @@ void launch_diffuse_to_step(const DiffuseParams& dp, hipStream_t s);
 // flags[i] = flags[i] != 0: msd_sample_keep's "any non-zero flag = known throughout" as the release word 1
 void launch_normalize_flags(const int32_t* in, int32_t* out, int n, hipStream_t s);
 
+// The multistep form's arguments (msd_sample_steps with MSD_SAMPLER_DPMPP_2M; kernel and launch: multistep_tail.h).  A
+// struct of its own for the keep form's reason: the plain instances' argument block stays what it is.
+// Row i of the side table coef_ms: {sigma_s / sigma_t, -alpha_s expm1(-h), 1 / (2r), 0} (msd_api.hip build_multistep_rows)
+enum { kMsZ = 0, kMsD, kMsHist, kMsPad, kMsCount };
+struct SamplerMultistepParams : SamplerParams {
+  float* x0_prev = nullptr;        // [n] in/out: the previous step's pred_x0; not read at scan index first_step
+  const float* coef_ms = nullptr;  // [K][kMsCount]
+  int first_step = -1;             // the scan index the call starts at (no history there)
+};
+void launch_sampler_step(const SamplerMultistepParams& sp, hipStream_t s);
+
 // g[step][slot][k] = gamma[k] * (film_scale[step][slot][k] + 1): the column multiplier of a
 // FiLM-modulated RMSNorm, tabulated for every step (folded-norm GEMM epilogues, gemm_h16.h)
 __global__ void build_g_kernel(const float* film, const float* gamma, float* g, int n_steps, int slots,

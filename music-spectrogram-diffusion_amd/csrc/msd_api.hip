@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -183,6 +184,12 @@ struct msd_model {
   // keep call (outside stream capture) and owned by the handle, so the captured keep graphs hold stable addresses
   float* keep_xk = nullptr;
   int32_t* keep_flags = nullptr;
+  // msd_sample_steps: the sampler's coefficient rows for a call of K steps (K | N), built on the first such call and kept
+  // (host copy + device table; K == N is d_coef itself), and -- MSD_SAMPLER_DPMPP_2M -- the multistep side table of K and
+  // the previous step's pred_x0 [Bmax][T][n]; all allocated outside stream capture and owned by the handle
+  struct StepTables { std::vector<float> h_coef; float* coef = nullptr; float* coef_ms = nullptr; };
+  std::map<int, StepTables> step_tables;
+  float* x0_prev = nullptr;
   int* d_step = nullptr;       // [2]
   int* d_nkeys_self = nullptr; // [passes*Bmax] = T
   int* d_nkeys_cross = nullptr;// [n_cross][Bmax] valid keys per key region and song
@@ -204,7 +211,9 @@ struct msd_model {
   // constants and the plan: equal plans, same graph.
   // `keep`: the graphs of msd_sample_keep launch the sampler's keep form (other kernel, other arguments), so a set is
   // looked up by (plan, keep) and a plain call never replays a keep graph, nor the other way round.
-  struct StepGraphs { StepPlan plan; bool keep = false; hipGraphExec_t exec = nullptr, exec1 = nullptr; };
+  // `steps`, `sampler`: msd_sample_steps' graphs bake another view of the step-indexed tables and maybe another sampler
+  // kernel in; the handle's own (N, cfg.sampler) is the key every other entry point looks up, as it always did.
+  struct StepGraphs { StepPlan plan; bool keep = false; int steps = 0, sampler = 0; hipGraphExec_t exec = nullptr, exec1 = nullptr; };
   std::vector<StepGraphs> graphs;
   int graph_steps = 8;              // DDPM steps per graph launch (msd_config.graph_steps; 1 -> 4 -> 10: 1.2000 -> 1.1963 -> 1.1955 ms/step)
   bool prefetch = true;        // producers warm the next GEMM's weights (msd_config.weight_prefetch; default: by model size)
@@ -376,10 +385,25 @@ void declare_weights(msd_model* m) {
 const float* W(msd_model* m, const std::string& name) { return m->weights[m->windex.at(name)].dev; }
 
 // ---- launch helpers ---------------------------------------------------------
+// A sampling call's view of the handle's step-indexed tables (msd_sample_steps).  The scan index in device memory counts
+// the CALL's steps, j = K - 1 .. 0; step j of a K-step call has the time of row (j + 1) N / K - 1 of the handle's N-step
+// tables ((j + 1) / K and (r + 1) / N are the same rational, correctly rounded: the same float32), so every reader of a
+// step-indexed table gets base + off rows and mul times the row stride, and no table or GEMM changes.  The sampler's own
+// coefficients also hold s = j / K, which is no row of the N-step table: a K-row table of their own.
+// The default is the handle's own view: what every launch had before there was another.
+struct StepView {
+  int steps = 0;                    // K; 0 = the handle's N
+  int off = 0, mul = 1;             // N / K - 1, N / K
+  const float* coef = nullptr;      // [K][kCoefCount]; null = the handle's d_coef
+  const float* coef_ms = nullptr;   // [K][kMsCount], MSD_SAMPLER_DPMPP_2M only
+  int sampler = -1;                 // msd_sampler_kind; -1 = the handle's
+};
+
 struct Ctx {
   msd_model* m;
   hipStream_t s;
   hipError_t err = hipSuccess;
+  StepView v = StepView();
   void begin(int kc) {
     if (m->prof.on) (void)hipEventRecord(m->prof.e0, s);
     (void)kc;
@@ -906,10 +930,12 @@ struct Schedule {
 
 // One row of sampler coefficients per scan index (elementwise.h kCoef*): everything in
 // eval_step.body that depends only on i (diffusion_utils.py:408-452, 120-163, 205-233, 369-379).
-bool build_coef_rows(const msd_config& cfg, std::vector<float>* out, std::string* err) {
-  const int N = cfg.num_steps;
+// steps = K > 0: the rows of a K-step scan (msd_sample_steps), t = (i + 1) / K and s = i / K; the sampler schedule's FUNCTION
+// stays the handle's -- for `linear` that is the cfg.num_steps-knot grid, evaluated at those times.
+bool build_coef_rows(const msd_config& cfg, std::vector<float>* out, std::string* err, int steps = 0) {
+  const int N = steps > 0 ? steps : cfg.num_steps;
   Schedule samp, train;
-  if (!samp.init(cfg.sampler_schedule, cfg.sampler_schedule_start, cfg.sampler_schedule_stop, N, err)) return false;
+  if (!samp.init(cfg.sampler_schedule, cfg.sampler_schedule_start, cfg.sampler_schedule_stop, cfg.num_steps, err)) return false;
   if (!train.init(cfg.train_schedule, cfg.train_schedule_start, cfg.train_schedule_stop,
                   cfg.train_schedule_num_steps, err)) return false;
   if (cfg.model_output < MSD_OUTPUT_EPS || cfg.model_output > MSD_OUTPUT_V) { *err = "Unknown model_output"; return false; }
@@ -962,6 +988,27 @@ bool build_coef_rows(const msd_config& cfg, std::vector<float>* out, std::string
     c[kCoefMSigma] = std::sqrt(sigmoid(-lm));
   }
   return true;
+}
+
+// The multistep form's side table (multistep_tail.h, kMs*) from the K rows of build_coef_rows: with lambda = logsnr / 2 of the
+// SAMPLER schedule's float32 table values, h = lambda_s - lambda_t, r = h_prev / h (h_prev = h of row i + 1, the step
+// before): {sigma_s / sigma_t, -alpha_s expm1(-h), 1 / (2r)}, in double, rounded once.  Row K - 1 has no step before it: 0.
+void build_multistep_rows(const std::vector<float>& rows, std::vector<float>* out) {
+  const int K = (int)(rows.size() / kCoefCount);
+  out->assign((size_t)K * kMsCount, 0.f);
+  auto half_step = [&](int i) {
+    return 0.5 * ((double)rows[(size_t)i * kCoefCount + kCoefLogsnrS] - (double)rows[(size_t)i * kCoefCount + kCoefLogsnrT]);
+  };
+  for (int i = 0; i < K; ++i) {
+    const double lt = rows[(size_t)i * kCoefCount + kCoefLogsnrT], ls = rows[(size_t)i * kCoefCount + kCoefLogsnrS];
+    const double sigma_t = std::sqrt(1.0 / (1.0 + std::exp(lt))), sigma_s = std::sqrt(1.0 / (1.0 + std::exp(ls)));
+    const double alpha_s = std::sqrt(1.0 / (1.0 + std::exp(-ls)));
+    const double h = half_step(i), h_prev = i + 1 < K ? half_step(i + 1) : 0.0;
+    float* c = &(*out)[(size_t)i * kMsCount];
+    c[kMsZ] = (float)(sigma_s / sigma_t);
+    c[kMsD] = (float)(-alpha_s * std::expm1(-h));
+    c[kMsHist] = h_prev > 0.0 ? (float)(h / (2.0 * h_prev)) : 0.f;
+  }
 }
 
 // The part-way start's coefficients (diffuse_to_step_kernel): alpha = sqrt(sigmoid(logsnr_t)), sigma = sqrt(sigmoid(-logsnr_t))
@@ -1247,9 +1294,16 @@ inline StepPlan plan_cfg_step(const msd_model* m, int batch) {
 }
 
 // ---- the decoder's tables and buffers, named once -------------------------------------------------------------------
-inline Gain g_tab(const msd_model* m, int slot) { return {m->d_g + (size_t)slot * m->D, 2 * m->Ld * m->D}; }
-inline RowScale dec_row_scale(const msd_model* m, const float* bias = nullptr, int bias_step_stride = 0) {
-  return row_scale(m->ssq, m->D / kNarrowTile, m->d_step, bias, bias_step_stride);
+// (every step-indexed table of the decoder is read through c.v: row `off` first, `mul` rows per step -- StepView)
+inline Gain g_tab(const Ctx& c, int slot) {
+  const msd_model* m = c.m;
+  const int stride = 2 * m->Ld * m->D;
+  return {m->d_g + (size_t)slot * m->D + (size_t)c.v.off * stride, stride * c.v.mul};
+}
+inline RowScale dec_row_scale(const Ctx& c, const float* bias = nullptr, int bias_step_stride = 0) {
+  const msd_model* m = c.m;
+  return row_scale(m->ssq, m->D / kNarrowTile, m->d_step, bias ? bias + (size_t)c.v.off * bias_step_stride : nullptr,
+                   bias_step_stride * c.v.mul);
 }
 template <int NP>
 EpiResidualNorm<NP> dec_residual(const msd_model* m, Gain lo, Gain hi, int split_row) {
@@ -1273,7 +1327,7 @@ void self_attention_block(Ctx& c, const StepPlan& p, int l) {
   const int D = m->D, J = m->J, T = m->T, BT = p.batch * T;
   const int nq = m->n_cross * J;              // the modules' queries, stacked
   // fused q|k|v projection (network.py:181-189 via layers.py:262-264) on the folded-norm planes y
-  const EpiQKV<NP> eq = epi_qkv<NP>(m->qk, m->vt, 2 * J, T, J, dec_row_scale(m, m->d_bw_self + (size_t)l * 3 * J, m->Ld * 3 * J));
+  const EpiQKV<NP> eq = epi_qkv<NP>(m->qk, m->vt, 2 * J, T, J, dec_row_scale(c, m->d_bw_self + (size_t)l * 3 * J, m->Ld * 3 * J));
   const WeightPrefetch pf_wo = prefetch_of<NP>(m, w.self.wo, sb.fold ? D + nq : D, J);   // (folded: + W2, right behind Wo)
   if constexpr (NP == 2) {
     if (sb.fold) {   // + (x0 (.) gamma_cross) . Wq on the launch's idle CUs, left in float32 for the attention-out launch
@@ -1306,7 +1360,7 @@ void self_attention_block(Ctx& c, const StepPlan& p, int l) {
     }
     gemm<NP, TK_TALL>(c, KC_GEMM_ATTN_OUT, m->ao, J, w.self.wo, J, sb.Ms, D, J, epi, 0, pf_out);
   };
-  const Gain g_mlp = g_tab(m, 2 * l + 1);
+  const Gain g_mlp = g_tab(c, 2 * l + 1);
   EpiResidualNorm<NP> er = dec_residual<NP>(m, p.cond0 ? Gain{w.ln_cross, 0} : g_mlp, g_mlp, p.cond0 ? BT : 0);
   if (sb.dup) {   // rows [0, BT) computed once, written as both passes: y[r] for the cross-attention norm, y[r + BT] for the MLP norm
     EpiResidualNorm<NP, true> ed = residual_form<true, false>(er);
@@ -1330,7 +1384,7 @@ void cross_attention_block(Ctx& c, const StepPlan& p, int l) {
   // every module projects its queries from the SAME normed input (network.py:196-198), so all query
   // projections run before the first output projection rewrites y
   for (int e = 0; e < m->n_cross && !fold; ++e)
-    gemm<NP, TK_SQUARE>(c, KC_GEMM_CROSS_Q, m->y, D, w.wq_cross[e], D, BT, J, D, epi_out<EpiStoreH16, NP>(*cq[e], J, dec_row_scale(m)), 0,
+    gemm<NP, TK_SQUARE>(c, KC_GEMM_CROSS_Q, m->y, D, w.wq_cross[e], D, BT, J, D, epi_out<EpiStoreH16, NP>(*cq[e], J, dec_row_scale(c)), 0,
                         prefetch_of<NP>(m, w.wo_cross[e], D, J));
   const size_t loff = (size_t)l * m->Bmax * m->S_pad * J;
   for (int e = 0; e < m->n_cross; ++e) {
@@ -1347,7 +1401,7 @@ void cross_attention_block(Ctx& c, const StepPlan& p, int l) {
   // other; the last one also writes the folded-norm inputs of the MLP block
   for (int e = 0; e < m->n_cross; ++e) {
     const bool last_mod = e + 1 == m->n_cross;
-    const EpiResidualNorm<NP> ec = dec_residual<NP>(m, last_mod ? g_tab(m, 2 * l + 1) : Gain(), Gain(), BT);
+    const EpiResidualNorm<NP> ec = dec_residual<NP>(m, last_mod ? g_tab(c, 2 * l + 1) : Gain(), Gain(), BT);
     gemm<NP, TK_SQUARE>(c, KC_GEMM_CROSS_OUT, *ao[e], J, w.wo_cross[e], J, BT, D, J, ec, 0,
                         last_mod && p.mlp_in_on_cross_out ? mlp_in_weights<NP>(m, l) : WeightPrefetch());
   }
@@ -1361,9 +1415,9 @@ void mlp_block(Ctx& c, const StepPlan& p, int l) {
   const int D = m->D, J = m->J, F = m->F, BT = p.batch * m->T, M = p.P * BT;
   const bool last_layer = (l + 1 == m->Ld);
   gemm<NP, TK_MLP_IN>(c, KC_GEMM_MLP_IN, m->y, D, w.mlp.wi, D, M, 2 * F, D,
-                      epi_out<EpiGeglu, NP>(m->g, F, dec_row_scale(m, m->d_bw_mlp + (size_t)l * 2 * F, m->Ld * 2 * F)), 0,
+                      epi_out<EpiGeglu, NP>(m->g, F, dec_row_scale(c, m->d_bw_mlp + (size_t)l * 2 * F, m->Ld * 2 * F)), 0,
                       prefetch_of<NP>(m, w.mlp.wo, D, F));
-  const Gain g_next = last_layer ? Gain{m->dec_final_ln, 0} : g_tab(m, 2 * (l + 1));   // decoder_norm has no FiLM
+  const Gain g_next = last_layer ? Gain{m->dec_final_ln, 0} : g_tab(c, 2 * (l + 1));   // decoder_norm has no FiLM
   const EpiResidualNorm<NP> eo = dec_residual<NP>(m, g_next, g_next, 0);
   // S6: the next layer's folded query projection reads x (.) gamma_cross of the conditional rows from this epilogue
   // (and its stacked Wq sits right behind Wq|Wk|Wv: one prefetch target)
@@ -1397,7 +1451,7 @@ void final_projection(Ctx& c, const StepPlan& p) {
     hipLaunchKernelGGL(final_proj_f32_kernel<1>, dim3(m->ND / 32, M / 16), dim3(64 * kFinalProjWaves), 0, c.s, fp);
     c.end(KC_FINAL_PROJ);
   } else {
-    gemm<NP, TK_NARROW>(c, KC_FINAL_PROJ, m->y, D, m->w_out_p, D, M, m->ND, D, epi_store_f32(m->eps, m->ND, dec_row_scale(m)));
+    gemm<NP, TK_NARROW>(c, KC_FINAL_PROJ, m->y, D, m->w_out_p, D, M, m->ND, D, epi_store_f32(m->eps, m->ND, dec_row_scale(c)));
   }
 }
 
@@ -1421,7 +1475,8 @@ void in_proj(Ctx& c, const StepPlan& p, bool publish_step = false) {
   EpiInProj<NP> ei;
   ei.x = m->x; ei.ldx = m->D; ei.pos = m->dec_pos; ei.T = m->T; ei.pass_rows = BT; ei.passes = s0.Ps;
   out_pair<NP>(ei.y, m->y); ei.ssq = m->ssq; ei.tiles = m->D / kNarrowTile;
-  ei.g = m->d_g; ei.g_stride = 2 * m->Ld * m->D; ei.step_ptr = m->d_step;
+  const Gain g0 = g_tab(c, 0);
+  ei.g = g0.g; ei.g_stride = g0.step_stride; ei.step_ptr = m->d_step;
   ei.step_copy = publish_step ? m->d_step : nullptr;
   if (s0.fold) { out_pair<NP>(ei.y2, m->xg); ei.g2 = m->dec[0].ln_cross; }
   gemm<NP, TK_NARROW>(c, KC_IN_PROJ, m->zp, m->ND, m->w_in_p, m->ND, BT, m->D, m->ND, ei, 0,
@@ -1439,22 +1494,30 @@ void split_z(msd_model* m, int64_t n, hipStream_t s) { split(m->z, m->zp, n, s, 
 
 // one DDPM step of the CFG sampler: the decoder on plan_cfg_step's plan, then the sampler update
 // keep: the sampler's keep form on the handle's known-frame buffers (msd_sample_keep)
+// c.v: the call's view of the step-indexed tables, its coefficient rows and its sampler (msd_sample_steps)
 void enqueue_step(Ctx& c, const StepPlan& p, bool keep = false) {
   msd_model* m = c.m;
   decoder_eval(c, p, /*publish_step=*/true);
+  const int sampler = c.v.sampler < 0 ? m->cfg.sampler : c.v.sampler;
   SamplerKeepParams sp;
-  sp.eps = m->eps; sp.z = m->z; sp.noise_slot = m->d_noise_slot; sp.coef = m->d_coef; sp.rng_key = m->d_rng_key;
+  sp.eps = m->eps; sp.z = m->z; sp.noise_slot = m->d_noise_slot; sp.coef = c.v.coef ? c.v.coef : m->d_coef; sp.rng_key = m->d_rng_key;
   sp.step_ptr = m->d_step; sp.n = p.batch * m->T * m->ND; sp.passes = p.P;
   if (m->T * m->ND % kRngRowBlock == 0) sp.row_blocks = m->T * m->ND / kRngRowBlock;   // (else: table row 0 only, msd_sample_rows refuses)
   sp.cond_wt = m->cfg.cfg_weight; sp.clip_x0 = m->cfg.clip_x0;
-  sp.ddim = m->cfg.sampler == MSD_SAMPLER_DDIM;
+  sp.ddim = sampler == MSD_SAMPLER_DDIM;
   sp.model_output = m->cfg.model_output;
   sp.z_hi = m->zp.p[0];
   sp.z_lo = m->NP == 2 ? m->zp.p[1] : nullptr;
   sp.sat = m->d_sat; sp.sat_tag = (unsigned)KC_SAMPLER + 1u;
   c.begin(KC_SAMPLER);
   sp.step_from_slot1 = 1;
-  if (keep) {
+  if (sampler == MSD_SAMPLER_DPMPP_2M) {   // (never with keep: sample_body refuses the pair)
+    SamplerMultistepParams mp;
+    static_cast<SamplerParams&>(mp) = sp;
+    mp.x0_prev = m->x0_prev; mp.coef_ms = c.v.coef_ms;
+    mp.first_step = (c.v.steps ? c.v.steps : m->N) - 1;
+    launch_sampler_step(mp, c.s);
+  } else if (keep) {
     sp.xk = m->keep_xk; sp.keep = m->keep_flags; sp.n_dims = m->ND;
     launch_sampler_step(sp, c.s);
   } else {
@@ -1509,7 +1572,8 @@ int msd_create(const msd_config* cfg, msd_model** out) {
       return MSD_ERR_UNSUPPORTED;
     }
   }
-  if (cfg->sampler != MSD_SAMPLER_DDPM && cfg->sampler != MSD_SAMPLER_DDIM) return bad("Unknown sampler type");
+  if (cfg->sampler != MSD_SAMPLER_DDPM && cfg->sampler != MSD_SAMPLER_DDIM && cfg->sampler != MSD_SAMPLER_DPMPP_2M)
+    return bad("Unknown sampler type");
   if (cfg->emb_dim % 64 || cfg->emb_dim > 1024 || cfg->emb_dim < 64) return bad("emb_dim must be a multiple of 64 in [64, 1024]");
   if (cfg->mlp_dim % 64) return bad("mlp_dim must be a multiple of 64");
   if (cfg->targets_length % 64 || cfg->targets_length <= 0) return bad("targets length must be a multiple of 64");
@@ -1908,7 +1972,52 @@ struct KeepFrames {
 };
 
 static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys, const float* init_z_dev,
-                       const float* noise_dev, float* out_dev, void* stream, const KeepFrames* keep = nullptr);
+                       const float* noise_dev, float* out_dev, void* stream, const KeepFrames* keep = nullptr,
+                       int num_steps = 0, int sampler = -1);
+
+// "1, 2, 4, ..." -- the step counts msd_sample_steps takes on a handle of n steps
+static std::string divisors_of(int n) {
+  std::string out;
+  for (int k = 1; k <= n; ++k)
+    if (n % k == 0) out += (out.empty() ? "" : ", ") + std::to_string(k);
+  return out;
+}
+
+// The view of a call of K steps with `sampler` (both already normalised: K | N, a known kind), with the tables it needs
+// built on first use: the K-row coefficient table (K == N: the handle's own), the multistep side table, x0_prev.  Runs
+// outside stream capture; every allocation is the handle's.
+static int make_step_view(msd_model* m, int K, int sampler, StepView* v) {
+  const int N = m->N;
+  *v = StepView();
+  v->steps = K; v->mul = N / K; v->off = N / K - 1; v->sampler = sampler;
+  // (the kernels index base + step * stride in 64 bits; the stride itself travels as an int)
+  const int64_t widest = std::max<int64_t>(std::max<int64_t>(2 * m->Ld * m->D, (int64_t)m->Ld * 3 * m->J), (int64_t)m->Ld * 2 * m->F);
+  if (widest * v->mul > 0x7FFFFFFFll)
+    return fail(m, MSD_ERR_UNSUPPORTED, "a stride of %d table rows does not fit the GEMM epilogues' 32-bit row stride", v->mul);
+  if (K == N && sampler != MSD_SAMPLER_DPMPP_2M) return MSD_OK;   // the handle's own view and tables
+  msd_model::StepTables& t = m->step_tables[K];
+  if (K == N) {
+    t.coef = m->d_coef;
+  } else if (!t.coef) {
+    std::string why;
+    if (!build_coef_rows(m->cfg, &t.h_coef, &why, K)) return fail(m, MSD_ERR_INVALID_ARGUMENT, "%s", why.c_str());
+    if (int rc = dalloc(m, &t.coef, t.h_coef.size())) return rc;
+    HIP_TRY(m, copy_sync(m, t.coef, t.h_coef.data(), t.h_coef.size() * sizeof(float), hipMemcpyHostToDevice));
+  }
+  v->coef = t.coef;
+  if (sampler == MSD_SAMPLER_DPMPP_2M) {
+    if (!t.coef_ms) {
+      std::vector<float> ms;
+      build_multistep_rows(K == N ? m->h_coef : t.h_coef, &ms);
+      if (int rc = dalloc(m, &t.coef_ms, ms.size())) return rc;
+      HIP_TRY(m, copy_sync(m, t.coef_ms, ms.data(), ms.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    v->coef_ms = t.coef_ms;
+    if (!m->x0_prev)
+      if (int rc = dalloc(m, &m->x0_prev, (size_t)m->Bmax * m->T * m->ND)) return rc;
+  }
+  return MSD_OK;
+}
 
 int msd_sample(msd_model* m, int batch, uint64_t seed, uint64_t stream_id, const float* init_z_dev,
                const float* noise_dev, float* out_dev, void* stream) {
@@ -1973,10 +2082,32 @@ int msd_sample_edit(msd_model* m, int batch, int rng, int per_row, const uint64_
   return sample_body(m, batch, rng, keys, init_z_dev, noise_dev, out_dev, stream, &keep);
 }
 
+int msd_sample_steps(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
+                     const float* init_z_dev, const float* noise_dev, int num_steps, int sampler, float* out_dev,
+                     void* stream) {
+  if (!m) return MSD_ERR_INVALID_ARGUMENT;
+  if (!seeds) return fail(m, MSD_ERR_INVALID_ARGUMENT, "seeds is null");
+  if (num_steps < 0 || (num_steps > 0 && m->N % num_steps))
+    return fail(m, MSD_ERR_INVALID_ARGUMENT, "num_steps %d does not divide the handle's %d steps; it takes 0 (= %d) or one of %s",
+                num_steps, m->N, m->N, divisors_of(m->N).c_str());
+  if (sampler != -1 && sampler != MSD_SAMPLER_DDPM && sampler != MSD_SAMPLER_DDIM && sampler != MSD_SAMPLER_DPMPP_2M)
+    return fail(m, MSD_ERR_INVALID_ARGUMENT, "Unknown sampler type: %d", sampler);
+  SampleKeys keys;
+  if (per_row) { keys.seeds = seeds; keys.stream_ids = stream_ids; }
+  else { keys.seed = seeds[0]; keys.stream_id = stream_ids ? stream_ids[0] : 0; }
+  return sample_body(m, batch, rng, keys, init_z_dev, noise_dev, out_dev, stream, nullptr, num_steps, sampler);
+}
+
 static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys, const float* init_z_dev,
-                       const float* noise_dev, float* out_dev, void* stream, const KeepFrames* keep) {
+                       const float* noise_dev, float* out_dev, void* stream, const KeepFrames* keep, int num_steps,
+                       int sampler) {
   if (!m) return MSD_ERR_INVALID_ARGUMENT;
   if (rng != MSD_RNG_PHILOX && rng != MSD_RNG_THREEFRY) return fail(m, MSD_ERR_INVALID_ARGUMENT, "unknown rng %d", rng);
+  // the call's step count and sampler, normalised: the handle's own are (N, cfg.sampler), however they were named
+  const int K = num_steps > 0 ? num_steps : m->N;
+  const int kind = sampler < 0 ? m->cfg.sampler : sampler;
+  if (keep && (K != m->N || kind == MSD_SAMPLER_DPMPP_2M))
+    return fail(m, MSD_ERR_UNSUPPORTED, "known frames run on the handle's own step count with ddpm or ddim (no multistep history across a release)");
   if (!m->encoded) return fail(m, MSD_ERR_BAD_STATE, "msd_encode has not run");
   if (batch != m->encoded_batch) return fail(m, MSD_ERR_INVALID_ARGUMENT, "batch %d != encoded batch %d", batch, m->encoded_batch);
   if (!out_dev) return fail(m, MSD_ERR_INVALID_ARGUMENT, "out is null");
@@ -1991,6 +2122,8 @@ static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys,
     if (int rc = dalloc(m, &m->keep_xk, (size_t)m->Bmax * row_n)) return rc;
   if (keep && !m->keep_flags)
     if (int rc = dalloc(m, &m->keep_flags, (size_t)m->Bmax * m->T)) return rc;
+  StepView view;
+  if (int rc = make_step_view(m, K, kind, &view)) return rc;
   hipStream_t s = static_cast<hipStream_t>(stream);
   const bool null_stream = (s == nullptr);
   if (null_stream) {
@@ -2002,8 +2135,8 @@ static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys,
     s = m->own_stream;
   }
   const int64_t n = (int64_t)batch * m->T * m->ND;
-  // the scan index the call starts at: N - 1 but for msd_sample_edit
-  const int start_step = keep && keep->release ? keep->start_step : m->N - 1;
+  // the scan index the call starts at: K - 1 (N - 1 but for msd_sample_steps), or msd_sample_edit's
+  const int start_step = keep && keep->release ? keep->start_step : K - 1;
   if (start_step < 0) {   // (msd_sample_edit: every frame known throughout) no step runs: the caller's mel
     HIP_TRY(m, hipMemcpyAsync(out_dev, keep->known_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
     HIP_TRY(m, hipStreamSynchronize(s));
@@ -2023,7 +2156,7 @@ static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys,
       if (rc) return fail(m, rc, "init_z fill failed");
     }
   }
-  if (start_step == m->N - 1) {
+  if (start_step == K - 1) {
     split_z(m, n, s);
     if (keep) {
       // the known mel enters the chain as the context does: scale_features(clip=True); init_z and the draws are untouched
@@ -2077,6 +2210,7 @@ static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys,
     hipGraph_t graph = nullptr;
     HIP_TRY(m, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
     Ctx c{m, s};
+    c.v = view;
     for (int k = 0; k < steps; ++k) enqueue_step(c, plan, keep != nullptr);
     hipError_t ce = hipStreamEndCapture(s, &graph);
     if (ce != hipSuccess || c.err != hipSuccess) {
@@ -2091,15 +2225,16 @@ static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys,
   // the graphs captured with this plan (msd_model::StepGraphs)
   msd_model::StepGraphs* g = nullptr;
   for (auto& e : m->graphs)
-    if (e.keep == (keep != nullptr) && memcmp(&e.plan, &plan, sizeof(plan)) == 0) g = &e;
+    if (e.keep == (keep != nullptr) && e.steps == K && e.sampler == kind && memcmp(&e.plan, &plan, sizeof(plan)) == 0) g = &e;
   if (!g) {
     if (m->graphs.size() >= 8) (void)msd_reset_graph(m);   // (a handle that cycles through more shapes than that re-captures)
     msd_model::StepGraphs ng;
     ng.plan = plan;
     ng.keep = keep != nullptr;
+    ng.steps = K; ng.sampler = kind;
     int rc = capture(m->graph_steps, &ng.exec);
     if (rc) return rc;
-    if (m->graph_steps > 1 && m->N % m->graph_steps) {
+    if (m->graph_steps > 1 && K % m->graph_steps) {
       rc = capture(1, &ng.exec1);
       if (rc) { (void)hipGraphExecDestroy(ng.exec); return rc; }
     }
@@ -2222,6 +2357,8 @@ int msd_profile_steps(msd_model* m, int batch, int n_steps, const char* const** 
   if (n_steps < 1 || n_steps > m->N) return fail(m, MSD_ERR_INVALID_ARGUMENT, "n_steps outside [1, N]");
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int64_t n = (int64_t)batch * m->T * m->ND;
+  StepView view;   // (a handle whose own sampler is the multistep form needs its side table and history buffer)
+  if (int rcv = make_step_view(m, m->N, m->cfg.sampler, &view)) return rcv;
   if (int rc0 = arm_range(m, s)) return rc0;
   int rc = msd_fill_normal(1, 0, 0, m->z, n, s);
   if (rc) return rc;
@@ -2237,6 +2374,7 @@ int msd_profile_steps(msd_model* m, int batch, int n_steps, const char* const** 
   for (int k = 0; k < KC_COUNT; ++k) { m->prof.ms[k] = 0; m->prof.launches[k] = 0; }
   m->prof.on = true;
   Ctx c{m, s};
+  c.v = view;
   const StepPlan plan = plan_cfg_step(m, batch);
   for (int i = 0; i < n_steps; ++i) enqueue_step(c, plan);
   m->prof.on = false;
@@ -2396,3 +2534,4 @@ int msd_vocoder_decode(msd_vocoder* v, int batch, int n_frames, const float* log
 }  // extern "C"
 
 #include "keep_frames_tail.h"   // last on purpose: see the file
+#include "multistep_tail.h"     // ... and behind it, for the same reason

@@ -1,5 +1,5 @@
 // The msd_op_* entry points: the library's building blocks one at a time, for the unit tests (tests/test_gpu_ops.py,
-// test_gpu_fused_ops.py, test_gpu_gemm_sites.py, test_gpu_keep_frames.py, test_gpu_edit_strength.py, test_gpu_threefry.py).  Host code only, and no
+// test_gpu_fused_ops.py, test_gpu_gemm_sites.py, test_gpu_keep_frames.py, test_gpu_edit_strength.py, test_gpu_few_steps.py, test_gpu_threefry.py).  Host code only, and no
 // part of the product's paths; the file belongs to msd_api.hip alone, which includes it behind its own entry points and
 // in front of the vocoder's.
 // Every GEMM here runs through the product's dispatch (gemm / gemm_on on a site's TileTable), so its tile is an entry of
@@ -675,6 +675,45 @@ int msd_op_sampler_step_release(const msd_config* cfg, int step_index, const flo
     return MSD_ERR_INVALID_ARGUMENT;
   return op_sampler_step(cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, noise_dev, known_scaled_dev, release_dev,
                          n_dims, z_out_dev, n, stream);
+}
+
+int msd_op_sampler_step_multistep(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
+                                  const float* out_uncond_dev, float* x0_prev_inout_dev, int first, float* z_out_dev,
+                                  int64_t n, void* stream) {
+  if (!cfg || cfg->struct_size != (int32_t)sizeof(msd_config) || !z_dev || !out_cond_dev || !x0_prev_inout_dev || !z_out_dev ||
+      n <= 0 || n % 4 || n > 0x7FFFFFFFll || step_index < 0 || step_index >= cfg->num_steps)
+    return MSD_ERR_INVALID_ARGUMENT;
+  const int passes = cfg->cfg_weight != 1.0f ? 2 : 1;
+  if (passes == 2 && !out_uncond_dev) return MSD_ERR_INVALID_ARGUMENT;
+  std::vector<float> rows, ms;
+  std::string why;
+  if (!build_coef_rows(*cfg, &rows, &why)) return MSD_ERR_INVALID_ARGUMENT;
+  build_multistep_rows(rows, &ms);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  OpKit kit(s, 1);
+  float* coef = kit.get<float>(rows.size());
+  float* coef_ms = kit.get<float>(ms.size());
+  float* eps = kit.get<float>((size_t)passes * n);
+  int* step = kit.get<int>(2);
+  if (!coef || !coef_ms || !eps || !step) return MSD_ERR_HIP;
+  const int st[2] = {step_index, step_index};
+  if (hipMemcpyAsync(coef, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(coef_ms, ms.data(), ms.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(eps, out_cond_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+      (passes == 2 && hipMemcpyAsync(eps + n, out_uncond_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) ||
+      hipMemcpyAsync(z_out_dev, z_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(step, st, sizeof(st), hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return MSD_ERR_HIP;
+  SamplerMultistepParams sp;   // (noise_slot / rng_key stay null: the form makes no draw and reads neither)
+  sp.eps = eps; sp.z = z_out_dev; sp.noise_slot = nullptr; sp.coef = coef; sp.step_ptr = step;
+  sp.n = (int)n; sp.passes = passes; sp.cond_wt = cfg->cfg_weight; sp.clip_x0 = cfg->clip_x0;
+  sp.ddim = 0; sp.model_output = cfg->model_output;
+  sp.z_hi = nullptr; sp.z_lo = nullptr; sp.step_from_slot1 = 1;
+  sp.x0_prev = x0_prev_inout_dev; sp.coef_ms = coef_ms; sp.first_step = first ? step_index : -1;
+  launch_sampler_step(sp, s);
+  if (hipGetLastError() != hipSuccess) return MSD_ERR_HIP;
+  return hipStreamSynchronize(s) == hipSuccess ? MSD_OK : MSD_ERR_HIP;
 }
 
 int msd_op_diffuse_to_step(const msd_config* cfg, int step_index, const float* mel_dev, const float* eps_dev,

@@ -29,6 +29,8 @@ MSD_PREC_BF16X3 = 3   # hi + lo bfloat16 planes                  } build answers
 ABI_VERSION = 7        # MSD_AMD_ABI_VERSION of include/msd_amd.h (tests/test_abi.py)
 MSD_SAMPLER_DDPM = 0
 MSD_SAMPLER_DDIM = 1
+MSD_SAMPLER_DPMPP_2M = 2   # (appended to ABI 7) DPM-Solver++(2M): deterministic, second order (msd_sample_steps)
+SAMPLERS = {'ddpm': MSD_SAMPLER_DDPM, 'ddim': MSD_SAMPLER_DDIM, 'dpmpp_2m': MSD_SAMPLER_DPMPP_2M}
 MSD_RNG_PHILOX = 0    # the library's own generator (msd_fill_normal)
 MSD_RNG_THREEFRY = 1  # the reference's: jax.random's Threefry draws for PRNGKey(seed), made on the device (ABI 7)
 RNGS = {'philox': MSD_RNG_PHILOX, 'threefry': MSD_RNG_THREEFRY}
@@ -67,7 +69,27 @@ EXPORTED_SYMBOLS = (
     # (appended to ABI 7) one GEMM launch site at a time
     'msd_op_gemm_site', 'msd_op_gemm_site_tiles', 'msd_op_gemm_site_name',
     # (appended to ABI 7) edit strength: per-frame release words and a part-way start of the sampler
-    'msd_sample_edit', 'msd_op_sampler_step_release', 'msd_op_diffuse_to_step')
+    'msd_sample_edit', 'msd_op_sampler_step_release', 'msd_op_diffuse_to_step',
+    # (appended to ABI 7) a step count and a sampler per call; the second-order multistep sampler
+    'msd_sample_steps', 'msd_op_sampler_step_multistep')
+
+
+def divisors(n: int):
+  return [k for k in range(1, n + 1) if n % k == 0]
+
+
+def plan_steps(num_steps: int, steps: int):
+  """A K-step call on a handle of N = num_steps steps as a view of the handle's step-indexed tables: (row_offset, stride)
+  = (N / K - 1, N / K) -- step j of the call has the time of table row (j + 1) N / K - 1, because (j + 1) / K and
+  (r + 1) / N are the same rational, correctly rounded.  K must be a positive integer that divides N: anything else
+  (0, negatives, bools, non-integers, non-divisors) is a ValueError that names the divisors of N.  No device needed."""
+  if isinstance(num_steps, bool) or not isinstance(num_steps, (int, np.integer)) or num_steps < 1:
+    raise ValueError('num_steps must be a positive integer: %r' % (num_steps,))
+  n = int(num_steps)
+  if isinstance(steps, (bool, np.bool_)) or not isinstance(steps, (int, np.integer)) or steps < 1 or n % int(steps):
+    raise ValueError('steps must divide the model\'s %d steps: got %r; the divisors are %s'
+                     % (n, steps, ', '.join(str(k) for k in divisors(n))))
+  return n // int(steps) - 1, n // int(steps)
 
 
 class NativeLibraryError(RuntimeError):
@@ -203,6 +225,9 @@ def load(planes: str = 'f16') -> ctypes.CDLL:
     lib.msd_sample_edit.argtypes = [vp, i32, i32, i32, c.POINTER(u64), c.POINTER(u64), vp, vp, vp, vp, i32, vp, vp]
     lib.msd_op_sampler_step_release.argtypes = [c.POINTER(MsdConfig), i32, vp, vp, vp, vp, vp, vp, i32, vp, i64, vp]
     lib.msd_op_diffuse_to_step.argtypes = [c.POINTER(MsdConfig), i32, vp, vp, vp, vp, vp, i64, vp]
+  if 'msd_sample_steps' in present:   # (appended to ABI 7)
+    lib.msd_sample_steps.argtypes = [vp, i32, i32, i32, c.POINTER(u64), c.POINTER(u64), vp, vp, i32, i32, vp, vp]
+    lib.msd_op_sampler_step_multistep.argtypes = [c.POINTER(MsdConfig), i32, vp, vp, vp, vp, i32, vp, i64, vp]
   if 'msd_fill_normal_threefry' in present:
     lib.msd_fill_normal_threefry.argtypes = [u64, i64, vp, i64, vp]
   if 'msd_op_threefry' in present:
@@ -350,7 +375,7 @@ class NativeModel:
 
   def sample(self, batch: int, out, seed: int = 0, stream_id: int = 0, init_z=None,
              noise=None, stream: int = 0, rng: str = 'philox', keep=None, keep_mask=None, release=None,
-             start_step: Optional[int] = None):
+             start_step: Optional[int] = None, steps: Optional[int] = None, sampler: Optional[str] = None):
     """rng: the generator of the draws that are not given -- 'philox' (the library's own, keyed by seed and stream_id)
     or 'threefry' (the reference's jax.random draws for PRNGKey(seed), made on the device; stream_id is ignored).
 
@@ -365,9 +390,29 @@ class NativeModel:
     keep with release (int32 NumPy [batch, T], the frames' release words) and start_step instead of keep_mask: the edit
     form (msd_sample_edit) -- a frame with word v >= 1 is known at scan indices >= v - 1 and free below, 0 = free
     throughout; the scan starts at start_step from the known mel diffused to that step (None = num_steps - 1: from
-    init_z, as ever)."""
+    init_z, as ever).
+
+    steps (K, a divisor of the handle's num_steps; None = all of them) / sampler ('ddpm', 'ddim', 'dpmpp_2m'; None = the
+    handle's): a step count and a sampler for THIS call (msd_sample_steps); noise is then [K, batch, T, n].  Not with
+    keep / release."""
     if rng not in RNGS:
       raise ValueError('rng must be one of %s: %r' % (sorted(RNGS), rng))
+    if steps is not None or sampler is not None:
+      if keep is not None or keep_mask is not None or release is not None or start_step is not None:
+        raise ValueError('steps / sampler cannot be combined with keep / keep_mask / release / start_step')
+      if sampler is not None and sampler not in SAMPLERS:
+        raise ValueError('sampler must be one of %s: %r' % (sorted(SAMPLERS), sampler))
+      k = 0
+      if steps is not None:
+        plan_steps(self.cfg.num_steps, steps)   # (its checks: a ValueError that names the divisors)
+        k = int(steps)
+      per_row = not (np.isscalar(seed) and np.isscalar(stream_id))
+      seeds, stream_ids = row_keys(batch if per_row else 1, seed, stream_id)
+      rc = self.lib.msd_sample_steps(self.handle, batch, RNGS[rng], int(per_row), (ctypes.c_uint64 * len(seeds))(*seeds),
+                                     (ctypes.c_uint64 * len(seeds))(*stream_ids), _ptr(init_z), _ptr(noise), k,
+                                     -1 if sampler is None else SAMPLERS[sampler], _ptr(out), stream)
+      _check(self.lib, self.handle, rc, 'msd_sample_steps')
+      return
     if release is not None:
       if keep is None or keep_mask is not None:
         raise ValueError('release goes with keep and without keep_mask')
@@ -589,6 +634,19 @@ def op_sampler_step_release(cfg: MsdConfig, step_index: int, z, out_cond, out_un
   _op_check(lib.msd_op_sampler_step_release(ctypes.byref(cfg), step_index, _ptr(z), _ptr(out_cond), _ptr(out_uncond),
                                             _ptr(noise), _ptr(known_scaled), _ptr(release), n_dims, _ptr(z_out), z.numel(),
                                             stream), 'msd_op_sampler_step_release')
+
+
+def op_sampler_step_multistep(cfg: MsdConfig, step_index: int, z, out_cond, out_uncond, x0_prev, first: bool, z_out,
+                              stream: int = 0):
+  """One update of the 'dpmpp_2m' sampler (msd_op_sampler_step_multistep): x0_prev float32 device tensor of z's element
+  count, the previous step's pred_x0 on entry (not read when `first`) and this step's on return."""
+  lib = load()
+  cfg.struct_size = ABI_STRUCT_SIZES[getattr(lib, '_msd_abi', None) or ABI_VERSION]
+  if x0_prev.numel() != z.numel() or z_out.numel() != z.numel():
+    raise ValueError('x0_prev and z_out must have z\'s element count')
+  _op_check(lib.msd_op_sampler_step_multistep(ctypes.byref(cfg), step_index, _ptr(z), _ptr(out_cond), _ptr(out_uncond),
+                                              _ptr(x0_prev), int(bool(first)), _ptr(z_out), z.numel(), stream),
+            'msd_op_sampler_step_multistep')
 
 
 def op_diffuse_to_step(cfg: MsdConfig, step_index: int, mel, eps, z_out, z_planes_out, xk_out, stream: int = 0):

@@ -4,7 +4,7 @@ beam/evaluation.py:161-223) on the MI355X path.
 
   python -m msd_amd.synthesize song.mid --checkpoint /path/to/base_with_context/checkpoint_500000 \\
       --out song_mel.npy [--preset base_with_context] [--gin-file train.gin --gin-bindings ...]
-      [--seed 0] [--rng threefry|jax] [--num-steps 1000] [--dry-run]
+      [--seed 0] [--rng threefry|jax] [--num-steps 1000] [--steps K] [--sampler ddpm|ddim|dpmpp_2m] [--dry-run]
       [--batch-segments B [--always-mask-context]]
       [--wav song.wav [--vocoder-iters 32]] [--context-audio earlier.wav]
       [--regenerate START:STOP [--blend FRAMES] (--edit-mel old_mel.npy | --edit-audio old.wav)]
@@ -29,6 +29,10 @@ of the scan only, less the farther they lie from the region (InferenceModel.rege
 frames at the matching noise level and runs round(STRENGTH * steps) steps -- 1 is a fresh rendering, 0 the old one
 (InferenceModel.vary).  An SDEdit-style restart: the network was never trained on known frames.
 
+--steps K renders every segment in K steps (K divides --num-steps; the model keeps its num-steps tables, so the same
+process could render in all of them next) and --sampler names the sampler of the run: dpmpp_2m is the second-order
+DPM-Solver++(2M), deterministic after the initial draw.  Not with --regenerate / --vary.
+
 --dry-run tokenises only (no GPU): prints the segment / token statistics the synthesis would see, and with --regenerate
 the plan: the segments touched and the frames each keeps."""
 from __future__ import annotations
@@ -49,6 +53,10 @@ def main(argv=None) -> int:
   ap.add_argument('--gin-file', default=None, help='training gin file (instead of --preset)')
   ap.add_argument('--gin-bindings', nargs='*', default=())
   ap.add_argument('--num-steps', type=int, default=1000)
+  ap.add_argument('--steps', type=int, default=None, metavar='K',
+                  help='sampling steps of this run; must divide the model\'s step count (--num-steps)')
+  ap.add_argument('--sampler', choices=['ddpm', 'ddim', 'dpmpp_2m'], default=None,
+                  help="the sampler of this run (default: the configuration's); 'dpmpp_2m' = DPM-Solver++(2M), second order")
   ap.add_argument('--cfg-weight', type=float, default=5.0)
   ap.add_argument('--seed', type=int, default=0)
   ap.add_argument('--rng', choices=['philox', 'threefry', 'jax'], default='philox',
@@ -99,6 +107,8 @@ def main(argv=None) -> int:
     ap.error('--vary wants a strength in [0, 1]: %r' % (args.vary,))
   if args.blend < 0 or (args.blend and not args.regenerate):
     ap.error('--blend FRAMES (>= 0) goes with --regenerate')
+  if (args.steps is not None or args.sampler) and (args.regenerate or args.vary is not None):
+    ap.error('--steps / --sampler do not go with --regenerate / --vary (few-step edits are not built)')
 
   import msd_amd
   from msd_amd.frontend import midi_io, tokenizer
@@ -106,6 +116,16 @@ def main(argv=None) -> int:
     spec = msd_amd.parse_training_gin_file(args.gin_file, list(args.gin_bindings))
   else:
     spec = msd_amd.config.preset(args.preset, num_steps=args.num_steps, cfg_weight=args.cfg_weight)
+  few = {}
+  if args.steps is not None:
+    from msd_amd import native
+    try:
+      native.plan_steps(spec.diffusion.sampler.schedule.num_steps, args.steps)
+    except ValueError as e:
+      ap.error('--steps: %s' % e)
+    few['steps'] = args.steps
+  if args.sampler:
+    few['sampler'] = args.sampler
   ns = midi_io.midi_file_to_note_sequence(args.midi)
   cfg = tokenizer.FrontendConfig.from_spec(spec)
   t0 = time.perf_counter()
@@ -174,7 +194,7 @@ def main(argv=None) -> int:
     init_context = context_from_audio(model, vocoder.read_wav(args.context_audio, model.audio_codec.sample_rate))
   mel, timing = model.predict_sequence(segments, seed=args.seed, rng=args.rng, return_timing=True, init_context=init_context,
                                        return_torch=True, always_mask_context=args.always_mask_context,
-                                       batch_segments=args.batch_segments)
+                                       batch_segments=args.batch_segments, **few)
   mel_dev, mel = mel, mel.cpu().numpy()
   frames = int(np.ceil(ns.total_time * cfg.frame_rate))
   mel = mel[0, :max(frames, 1)]
