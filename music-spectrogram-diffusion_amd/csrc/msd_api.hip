@@ -121,8 +121,7 @@ struct StepPlan {
   bool cross_qb4[2];
   bool cond0, mlp_in_on_cross_out;
 };
-// Captured step graphs are looked up by comparing plans bytewise (msd_sample_rng)
-static_assert(std::has_unique_object_representations<StepPlan>::value, "StepPlan must not have padding bytes: group its bools in fours");
+// (captured step graphs are looked up by comparing plans bytewise, msd_model::GraphKey: no padding bytes -- group its bools in fours)
 
 
 struct Profiler {
@@ -209,11 +208,13 @@ struct msd_model {
   // plan of a CFG step is a function of the handle's constants, the batch and the key counts msd_encode saw (they choose
   // the cross-attention's key splits, cross_split), and the launch sequence of a step is a function of the handle's
   // constants and the plan: equal plans, same graph.
-  // `keep`: the graphs of msd_sample_keep launch the sampler's keep form (other kernel, other arguments), so a set is
-  // looked up by (plan, keep) and a plain call never replays a keep graph, nor the other way round.
+  // `keep`: the graphs of msd_sample_keep launch the sampler's keep form (other kernel, other arguments), so a plain call
+  // never replays a keep graph, nor the other way round.
   // `steps`, `sampler`: msd_sample_steps' graphs bake another view of the step-indexed tables and maybe another sampler
   // kernel in; the handle's own (N, cfg.sampler) is the key every other entry point looks up, as it always did.
-  struct StepGraphs { StepPlan plan; bool keep = false; int steps = 0, sampler = 0; hipGraphExec_t exec = nullptr, exec1 = nullptr; };
+  struct GraphKey { StepPlan plan; int steps, sampler, keep; };   // ONE key, compared bytewise (find_graphs)
+  static_assert(std::has_unique_object_representations<GraphKey>::value, "GraphKey (StepPlan included) must not have padding bytes");
+  struct StepGraphs { GraphKey key; hipGraphExec_t exec = nullptr, exec1 = nullptr; };
   std::vector<StepGraphs> graphs;
   int graph_steps = 8;              // DDPM steps per graph launch (msd_config.graph_steps; 1 -> 4 -> 10: 1.2000 -> 1.1963 -> 1.1955 ms/step)
   bool prefetch = true;        // producers warm the next GEMM's weights (msd_config.weight_prefetch; default: by model size)
@@ -390,13 +391,15 @@ const float* W(msd_model* m, const std::string& name) { return m->weights[m->win
 // tables ((j + 1) / K and (r + 1) / N are the same rational, correctly rounded: the same float32), so every reader of a
 // step-indexed table gets base + off rows and mul times the row stride, and no table or GEMM changes.  The sampler's own
 // coefficients also hold s = j / K, which is no row of the N-step table: a K-row table of their own.
-// The default is the handle's own view: what every launch had before there was another.
+// make_step_view fills EVERY field for every sampling call, the handle's own (N, cfg.sampler) included; the default below is
+// what a Ctx outside a sampling call reads its tables through (off, mul: the handle's rows) -- no step is enqueued on it.
 struct StepView {
-  int steps = 0;                    // K; 0 = the handle's N
+  int steps = 0;                    // K
   int off = 0, mul = 1;             // N / K - 1, N / K
-  const float* coef = nullptr;      // [K][kCoefCount]; null = the handle's d_coef
+  const float* coef = nullptr;      // [K][kCoefCount]
   const float* coef_ms = nullptr;   // [K][kMsCount], MSD_SAMPLER_DPMPP_2M only
-  int sampler = -1;                 // msd_sampler_kind; -1 = the handle's
+  int sampler = 0;                  // msd_sampler_kind
+  bool keep = false;                // the sampler's keep form on the handle's known-frame buffers (msd_sample_keep / _edit)
 };
 
 struct Ctx {
@@ -1493,14 +1496,13 @@ void decoder_eval(Ctx& c, const StepPlan& p, bool publish_step) {
 void split_z(msd_model* m, int64_t n, hipStream_t s) { split(m->z, m->zp, n, s, m->d_sat, (unsigned)KC_SAMPLER + 1u); }
 
 // one DDPM step of the CFG sampler: the decoder on plan_cfg_step's plan, then the sampler update
-// keep: the sampler's keep form on the handle's known-frame buffers (msd_sample_keep)
-// c.v: the call's view of the step-indexed tables, its coefficient rows and its sampler (msd_sample_steps)
-void enqueue_step(Ctx& c, const StepPlan& p, bool keep = false) {
+// c.v: the call's view of the step-indexed tables, its coefficient rows, its sampler and whether that runs in its keep form
+void enqueue_step(Ctx& c, const StepPlan& p) {
   msd_model* m = c.m;
   decoder_eval(c, p, /*publish_step=*/true);
-  const int sampler = c.v.sampler < 0 ? m->cfg.sampler : c.v.sampler;
+  const int sampler = c.v.sampler;
   SamplerKeepParams sp;
-  sp.eps = m->eps; sp.z = m->z; sp.noise_slot = m->d_noise_slot; sp.coef = c.v.coef ? c.v.coef : m->d_coef; sp.rng_key = m->d_rng_key;
+  sp.eps = m->eps; sp.z = m->z; sp.noise_slot = m->d_noise_slot; sp.coef = c.v.coef; sp.rng_key = m->d_rng_key;
   sp.step_ptr = m->d_step; sp.n = p.batch * m->T * m->ND; sp.passes = p.P;
   if (m->T * m->ND % kRngRowBlock == 0) sp.row_blocks = m->T * m->ND / kRngRowBlock;   // (else: table row 0 only, msd_sample_rows refuses)
   sp.cond_wt = m->cfg.cfg_weight; sp.clip_x0 = m->cfg.clip_x0;
@@ -1511,13 +1513,13 @@ void enqueue_step(Ctx& c, const StepPlan& p, bool keep = false) {
   sp.sat = m->d_sat; sp.sat_tag = (unsigned)KC_SAMPLER + 1u;
   c.begin(KC_SAMPLER);
   sp.step_from_slot1 = 1;
-  if (sampler == MSD_SAMPLER_DPMPP_2M) {   // (never with keep: sample_body refuses the pair)
+  if (sampler == MSD_SAMPLER_DPMPP_2M) {   // (never with keep: check_call refuses the pair)
     SamplerMultistepParams mp;
     static_cast<SamplerParams&>(mp) = sp;
     mp.x0_prev = m->x0_prev; mp.coef_ms = c.v.coef_ms;
-    mp.first_step = (c.v.steps ? c.v.steps : m->N) - 1;
+    mp.first_step = c.v.steps - 1;
     launch_sampler_step(mp, c.s);
-  } else if (keep) {
+  } else if (c.v.keep) {
     sp.xk = m->keep_xk; sp.keep = m->keep_flags; sp.n_dims = m->ND;
     launch_sampler_step(sp, c.s);
   } else {
@@ -1947,8 +1949,7 @@ static void fill_rng_key(uint32_t* key, int rng, uint64_t seed, uint64_t stream_
 // (msd_sample, msd_sample_rng), or one per row (msd_sample_rows; stream_ids may be NULL = zeros).
 struct SampleKeys {
   uint64_t seed = 0, stream_id = 0;
-  const uint64_t* seeds = nullptr;
-  const uint64_t* stream_ids = nullptr;
+  const uint64_t *seeds = nullptr, *stream_ids = nullptr;
   bool per_row() const { return seeds != nullptr; }
   uint64_t seed_of(int b) const { return seeds ? seeds[b] : seed; }
   uint64_t stream_of(int b) const { return seeds ? (stream_ids ? stream_ids[b] : 0) : stream_id; }
@@ -1962,18 +1963,29 @@ static hipError_t upload_rng_keys(msd_model* m, int batch, int rng, const Sample
   return hipMemcpyAsync(m->d_rng_key, m->h_rng_key.data(), m->h_rng_key.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s);
 }
 
-// The known frames of msd_sample_keep: the caller's mel [batch, T, n] (device) and frame flags [batch, T] (host or device);
-// of msd_sample_edit: release words instead (host, validated by the entry point) and the scan index the call starts at
-struct KeepFrames {
-  const float* known_dev = nullptr;
-  const int32_t* mask = nullptr;
-  const int32_t* release = nullptr;
-  int start_step = -2;   // (msd_sample_keep: N - 1, set by sample_body)
+// One sampling call as its entry point describes it to sample_body: filled once, checked once, handed down.  Every field is
+// the value the call runs with: no known frames = a null `known`; steps, sampler and start_step are resolved on filling.
+struct SampleCall {
+  int batch, rng;                // rows of z; the msd_rng_kind of the draws that are not given
+  SampleKeys keys;
+  const float *init_z, *noise;   // device; null = drawn
+  float* out; void* stream;
+  const float* known;            // msd_sample_keep / msd_sample_edit: the caller's mel [batch, T, n] (device)
+  const int32_t* mask;           // msd_sample_keep: frame flags [batch, T] (host or device)
+  const int32_t* release;        // msd_sample_edit: release words [batch, T] (host, validated by the entry point)
+  int start_step;                // the scan index the call starts at: steps - 1, or msd_sample_edit's
+  int steps, sampler;            // K (K | N) and the msd_sampler_kind
 };
 
-static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys, const float* init_z_dev,
-                       const float* noise_dev, float* out_dev, void* stream, const KeepFrames* keep = nullptr,
-                       int num_steps = 0, int sampler = -1);
+static SampleKeys sample_keys(int per_row, const uint64_t* seeds, const uint64_t* stream_ids) {
+  if (per_row) return {0, 0, seeds, stream_ids};
+  return {seeds[0], stream_ids ? stream_ids[0] : 0};
+}
+
+// the call of msd_sample_rng / msd_sample_rows: all of the handle's steps with its sampler, no known frames
+static SampleCall plain_call(const msd_model* m, int batch, int rng, const SampleKeys& keys, const float* init_z, const float* noise, float* out, void* stream) {
+  return {batch, rng, keys, init_z, noise, out, stream, nullptr, nullptr, nullptr, m->N - 1, m->N, m->cfg.sampler};
+}
 
 // "1, 2, 4, ..." -- the step counts msd_sample_steps takes on a handle of n steps
 static std::string divisors_of(int n) {
@@ -1983,18 +1995,23 @@ static std::string divisors_of(int n) {
   return out;
 }
 
-// The view of a call of K steps with `sampler` (both already normalised: K | N, a known kind), with the tables it needs
-// built on first use: the K-row coefficient table (K == N: the handle's own), the multistep side table, x0_prev.  Runs
-// outside stream capture; every allocation is the handle's.
-static int make_step_view(msd_model* m, int K, int sampler, StepView* v) {
+// The view of a call of K steps with `sampler` (K | N, a known kind) in the keep form or not, every field filled, with what
+// it needs built on first use: the known-frame buffers (each on its own, so that a call after a failed allocation tries
+// again for the one that is missing), the K-row coefficient table (K == N: the handle's own), the multistep side table,
+// x0_prev.  Runs outside stream capture; every allocation is the handle's.
+static int make_step_view(msd_model* m, int K, int sampler, bool keep, StepView* v) {
   const int N = m->N;
+  if (keep && !m->keep_xk)
+    if (int rc = dalloc(m, &m->keep_xk, (size_t)m->Bmax * m->T * m->ND)) return rc;
+  if (keep && !m->keep_flags)
+    if (int rc = dalloc(m, &m->keep_flags, (size_t)m->Bmax * m->T)) return rc;
   *v = StepView();
-  v->steps = K; v->mul = N / K; v->off = N / K - 1; v->sampler = sampler;
+  v->steps = K; v->mul = N / K; v->off = N / K - 1; v->coef = m->d_coef; v->sampler = sampler; v->keep = keep;
   // (the kernels index base + step * stride in 64 bits; the stride itself travels as an int)
   const int64_t widest = std::max<int64_t>(std::max<int64_t>(2 * m->Ld * m->D, (int64_t)m->Ld * 3 * m->J), (int64_t)m->Ld * 2 * m->F);
   if (widest * v->mul > 0x7FFFFFFFll)
     return fail(m, MSD_ERR_UNSUPPORTED, "a stride of %d table rows does not fit the GEMM epilogues' 32-bit row stride", v->mul);
-  if (K == N && sampler != MSD_SAMPLER_DPMPP_2M) return MSD_OK;   // the handle's own view and tables
+  if (K == N && sampler != MSD_SAMPLER_DPMPP_2M) return MSD_OK;   // the handle's own tables
   msd_model::StepTables& t = m->step_tables[K];
   if (K == N) {
     t.coef = m->d_coef;
@@ -2019,6 +2036,178 @@ static int make_step_view(msd_model* m, int K, int sampler, StepView* v) {
   return MSD_OK;
 }
 
+// ---- the phases of a sampling call, in the order sample_body runs them ---------------------------------------------
+static int check_call(msd_model* m, const SampleCall& c) {
+  if (c.rng != MSD_RNG_PHILOX && c.rng != MSD_RNG_THREEFRY) return fail(m, MSD_ERR_INVALID_ARGUMENT, "unknown rng %d", c.rng);
+  if (c.known && (c.steps != m->N || c.sampler == MSD_SAMPLER_DPMPP_2M))
+    return fail(m, MSD_ERR_UNSUPPORTED, "known frames run on the handle's own step count with ddpm or ddim (no multistep history across a release)");
+  if (!m->encoded) return fail(m, MSD_ERR_BAD_STATE, "msd_encode has not run");
+  if (c.batch != m->encoded_batch) return fail(m, MSD_ERR_INVALID_ARGUMENT, "batch %d != encoded batch %d", c.batch, m->encoded_batch);
+  if (!c.out) return fail(m, MSD_ERR_INVALID_ARGUMENT, "out is null");
+  const int64_t row_n = (int64_t)m->T * m->ND;
+  if (c.keys.per_row() && row_n % kRngRowBlock)   // a block of the sampler launch would straddle two rows' keys
+    return fail(m, MSD_ERR_UNSUPPORTED, "per-row keys need targets_length * n_dims %% %d == 0 (got %lld)", (int)kRngRowBlock, (long long)row_n);
+  if (c.known && m->ND % 4)   // a thread of the sampler holds four consecutive elements and ONE frame flag
+    return fail(m, MSD_ERR_UNSUPPORTED, "kept frames need n_dims %% 4 == 0 (got %d)", m->ND);
+  return MSD_OK;
+}
+
+// The legacy NULL stream cannot be captured: the call runs on the handle's own (non-blocking) stream.  What the caller
+// enqueued on the NULL stream before this call (its init_z / noise / out buffers) is ordered in front by ONE
+// hipStreamSynchronize of it -- NOT hipDeviceSynchronize (round 5): that waited for every other handle's stream on the
+// device as well, against the header's "handles are independent, also on one device".
+static int choose_stream(msd_model* m, void* stream, hipStream_t* s) {
+  *s = stream ? static_cast<hipStream_t>(stream) : m->own_stream;
+  if (!stream) HIP_TRY(m, hipStreamSynchronize(nullptr));
+  return MSD_OK;
+}
+
+// z, its planes and -- known frames -- xk and the frames' release words, at the scan index the call starts at
+static int write_initial_state(msd_model* m, const SampleCall& c, hipStream_t s) {
+  const int64_t n = (int64_t)c.batch * m->T * m->ND;
+  if (c.init_z) {
+    HIP_TRY(m, hipMemcpyAsync(m->z, c.init_z, n * sizeof(float), hipMemcpyDeviceToDevice, s));
+  } else {
+    // one fill over the whole array, or -- per-row keys -- one per row over its T * n elements under its own key
+    const int fills = c.keys.per_row() ? c.batch : 1;
+    const int64_t fill_n = n / fills;
+    for (int b = 0; b < fills; ++b) {
+      float* zb = m->z + b * fill_n;
+      int rc = c.rng == MSD_RNG_THREEFRY ? msd_fill_normal_threefry(c.keys.seed_of(b), -1, zb, fill_n, s)   // normal(PRNGKey(seed), [batch | 1, T, n])
+                                         : msd_fill_normal(c.keys.seed_of(b), c.keys.stream_of(b), 0, zb, fill_n, s);
+      if (rc) return fail(m, rc, "init_z fill failed");
+    }
+  }
+  if (c.start_step == c.steps - 1) {
+    split_z(m, n, s);
+    if (c.known) {
+      // the known mel enters the chain as the context does: scale_features(clip=True); init_z and the draws are untouched
+      hipLaunchKernelGGL(scale_clip_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c.known, m->keep_xk, (int)n, m->cfg.feature_min, m->cfg.feature_max);
+      HIP_TRY(m, hipGetLastError());
+    }
+  } else {
+    // part-way start (msd_sample_edit): z holds the call's initial draw eps; one pass makes xk and z = alpha xk + sigma eps
+    // at the start index's noise level, with z's planes and the range flag (what split_z does for the plain start)
+    DiffuseParams dp;
+    dp.mel = c.known; dp.eps = m->z; dp.xk = m->keep_xk; dp.z = m->z;
+    dp.z_hi = m->zp.p[0]; dp.z_lo = m->NP == 2 ? m->zp.p[1] : nullptr;
+    dp.n = (int)n; dp.fmin = m->cfg.feature_min; dp.fmax = m->cfg.feature_max;
+    diffuse_coefs(m->h_coef[(size_t)c.start_step * kCoefCount + kCoefLogsnrT], &dp.alpha, &dp.sigma);
+    dp.sat = m->d_sat; dp.sat_tag = (unsigned)KC_SAMPLER + 1u;
+    launch_diffuse_to_step(dp, s);
+    HIP_TRY(m, hipGetLastError());
+  }
+  if (c.known) {
+    // the frames' release words: msd_sample_edit's as given; msd_sample_keep's flags (host or device) as 0 / 1
+    HIP_TRY(m, hipMemcpyAsync(m->keep_flags, c.release ? c.release : c.mask, (size_t)c.batch * m->T * sizeof(int32_t), hipMemcpyDefault, s));
+    if (!c.release) {
+      launch_normalize_flags(m->keep_flags, m->keep_flags, c.batch * m->T, s);
+      HIP_TRY(m, hipGetLastError());
+    }
+  }
+  return MSD_OK;
+}
+
+// What a step reads in device memory besides z: the key table, the noise slot and the scan index (msd_profile_steps arms
+// them the same way).  Returns with the stream idle: the host temporaries are on the stack.
+// noise: the caller's [K][batch, T, n] buffer, or NULL = drawn INSIDE sampler_step_kernel (elementwise.h): step i's draw is
+// sub-sequence 1 + i of the (seed, stream_id) Philox stream, bit-identical to a buffer of those rows (tests/test_gpu_model.py);
+// MSD_RNG_THREEFRY: normal(fold_in(PRNGKey(seed), i), [batch, T, n]), what msd_fill_normal_threefry(seed, i, ...) writes.
+// Per-row keys: row b of z draws under row b of the key table what a ONE-row call (seed_b, stream_b) draws.  Kind and mode
+// are words of that table, so the same captured graphs serve every combination.
+// reset_tickets (a sampling call): the in-launch merge's arrival counters are zero between launches by construction (the
+// reducer resets its own); once per call in case an aborted launch left a count behind.
+static int arm_scan(msd_model* m, int batch, int rng, const SampleKeys& keys, const float* noise, int start_step, bool reset_tickets, hipStream_t s) {
+  HIP_TRY(m, upload_rng_keys(m, batch, rng, keys, s));
+  if (reset_tickets) HIP_TRY(m, hipMemsetAsync(m->att_tickets, 0, (size_t)m->att_ticket_count * sizeof(int), s));
+  HIP_TRY(m, hipMemcpyAsync(m->d_noise_slot, &noise, sizeof(float*), hipMemcpyHostToDevice, s));
+  const int start[2] = {start_step, start_step};
+  HIP_TRY(m, hipMemcpyAsync(m->d_step, start, sizeof(start), hipMemcpyHostToDevice, s));
+  HIP_TRY(m, hipStreamSynchronize(s));
+  return MSD_OK;
+}
+
+// `steps` consecutive steps of the view's form, captured on s and instantiated
+static int capture_steps(msd_model* m, const StepView& view, const StepPlan& plan, int steps, hipStream_t s, hipGraphExec_t* out) {
+  hipGraph_t graph = nullptr;
+  HIP_TRY(m, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+  Ctx c{m, s};
+  c.v = view;
+  for (int k = 0; k < steps; ++k) enqueue_step(c, plan);
+  hipError_t ce = hipStreamEndCapture(s, &graph);
+  if (ce != hipSuccess || c.err != hipSuccess) {
+    if (graph) (void)hipGraphDestroy(graph);
+    return fail(m, MSD_ERR_HIP, "graph capture failed: %s / %s", hipGetErrorString(ce), hipGetErrorString(c.err));
+  }
+  hipError_t ie = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(graph);
+  if (ie != hipSuccess) { *out = nullptr; return fail(m, MSD_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie)); }
+  return MSD_OK;
+}
+
+// The graphs of (plan, view), from the handle's cache or captured now.  One graph = `graph_steps` consecutive steps (the
+// scan index lives in device memory, so the same graph serves every position); a second, single-step graph covers what
+// a call of view.steps steps, or this call of run_steps, leaves over.
+static int find_graphs(msd_model* m, const StepView& view, const StepPlan& plan, int run_steps, hipStream_t s, msd_model::StepGraphs** out) {
+  const msd_model::GraphKey key = {plan, view.steps, view.sampler, view.keep};
+  msd_model::StepGraphs* g = nullptr;
+  for (auto& e : m->graphs)
+    if (memcmp(&e.key, &key, sizeof(key)) == 0) g = &e;
+  if (__builtin_expect(!g, 0)) {   // (a capture is the rare path; said so, the compiler keeps it out of line as it was inside the one long function)
+    if (m->graphs.size() >= 8) (void)msd_reset_graph(m);   // (a handle that cycles through more shapes than that re-captures)
+    msd_model::StepGraphs ng = {key};
+    if (int rc = capture_steps(m, view, plan, m->graph_steps, s, &ng.exec)) return rc;
+    if (m->graph_steps > 1 && view.steps % m->graph_steps)
+      if (int rc = capture_steps(m, view, plan, 1, s, &ng.exec1)) { (void)hipGraphExecDestroy(ng.exec); return rc; }
+    m->graphs.push_back(ng);
+    g = &m->graphs.back();
+  }
+  // (msd_sample_edit's part-way start on a handle whose N is a whole number of graphs: on first need, in the same entry)
+  if (m->graph_steps > 1 && run_steps % m->graph_steps && !g->exec1)
+    if (int rc = capture_steps(m, view, plan, 1, s, &g->exec1)) return rc;
+  *out = g;
+  return MSD_OK;
+}
+
+static int replay(msd_model* m, const msd_model::StepGraphs& g, int steps, hipStream_t s) {
+  for (int i = 0; i < steps / m->graph_steps; ++i) HIP_TRY(m, hipGraphLaunch(g.exec, s));
+  for (int i = 0; i < steps % m->graph_steps; ++i) HIP_TRY(m, hipGraphLaunch(m->graph_steps > 1 ? g.exec1 : g.exec, s));
+  return MSD_OK;
+}
+
+// z -> the caller's mel units; kept frames: the caller's own values, not a round trip through model units
+static int unscale(msd_model* m, const SampleCall& c, hipStream_t s) {
+  const int64_t n = (int64_t)c.batch * m->T * m->ND;
+  if (c.known) launch_unscale_keep(m->z, c.known, m->keep_flags, c.out, (int)n, m->ND, m->cfg.feature_min, m->cfg.feature_max, s);
+  else hipLaunchKernelGGL(unscale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, m->z, c.out, (int)n, m->cfg.feature_min, m->cfg.feature_max);
+  HIP_TRY(m, hipGetLastError());
+  return MSD_OK;
+}
+
+static int sample_body(msd_model* m, const SampleCall& c) {
+  if (int rc = check_call(m, c)) return rc;
+  StepView view;
+  if (int rc = make_step_view(m, c.steps, c.sampler, c.known != nullptr, &view)) return rc;   // (+ the handle's buffers and tables)
+  hipStream_t s;
+  if (int rc = choose_stream(m, c.stream, &s)) return rc;
+  const int steps = c.start_step + 1;   // the steps the call runs: all of c.steps but for msd_sample_edit's part-way start
+  if (steps <= 0) {   // (msd_sample_edit: every frame known throughout) no step runs: the caller's mel
+    HIP_TRY(m, hipMemcpyAsync(c.out, c.known, (size_t)c.batch * m->T * m->ND * sizeof(float), hipMemcpyDeviceToDevice, s));
+    HIP_TRY(m, hipStreamSynchronize(s));
+    return MSD_OK;
+  }
+  if (int rc = arm_range(m, s)) return rc;
+  if (int rc = write_initial_state(m, c, s)) return rc;
+  if (int rc = arm_scan(m, c.batch, c.rng, c.keys, c.noise, c.start_step, /*reset_tickets=*/true, s)) return rc;
+  msd_model::StepGraphs* g = nullptr;
+  if (int rc = find_graphs(m, view, plan_cfg_step(m, c.batch), steps, s, &g)) return rc;
+  if (int rc = replay(m, *g, steps, s)) return rc;
+  if (int rc = unscale(m, c, s)) return rc;
+  // ONE stream synchronisation ends the call (tens of microseconds against a ~1 s segment); behind it the half-plane range flag is read: a bad run fails THIS call
+  return check_range(m, s, "msd_sample");
+}
+
+// ---- the entry points: each checks what only it knows, fills the call and runs it ----------------------------------
 int msd_sample(msd_model* m, int batch, uint64_t seed, uint64_t stream_id, const float* init_z_dev,
                const float* noise_dev, float* out_dev, void* stream) {
   return msd_sample_rng(m, batch, MSD_RNG_PHILOX, seed, stream_id, init_z_dev, noise_dev, out_dev, stream);
@@ -2026,18 +2215,15 @@ int msd_sample(msd_model* m, int batch, uint64_t seed, uint64_t stream_id, const
 
 int msd_sample_rng(msd_model* m, int batch, int rng, uint64_t seed, uint64_t stream_id, const float* init_z_dev,
                    const float* noise_dev, float* out_dev, void* stream) {
-  SampleKeys keys;
-  keys.seed = seed; keys.stream_id = stream_id;
-  return sample_body(m, batch, rng, keys, init_z_dev, noise_dev, out_dev, stream);
+  if (!m) return MSD_ERR_INVALID_ARGUMENT;
+  return sample_body(m, plain_call(m, batch, rng, sample_keys(0, &seed, &stream_id), init_z_dev, noise_dev, out_dev, stream));
 }
 
 int msd_sample_rows(msd_model* m, int batch, int rng, const uint64_t* seeds, const uint64_t* stream_ids,
                     const float* init_z_dev, const float* noise_dev, float* out_dev, void* stream) {
   if (!m) return MSD_ERR_INVALID_ARGUMENT;
   if (!seeds) return fail(m, MSD_ERR_INVALID_ARGUMENT, "seeds is null");
-  SampleKeys keys;
-  keys.seeds = seeds; keys.stream_ids = stream_ids;
-  return sample_body(m, batch, rng, keys, init_z_dev, noise_dev, out_dev, stream);
+  return sample_body(m, plain_call(m, batch, rng, sample_keys(1, seeds, stream_ids), init_z_dev, noise_dev, out_dev, stream));
 }
 
 int msd_sample_keep(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
@@ -2046,12 +2232,9 @@ int msd_sample_keep(msd_model* m, int batch, int rng, int per_row, const uint64_
   if (!m) return MSD_ERR_INVALID_ARGUMENT;
   if (!seeds) return fail(m, MSD_ERR_INVALID_ARGUMENT, "seeds is null");
   if (!known_dev || !keep_mask) return fail(m, MSD_ERR_INVALID_ARGUMENT, "known mel or keep mask is null");
-  SampleKeys keys;
-  if (per_row) { keys.seeds = seeds; keys.stream_ids = stream_ids; }
-  else { keys.seed = seeds[0]; keys.stream_id = stream_ids ? stream_ids[0] : 0; }
-  KeepFrames keep;
-  keep.known_dev = known_dev; keep.mask = keep_mask;
-  return sample_body(m, batch, rng, keys, init_z_dev, noise_dev, out_dev, stream, &keep);
+  SampleCall c = plain_call(m, batch, rng, sample_keys(per_row, seeds, stream_ids), init_z_dev, noise_dev, out_dev, stream);
+  c.known = known_dev; c.mask = keep_mask;
+  return sample_body(m, c);
 }
 
 int msd_sample_edit(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
@@ -2074,12 +2257,9 @@ int msd_sample_edit(msd_model* m, int batch, int rng, int per_row, const uint64_
       return fail(m, MSD_ERR_INVALID_ARGUMENT, "release word %d of row %d, frame %d: a call that starts at scan index %d needs "
                   "every frame known at the steps it skips (words in [1, %d])", v, (int)(k / m->T), (int)(k % m->T), start_step, v_hi);
   }
-  SampleKeys keys;
-  if (per_row) { keys.seeds = seeds; keys.stream_ids = stream_ids; }
-  else { keys.seed = seeds[0]; keys.stream_id = stream_ids ? stream_ids[0] : 0; }
-  KeepFrames keep;
-  keep.known_dev = known_dev; keep.release = release; keep.start_step = start_step;
-  return sample_body(m, batch, rng, keys, init_z_dev, noise_dev, out_dev, stream, &keep);
+  SampleCall c = plain_call(m, batch, rng, sample_keys(per_row, seeds, stream_ids), init_z_dev, noise_dev, out_dev, stream);
+  c.known = known_dev; c.release = release; c.start_step = start_step;
+  return sample_body(m, c);
 }
 
 int msd_sample_steps(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
@@ -2092,172 +2272,10 @@ int msd_sample_steps(msd_model* m, int batch, int rng, int per_row, const uint64
                 num_steps, m->N, m->N, divisors_of(m->N).c_str());
   if (sampler != -1 && sampler != MSD_SAMPLER_DDPM && sampler != MSD_SAMPLER_DDIM && sampler != MSD_SAMPLER_DPMPP_2M)
     return fail(m, MSD_ERR_INVALID_ARGUMENT, "Unknown sampler type: %d", sampler);
-  SampleKeys keys;
-  if (per_row) { keys.seeds = seeds; keys.stream_ids = stream_ids; }
-  else { keys.seed = seeds[0]; keys.stream_id = stream_ids ? stream_ids[0] : 0; }
-  return sample_body(m, batch, rng, keys, init_z_dev, noise_dev, out_dev, stream, nullptr, num_steps, sampler);
-}
-
-static int sample_body(msd_model* m, int batch, int rng, const SampleKeys& keys, const float* init_z_dev,
-                       const float* noise_dev, float* out_dev, void* stream, const KeepFrames* keep, int num_steps,
-                       int sampler) {
-  if (!m) return MSD_ERR_INVALID_ARGUMENT;
-  if (rng != MSD_RNG_PHILOX && rng != MSD_RNG_THREEFRY) return fail(m, MSD_ERR_INVALID_ARGUMENT, "unknown rng %d", rng);
-  // the call's step count and sampler, normalised: the handle's own are (N, cfg.sampler), however they were named
-  const int K = num_steps > 0 ? num_steps : m->N;
-  const int kind = sampler < 0 ? m->cfg.sampler : sampler;
-  if (keep && (K != m->N || kind == MSD_SAMPLER_DPMPP_2M))
-    return fail(m, MSD_ERR_UNSUPPORTED, "known frames run on the handle's own step count with ddpm or ddim (no multistep history across a release)");
-  if (!m->encoded) return fail(m, MSD_ERR_BAD_STATE, "msd_encode has not run");
-  if (batch != m->encoded_batch) return fail(m, MSD_ERR_INVALID_ARGUMENT, "batch %d != encoded batch %d", batch, m->encoded_batch);
-  if (!out_dev) return fail(m, MSD_ERR_INVALID_ARGUMENT, "out is null");
-  const int64_t row_n = (int64_t)m->T * m->ND;
-  if (keys.per_row() && row_n % kRngRowBlock)   // a block of the sampler launch would straddle two rows' keys
-    return fail(m, MSD_ERR_UNSUPPORTED, "per-row keys need targets_length * n_dims %% %d == 0 (got %lld)", (int)kRngRowBlock, (long long)row_n);
-  if (keep && m->ND % 4)   // a thread of the sampler holds four consecutive elements and ONE frame flag
-    return fail(m, MSD_ERR_UNSUPPORTED, "kept frames need n_dims %% 4 == 0 (got %d)", m->ND);
-  // first keep call of the handle (nothing is being captured here); each buffer on its own, so that a call after a failed
-  // allocation tries again for the one that is missing
-  if (keep && !m->keep_xk)
-    if (int rc = dalloc(m, &m->keep_xk, (size_t)m->Bmax * row_n)) return rc;
-  if (keep && !m->keep_flags)
-    if (int rc = dalloc(m, &m->keep_flags, (size_t)m->Bmax * m->T)) return rc;
-  StepView view;
-  if (int rc = make_step_view(m, K, kind, &view)) return rc;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  const bool null_stream = (s == nullptr);
-  if (null_stream) {
-    // The legacy NULL stream cannot be captured: the call runs on the handle's own (non-blocking) stream.  What the
-    // caller enqueued on the NULL stream before this call (its init_z / noise / out buffers) is ordered in front by ONE
-    // hipStreamSynchronize of the NULL stream -- NOT hipDeviceSynchronize (round 5): that waited for every other handle's
-    // stream on the device as well, against the header's "handles are independent, also on one device".
-    HIP_TRY(m, hipStreamSynchronize(nullptr));
-    s = m->own_stream;
-  }
-  const int64_t n = (int64_t)batch * m->T * m->ND;
-  // the scan index the call starts at: K - 1 (N - 1 but for msd_sample_steps), or msd_sample_edit's
-  const int start_step = keep && keep->release ? keep->start_step : K - 1;
-  if (start_step < 0) {   // (msd_sample_edit: every frame known throughout) no step runs: the caller's mel
-    HIP_TRY(m, hipMemcpyAsync(out_dev, keep->known_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-    HIP_TRY(m, hipStreamSynchronize(s));
-    return MSD_OK;
-  }
-  if (int rc0 = arm_range(m, s)) return rc0;
-  if (init_z_dev) {
-    HIP_TRY(m, hipMemcpyAsync(m->z, init_z_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s));
-  } else {
-    // one fill over the whole array, or -- per-row keys -- one per row over its T * n elements under its own key
-    const int fills = keys.per_row() ? batch : 1;
-    const int64_t fill_n = keys.per_row() ? row_n : n;
-    for (int b = 0; b < fills; ++b) {
-      float* zb = m->z + b * fill_n;
-      int rc = rng == MSD_RNG_THREEFRY ? msd_fill_normal_threefry(keys.seed_of(b), -1, zb, fill_n, s)   // normal(PRNGKey(seed), [batch | 1, T, n])
-                                       : msd_fill_normal(keys.seed_of(b), keys.stream_of(b), 0, zb, fill_n, s);
-      if (rc) return fail(m, rc, "init_z fill failed");
-    }
-  }
-  if (start_step == K - 1) {
-    split_z(m, n, s);
-    if (keep) {
-      // the known mel enters the chain as the context does: scale_features(clip=True); init_z and the draws are untouched
-      hipLaunchKernelGGL(scale_clip_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, keep->known_dev, m->keep_xk,
-                         (int)n, m->cfg.feature_min, m->cfg.feature_max);
-      HIP_TRY(m, hipGetLastError());
-    }
-  } else {
-    // part-way start (msd_sample_edit): z holds the call's initial draw eps; one pass makes xk and z = alpha xk + sigma eps
-    // at the start index's noise level, with z's planes and the range flag (what split_z does for the plain start)
-    DiffuseParams dp;
-    dp.mel = keep->known_dev; dp.eps = m->z; dp.xk = m->keep_xk; dp.z = m->z;
-    dp.z_hi = m->zp.p[0]; dp.z_lo = m->NP == 2 ? m->zp.p[1] : nullptr;
-    dp.n = (int)n; dp.fmin = m->cfg.feature_min; dp.fmax = m->cfg.feature_max;
-    diffuse_coefs(m->h_coef[(size_t)start_step * kCoefCount + kCoefLogsnrT], &dp.alpha, &dp.sigma);
-    dp.sat = m->d_sat; dp.sat_tag = (unsigned)KC_SAMPLER + 1u;
-    launch_diffuse_to_step(dp, s);
-    HIP_TRY(m, hipGetLastError());
-  }
-  if (keep) {
-    // the frames' release words: msd_sample_edit's as given; msd_sample_keep's flags (host or device) as 0 / 1
-    HIP_TRY(m, hipMemcpyAsync(m->keep_flags, keep->release ? keep->release : keep->mask, (size_t)batch * m->T * sizeof(int32_t),
-                              hipMemcpyDefault, s));
-    if (!keep->release) {
-      launch_normalize_flags(m->keep_flags, m->keep_flags, batch * m->T, s);
-      HIP_TRY(m, hipGetLastError());
-    }
-  }
-  // Step noise: the caller's buffer, or -- noise_dev == NULL -- drawn INSIDE sampler_step_kernel (round 6): step i's draw is
-  // sub-sequence 1 + i of the (seed, stream_id) Philox stream, the row philox_normal_kernel used to write into an
-  // [N][n] buffer up front (131 MB x songs at base, with a hipMalloc in here on the first call of a batch size).  Same
-  // function, same counters: bit-identical to the buffered form (tests/test_gpu_model.py).  The slot holds NULL then.
-  // MSD_RNG_THREEFRY: step i's draw is normal(fold_in(PRNGKey(seed), i), [batch, T, n]) instead, what
-  // msd_fill_normal_threefry(seed, i, ...) writes; the kind travels in device memory, so the captured graphs below serve both.
-  // Per-row keys: row b of z draws under row b of the key table what a ONE-row call (seed_b, stream_b) draws; the mode
-  // is a word of that table too, so the same graphs serve it.
-  const float* noise = noise_dev;
-  HIP_TRY(m, upload_rng_keys(m, batch, rng, keys, s));
-  // arrival counters of the in-launch merge: zero between launches by construction (the reducer resets its own); once
-  // per call in case an aborted launch left a count behind
-  HIP_TRY(m, hipMemsetAsync(m->att_tickets, 0, (size_t)m->att_ticket_count * sizeof(int), s));
-  HIP_TRY(m, hipMemcpyAsync(m->d_noise_slot, &noise, sizeof(float*), hipMemcpyHostToDevice, s));
-  const int start[2] = {start_step, start_step};
-  HIP_TRY(m, hipMemcpyAsync(m->d_step, start, sizeof(start), hipMemcpyHostToDevice, s));
-  HIP_TRY(m, hipStreamSynchronize(s));  // host temporaries above are on the stack
-
-  // One graph = `graph_steps` consecutive DDPM steps (the scan index lives in device memory, so
-  // the same graph serves every position); a second, single-step graph covers N mod graph_steps.
-  const StepPlan plan = plan_cfg_step(m, batch);
-  auto capture = [&](int steps, hipGraphExec_t* out) -> int {
-    hipGraph_t graph = nullptr;
-    HIP_TRY(m, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-    Ctx c{m, s};
-    c.v = view;
-    for (int k = 0; k < steps; ++k) enqueue_step(c, plan, keep != nullptr);
-    hipError_t ce = hipStreamEndCapture(s, &graph);
-    if (ce != hipSuccess || c.err != hipSuccess) {
-      if (graph) (void)hipGraphDestroy(graph);
-      return fail(m, MSD_ERR_HIP, "graph capture failed: %s / %s", hipGetErrorString(ce), hipGetErrorString(c.err));
-    }
-    hipError_t ie = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(graph);
-    if (ie != hipSuccess) { *out = nullptr; return fail(m, MSD_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie)); }
-    return MSD_OK;
-  };
-  // the graphs captured with this plan (msd_model::StepGraphs)
-  msd_model::StepGraphs* g = nullptr;
-  for (auto& e : m->graphs)
-    if (e.keep == (keep != nullptr) && e.steps == K && e.sampler == kind && memcmp(&e.plan, &plan, sizeof(plan)) == 0) g = &e;
-  if (!g) {
-    if (m->graphs.size() >= 8) (void)msd_reset_graph(m);   // (a handle that cycles through more shapes than that re-captures)
-    msd_model::StepGraphs ng;
-    ng.plan = plan;
-    ng.keep = keep != nullptr;
-    ng.steps = K; ng.sampler = kind;
-    int rc = capture(m->graph_steps, &ng.exec);
-    if (rc) return rc;
-    if (m->graph_steps > 1 && K % m->graph_steps) {
-      rc = capture(1, &ng.exec1);
-      if (rc) { (void)hipGraphExecDestroy(ng.exec); return rc; }
-    }
-    m->graphs.push_back(ng);
-    g = &m->graphs.back();
-  }
-  // the call runs start_step + 1 steps (N but for msd_sample_edit's part-way start, whose remainder may need the single-step
-  // graph on a handle whose N is a whole number of graphs: captured on first need, kept in the same entry)
-  const int steps = start_step + 1;
-  if (m->graph_steps > 1 && steps % m->graph_steps && !g->exec1)
-    if (int rc = capture(1, &g->exec1)) return rc;
-  for (int i = 0; i < steps / m->graph_steps; ++i) HIP_TRY(m, hipGraphLaunch(g->exec, s));
-  for (int i = 0; i < steps % m->graph_steps; ++i)
-    HIP_TRY(m, hipGraphLaunch(m->graph_steps > 1 ? g->exec1 : g->exec, s));
-  if (keep)   // kept frames: the caller's own values, not a round trip through model units
-    launch_unscale_keep(m->z, keep->known_dev, m->keep_flags, out_dev, (int)n, m->ND, m->cfg.feature_min, m->cfg.feature_max, s);
-  else
-    hipLaunchKernelGGL(unscale_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, m->z, out_dev,
-                       (int)n, m->cfg.feature_min, m->cfg.feature_max);
-  HIP_TRY(m, hipGetLastError());
-  // The call ends with ONE stream synchronisation (tens of microseconds against a ~1 s segment): behind it the
-  // half-plane range flag is read, so that a bad run fails THIS call.
-  return check_range(m, s, "msd_sample");
+  SampleCall c = plain_call(m, batch, rng, sample_keys(per_row, seeds, stream_ids), init_z_dev, noise_dev, out_dev, stream);
+  if (num_steps > 0) { c.steps = num_steps; c.start_step = num_steps - 1; }   // (the handle's own are (N, cfg.sampler), however they were named)
+  if (sampler >= 0) c.sampler = sampler;
+  return sample_body(m, c);
 }
 
 int msd_reset_graph(msd_model* m) {
@@ -2358,19 +2376,13 @@ int msd_profile_steps(msd_model* m, int batch, int n_steps, const char* const** 
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int64_t n = (int64_t)batch * m->T * m->ND;
   StepView view;   // (a handle whose own sampler is the multistep form needs its side table and history buffer)
-  if (int rcv = make_step_view(m, m->N, m->cfg.sampler, &view)) return rcv;
+  if (int rcv = make_step_view(m, m->N, m->cfg.sampler, /*keep=*/false, &view)) return rcv;
   if (int rc0 = arm_range(m, s)) return rc0;
   int rc = msd_fill_normal(1, 0, 0, m->z, n, s);
   if (rc) return rc;
   split_z(m, n, s);
-  const float* noise = nullptr;   // the sampler kernel draws the steps' noise itself (Philox stream (1, 0): elementwise.h)
-  SampleKeys keys;
-  keys.seed = 1;
-  HIP_TRY(m, upload_rng_keys(m, batch, kRngPhilox, keys, s));
-  HIP_TRY(m, hipMemcpyAsync(m->d_noise_slot, &noise, sizeof(float*), hipMemcpyHostToDevice, s));
-  const int start[2] = {m->N - 1, m->N - 1};
-  HIP_TRY(m, hipMemcpyAsync(m->d_step, start, sizeof(start), hipMemcpyHostToDevice, s));
-  HIP_TRY(m, hipStreamSynchronize(s));
+  // the sampler kernel draws the steps' noise itself (Philox stream (1, 0): elementwise.h)
+  if (int rc1 = arm_scan(m, batch, kRngPhilox, SampleKeys{1}, /*noise=*/nullptr, m->N - 1, /*reset_tickets=*/false, s)) return rc1;
   for (int k = 0; k < KC_COUNT; ++k) { m->prof.ms[k] = 0; m->prof.launches[k] = 0; }
   m->prof.on = true;
   Ctx c{m, s};

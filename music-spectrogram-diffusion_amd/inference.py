@@ -26,6 +26,7 @@ tokeniser uses (inference.py:108-111).
 """
 from __future__ import annotations
 
+import dataclasses
 import os
 import time
 from typing import Any, Dict, List, Mapping, Optional, Sequence, Tuple, Union
@@ -304,6 +305,39 @@ def check_keep(keep, keep_mask, b: int, t: int, n: int):
   return keep, np.ascontiguousarray(flags != 0, dtype=np.int32)
 
 
+@dataclasses.dataclass(frozen=True)
+class SampleCall:
+  """The form of one sampling call, by NativeModel.sample's keyword names: known frames (keep + keep_mask), an edit
+  (keep + release words + the scan index it starts at) or a few-step call (steps and / or sampler); all None = plain."""
+  keep: Any = None
+  keep_mask: Any = None
+  release: Any = None
+  start_step: Optional[int] = None
+  steps: Optional[int] = None
+  sampler: Optional[str] = None
+
+
+def plan_call(keep, keep_mask, strength, steps, sampler, b: int, t: int, n: int, num_steps: int) -> SampleCall:
+  """predict's keep / keep_mask / strength / steps / sampler, checked and planned once.  Pure: no device; every
+  ValueError predict raises for them is raised here."""
+  if steps is not None or sampler is not None:
+    if keep is not None or keep_mask is not None or strength is not None:
+      raise ValueError('steps= / sampler= cannot be combined with keep= / keep_mask= / strength= (few-step edits are not built)')
+    if sampler is not None and sampler not in native.SAMPLERS:
+      raise ValueError('sampler must be one of %s: %r' % (sorted(native.SAMPLERS), sampler))
+    if steps is not None:
+      plan_steps(num_steps, steps)   # (its checks)
+    return SampleCall(steps=None if steps is None else int(steps), sampler=sampler)
+  if strength is None:
+    keep, keep_mask = check_keep(keep, keep_mask, b, t, n)
+    return SampleCall(keep=keep, keep_mask=keep_mask)
+  if keep is None:
+    raise ValueError('strength needs keep: the mel it is a variation of')
+  keep, flags = check_keep(keep, np.zeros((b, t), np.int32) if keep_mask is None else keep_mask, b, t, n)
+  words, start = plan_strength(check_strength(strength, flags, b, t), num_steps)
+  return SampleCall(keep=keep, release=words, start_step=start)
+
+
 class InferenceModel(object):
   """Wrapper of the HIP synthesizer with the reference's InferenceModel API."""
 
@@ -521,30 +555,12 @@ class InferenceModel(object):
       across a frame's release, are a separate piece of work -- a ValueError in this version.
     Returns (decodes float32 [B,T,n] in mel units, scores float32 [B] zeros).
     """
-    b, t, n = np.shape(batch['encoder_input_tokens'])[0], self.targets_length, self.audio_codec.n_dims
-    edit = None   # (release words, start_step) of the edit form
-    few = None    # (K, sampler) of the few-step form
-    if steps is not None or sampler is not None:
-      if keep is not None or keep_mask is not None or strength is not None:
-        raise ValueError('steps= / sampler= cannot be combined with keep= / keep_mask= / strength= (few-step edits are not built)')
-      if sampler is not None and sampler not in native.SAMPLERS:
-        raise ValueError('sampler must be one of %s: %r' % (sorted(native.SAMPLERS), sampler))
-      if steps is not None:
-        plan_steps(self.spec.diffusion.sampler.schedule.num_steps, steps)   # (its checks)
-      few = (None if steps is None else int(steps), sampler)
-    if strength is not None:
-      if keep is None:
-        raise ValueError('strength needs keep: the mel it is a variation of')
-      keep, flags = check_keep(keep, np.zeros((b, t), np.int32) if keep_mask is None else keep_mask, b, t, n)
-      edit = plan_strength(check_strength(strength, flags, b, t), self.spec.diffusion.sampler.schedule.num_steps)
-      keep_mask = None
-    else:
-      keep, keep_mask = check_keep(keep, keep_mask, b, t, n)
+    call = plan_call(keep, keep_mask, strength, steps, sampler, np.shape(batch['encoder_input_tokens'])[0], self.targets_length,
+                     self.audio_codec.n_dims, self.spec.diffusion.sampler.schedule.num_steps)
     if rng is None:
       rng = self.rng
-    few_kw = {} if few is None else dict(few=few)   # (the call without them is the call as it was)
     try:
-      return self._predict_once(batch, seed, segment, init_z, noise, return_torch, rng, keep, keep_mask, edit, **few_kw)
+      return self._predict_once(batch, seed, segment, init_z, noise, return_torch, rng, call)
     except native.RangeError:
       if not (self.range_fallback and self.precision in ('f16x3', 'f16')):
         raise
@@ -556,10 +572,9 @@ class InferenceModel(object):
       if self._native is not None:
         self._native.close()
       self._native = None
-      return self._predict_once(batch, seed, segment, init_z, noise, return_torch, rng, keep, keep_mask, edit, **few_kw)
+      return self._predict_once(batch, seed, segment, init_z, noise, return_torch, rng, call)
 
-  def _predict_once(self, batch, seed, segment, init_z, noise, return_torch, rng, keep=None, keep_mask=None, edit=None,
-                    few=None):
+  def _predict_once(self, batch, seed, segment, init_z, noise, return_torch, rng, call=SampleCall()):
     torch = self._torch
     nm = self._get_native()
     dev = self.device
@@ -596,7 +611,7 @@ class InferenceModel(object):
       if per_row:
         seed, segment = native.row_keys(b, seed, segment)
       # the call's step count: its noise is [K, B, T, n] and its host draws are those of a K-step model
-      k_steps = self.spec.diffusion.sampler.schedule.num_steps if few is None or few[0] is None else few[0]
+      k_steps = self.spec.diffusion.sampler.schedule.num_steps if call.steps is None else call.steps
       if rng == 'jax' and init_z is None and noise is None:
         init_z, noise = self._jax_noise_rows(seed, k_steps) if per_row else self._jax_noise(seed, b, k_steps)
       elif rng not in RNG_MODES:
@@ -608,11 +623,9 @@ class InferenceModel(object):
       if nz is not None and tuple(nz.shape) != (k_steps, b, t, n):
         raise ValueError('noise must be [num_steps, batch, %d, %d] = %r: got %r' % (t, n, (k_steps, b, t, n), tuple(nz.shape)))
       # explicit draws keep precedence in every mode; 'jax' has none left to generate
-      known = None if keep is None else _to_device(torch, keep, dev, torch.float32)
+      known = None if call.keep is None else _to_device(torch, call.keep, dev, torch.float32)
       nm.sample(b, out, seed=seed, stream_id=segment, init_z=z0, noise=nz, stream=s,
-                rng='threefry' if rng == 'threefry' else 'philox', keep=known, keep_mask=keep_mask,
-                release=None if edit is None else edit[0], start_step=None if edit is None else edit[1],
-                **({} if few is None else dict(steps=few[0], sampler=few[1])))
+                rng='threefry' if rng == 'threefry' else 'philox', **vars(dataclasses.replace(call, keep=known)))
       self._stream.synchronize()
     t2 = time.perf_counter()
     self.last_timing = {'encode_s': t1 - t0, 'sample_s': t2 - t1, 'total_s': t2 - t0}
@@ -621,9 +634,8 @@ class InferenceModel(object):
       return out, torch.zeros((b,), dtype=torch.float32, device=dev)
     return out.cpu().numpy(), scores
 
-  def _jax_noise(self, seed: int, b: int, steps: Optional[int] = None):
+  def _jax_noise(self, seed: int, b: int, steps: int):
     """Device-resident (init_z, noise) of jax_random.reference_noise, cached for the last (seed, b, steps)."""
-    steps = self.spec.diffusion.sampler.schedule.num_steps if steps is None else steps
     key = (int(seed), int(b), int(steps))
     if getattr(self, '_jax_noise_key', None) != key:
       from . import jax_random
@@ -633,12 +645,11 @@ class InferenceModel(object):
       self._jax_noise_key = key
     return self._jax_noise_val
 
-  def _jax_noise_rows(self, seeds: Sequence[int], steps: Optional[int] = None):
+  def _jax_noise_rows(self, seeds: Sequence[int], steps: int):
     """(init_z [B,T,n], noise [N,B,T,n]) whose row b is the one-row host draw of seeds[b]: one draw per distinct seed."""
     from . import jax_random
     torch = self._torch
     t, n = self.targets_length, self.audio_codec.n_dims
-    steps = self.spec.diffusion.sampler.schedule.num_steps if steps is None else steps
     drawn = {}
     for sd in seeds:
       if sd not in drawn:
@@ -680,20 +691,13 @@ class InferenceModel(object):
     torch = self._torch
     n = self.audio_codec.n_dims
     c_len = self.targets_context_length
-    pred = None
-    if c_len is not None:
-      pred = torch.zeros((1, c_len, n), dtype=torch.float32, device=self.device)
-      if init_context is not None:
-        pred = _to_device(torch, init_context, self.device, torch.float32).reshape(1, c_len, n)
+    pred = None   # (the first segment's context: zeros)
+    if c_len is not None and init_context is not None:
+      pred = _to_device(torch, init_context, self.device, torch.float32).reshape(1, c_len, n)
     outs, seconds = [], []
     for i, toks in enumerate(segments_tokens):
       gi = first_segment_index + i
-      toks = np.asarray(toks, np.int32).reshape(1, -1)
-      batch = {'encoder_input_tokens': toks}
-      if c_len is not None:
-        batch['encoder_continuous_inputs'] = pred
-        no_ctx = always_mask_context or (i == 0 and init_context is None)
-        batch['encoder_continuous_mask'] = (np.zeros if no_ctx else np.ones)((1, c_len), np.int32)
+      batch = self._segment_batch(toks, pred, always_mask_context or (i == 0 and init_context is None))
       tick = time.perf_counter()
       out, _ = self.predict(batch, seed=seed, segment=gi, return_torch=True, rng=rng, **few)
       if i != 0:
@@ -716,17 +720,24 @@ class InferenceModel(object):
       raise ValueError('song has %d frames but %d segments of tokens (%d frames each) were given'
                        % (np.shape(song)[1], len(segments_tokens), t))
 
+  def _segment_batch(self, tokens, context, no_ctx: bool):
+    """predict's batch of one segment: its tokens and -- a model with context -- `context` [1, C, n] on the device (None =
+    zeros) under a mask of ones, or of zeros when no_ctx."""
+    batch = {'encoder_input_tokens': np.asarray(tokens, np.int32).reshape(1, -1)}
+    c_len = self.targets_context_length
+    if c_len is not None:
+      if context is None:
+        context = self._torch.zeros((1, c_len, self.audio_codec.n_dims), dtype=self._torch.float32, device=self.device)
+      batch['encoder_continuous_inputs'] = context
+      batch['encoder_continuous_mask'] = (np.zeros if no_ctx else np.ones)((1, c_len), np.int32)
+    return batch
+
   def _edit_segment(self, new, k, tokens, always_mask_context, seed, rng, **keep_kw):
     """predict for segment k of the song `new` as it stands ([1, K * T, n] on the device): its context is segment k - 1 of
     `new` (zeros and mask 0 for segment 0 and always_mask_context), its key (seed, k), its known mel its own frames."""
-    torch = self._torch
-    t, n, c_len = self.targets_length, self.audio_codec.n_dims, self.targets_context_length
-    batch = {'encoder_input_tokens': np.asarray(tokens, np.int32).reshape(1, -1)}
-    if c_len is not None:
-      no_ctx = always_mask_context or k == 0
-      batch['encoder_continuous_inputs'] = (torch.zeros((1, c_len, n), dtype=torch.float32, device=self.device)
-                                            if no_ctx else new[:, (k - 1) * t:k * t].clone())
-      batch['encoder_continuous_mask'] = (np.zeros if no_ctx else np.ones)((1, c_len), np.int32)
+    t = self.targets_length
+    no_ctx = always_mask_context or k == 0 or self.targets_context_length is None
+    batch = self._segment_batch(tokens, None if no_ctx else new[:, (k - 1) * t:k * t].clone(), no_ctx)
     out, _ = self.predict(batch, seed=seed, segment=k, return_torch=True, rng=rng, keep=new[:, k * t:(k + 1) * t].clone(),
                           **keep_kw)
     return out.to(self.device)
@@ -776,34 +787,22 @@ class InferenceModel(object):
     frames whose share rounds to no step at all, are the input's bit for bit.  0 is the hard edge above, unchanged."""
     torch = self._torch
     t, n = self.targets_length, self.audio_codec.n_dims
-    c_len = self.targets_context_length
     if len(np.shape(song)) != 3 or np.shape(song)[0] != 1 or np.shape(song)[2] != n:
       raise ValueError('song must be [1, frames, %d]: got %r' % (n, tuple(np.shape(song))))
-    plan = plan_region(np.shape(song)[1], t, start_frame, stop_frame)
-    if blend_frames != 0:
-      soft = region_strength(np.shape(song)[1], t, start_frame, stop_frame, blend_frames)
+    plan = plan_region(np.shape(song)[1], t, start_frame, stop_frame)   # [(segment, mask row)]; soft: [(segment, strength row)]
+    soft = blend_frames != 0
+    if soft:
+      plan = region_strength(np.shape(song)[1], t, start_frame, stop_frame, blend_frames)
       self._check_song(song, segments_tokens)
-      new = _to_device(torch, song, self.device, torch.float32).clone()
-      for k, row in soft:
-        out = self._edit_segment(new, k, segments_tokens[k], always_mask_context, seed, rng, strength=row[None])
-        free = torch.as_tensor(row > 0.0, device=self.device)
-        new[0, k * t:(k + 1) * t][free] = out[0][free]
-      return new if return_torch else new.cpu().numpy()
-    if np.shape(song)[1] != t * len(segments_tokens):
+    elif np.shape(song)[1] != t * len(segments_tokens):
       raise ValueError('song has %d segments of %d frames but %d segments of tokens were given'
                        % (np.shape(song)[1] // t, t, len(segments_tokens)))
     new = _to_device(torch, song, self.device, torch.float32).clone()
     for k, row in plan:
-      batch = {'encoder_input_tokens': np.asarray(segments_tokens[k], np.int32).reshape(1, -1)}
-      if c_len is not None:
-        no_ctx = always_mask_context or k == 0
-        batch['encoder_continuous_inputs'] = (torch.zeros((1, c_len, n), dtype=torch.float32, device=self.device)
-                                              if no_ctx else new[:, (k - 1) * t:k * t].clone())
-        batch['encoder_continuous_mask'] = (np.zeros if no_ctx else np.ones)((1, c_len), np.int32)
-      out, _ = self.predict(batch, seed=seed, segment=k, return_torch=True, rng=rng,
-                            keep=new[:, k * t:(k + 1) * t].clone(), keep_mask=row[None])
-      free = torch.as_tensor(row == 0, device=self.device)
-      new[0, k * t:(k + 1) * t][free] = out[0].to(self.device)[free]   # (the kept frames of `out` are the song's already)
+      out = self._edit_segment(new, k, segments_tokens[k], always_mask_context, seed, rng,
+                               **({'strength': row[None]} if soft else {'keep_mask': row[None]}))
+      free = torch.as_tensor(row > 0.0 if soft else row == 0, device=self.device)
+      new[0, k * t:(k + 1) * t][free] = out[0][free]   # (the other frames of `out` are the song's already)
     return new if return_torch else new.cpu().numpy()
 
   def _sequence_timing(self, seconds: Sequence[float]) -> Dict[str, float]:

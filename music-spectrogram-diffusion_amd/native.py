@@ -395,60 +395,47 @@ class NativeModel:
     steps (K, a divisor of the handle's num_steps; None = all of them) / sampler ('ddpm', 'ddim', 'dpmpp_2m'; None = the
     handle's): a step count and a sampler for THIS call (msd_sample_steps); noise is then [K, batch, T, n].  Not with
     keep / release."""
+    few, edit = steps is not None or sampler is not None, release is not None
+    # (1) what the call may not combine or name
     if rng not in RNGS:
       raise ValueError('rng must be one of %s: %r' % (sorted(RNGS), rng))
-    if steps is not None or sampler is not None:
-      if keep is not None or keep_mask is not None or release is not None or start_step is not None:
-        raise ValueError('steps / sampler cannot be combined with keep / keep_mask / release / start_step')
-      if sampler is not None and sampler not in SAMPLERS:
-        raise ValueError('sampler must be one of %s: %r' % (sorted(SAMPLERS), sampler))
-      k = 0
-      if steps is not None:
-        plan_steps(self.cfg.num_steps, steps)   # (its checks: a ValueError that names the divisors)
-        k = int(steps)
-      per_row = not (np.isscalar(seed) and np.isscalar(stream_id))
-      seeds, stream_ids = row_keys(batch if per_row else 1, seed, stream_id)
-      rc = self.lib.msd_sample_steps(self.handle, batch, RNGS[rng], int(per_row), (ctypes.c_uint64 * len(seeds))(*seeds),
-                                     (ctypes.c_uint64 * len(seeds))(*stream_ids), _ptr(init_z), _ptr(noise), k,
-                                     -1 if sampler is None else SAMPLERS[sampler], _ptr(out), stream)
-      _check(self.lib, self.handle, rc, 'msd_sample_steps')
-      return
-    if release is not None:
-      if keep is None or keep_mask is not None:
-        raise ValueError('release goes with keep and without keep_mask')
-      words = np.ascontiguousarray(release, dtype=np.int32)
-      if words.size != batch * self.cfg.targets_length:
+    if few and (keep is not None or keep_mask is not None or edit or start_step is not None):
+      raise ValueError('steps / sampler cannot be combined with keep / keep_mask / release / start_step')
+    if sampler is not None and sampler not in SAMPLERS:
+      raise ValueError('sampler must be one of %s: %r' % (sorted(SAMPLERS), sampler))
+    if steps is not None:
+      plan_steps(self.cfg.num_steps, steps)   # (its checks: a ValueError that names the divisors)
+    if edit and (keep is None or keep_mask is not None):
+      raise ValueError('release goes with keep and without keep_mask')
+    if edit:
+      release = np.ascontiguousarray(release, dtype=np.int32)
+      if release.size != batch * self.cfg.targets_length:
         raise ValueError('release must hold one word per frame: [%d, %d]' % (batch, self.cfg.targets_length))
-      per_row = not (np.isscalar(seed) and np.isscalar(stream_id))
-      seeds, stream_ids = row_keys(batch if per_row else 1, seed, stream_id)
-      start = self.cfg.num_steps - 1 if start_step is None else int(start_step)
-      rc = self.lib.msd_sample_edit(self.handle, batch, RNGS[rng], int(per_row), (ctypes.c_uint64 * len(seeds))(*seeds),
-                                    (ctypes.c_uint64 * len(seeds))(*stream_ids), _ptr(init_z), _ptr(noise), _ptr(keep),
-                                    _ptr(words), start, _ptr(out), stream)
-      _check(self.lib, self.handle, rc, 'msd_sample_edit')
-      return
-    if start_step is not None:
+    elif start_step is not None:
       raise ValueError('start_step goes with release')
-    if (keep is None) != (keep_mask is None):
+    elif (keep is None) != (keep_mask is None):
       raise ValueError('keep and keep_mask go together')
-    if keep is not None:
-      per_row = not (np.isscalar(seed) and np.isscalar(stream_id))
-      seeds, stream_ids = row_keys(batch if per_row else 1, seed, stream_id)
-      rc = self.lib.msd_sample_keep(self.handle, batch, RNGS[rng], int(per_row), (ctypes.c_uint64 * len(seeds))(*seeds),
-                                    (ctypes.c_uint64 * len(seeds))(*stream_ids), _ptr(init_z), _ptr(noise), _ptr(keep),
-                                    _ptr(keep_mask), _ptr(out), stream)
-      _check(self.lib, self.handle, rc, 'msd_sample_keep')
-      return
-    if not (np.isscalar(seed) and np.isscalar(stream_id)):
-      seeds, stream_ids = row_keys(batch, seed, stream_id)
-      rc = self.lib.msd_sample_rows(self.handle, batch, RNGS[rng], (ctypes.c_uint64 * batch)(*seeds),
-                                    (ctypes.c_uint64 * batch)(*stream_ids), _ptr(init_z), _ptr(noise), _ptr(out), stream)
+    # (2) the keys: one for the whole array, or one per row
+    per_row = not (np.isscalar(seed) and np.isscalar(stream_id))
+    seeds, stream_ids = row_keys(batch if per_row else 1, seed, stream_id)
+    keys = (ctypes.c_uint64 * len(seeds))(*seeds), (ctypes.c_uint64 * len(seeds))(*stream_ids)
+    # (3) the entry point
+    lib, h, kind, draws, tail = self.lib, self.handle, RNGS[rng], (_ptr(init_z), _ptr(noise)), (_ptr(out), stream)
+    if few:
+      name, rc = 'msd_sample_steps', lib.msd_sample_steps(h, batch, kind, int(per_row), *keys, *draws, int(steps or 0),
+                                                          -1 if sampler is None else SAMPLERS[sampler], *tail)
+    elif edit:
+      start = self.cfg.num_steps - 1 if start_step is None else int(start_step)
+      name, rc = 'msd_sample_edit', lib.msd_sample_edit(h, batch, kind, int(per_row), *keys, *draws, _ptr(keep), _ptr(release), start, *tail)
+    elif keep is not None:
+      name, rc = 'msd_sample_keep', lib.msd_sample_keep(h, batch, kind, int(per_row), *keys, *draws, _ptr(keep), _ptr(keep_mask), *tail)
+    elif per_row:
+      name, rc = 'msd_sample', lib.msd_sample_rows(h, batch, kind, *keys, *draws, *tail)
     elif rng == 'philox':   # (the entry point every ABI has: an older library under MSD_AMD_LIB still runs)
-      rc = self.lib.msd_sample(self.handle, batch, seed, stream_id, _ptr(init_z), _ptr(noise), _ptr(out), stream)
+      name, rc = 'msd_sample', lib.msd_sample(h, batch, seed, stream_id, *draws, *tail)
     else:
-      rc = self.lib.msd_sample_rng(self.handle, batch, RNGS[rng], seed, stream_id, _ptr(init_z), _ptr(noise),
-                                   _ptr(out), stream)
-    _check(self.lib, self.handle, rc, 'msd_sample')
+      name, rc = 'msd_sample', lib.msd_sample_rng(h, batch, kind, seed, stream_id, *draws, *tail)
+    _check(lib, h, rc, name)
 
   def reset_graph(self):
     _check(self.lib, self.handle, self.lib.msd_reset_graph(self.handle), 'msd_reset_graph')

@@ -227,13 +227,16 @@ def test_predict_plans_the_strength_and_hands_it_to_the_device_call():
   mask = np.zeros((1, 64), bool)
   mask[0, :8] = True
   assert m.predict(batch, keep=known, strength=0.5, keep_mask=mask) == 'out'
-  keep, keep_mask, (words, start) = seen[0][-3:]
-  assert keep is known and keep_mask is None and start == 1            # N = 4: two steps
+  call = seen[0][-1]   # (the one call form predict hands down: inference.SampleCall)
+  words = call.release
+  assert call.keep is known and call.keep_mask is None and call.start_step == 1            # N = 4: two steps
   assert (words[0, :8] == 1).all() and (words[0, 8:] == 3).all()
+  assert call.steps is None and call.sampler is None
   # keep + keep_mask without strength: today's call, untouched
   m.predict(batch, keep=known, keep_mask=mask)
-  keep, keep_mask, edit = seen[1][-3:]
-  assert edit is None and keep_mask.dtype == np.int32 and keep_mask.sum() == 8
+  call = seen[1][-1]
+  assert call.release is None and call.start_step is None and call.keep is known
+  assert call.keep_mask.dtype == np.int32 and call.keep_mask.sum() == 8
 
 
 def _stub(m, seen):
