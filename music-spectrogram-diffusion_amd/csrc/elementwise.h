@@ -288,7 +288,7 @@ struct SamplerParams {
 
 // The keep form's arguments (msd_sample_keep): frames of the target that are KNOWN.  A struct of its own, so that the
 // plain instances' argument block stays at its 120 bytes -- two of the 64-byte lines warm_kernargs counts in, one 128-byte
-// cache line -- and their code is what it was; the keep form's 144 bytes take a third 64-byte line.
+// cache line; the keep form's 144 bytes take a third 64-byte line.
 struct SamplerKeepParams : SamplerParams {
   const float* xk = nullptr;     // [n] the known mel in model units (scale_clip_kernel of the caller's mel)
   const int32_t* keep = nullptr; // [n / n_dims] per frame, a release word v: 0 = free at every step; v >= 1 = known at scan
@@ -296,67 +296,20 @@ struct SamplerKeepParams : SamplerParams {
   int n_dims = 0;                // elements per frame, % 4 == 0: a thread's four elements lie in one frame
 };
 
+// The update's arithmetic is ONE text, and the operation order is that text: contraction is off, every fused
+// multiply-add is an fmaf written here, and every form of the update -- plain, keep, the multistep form's x0 -- is an
+// instance of sampler_update below.  ("A zero keep mask is the plain call, bit for bit" is a statement about rounding:
+// with contraction left to the compiler the forms fused the DDPM line differently, 26 % of the free elements off by an ulp
+// or more on the MI355X)  The order is the one the compiler chose for the first, unpinned text, read off its
+// disassembly: every difference of a product fused (fma(-a, b, c)), the CFG combine as two rounded products and a sum,
+// the DDPM line as fma(std, nz, (a z) + (b x0)), the DDIM line as fma(sigma, eps, alpha x0).  v mode's alpha z - sigma v
+// rounds both products in the conditional pass and fuses the second in the unconditional one: that pass reused the
+// first product, so only the other was left to fuse.
+//
 // model output -> (eps, x0) at the TRAIN schedule's log-SNR (diffusion_utils.py:288-322)
 template <int mode>
 __device__ __forceinline__ void convert_model_output(const float (&c)[kCoefCount], float z, float o,
-                                                     float& eps, float& x0) {
-  if constexpr (mode == kOutEps) {
-    eps = o;
-    x0 = c[kCoefMX0Scale] * (z - o * c[kCoefMX0Eps]);
-  } else if constexpr (mode == kOutX0) {
-    x0 = o;
-    eps = c[kCoefMEpsScale] * (z - o * c[kCoefMEpsX0]);
-  } else {  // v: x0 = alpha z - sigma v
-    x0 = c[kCoefMAlpha] * z - c[kCoefMSigma] * o;
-    eps = c[kCoefMEpsScale] * (z - x0 * c[kCoefMEpsX0]);
-  }
-}
-
-// one element of eval_step.body after the decoder calls (diffusion_utils.py:416-452):
-// o_c / o_u = conditional / unconditional model output, nz = the step's normal draw
-template <int MODE>
-__device__ __forceinline__ float sampler_update(const SamplerParams& p, const float (&c)[kCoefCount], int i, float z,
-                                                float o_c, float o_u, float nz) {
-  float eps, x0;
-  convert_model_output<MODE>(c, z, o_c, eps, x0);
-  if (p.passes == 2) {
-    float eps_u, x0_u;
-    convert_model_output<MODE>(c, z, o_u, eps_u, x0_u);
-    eps = p.cond_wt * eps + (1.0f - p.cond_wt) * eps_u;
-    x0 = c[kCoefX0Scale] * (z - eps * c[kCoefX0Eps]);
-  }
-  if (p.clip_x0) {
-    // jnp.clip semantics: a NaN stays a NaN (fminf / fmaxf would turn it into a bound and hide a poisoned input --
-    // the half-plane range flag sees Inf but not NaN: v_max3_f32 drops NaN operands)
-    x0 = x0 < -1.0f ? -1.0f : (x0 > 1.0f ? 1.0f : x0);
-    eps = c[kCoefEpsScale] * (z - x0 * c[kCoefEpsX0]);
-  }
-  float zs;
-  if (p.ddim) zs = c[kCoefAlphaS] * x0 + c[kCoefSigmaS] * eps;
-  else zs = c[kCoefMeanZ] * z + c[kCoefMeanX0] * x0 + c[kCoefStd] * nz;
-  return (i == 0) ? x0 : zs;
-}
-
-// The update with KNOWN frames (msd_sample_keep): sampler_update plus x0-replacement.  On a kept element (kf, xk = its
-// known value in model units), after the CFG combine and the clip: pred_x0 := xk, pred_eps := predict_eps_from_x0(z_t, xk,
-// logsnr_t) -- the clip branch's expression -- and the ordinary step: the element follows the posterior
-// q(z_s | z_t, x0 = xk) and arrives at xk at i == 0.
-//
-// Why this is a second text and not a branch inside sampler_update: a zero keep mask has to give the plain form's BITS,
-// and which products the compiler fuses into which sums is its own choice per compilation -- with the replacement as an
-// `if constexpr` inside the one function the DDPM line came out as fma(std, nz, a z + b x0) in the plain instances and as
-// fma(b, x0, a z) + std nz in the keep instances (measured on the MI355X: 26 % of the free elements off by an ulp or
-// more), and routing both through shared helpers moved the plain instances' code.  So sampler_update stays the text it
-// was -- its instances are instruction for instruction what they were before there was a keep form -- and this function
-// WRITES OUT the operations that text compiles to, with contraction off: every difference of a product fused
-// (fma(-a, b, c)), the CFG combine as two rounded products and a sum, the DDPM line as fma(std, nz, (a z) + (b x0)), the
-// DDIM line as fma(sigma, eps, alpha x0); v mode: alpha z - sigma v with both products rounded in the conditional pass
-// and the second fused in the unconditional one (that pass reuses the first product).  tests/test_gpu_keep_frames.py
-// holds the two together bit for bit on thirteen combinations of the branches (OP_CASES there); should a compiler choose otherwise for sampler_update, those
-// tests fail and this function follows it.
-template <int mode>
-__device__ __forceinline__ void convert_model_output_pinned(const float (&c)[kCoefCount], float z, float o,
-                                                            float& eps, float& x0, bool uncond) {
+                                                     float& eps, float& x0, bool uncond) {
 #pragma clang fp contract(off)
   if constexpr (mode == kOutEps) {
     eps = o;
@@ -364,32 +317,47 @@ __device__ __forceinline__ void convert_model_output_pinned(const float (&c)[kCo
   } else if constexpr (mode == kOutX0) {
     x0 = o;
     eps = c[kCoefMEpsScale] * fmaf(-o, c[kCoefMEpsX0], z);
-  } else {
+  } else {  // v: x0 = alpha z - sigma v
     const float az = c[kCoefMAlpha] * z;
     x0 = uncond ? fmaf(-o, c[kCoefMSigma], az) : az - c[kCoefMSigma] * o;
     eps = c[kCoefMEpsScale] * fmaf(-x0, c[kCoefMEpsX0], z);
   }
 }
 
-template <int MODE>
-__device__ __forceinline__ float sampler_update_keep(const SamplerParams& p, const float (&c)[kCoefCount], int i, float z,
-                                                     float o_c, float o_u, float nz, float xk, bool kf) {
+// one element of eval_step.body after the decoder calls (diffusion_utils.py:416-452):
+// o_c / o_u = conditional / unconditional model output, nz = the step's normal draw.
+// FORM: kFormPlain = the step; kFormKeep = the step with KNOWN frames (msd_sample_keep): on a kept element (kf, xk = its
+// known value in model units), after the CFG combine and the clip, pred_x0 := xk and pred_eps := predict_eps_from_x0(z_t,
+// xk, logsnr_t) -- the clip branch's expression -- so the element follows the posterior q(z_s | z_t, x0 = xk) and arrives
+// at xk at i == 0; kFormX0 = pred_x0 alone (converted, combined, clipped), what the multistep form steps from.
+enum { kFormPlain = 0, kFormKeep, kFormX0 };
+template <int MODE, int FORM>
+__device__ __forceinline__ float sampler_update(const SamplerParams& p, const float (&c)[kCoefCount], int i, float z,
+                                                float o_c, float o_u, float nz = 0.f, float xk = 0.f, bool kf = false) {
 #pragma clang fp contract(off)
   float eps, x0;
-  convert_model_output_pinned<MODE>(c, z, o_c, eps, x0, /*uncond=*/false);
+  convert_model_output<MODE>(c, z, o_c, eps, x0, /*uncond=*/false);
   if (p.passes == 2) {
     float eps_u, x0_u;
-    convert_model_output_pinned<MODE>(c, z, o_u, eps_u, x0_u, /*uncond=*/true);
+    convert_model_output<MODE>(c, z, o_u, eps_u, x0_u, /*uncond=*/true);
     eps = p.cond_wt * eps + (1.0f - p.cond_wt) * eps_u;
     x0 = c[kCoefX0Scale] * fmaf(-eps, c[kCoefX0Eps], z);
   }
+  // jnp.clip semantics: a NaN stays a NaN (fminf / fmaxf would turn it into a bound and hide a poisoned input --
+  // the half-plane range flag sees Inf but not NaN: v_max3_f32 drops NaN operands)
+  if constexpr (FORM == kFormX0) {
+    if (p.clip_x0) x0 = x0 < -1.0f ? -1.0f : (x0 > 1.0f ? 1.0f : x0);
+    return x0;
+  }
   if (p.clip_x0) {
-    x0 = x0 < -1.0f ? -1.0f : (x0 > 1.0f ? 1.0f : x0);   // (jnp.clip semantics, as in sampler_update)
+    x0 = x0 < -1.0f ? -1.0f : (x0 > 1.0f ? 1.0f : x0);
     eps = c[kCoefEpsScale] * fmaf(-x0, c[kCoefEpsX0], z);
   }
-  if (kf) {
-    x0 = xk;
-    eps = c[kCoefEpsScale] * fmaf(-xk, c[kCoefEpsX0], z);
+  if constexpr (FORM == kFormKeep) {
+    if (kf) {
+      x0 = xk;
+      eps = c[kCoefEpsScale] * fmaf(-xk, c[kCoefEpsX0], z);
+    }
   }
   float zs;
   if (p.ddim) zs = fmaf(c[kCoefSigmaS], eps, c[kCoefAlphaS] * x0);
@@ -397,11 +365,26 @@ __device__ __forceinline__ float sampler_update_keep(const SamplerParams& p, con
   return (i == 0) ? x0 : zs;
 }
 
+// What both sampler kernels (this file, multistep_tail.h) share around the update.  (Their third common piece, the store
+// of z as operand planes, stays written out in each kernel and in diffuse_to_step_kernel: as a helper, by reference or
+// by value, it changed the instructions of all nine sampler instances and of that kernel.)
+// Row i of the coefficient table as five 16-byte loads (20 floats, rows 80 bytes apart)
+__device__ __forceinline__ void load_coef_row(const float* coef, int i, f32x4 (&cr)[5]) {
+  static_assert(kCoefCount == 20, "five 16-byte loads per row");
+#pragma unroll
+  for (int k = 0; k < 5; ++k) cr[k] = reinterpret_cast<const f32x4*>(coef + (size_t)i * kCoefCount)[k];
+}
+// The next scan index, published by the launch's last block: every block has read *step_ptr before any kernel of the
+// next step can start (kernel boundary); the decrement is ordered by the same boundary.
+__device__ __forceinline__ void publish_next_step(const SamplerParams& p, int i) {
+  __syncthreads();
+  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) p.step_ptr[p.step_from_slot1 ? 0 : 1] = i - 1;
+}
+
 // MODE = p.model_output as a compile-time constant: with the run-time switch the conversions' two results travelled
 // through scratch memory and a maze of scalar branches (885 lines of ISA for an elementwise kernel)
 // P = SamplerKeepParams: the keep form -- the frame flag and the known values are loaded with z / eps and handed to
-// sampler_update_keep.  One kernel for both, the difference under `if constexpr`: the plain instances' code is what it
-// was when there was no other form.
+// sampler_update's keep form.  One kernel for both, the difference under `if constexpr`.
 template <int MODE, class P = SamplerParams>
 __global__ void __launch_bounds__(256) sampler_step_kernel(P p) {
   constexpr bool KEEP = std::is_same<P, SamplerKeepParams>::value;
@@ -441,10 +424,8 @@ __global__ void __launch_bounds__(256) sampler_step_kernel(P p) {
       // the frame's release word -> known in THIS step: one unsigned compare (v == 0 wraps to 2^32 - 1: never known)
       kf = (uint32_t)p.keep[(uint32_t)idx / (uint32_t)p.n_dims] - 1u <= (uint32_t)i;
     }
-    static_assert(kCoefCount == 20, "five 16-byte loads per row");
     f32x4 cr[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) cr[k] = reinterpret_cast<const f32x4*>(p.coef + (size_t)i * kCoefCount)[k];
+    load_coef_row(p.coef, i, cr);
     if (!p.ddim && i != 0) {
       // per-row mode (the same in every lane): the draw covers this row's R = row_blocks * kRngRowBlock elements and e is
       // the element inside the row -- what a one-row call under this row's key draws; else the whole array, e = idx
@@ -472,10 +453,8 @@ __global__ void __launch_bounds__(256) sampler_step_kernel(P p) {
     for (int k = 0; k < kCoefCount; ++k) c[k] = cr[k >> 2][k & 3];
     f32x4 out;
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      if constexpr (KEEP) out[k] = sampler_update_keep<MODE>(p, c, i, zz[k], ec[k], eu[k], nz[k], xk[k], kf != 0);
-      else out[k] = sampler_update<MODE>(p, c, i, zz[k], ec[k], eu[k], nz[k]);
-    }
+    for (int k = 0; k < 4; ++k)
+      out[k] = sampler_update<MODE, KEEP ? kFormKeep : kFormPlain>(p, c, i, zz[k], ec[k], eu[k], nz[k], xk[k], kf != 0);
     *reinterpret_cast<f32x4*>(p.z + idx) = out;
     if (p.z_hi) {
       uint32_t h[2], l[2];
@@ -490,17 +469,21 @@ __global__ void __launch_bounds__(256) sampler_step_kernel(P p) {
       rc.commit(p.sat, p.sat_tag);
     }
   }
-  // every block has read *step_ptr before any kernel of the next step can start
-  // (kernel boundary); the decrement is ordered by the same boundary.
-  __syncthreads();
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) p.step_ptr[p.step_from_slot1 ? 0 : 1] = i - 1;
+  publish_next_step(p, i);
 }
 
-inline void launch_sampler_step(const SamplerParams& sp, hipStream_t s) {
+// One launch of a family of sampler kernels, a float4 per thread: sp.model_output picks the instance, and
+// kernel_of(ModeTag<MODE>) names the family's kernel of that mode.
+template <int MODE> using ModeTag = std::integral_constant<int, MODE>;
+template <class P, class F>
+static inline void launch_sampler_family(const P& sp, hipStream_t s, F kernel_of) {
   const dim3 grid((sp.n / 4 + 255) / 256), block(256);
-  if (sp.model_output == kOutX0) hipLaunchKernelGGL(sampler_step_kernel<kOutX0>, grid, block, 0, s, sp);
-  else if (sp.model_output == kOutV) hipLaunchKernelGGL(sampler_step_kernel<kOutV>, grid, block, 0, s, sp);
-  else hipLaunchKernelGGL(sampler_step_kernel<kOutEps>, grid, block, 0, s, sp);
+  if (sp.model_output == kOutX0) hipLaunchKernelGGL(kernel_of(ModeTag<kOutX0>{}), grid, block, 0, s, sp);
+  else if (sp.model_output == kOutV) hipLaunchKernelGGL(kernel_of(ModeTag<kOutV>{}), grid, block, 0, s, sp);
+  else hipLaunchKernelGGL(kernel_of(ModeTag<kOutEps>{}), grid, block, 0, s, sp);
+}
+inline void launch_sampler_step(const SamplerParams& sp, hipStream_t s) {
+  launch_sampler_family(sp, s, [](auto m) { return sampler_step_kernel<decltype(m)::value, SamplerParams>; });
 }
 // the keep form's launches: keep_frames_tail.h, which msd_api.hip includes last (the reason is written there)
 void launch_sampler_step(const SamplerKeepParams& sp, hipStream_t s);
@@ -527,7 +510,7 @@ void launch_diffuse_to_step(const DiffuseParams& dp, hipStream_t s);
 void launch_normalize_flags(const int32_t* in, int32_t* out, int n, hipStream_t s);
 
 // The multistep form's arguments (msd_sample_steps with MSD_SAMPLER_DPMPP_2M; kernel and launch: multistep_tail.h).  A
-// struct of its own for the keep form's reason: the plain instances' argument block stays what it is.
+// struct of its own for the keep form's reason: the plain instances' argument block stays at its two 64-byte lines.
 // Row i of the side table coef_ms: {sigma_s / sigma_t, -alpha_s expm1(-h), 1 / (2r), 0} (msd_api.hip build_multistep_rows)
 enum { kMsZ = 0, kMsD, kMsHist, kMsPad, kMsCount };
 struct SamplerMultistepParams : SamplerParams {

@@ -11,10 +11,7 @@
 #include "elementwise.h"
 namespace msd {
 void launch_sampler_step(const SamplerKeepParams& sp, hipStream_t s) {
-  const dim3 grid((sp.n / 4 + 255) / 256), block(256);
-  if (sp.model_output == kOutX0) hipLaunchKernelGGL((sampler_step_kernel<kOutX0, SamplerKeepParams>), grid, block, 0, s, sp);
-  else if (sp.model_output == kOutV) hipLaunchKernelGGL((sampler_step_kernel<kOutV, SamplerKeepParams>), grid, block, 0, s, sp);
-  else hipLaunchKernelGGL((sampler_step_kernel<kOutEps, SamplerKeepParams>), grid, block, 0, s, sp);
+  launch_sampler_family(sp, s, [](auto m) { return sampler_step_kernel<decltype(m)::value, SamplerKeepParams>; });
 }
 
 // the same on the free frames; a frame known THROUGHOUT (release word 1: msd_sample_keep's kept frame) gets the caller's own

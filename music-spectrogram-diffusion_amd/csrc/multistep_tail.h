@@ -1,14 +1,15 @@
 // The sampler's MULTISTEP form (msd_sample_steps with MSD_SAMPLER_DPMPP_2M): DPM-Solver++(2M) in data-prediction form, one
 // kernel per model-output mode, and its launch.  Like keep_frames_tail.h this file belongs to msd_api.hip alone and is
-// included LAST, behind keep_frames_tail.h: its instances land behind every kernel the library had before, and the plain
-// and keep instances of sampler_step_kernel stay instruction for instruction what they were (elementwise.h, "Why this is
-// a second text").  It is a kernel of its own and not a third form of sampler_step_kernel for the same reason.
+// included LAST, behind keep_frames_tail.h: its instances land behind every kernel the library had before (placement
+// shows on the clock: keep_frames_tail.h).  It is a kernel of its own and not a third form of sampler_step_kernel, whose
+// load order is a measured form: this one makes no draw and has none of that kernel's noise and key loads.
 //
 // With the half-log-SNR lambda = logsnr / 2, h = lambda_s - lambda_t and r = h_prev / h (h_prev: the step before this one):
 //   D   = x0_t                                      on the first step of a call
 //   D   = x0_t + (1 / (2r)) (x0_t - x0_prev)        afterwards          [= (1 + 1/(2r)) x0_t - (1/(2r)) x0_prev]
 //   z_s = (sigma_s / sigma_t) z_t + (-alpha_s expm1(-h)) D              i == 0 returns x0_t (the reference's convention)
-// x0_t is sampler_update's pred_x0: after the model-output conversion, the CFG combine and the clip.  With D = x0_t the
+// x0_t is sampler_update's x0-only form (elementwise.h: one text for every form): pred_x0 after the model-output
+// conversion, the CFG combine and the clip.  With D = x0_t the
 // last line is ddim_step, rearranged.  No draw: the form is deterministic after init_z.
 //
 // The three step coefficients come from a [K][4] side table (msd_api.hip build_multistep_rows: {sigma_s / sigma_t,
@@ -17,23 +18,6 @@
 #pragma once
 #include "elementwise.h"
 namespace msd {
-// pred_x0 of sampler_update, on the pinned conversions of the keep form (contraction off: the operation order is the text)
-template <int MODE>
-__device__ __forceinline__ float multistep_pred_x0(const SamplerParams& p, const float (&c)[kCoefCount], float z, float o_c,
-                                                   float o_u) {
-#pragma clang fp contract(off)
-  float eps, x0;
-  convert_model_output_pinned<MODE>(c, z, o_c, eps, x0, /*uncond=*/false);
-  if (p.passes == 2) {
-    float eps_u, x0_u;
-    convert_model_output_pinned<MODE>(c, z, o_u, eps_u, x0_u, /*uncond=*/true);
-    eps = p.cond_wt * eps + (1.0f - p.cond_wt) * eps_u;
-    x0 = c[kCoefX0Scale] * fmaf(-eps, c[kCoefX0Eps], z);
-  }
-  if (p.clip_x0) x0 = x0 < -1.0f ? -1.0f : (x0 > 1.0f ? 1.0f : x0);   // (jnp.clip semantics, as in sampler_update)
-  return x0;
-}
-
 template <int MODE>
 __global__ void __launch_bounds__(256) sampler_multistep_kernel(SamplerMultistepParams p) {
 #pragma clang fp contract(off)
@@ -48,10 +32,8 @@ __global__ void __launch_bounds__(256) sampler_multistep_kernel(SamplerMultistep
     if (p.passes == 2) eu = *reinterpret_cast<const f32x4*>(p.eps + p.n + idx);
     const bool first = i == p.first_step;   // (the same in every lane) no history yet: x0_prev is not read
     if (!first) xp = *reinterpret_cast<const f32x4*>(p.x0_prev + idx);
-    static_assert(kCoefCount == 20, "five 16-byte loads per row");
     f32x4 cr[5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k) cr[k] = reinterpret_cast<const f32x4*>(p.coef + (size_t)i * kCoefCount)[k];
+    load_coef_row(p.coef, i, cr);
     const f32x4 ms = *reinterpret_cast<const f32x4*>(p.coef_ms + (size_t)i * kMsCount);
     float c[kCoefCount];
 #pragma unroll
@@ -59,7 +41,7 @@ __global__ void __launch_bounds__(256) sampler_multistep_kernel(SamplerMultistep
     f32x4 out, x0v;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float x0 = multistep_pred_x0<MODE>(p, c, zz[k], ec[k], eu[k]);
+      const float x0 = sampler_update<MODE, kFormX0>(p, c, i, zz[k], ec[k], eu[k]);
       const float d = first ? x0 : fmaf(ms[kMsHist], x0 - xp[k], x0);
       const float zs = fmaf(ms[kMsZ], zz[k], ms[kMsD] * d);
       x0v[k] = x0;
@@ -80,15 +62,10 @@ __global__ void __launch_bounds__(256) sampler_multistep_kernel(SamplerMultistep
       rc.commit(p.sat, p.sat_tag);
     }
   }
-  // the scan index is published as sampler_step_kernel publishes it
-  __syncthreads();
-  if (blockIdx.x == gridDim.x - 1 && threadIdx.x == 0) p.step_ptr[p.step_from_slot1 ? 0 : 1] = i - 1;
+  publish_next_step(p, i);
 }
 
 void launch_sampler_step(const SamplerMultistepParams& sp, hipStream_t s) {
-  const dim3 grid((sp.n / 4 + 255) / 256), block(256);
-  if (sp.model_output == kOutX0) hipLaunchKernelGGL(sampler_multistep_kernel<kOutX0>, grid, block, 0, s, sp);
-  else if (sp.model_output == kOutV) hipLaunchKernelGGL(sampler_multistep_kernel<kOutV>, grid, block, 0, s, sp);
-  else hipLaunchKernelGGL(sampler_multistep_kernel<kOutEps>, grid, block, 0, s, sp);
+  launch_sampler_family(sp, s, [](auto m) { return sampler_multistep_kernel<decltype(m)::value>; });
 }
 }  // namespace msd

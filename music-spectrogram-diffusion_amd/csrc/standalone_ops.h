@@ -478,44 +478,62 @@ msd_gemm_site_args forced_site_args(TileShape tile, int M, int N, int K) {
   return g;
 }
 
+// What the sampler ops share, in ONE place: the argument checks, the coefficient rows of cfg (handed back: the multistep
+// entry derives its side table from them), the staged operands -- the passes of the model output side by side, z copied
+// into z_out (the kernel updates in place), the scan index in both slots -- and the SamplerParams every form starts from
+// (no draw, no planes).  Each entry adds its form's fields on top.
+int sampler_op_base(OpKit& kit, const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
+                    const float* out_uncond_dev, float* z_out_dev, int64_t n, SamplerParams* sp, std::vector<float>* rows) {
+  if (!cfg || cfg->struct_size != (int32_t)sizeof(msd_config) || !z_dev || !out_cond_dev || !z_out_dev ||
+      n <= 0 || n % 4 || n > 0x7FFFFFFFll || step_index < 0 || step_index >= cfg->num_steps)
+    return MSD_ERR_INVALID_ARGUMENT;
+  const int passes = cfg->cfg_weight != 1.0f ? 2 : 1;
+  if (passes == 2 && !out_uncond_dev) return MSD_ERR_INVALID_ARGUMENT;
+  std::string why;
+  if (!build_coef_rows(*cfg, rows, &why)) return MSD_ERR_INVALID_ARGUMENT;
+  hipStream_t s = kit.s;
+  float* coef = kit.get<float>(rows->size());
+  float* eps = kit.get<float>((size_t)passes * n);
+  int* step = kit.get<int>(2);
+  if (!coef || !eps || !step) return MSD_ERR_HIP;
+  const int st[2] = {step_index, step_index};
+  if (hipMemcpyAsync(coef, rows->data(), rows->size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(eps, out_cond_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+      (passes == 2 && hipMemcpyAsync(eps + n, out_uncond_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) ||
+      hipMemcpyAsync(z_out_dev, z_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(step, st, sizeof(st), hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return MSD_ERR_HIP;
+  sp->eps = eps; sp->z = z_out_dev; sp->noise_slot = nullptr; sp->coef = coef; sp->step_ptr = step;
+  sp->n = (int)n; sp->passes = passes; sp->cond_wt = cfg->cfg_weight; sp->clip_x0 = cfg->clip_x0;
+  sp->ddim = 0; sp->model_output = cfg->model_output;
+  sp->z_hi = nullptr; sp->z_lo = nullptr; sp->step_from_slot1 = 1;
+  return MSD_OK;
+}
+int sampler_op_finish(hipStream_t s) {
+  if (hipGetLastError() != hipSuccess) return MSD_ERR_HIP;
+  return hipStreamSynchronize(s) == hipSuccess ? MSD_OK : MSD_ERR_HIP;
+}
+
 // one launch of the sampler update on the caller's arrays; known_scaled_dev != NULL: the keep form, keep_mask_dev its
 // frames' release words, or -- flags -- msd_sample_keep's flags (any non-zero = known throughout)
 int op_sampler_step(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
                     const float* out_uncond_dev, const float* noise_dev, const float* known_scaled_dev,
                     const int32_t* keep_mask_dev, int n_dims, float* z_out_dev, int64_t n, void* stream, bool flags = false) {
-  if (!cfg || cfg->struct_size != (int32_t)sizeof(msd_config) || !z_dev || !out_cond_dev || !z_out_dev ||
-      n <= 0 || n % 4 || step_index < 0 || step_index >= cfg->num_steps)
-    return MSD_ERR_INVALID_ARGUMENT;
-  const int passes = cfg->cfg_weight != 1.0f ? 2 : 1;
-  if (passes == 2 && !out_uncond_dev) return MSD_ERR_INVALID_ARGUMENT;
-  std::vector<float> rows;
-  std::string why;
-  if (!build_coef_rows(*cfg, &rows, &why)) return MSD_ERR_INVALID_ARGUMENT;
   hipStream_t s = static_cast<hipStream_t>(stream);
   OpKit kit(s, 1);
-  float* coef = kit.get<float>(rows.size());
-  float* eps = kit.get<float>((size_t)passes * n);
+  SamplerKeepParams sp;
+  std::vector<float> rows;
+  if (const int rc = sampler_op_base(kit, cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, z_out_dev, n, &sp, &rows)) return rc;
   float* noise = kit.get<float>((size_t)n);   // one step's draw (zeros) when the caller gives none
   const float** slot = kit.get<const float*>(1);
-  int* step = kit.get<int>(2);
   uint32_t* key = kit.get<uint32_t>(kRngWords);   // the kernel fetches the words of its own draw up front, used or not (table row 0: SamplerParams::row_blocks' default)
-  if (!coef || !eps || !noise || !slot || !step || !key) return MSD_ERR_HIP;
+  if (!noise || !slot || !key) return MSD_ERR_HIP;
   // the kernel indexes noise as base + i * n: hand it base = draw - i * n
   const float* base = (noise_dev ? noise_dev : noise) - (size_t)step_index * n;
-  const int st[2] = {step_index, step_index};
-  if (hipMemcpyAsync(coef, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(eps, out_cond_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-      (passes == 2 && hipMemcpyAsync(eps + n, out_uncond_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) ||
-      hipMemcpyAsync(z_out_dev, z_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(slot, &base, sizeof(base), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(step, st, sizeof(st), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess)
+  if (hipMemcpyAsync(slot, &base, sizeof(base), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
     return MSD_ERR_HIP;
-  SamplerKeepParams sp;
-  sp.eps = eps; sp.z = z_out_dev; sp.noise_slot = slot; sp.coef = coef; sp.step_ptr = step; sp.rng_key = key;
-  sp.n = (int)n; sp.passes = passes; sp.cond_wt = cfg->cfg_weight; sp.clip_x0 = cfg->clip_x0;
-  sp.ddim = cfg->sampler == MSD_SAMPLER_DDIM; sp.model_output = cfg->model_output;
-  sp.z_hi = nullptr; sp.z_lo = nullptr; sp.step_from_slot1 = 1;
+  sp.noise_slot = slot; sp.rng_key = key; sp.ddim = cfg->sampler == MSD_SAMPLER_DDIM;
   if (known_scaled_dev) {
     sp.xk = known_scaled_dev; sp.keep = keep_mask_dev; sp.n_dims = n_dims;
     if (flags) {
@@ -528,8 +546,7 @@ int op_sampler_step(const msd_config* cfg, int step_index, const float* z_dev, c
   } else {
     launch_sampler_step(static_cast<const SamplerParams&>(sp), s);
   }
-  if (hipGetLastError() != hipSuccess) return MSD_ERR_HIP;
-  return hipStreamSynchronize(s) == hipSuccess ? MSD_OK : MSD_ERR_HIP;
+  return sampler_op_finish(s);
 }
 }  // namespace
 
@@ -680,40 +697,21 @@ int msd_op_sampler_step_release(const msd_config* cfg, int step_index, const flo
 int msd_op_sampler_step_multistep(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
                                   const float* out_uncond_dev, float* x0_prev_inout_dev, int first, float* z_out_dev,
                                   int64_t n, void* stream) {
-  if (!cfg || cfg->struct_size != (int32_t)sizeof(msd_config) || !z_dev || !out_cond_dev || !x0_prev_inout_dev || !z_out_dev ||
-      n <= 0 || n % 4 || n > 0x7FFFFFFFll || step_index < 0 || step_index >= cfg->num_steps)
-    return MSD_ERR_INVALID_ARGUMENT;
-  const int passes = cfg->cfg_weight != 1.0f ? 2 : 1;
-  if (passes == 2 && !out_uncond_dev) return MSD_ERR_INVALID_ARGUMENT;
-  std::vector<float> rows, ms;
-  std::string why;
-  if (!build_coef_rows(*cfg, &rows, &why)) return MSD_ERR_INVALID_ARGUMENT;
-  build_multistep_rows(rows, &ms);
+  if (!x0_prev_inout_dev) return MSD_ERR_INVALID_ARGUMENT;
   hipStream_t s = static_cast<hipStream_t>(stream);
   OpKit kit(s, 1);
-  float* coef = kit.get<float>(rows.size());
+  SamplerMultistepParams sp;   // (noise_slot / rng_key stay null: the form makes no draw and reads neither)
+  std::vector<float> rows, ms;
+  if (const int rc = sampler_op_base(kit, cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, z_out_dev, n, &sp, &rows)) return rc;
+  build_multistep_rows(rows, &ms);
   float* coef_ms = kit.get<float>(ms.size());
-  float* eps = kit.get<float>((size_t)passes * n);
-  int* step = kit.get<int>(2);
-  if (!coef || !coef_ms || !eps || !step) return MSD_ERR_HIP;
-  const int st[2] = {step_index, step_index};
-  if (hipMemcpyAsync(coef, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(coef_ms, ms.data(), ms.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(eps, out_cond_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-      (passes == 2 && hipMemcpyAsync(eps + n, out_uncond_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) ||
-      hipMemcpyAsync(z_out_dev, z_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(step, st, sizeof(st), hipMemcpyHostToDevice, s) != hipSuccess ||
+  if (!coef_ms) return MSD_ERR_HIP;
+  if (hipMemcpyAsync(coef_ms, ms.data(), ms.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
     return MSD_ERR_HIP;
-  SamplerMultistepParams sp;   // (noise_slot / rng_key stay null: the form makes no draw and reads neither)
-  sp.eps = eps; sp.z = z_out_dev; sp.noise_slot = nullptr; sp.coef = coef; sp.step_ptr = step;
-  sp.n = (int)n; sp.passes = passes; sp.cond_wt = cfg->cfg_weight; sp.clip_x0 = cfg->clip_x0;
-  sp.ddim = 0; sp.model_output = cfg->model_output;
-  sp.z_hi = nullptr; sp.z_lo = nullptr; sp.step_from_slot1 = 1;
   sp.x0_prev = x0_prev_inout_dev; sp.coef_ms = coef_ms; sp.first_step = first ? step_index : -1;
   launch_sampler_step(sp, s);
-  if (hipGetLastError() != hipSuccess) return MSD_ERR_HIP;
-  return hipStreamSynchronize(s) == hipSuccess ? MSD_OK : MSD_ERR_HIP;
+  return sampler_op_finish(s);
 }
 
 int msd_op_diffuse_to_step(const msd_config* cfg, int step_index, const float* mel_dev, const float* eps_dev,

@@ -1,5 +1,8 @@
 """Shared test helpers: product spec -> oracle configs, seeded inputs."""
+import dataclasses
+
 import numpy as np
+import pytest
 
 import msd_amd
 from oracle import backend, fast, net, predict, sampler
@@ -56,6 +59,63 @@ def make_noise(spec, batch=1, seed=11):
   steps = spec.diffusion.sampler.schedule.num_steps
   return (rng.standard_normal((batch, t, n)).astype(np.float32),
           rng.standard_normal((steps, batch, t, n)).astype(np.float32))
+
+
+# ---- what the GPU suites of the sampler's forms share (test_gpu_keep_frames, _edit_strength, _few_steps, _sample_forms,
+# the sampler cases of test_gpu_fused_ops) ----
+@pytest.fixture(scope='module', name='torch')
+def gpu_torch():
+  """Those modules' `torch` fixture (a module imports this function by name): torch, with the MI355X present and the
+  library loaded."""
+  import torch
+  assert torch.cuda.is_available(), 'these tests need the MI355X'
+  msd_amd.native.load()
+  return torch
+
+
+def dev(torch, a, dtype=np.float32):
+  return torch.as_tensor(np.ascontiguousarray(a, dtype)).cuda()
+
+
+def bits(a):
+  return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+def known_mel(shape, seed=21):
+  """A mel that leaves the codec's range [log 1e-5, 4] at both ends."""
+  return np.random.default_rng(seed).uniform(-13.0, 5.0, shape).astype(np.float32)
+
+
+def sampler_spec(sampler='ddpm', model_output='eps', logvar='large', schedule='cosine', train='cosine',
+                 cfg_weight=5.0, clip=True, steps=50):
+  """The tiny preset with every switch of the sampler update's arithmetic (the stand-alone sampler ops)."""
+  from msd_amd import config as C
+  spec = msd_amd.config.preset('tiny', num_steps=steps, cfg_weight=cfg_weight)
+  d = spec.diffusion
+  ss = C.DiffusionSchedule(schedule, start=1e-4 if schedule == 'linear' else None,
+                           stop=2e-2 if schedule == 'linear' else None, num_steps=steps)
+  ts = C.DiffusionSchedule(train, start=2e-4 if train == 'linear' else None,
+                           stop=3e-2 if train == 'linear' else None, num_steps=80 if train == 'linear' else None)
+  d = dataclasses.replace(d, model_output=model_output, train_schedule=ts,
+                          sampler=dataclasses.replace(d.sampler, name=sampler, logvar_type=logvar, clip_x0=clip,
+                                                      schedule=ss))
+  return dataclasses.replace(spec, diffusion=d)
+
+
+def preset_spec(preset, steps, sampler='ddpm'):
+  spec = msd_amd.config.preset(preset, num_steps=steps)
+  d = spec.diffusion
+  return dataclasses.replace(spec, diffusion=dataclasses.replace(d, sampler=dataclasses.replace(d.sampler, name=sampler)))
+
+
+def cached_model(cache, preset, steps, sampler='ddpm'):
+  """(spec, params, model) -- one two-row handle per configuration in the calling module's `cache`."""
+  key = (preset, steps, sampler)
+  if key not in cache:
+    spec = preset_spec(preset, steps, sampler)
+    params = msd_amd.synthetic.init_params(spec, 3, norm_scale_jitter=0.1)
+    cache[key] = (spec, params, msd_amd.InferenceModel(params, spec, batch_size=2, **ALL_PLANES))
+  return cache[key]
 
 
 def rms(a, b):

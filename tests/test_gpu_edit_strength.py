@@ -3,37 +3,14 @@ regenerate(blend_frames=)) against the specification of tests/edit_spec.py: test
 keep := (i >= f) per step, a scan from start_step down and the known mel diffused to the start index.
 
 Presets tiny / tiny_context: T = 64, n = 128, i.e. eight 1024-element sampler blocks per row, 32 threads per frame."""
-import dataclasses
-
 import numpy as np
 import pytest
 
 import msd_amd
 from tests import edit_spec, helpers, keep_spec
-from tests.test_gpu_fused_ops import _sampler_spec
+from tests.helpers import gpu_torch  # noqa: F401  (the `torch` fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope='module')
-def torch():
-  import torch
-  assert torch.cuda.is_available(), 'these tests need the MI355X'
-  msd_amd.native.load()
-  return torch
-
-
-def _dev(torch, a, dtype=np.float32):
-  return torch.as_tensor(np.ascontiguousarray(a, dtype)).cuda()
-
-
-def _known(shape, seed=21):
-  """A mel that leaves the codec's range [log 1e-5, 4] at both ends."""
-  return np.random.default_rng(seed).uniform(-13.0, 5.0, shape).astype(np.float32)
-
-
-def _bits(a):
-  return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -49,7 +26,7 @@ def test_op_release_is_the_keep_op_or_the_plain_op_per_frame(torch, case):
   and i + 2 in another pattern per row: a frame with i >= v - 1 (v >= 1) holds msd_op_sampler_step_keep's bits with flag
   1, every other frame msd_op_sampler_step's; at i == 0 only v == 1 frames are the known values' bits."""
   from msd_amd import inference, native
-  spec = _sampler_spec(**case)
+  spec = helpers.sampler_spec(**case)
   cfg = inference._to_native_config(spec, msd_amd.audio_codecs.MelGAN(), 1, 'f16x3')
   steps = spec.diffusion.sampler.schedule.num_steps
   two_pass = spec.diffusion.classifier_free_guidance.eval_condition_weight != 1
@@ -62,22 +39,22 @@ def test_op_release_is_the_keep_op_or_the_plain_op_per_frame(torch, case):
     assert known_now.any() and (~known_now).any() and (words[known_now] > 1).any() == (i > 0)
     z, oc, ou, nz = (rng.standard_normal(shape).astype(np.float32) for _ in range(4))
     xk = rng.uniform(-1.0, 1.0, shape).astype(np.float32)
-    args = (_dev(torch, z), _dev(torch, oc), _dev(torch, ou) if two_pass else None, _dev(torch, nz))
-    xk_t = _dev(torch, xk)
+    args = (helpers.dev(torch, z), helpers.dev(torch, oc), helpers.dev(torch, ou) if two_pass else None, helpers.dev(torch, nz))
+    xk_t = helpers.dev(torch, xk)
     outs = {}
     for name in ('release', 'keep', 'plain'):
       outs[name] = torch.full(shape, float('nan'), dtype=torch.float32, device='cuda')
-    native.op_sampler_step_release(cfg, i, *args, xk_t, _dev(torch, words, np.int32), outs['release'])
-    native.op_sampler_step_keep(cfg, i, *args, xk_t, _dev(torch, 7 * np.ones((2, 16)), np.int32), outs['keep'])   # (any non-zero flag)
+    native.op_sampler_step_release(cfg, i, *args, xk_t, helpers.dev(torch, words, np.int32), outs['release'])
+    native.op_sampler_step_keep(cfg, i, *args, xk_t, helpers.dev(torch, 7 * np.ones((2, 16)), np.int32), outs['keep'])   # (any non-zero flag)
     native.op_sampler_step(cfg, i, *args, outs['plain'])
     got, keep, plain = (outs[k].cpu().numpy() for k in ('release', 'keep', 'plain'))
     kn = np.broadcast_to(known_now[..., None], shape)
-    np.testing.assert_array_equal(_bits(got[kn]), _bits(keep[kn]))
-    np.testing.assert_array_equal(_bits(got[~kn]), _bits(plain[~kn]))
+    np.testing.assert_array_equal(helpers.bits(got[kn]), helpers.bits(keep[kn]))
+    np.testing.assert_array_equal(helpers.bits(got[~kn]), helpers.bits(plain[~kn]))
     assert not np.array_equal(keep[kn], plain[kn])   # (the two differ where it matters)
     if i == 0:
       np.testing.assert_array_equal(known_now, words == 1)
-      np.testing.assert_array_equal(_bits(got[kn]), _bits(xk[kn]))
+      np.testing.assert_array_equal(helpers.bits(got[kn]), helpers.bits(xk[kn]))
       assert not np.array_equal(got[~kn], xk[~kn])
 
 
@@ -94,7 +71,7 @@ def test_op_diffuse_to_step_vs_spec(torch, n, precision):
   from msd_amd import inference, native
   from oracle import backend, predict
   shape = (1, n // 4, 4)
-  spec = _sampler_spec()
+  spec = helpers.sampler_spec()
   codec = predict.MelGANCodec()
   cfg = inference._to_native_config(spec, msd_amd.audio_codecs.MelGAN(), 1, precision)
   _, dc = helpers.oracle_configs(spec)
@@ -113,9 +90,9 @@ def test_op_diffuse_to_step_vs_spec(torch, n, precision):
       xk = codec.scale_features(xp, xp.asarray(mel), (-1., 1.), clip=True)
       refs[name] = np.asarray(edit_spec.start_state(xp, dc, xk, xp.asarray(eps), i), np.float64)
     z_t, zp_t, xk_t = (torch.full(shape, float('nan'), dtype=torch.float32, device='cuda') for _ in range(3))
-    native.op_diffuse_to_step(cfg, i, _dev(torch, mel), _dev(torch, eps), z_t, zp_t, xk_t)
+    native.op_diffuse_to_step(cfg, i, helpers.dev(torch, mel), helpers.dev(torch, eps), z_t, zp_t, xk_t)
     z, zp, xk_dev = z_t.cpu().numpy(), zp_t.cpu().numpy(), xk_t.cpu().numpy()
-    np.testing.assert_array_equal(_bits(xk_dev), _bits(xk_bits))
+    np.testing.assert_array_equal(helpers.bits(xk_dev), helpers.bits(xk_bits))
     scale = max(1.0, float(np.abs(refs['f64']).max()))
     e_dev = np.abs(z.astype(np.float64) - refs['f64']).max() / scale
     e_f32 = np.abs(refs['f32'] - refs['f64']).max() / scale
@@ -132,12 +109,6 @@ def test_op_diffuse_to_step_vs_spec(torch, n, precision):
 # --------------------------------------------------------------------------------------------------
 # models
 # --------------------------------------------------------------------------------------------------
-def _spec(preset, steps, sampler='ddpm'):
-  spec = msd_amd.config.preset(preset, num_steps=steps)
-  d = spec.diffusion
-  return dataclasses.replace(spec, diffusion=dataclasses.replace(d, sampler=dataclasses.replace(d.sampler, name=sampler)))
-
-
 _models = {}
 
 
@@ -146,13 +117,7 @@ def _handle(spec, params):
 
 
 def _model(torch, preset='tiny_context', steps=16, sampler='ddpm'):
-  """(spec, params, model) -- one handle per configuration for the whole module."""
-  key = (preset, steps, sampler)
-  if key not in _models:
-    spec = _spec(preset, steps, sampler)
-    params = msd_amd.synthetic.init_params(spec, 3, norm_scale_jitter=0.1)
-    _models[key] = (spec, params, _handle(spec, params))
-  return _models[key]
+  return helpers.cached_model(_models, preset, steps, sampler)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -164,13 +129,13 @@ def test_strength_one_minus_mask_is_the_keep_call(torch, steps, rng):
   spec, _, model = _model(torch, 'tiny_context', steps)
   for b, keys in ((1, dict(seed=4, segment=2)), (2, dict(seed=4, segment=2)), (2, dict(seed=[4, 9], segment=[2, 0]))):
     batch = helpers.make_batch(spec, batch=b, ctx_mask='ragged')
-    known, mask = _known((b, 64, 128)), keep_spec.parity_masks(b)
+    known, mask = helpers.known_mel((b, 64, 128)), keep_spec.parity_masks(b)
     want, _ = model.predict(batch, rng=rng, keep=known, keep_mask=mask, **keys)
     got, _ = model.predict(batch, rng=rng, keep=known, strength=1.0 - mask, **keys)
-    np.testing.assert_array_equal(_bits(got), _bits(want))
+    np.testing.assert_array_equal(helpers.bits(got), helpers.bits(want))
     # ... and strength 1 with the mask beside it: the mask's frames get strength 0
     got, _ = model.predict(batch, rng=rng, keep=known, strength=1.0, keep_mask=mask, **keys)
-    np.testing.assert_array_equal(_bits(got), _bits(want))
+    np.testing.assert_array_equal(helpers.bits(got), helpers.bits(want))
 
 
 # --------------------------------------------------------------------------------------------------
@@ -195,14 +160,14 @@ def _chain(torch, model_key, b, strength, want_start, what, model=None):
   init_z, noise = helpers.make_noise(spec, batch=b)
   if spec.diffusion.sampler.name == 'ddim':
     noise = None
-  known = _known((b, 64, 128))
+  known = helpers.known_mel((b, 64, 128))
   strength = np.broadcast_to(np.asarray(strength, np.float64), (b, 64))
   words, start = inference.plan_strength(strength, steps)
   assert start == want_start
   got, _ = model.predict(batch, init_z=init_z, noise=noise, keep=known, strength=strength)
   ref64, ref32 = _spec_refs(spec, params, batch, init_z, noise, known, words, start)
   verbatim = words == 1
-  np.testing.assert_array_equal(_bits(got[verbatim]), _bits(known[verbatim]))
+  np.testing.assert_array_equal(helpers.bits(got[verbatim]), helpers.bits(known[verbatim]))
   assert np.isfinite(got).all()
   helpers.assert_fp32_class(got[~verbatim], ref64[~verbatim], ref32[~verbatim], what)
   return got, known, words
@@ -234,8 +199,8 @@ def test_chain_ramps_from_the_full_scan(torch):
   s[1, 7] = 0.0
   got, known, words = _chain(torch, ('tiny_context', 16), 2, s, 15, 'edit ramps')
   assert words[0, 0] == 1 and words[1, 7] == 1 and words[0, -1] == 0 and len(set(words.ravel().tolist())) >= 15
-  np.testing.assert_array_equal(_bits(got[0, 0]), _bits(known[0, 0]))
-  np.testing.assert_array_equal(_bits(got[1, 7]), _bits(known[1, 7]))
+  np.testing.assert_array_equal(helpers.bits(got[0, 0]), helpers.bits(known[0, 0]))
+  np.testing.assert_array_equal(helpers.bits(got[1, 7]), helpers.bits(known[1, 7]))
 
 
 def test_chain_ddim_without_context(torch):
@@ -246,8 +211,8 @@ def test_chain_ddim_without_context(torch):
   s[1, 50:] = 0.3
   got, known, words = _chain(torch, ('tiny', 8, 'ddim'), 2, s, 4, 'edit ddim')
   assert (words == 1).sum() == 20
-  np.testing.assert_array_equal(_bits(got[0, :9]), _bits(known[0, :9]))
-  np.testing.assert_array_equal(_bits(got[1, 30:41]), _bits(known[1, 30:41]))
+  np.testing.assert_array_equal(helpers.bits(got[0, :9]), helpers.bits(known[0, :9]))
+  np.testing.assert_array_equal(helpers.bits(got[1, 30:41]), helpers.bits(known[1, 30:41]))
 
 
 def test_generated_draws_start_the_part_way_call(torch):
@@ -256,7 +221,7 @@ def test_generated_draws_start_the_part_way_call(torch):
   from msd_amd import native
   spec, _, model = _model(torch, 'tiny_context', 16)
   batch = helpers.make_batch(spec, batch=2, ctx_mask='ragged')
-  known = _known((2, 64, 128))
+  known = helpers.known_mel((2, 64, 128))
   rows = [torch.empty((64, 128), dtype=torch.float32, device='cuda') for _ in range(2)]
   for b, (seed, segment) in enumerate([(4, 2), (9, 0)]):
     native.fill_normal(rows[b], seed, segment, 0)
@@ -264,12 +229,12 @@ def test_generated_draws_start_the_part_way_call(torch):
   got, _ = model.predict(batch, seed=[4, 9], segment=[2, 0], keep=known, strength=0.5)
   # (the step noise is keyed by the same rows: sub-sequence 1 + i, drawn in the kernel either way)
   want, _ = model.predict(batch, seed=[4, 9], segment=[2, 0], keep=known, strength=0.5, init_z=z_rows)
-  np.testing.assert_array_equal(_bits(got), _bits(want))
+  np.testing.assert_array_equal(helpers.bits(got), helpers.bits(want))
   whole = torch.empty((2, 64, 128), dtype=torch.float32, device='cuda')
   native.fill_normal_threefry(whole, 4)
   got, _ = model.predict(batch, seed=4, rng='threefry', keep=known, strength=0.5)
   want, _ = model.predict(batch, seed=4, rng='threefry', keep=known, strength=0.5, init_z=whole)
-  np.testing.assert_array_equal(_bits(got), _bits(want))
+  np.testing.assert_array_equal(helpers.bits(got), helpers.bits(want))
   assert np.abs(got - known).max() > 1e-2
 
 
@@ -281,7 +246,7 @@ def test_plain_keep_and_edit_calls_alternate_on_one_handle(torch):
   of the plain call before it, and every call the bits a fresh handle returns."""
   spec, params, _ = _model(torch, 'tiny_context', 16)
   batch = helpers.make_batch(spec, batch=2, ctx_mask='ragged')
-  known, mask = _known((2, 64, 128)), keep_spec.parity_masks(2)
+  known, mask = helpers.known_mel((2, 64, 128)), keep_spec.parity_masks(2)
   kw = dict(seed=[6, 7], segment=[1, 2])
   strength = np.full((2, 64), 0.25)
   strength[1, :10] = 0.0
@@ -290,13 +255,13 @@ def test_plain_keep_and_edit_calls_alternate_on_one_handle(torch):
   runs = [one.predict(batch, **kw, **c)[0] for c in calls]
   fresh = [_handle(spec, params).predict(batch, **kw, **c)[0] for c in calls[:3]]
   for k in range(3):
-    np.testing.assert_array_equal(_bits(runs[k]), _bits(fresh[k]))
-  np.testing.assert_array_equal(_bits(runs[3]), _bits(runs[0]))
+    np.testing.assert_array_equal(helpers.bits(runs[k]), helpers.bits(fresh[k]))
+  np.testing.assert_array_equal(helpers.bits(runs[3]), helpers.bits(runs[0]))
   assert not np.array_equal(runs[0], runs[1]) and not np.array_equal(runs[1], runs[2])
   # and once more round: the cached graphs of all three forms replay
   again = [one.predict(batch, **kw, **c)[0] for c in calls[1:3]]
-  np.testing.assert_array_equal(_bits(again[0]), _bits(runs[1]))
-  np.testing.assert_array_equal(_bits(again[1]), _bits(runs[2]))
+  np.testing.assert_array_equal(helpers.bits(again[0]), helpers.bits(runs[1]))
+  np.testing.assert_array_equal(helpers.bits(again[1]), helpers.bits(runs[2]))
 
 
 # --------------------------------------------------------------------------------------------------
@@ -306,36 +271,36 @@ def test_vary_and_blended_regenerate_on_a_song(torch):
   from msd_amd import inference
   spec, _, model = _model(torch, 'tiny_context', 8)
   toks = [msd_amd.synthetic.segment_tokens(spec, k, min_len=8, max_len=126) for k in range(3)]
-  song = _known((1, 192, 128), seed=8)
+  song = helpers.known_mel((1, 192, 128), seed=8)
   # vary at full strength is predict_sequence
   want = model.predict_sequence(toks, seed=12)
   got = model.vary(song, toks, 1.0, seed=12)
   assert got.shape == song.shape and got.dtype == np.float32
-  np.testing.assert_array_equal(_bits(got), _bits(want))
+  np.testing.assert_array_equal(helpers.bits(got), helpers.bits(want))
   # a variation: strength 0.5 but for a stretch of strength 0, which is the input's
   s = np.full(192, 0.5)
   s[50:80] = 0.0
   got = model.vary(song, toks, s, seed=12)
   assert got.shape == song.shape and np.isfinite(got).all()
-  np.testing.assert_array_equal(_bits(got[:, 50:80]), _bits(song[:, 50:80]))
+  np.testing.assert_array_equal(helpers.bits(got[:, 50:80]), helpers.bits(song[:, 50:80]))
   assert np.abs(got[:, :50] - song[:, :50]).max() > 1e-2 and np.abs(got[:, :50] - want[:, :50]).max() > 1e-2
-  np.testing.assert_array_equal(_bits(model.vary(song, toks, 0.0, seed=12)), _bits(song))
+  np.testing.assert_array_equal(helpers.bits(model.vary(song, toks, 0.0, seed=12)), helpers.bits(song))
   # regenerate: blend_frames = 0 is the call as it was
   hard = model.regenerate(song, toks, 40, 100, seed=12)
-  np.testing.assert_array_equal(_bits(model.regenerate(song, toks, 40, 100, seed=12, blend_frames=0)), _bits(hard))
+  np.testing.assert_array_equal(helpers.bits(model.regenerate(song, toks, 40, 100, seed=12, blend_frames=0)), helpers.bits(hard))
   # a ramp of 15 frames: strengths 15/16 .. 1/16; at N = 8 the outermost (1/16 -> 0.5 -> one step) is still released
   soft = model.regenerate(song, toks, 40, 100, seed=12, blend_frames=15)
   assert soft.shape == song.shape and np.isfinite(soft).all()
-  np.testing.assert_array_equal(_bits(soft[:, :25]), _bits(song[:, :25]))
-  np.testing.assert_array_equal(_bits(soft[:, 115:]), _bits(song[:, 115:]))
+  np.testing.assert_array_equal(helpers.bits(soft[:, :25]), helpers.bits(song[:, :25]))
+  np.testing.assert_array_equal(helpers.bits(soft[:, 115:]), helpers.bits(song[:, 115:]))
   assert np.abs(soft[:, 25:40] - song[:, 25:40]).max() > 1e-3 and np.abs(soft[:, 100:115] - song[:, 100:115]).max() > 1e-3
   plan = inference.region_strength(192, 64, 40, 100, 15)
   assert [k for k, _ in plan] == [0, 1]
   # a region whose ramp alone reaches segment 2: that segment is sampled too, its frames beyond the ramp untouched
   soft = model.regenerate(song, toks, 100, 128, seed=12, blend_frames=3)
   assert np.abs(soft[:, 128:131] - song[:, 128:131]).max() > 1e-3
-  np.testing.assert_array_equal(_bits(soft[:, 131:]), _bits(song[:, 131:]))
-  np.testing.assert_array_equal(_bits(soft[:, :97]), _bits(song[:, :97]))
+  np.testing.assert_array_equal(helpers.bits(soft[:, 131:]), helpers.bits(song[:, 131:]))
+  np.testing.assert_array_equal(helpers.bits(soft[:, :97]), helpers.bits(song[:, :97]))
 
 
 # --------------------------------------------------------------------------------------------------
@@ -344,7 +309,7 @@ def test_vary_and_blended_regenerate_on_a_song(torch):
 def test_errors(torch):
   spec, _, model = _model(torch, 'tiny_context', 16)
   batch = helpers.make_batch(spec, batch=2, ctx_mask='ragged')
-  known = _known((2, 64, 128))
+  known = helpers.known_mel((2, 64, 128))
   with pytest.raises(ValueError, match='strength needs keep'):
     model.predict(batch, strength=0.5)
   with pytest.raises(ValueError):
@@ -353,7 +318,7 @@ def test_errors(torch):
   good, _ = model.predict(batch, keep=known, strength=0.25)   # (encoded, buffers allocated)
   nm = model._get_native()
   out = torch.empty((2, 64, 128), dtype=torch.float32, device='cuda')
-  known_t = _dev(torch, known)
+  known_t = helpers.dev(torch, known)
   words = np.full((2, 64), 3, np.int32)
   s = model._stream.cuda_stream
 
@@ -373,11 +338,11 @@ def test_errors(torch):
     call(words, -1)                                  # no step runs only where every frame is known throughout
   call(np.ones((2, 64), np.int32), -1)
   model._stream.synchronize()
-  np.testing.assert_array_equal(_bits(out.cpu().numpy()), _bits(known))
+  np.testing.assert_array_equal(helpers.bits(out.cpu().numpy()), helpers.bits(known))
   with pytest.raises(ValueError):
     nm.sample(2, out, seed=1, keep=known_t, release=words[:1], start_step=3, stream=s)
   with pytest.raises(ValueError):
     nm.sample(2, out, seed=1, start_step=3, stream=s)
   # the handle still works
   again, _ = model.predict(batch, keep=known, strength=0.25)
-  np.testing.assert_array_equal(_bits(again), _bits(good))
+  np.testing.assert_array_equal(helpers.bits(again), helpers.bits(good))

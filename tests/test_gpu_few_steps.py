@@ -5,38 +5,17 @@ oracle's functions.
 Presets tiny / tiny_context: T = 64, n = 128.  The handle has N = 96 steps (graph_steps 8): K = 24 is three step graphs,
 K = 12 one graph and four single-step launches, K = 1 a single launch."""
 import ctypes
-import dataclasses
 
 import numpy as np
 import pytest
 
 import msd_amd
 from tests import helpers, multistep_spec as ms
-from tests.test_gpu_fused_ops import _sampler_spec
+from tests.helpers import gpu_torch  # noqa: F401  (the `torch` fixture)
 
 pytestmark = pytest.mark.gpu
 
 N = 96
-
-
-@pytest.fixture(scope='module')
-def torch():
-  import torch
-  assert torch.cuda.is_available(), 'these tests need the MI355X'
-  msd_amd.native.load()
-  return torch
-
-
-def _dev(torch, a, dtype=np.float32):
-  return torch.as_tensor(np.ascontiguousarray(a, dtype)).cuda()
-
-
-def _bits(a):
-  return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _rms(a, b):
-  return helpers.rms(a, b)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -52,7 +31,7 @@ def test_op_multistep_vs_spec(torch, case):
   holds the update's pred_x0 afterwards; at i == 0 the output is pred_x0."""
   from msd_amd import inference, native
   from oracle import backend
-  spec = _sampler_spec(**case)
+  spec = helpers.sampler_spec(**case)
   cfg = inference._to_native_config(spec, msd_amd.audio_codecs.MelGAN(), 1, 'f16x3')
   _, dc = helpers.oracle_configs(spec)
   steps = dc.sampler.schedule.num_steps
@@ -71,9 +50,9 @@ def test_op_multistep_vs_spec(torch, case):
       zs, x0 = ms.step(xp, dc, xp.asarray(z), i, pred, xp.asarray(prev), first)
       refs[name] = (np.asarray(zs, np.float64), np.asarray(x0, np.float64))
     # the history buffer on entry: NaN on the first step -- it must not be read there
-    prev_t = torch.full(shape, float('nan'), dtype=torch.float32, device='cuda') if first else _dev(torch, prev)
+    prev_t = torch.full(shape, float('nan'), dtype=torch.float32, device='cuda') if first else helpers.dev(torch, prev)
     out_t = torch.full(shape, float('nan'), dtype=torch.float32, device='cuda')
-    native.op_sampler_step_multistep(cfg, i, _dev(torch, z), _dev(torch, oc), _dev(torch, ou) if two_pass else None, prev_t,
+    native.op_sampler_step_multistep(cfg, i, helpers.dev(torch, z), helpers.dev(torch, oc), helpers.dev(torch, ou) if two_pass else None, prev_t,
                                      first, out_t)
     got, got_x0 = out_t.cpu().numpy(), prev_t.cpu().numpy()
     assert np.isfinite(got).all() and np.isfinite(got_x0).all()
@@ -84,17 +63,17 @@ def test_op_multistep_vs_spec(torch, case):
       print('multistep %s i=%d %s: scaled error device %.3e / float32 %.3e' % (case, i, what, e_dev, e_f32))
       assert e_dev <= 1e-6 + 4 * e_f32, (i, what, e_dev, e_f32)
     if i == 0:
-      np.testing.assert_array_equal(_bits(got), _bits(got_x0))
+      np.testing.assert_array_equal(helpers.bits(got), helpers.bits(got_x0))
       if dc.sampler.clip_x0:
         assert np.abs(got).max() <= 1.0
     else:
       assert not np.array_equal(got, got_x0)
     if not first and 0 < i:   # the history entered: the first-order result differs
-      fo_prev, fo_out = _dev(torch, prev), torch.empty(shape, dtype=torch.float32, device='cuda')
-      native.op_sampler_step_multistep(cfg, i, _dev(torch, z), _dev(torch, oc), _dev(torch, ou) if two_pass else None,
+      fo_prev, fo_out = helpers.dev(torch, prev), torch.empty(shape, dtype=torch.float32, device='cuda')
+      native.op_sampler_step_multistep(cfg, i, helpers.dev(torch, z), helpers.dev(torch, oc), helpers.dev(torch, ou) if two_pass else None,
                                        fo_prev, True, fo_out)
       assert not np.array_equal(fo_out.cpu().numpy(), got)
-      np.testing.assert_array_equal(_bits(fo_prev.cpu().numpy()), _bits(got_x0))
+      np.testing.assert_array_equal(helpers.bits(fo_prev.cpu().numpy()), helpers.bits(got_x0))
 
 
 # --------------------------------------------------------------------------------------------------
@@ -114,15 +93,15 @@ def test_closed_form_chain_on_the_device(torch, steps):
   xp = backend.NumpyBackend('float64')
   ends = {}
   for sampler in ('dpmpp_2m', 'ddim'):
-    spec = _sampler_spec(sampler='ddim', cfg_weight=1.0, clip=False, steps=steps)
+    spec = helpers.sampler_spec(sampler='ddim', cfg_weight=1.0, clip=False, steps=steps)
     cfg = inference._to_native_config(spec, msd_amd.audio_codecs.MelGAN(), 1, 'f16x3')
     _, dc = helpers.oracle_configs(spec)
     pred = ms.ideal_pred_fn(xp, dc)
-    z = _dev(torch, z1)
+    z = helpers.dev(torch, z1)
     prev = torch.full(shape, float('nan'), dtype=torch.float32, device='cuda')
     for i in reversed(range(steps)):
       time = np.full((1,), (i + 1.0) / steps)
-      eps = _dev(torch, pred(z.cpu().numpy().astype(np.float64), time, True))
+      eps = helpers.dev(torch, pred(z.cpu().numpy().astype(np.float64), time, True))
       out = torch.empty_like(z)
       if sampler == 'ddim':
         native.op_sampler_step(cfg, i, z, eps, None, None, out)
@@ -131,8 +110,8 @@ def test_closed_form_chain_on_the_device(torch, steps):
       z = out
     ends[sampler] = z.cpu().numpy().astype(np.float64)
   spec_chain = ms.scan(xp, z1.astype(np.float64), pred, dc)
-  e_2m, e_ddim = _rms(ends['dpmpp_2m'], exact), _rms(ends['ddim'], exact)
-  d_spec = _rms(ends['dpmpp_2m'], spec_chain)
+  e_2m, e_ddim = helpers.rms(ends['dpmpp_2m'], exact), helpers.rms(ends['ddim'], exact)
+  d_spec = helpers.rms(ends['dpmpp_2m'], spec_chain)
   print('closed form K = %d: device rms error 2M %.3e, DDIM %.3e (ratio %.2f); device 2M vs float64 spec chain %.3e'
         % (steps, e_2m, e_ddim, e_ddim / e_2m, d_spec))
   assert e_2m < 0.25 * e_ddim
@@ -142,18 +121,12 @@ def test_closed_form_chain_on_the_device(torch, steps):
 # --------------------------------------------------------------------------------------------------
 # models
 # --------------------------------------------------------------------------------------------------
-def _spec(preset, steps, sampler='ddpm'):
-  spec = msd_amd.config.preset(preset, num_steps=steps)
-  d = spec.diffusion
-  return dataclasses.replace(spec, diffusion=dataclasses.replace(d, sampler=dataclasses.replace(d.sampler, name=sampler)))
-
-
 _models, _params = {}, {}
 
 
 def _weights(preset):
   if preset not in _params:
-    _params[preset] = msd_amd.synthetic.init_params(_spec(preset, N), 3, norm_scale_jitter=0.1)
+    _params[preset] = msd_amd.synthetic.init_params(helpers.preset_spec(preset, N), 3, norm_scale_jitter=0.1)
   return _params[preset]
 
 
@@ -161,7 +134,7 @@ def _model(torch, preset='tiny', steps=N, sampler='ddpm'):
   """(spec, model) -- one handle per configuration for the whole module; the weights do not depend on the step count."""
   key = (preset, steps, sampler)
   if key not in _models:
-    spec = _spec(preset, steps, sampler)
+    spec = helpers.preset_spec(preset, steps, sampler)
     _models[key] = (spec, msd_amd.InferenceModel(_weights(preset), spec, batch_size=2, **helpers.ALL_PLANES))
   return _models[key]
 
@@ -188,7 +161,7 @@ def _oracle(preset, steps, sampler, batch, init_z, noise):
   """[float64, float32] decodes of the oracle configured with num_steps = steps ('dpmpp_2m': the spec's scan over the
   oracle's network)."""
   from oracle import backend, fast
-  spec = _spec(preset, steps, 'ddim' if sampler == 'dpmpp_2m' else sampler)
+  spec = helpers.preset_spec(preset, steps, 'ddim' if sampler == 'dpmpp_2m' else sampler)
   cfg, dc = helpers.oracle_configs(spec)
   refs = []
   for dtype in ('float64', 'float32'):
@@ -228,7 +201,7 @@ def test_strided_call_is_the_k_step_model(torch, case):
   keys = dict(seed=4, segment=2)
   init_z, noise = _draws(torch, rng, k, b, keys['seed'], keys['segment'])
   if case.get('supplied'):
-    init_z, noise = helpers.make_noise(_spec(preset, k), batch=b)   # [B,T,n], [K,B,T,n]
+    init_z, noise = helpers.make_noise(helpers.preset_spec(preset, k), batch=b)   # [B,T,n], [K,B,T,n]
     call = dict(init_z=init_z, noise=noise)
   else:
     call = dict(rng=rng, **keys)
@@ -238,7 +211,7 @@ def test_strided_call_is_the_k_step_model(torch, case):
   helpers.assert_fp32_class(got, ref64, ref32, 'strided %s' % case)
   _, fresh_model = _model(torch, preset, k, sampler or 'ddpm')
   fresh, _ = fresh_model.predict(batch, **call)
-  same = np.array_equal(_bits(got), _bits(fresh))
+  same = np.array_equal(helpers.bits(got), helpers.bits(fresh))
   d, yard = np.abs(got.astype(np.float64) - fresh).max(), np.abs(ref32 - ref64).max()
   print('strided %s: bit-identical to the fresh %d-step handle: %s (max |diff| %.3e; float32 oracle vs float64 %.3e)'
         % (case, k, same, d, yard))
@@ -253,7 +226,7 @@ def test_all_steps_and_none_are_the_default_call(torch):
     want, _ = model.predict(batch, seed=4, segment=2, rng=rng)
     for kw in (dict(steps=N), dict(steps=None), dict(steps=N, sampler='ddpm'), dict(sampler='ddpm')):
       got, _ = model.predict(batch, seed=4, segment=2, rng=rng, **kw)
-      np.testing.assert_array_equal(_bits(got), _bits(want))
+      np.testing.assert_array_equal(helpers.bits(got), helpers.bits(want))
 
 
 # --------------------------------------------------------------------------------------------------
@@ -272,9 +245,9 @@ def test_dpmpp_2m_through_predict(torch, steps):
   helpers.assert_fp32_class(got, ref64, ref32, 'dpmpp_2m, %d steps' % steps)
   # deterministic after init_z: neither the keys nor a noise tensor enter
   again, _ = model.predict(batch, init_z=init_z, steps=steps, sampler='dpmpp_2m', seed=77, segment=5)
-  np.testing.assert_array_equal(_bits(again), _bits(got))
+  np.testing.assert_array_equal(helpers.bits(again), helpers.bits(got))
   ddim, _ = model.predict(batch, init_z=init_z, steps=steps, sampler='ddim')
-  assert _rms(ddim, got) > 1e-3   # (another solver of the same ODE)
+  assert helpers.rms(ddim, got) > 1e-3   # (another solver of the same ODE)
 
 
 def test_dpmpp_2m_as_the_handles_default(torch):
@@ -285,7 +258,7 @@ def test_dpmpp_2m_as_the_handles_default(torch):
   batch = helpers.make_batch(spec, batch=1, ctx_mask='ragged')
   want, _ = model.predict(batch, seed=4, segment=2, steps=12, sampler='dpmpp_2m')
   got, _ = own.predict(batch, seed=4, segment=2)
-  np.testing.assert_array_equal(_bits(got), _bits(want))
+  np.testing.assert_array_equal(helpers.bits(got), helpers.bits(want))
 
 
 def test_jax_mode_draws_for_the_calls_step_count(torch):
@@ -297,10 +270,10 @@ def test_jax_mode_draws_for_the_calls_step_count(torch):
   z, nz = jax_random.reference_noise(5, (1, 64, 128), 12)
   assert nz.shape == (12, 1, 64, 128)
   want, _ = model.predict(batch, init_z=z, noise=nz, steps=12)
-  np.testing.assert_array_equal(_bits(got), _bits(want))
+  np.testing.assert_array_equal(helpers.bits(got), helpers.bits(want))
   full, _ = model.predict(batch, seed=5, rng='jax')   # ... and the cached draws of another step count are not reused
   z96, nz96 = jax_random.reference_noise(5, (1, 64, 128), N)
-  np.testing.assert_array_equal(_bits(full), _bits(model.predict(batch, init_z=z96, noise=nz96)[0]))
+  np.testing.assert_array_equal(helpers.bits(full), helpers.bits(model.predict(batch, init_z=z96, noise=nz96)[0]))
 
 
 # --------------------------------------------------------------------------------------------------
@@ -316,8 +289,8 @@ def test_rows_are_their_one_row_calls(torch, rng, sampler):
   for b in range(2):
     row = {k: np.ascontiguousarray(v[b:b + 1]) for k, v in batch.items()}
     one, _ = model.predict(row, seed=seeds[b], segment=segments[b], rng=rng, steps=24, sampler=sampler)
-    np.testing.assert_array_equal(_bits(got[b:b + 1]), _bits(one))
-  assert _rms(got[0], got[1]) > 0.05
+    np.testing.assert_array_equal(helpers.bits(got[b:b + 1]), helpers.bits(one))
+  assert helpers.rms(got[0], got[1]) > 0.05
 
 
 # --------------------------------------------------------------------------------------------------
@@ -330,18 +303,18 @@ def test_graph_cache_keeps_the_default_graphs_and_survives_a_reset(torch):
   first, _ = model.predict(batch, **keys)
   few, _ = model.predict(batch, steps=24, **keys)
   third, _ = model.predict(batch, **keys)
-  np.testing.assert_array_equal(_bits(first), _bits(third))
-  assert _rms(first, few) > 1e-3
+  np.testing.assert_array_equal(helpers.bits(first), helpers.bits(third))
+  assert helpers.rms(first, few) > 1e-3
   # nine distinct (K, sampler) in a row: more than the eight cached sets, so the cache is reset on the way
   combos = [(k, s) for s in ('ddim', 'dpmpp_2m') for k in (1, 2, 3, 4, 6)][:9]
   assert len(set(combos)) == 9
   runs = [model.predict(batch, steps=k, sampler=s, **keys)[0] for k, s in combos]
   again, _ = model.predict(batch, steps=combos[0][0], sampler=combos[0][1], **keys)
-  np.testing.assert_array_equal(_bits(again), _bits(runs[0]))
+  np.testing.assert_array_equal(helpers.bits(again), helpers.bits(runs[0]))
   for (k, s), r in zip(combos, runs):
     assert np.isfinite(r).all(), (k, s)
-  np.testing.assert_array_equal(_bits(model.predict(batch, steps=24, **keys)[0]), _bits(few))
-  np.testing.assert_array_equal(_bits(model.predict(batch, **keys)[0]), _bits(first))
+  np.testing.assert_array_equal(helpers.bits(model.predict(batch, steps=24, **keys)[0]), helpers.bits(few))
+  np.testing.assert_array_equal(helpers.bits(model.predict(batch, **keys)[0]), helpers.bits(first))
 
 
 # --------------------------------------------------------------------------------------------------

@@ -10,10 +10,10 @@ These are the pieces that carry the tricky algebra and that whole-decoder tests 
   * final_proj_f32_kernel (decoder_norm folded, exact fp32)      vs oracle rms_layer_norm + matmul
   * op_geglu / op_qkv                                            vs the launch sites they run (op_gemm_site), bit for bit
 """
-import dataclasses
-
 import numpy as np
 import pytest
+
+from tests import helpers
 
 pytestmark = pytest.mark.gpu
 
@@ -38,22 +38,6 @@ def _relmax(got, ref):
 # --------------------------------------------------------------------------------------------------
 # sampler
 # --------------------------------------------------------------------------------------------------
-def _sampler_spec(sampler='ddpm', model_output='eps', logvar='large', schedule='cosine', train='cosine',
-                  cfg_weight=5.0, clip=True, steps=50):
-  import msd_amd
-  from msd_amd import config as C
-  spec = msd_amd.config.preset('tiny', num_steps=steps, cfg_weight=cfg_weight)
-  d = spec.diffusion
-  ss = C.DiffusionSchedule(schedule, start=1e-4 if schedule == 'linear' else None,
-                           stop=2e-2 if schedule == 'linear' else None, num_steps=steps)
-  ts = C.DiffusionSchedule(train, start=2e-4 if train == 'linear' else None,
-                           stop=3e-2 if train == 'linear' else None, num_steps=80 if train == 'linear' else None)
-  d = dataclasses.replace(d, model_output=model_output, train_schedule=ts,
-                          sampler=dataclasses.replace(d.sampler, name=sampler, logvar_type=logvar, clip_x0=clip,
-                                                      schedule=ss))
-  return dataclasses.replace(spec, diffusion=d)
-
-
 CASES = [
     dict(),                                                   # the shipped configuration: DDPM, eps, large, CFG 5
     dict(cfg_weight=1.0),                                     # single pass
@@ -80,7 +64,7 @@ def test_sampler_step_vs_oracle(env, case):
   from msd_amd import inference
   from oracle import backend, sampler
   from tests import helpers
-  spec = _sampler_spec(**case)
+  spec = helpers.sampler_spec(**case)
   cfg = inference._to_native_config(spec, msd_amd.audio_codecs.MelGAN(), 1, 'bf16x3')
   _, dc = helpers.oracle_configs(spec)
   steps = dc.sampler.schedule.num_steps
@@ -130,7 +114,7 @@ def test_schedule_table_linear_and_cosine_vs_oracle(env):
   # schedule sits on the pole of tan (logsnr = -20), where float32 is ~5e-5 relative from float64
   xp = backend.NumpyBackend('float64')
   for case in (dict(), dict(schedule='linear', train='linear')):
-    spec = _sampler_spec(steps=40, **case)
+    spec = helpers.sampler_spec(steps=40, **case)
     model = msd_amd.InferenceModel('synthetic:0', spec)
     tab = model._get_native().schedule()
     n = 40

@@ -3,33 +3,14 @@ regenerate) against the specification of tests/keep_spec.py: the reference's eva
 lines, over oracle.fast.FastModel.
 
 Presets tiny / tiny_context: T = 64, n = 128, i.e. eight 1024-element sampler blocks per row, 32 threads per frame."""
-import dataclasses
-
 import numpy as np
 import pytest
 
 import msd_amd
 from tests import helpers, keep_spec
-from tests.test_gpu_fused_ops import _sampler_spec
+from tests.helpers import gpu_torch  # noqa: F401  (the `torch` fixture)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope='module')
-def torch():
-  import torch
-  assert torch.cuda.is_available(), 'these tests need the MI355X'
-  msd_amd.native.load()
-  return torch
-
-
-def _dev(torch, a, dtype=np.float32):
-  return torch.as_tensor(np.ascontiguousarray(a, dtype)).cuda()
-
-
-def _known(shape, seed=21):
-  """A mel that leaves the codec's range [log 1e-5, 4] at both ends."""
-  return np.random.default_rng(seed).uniform(-13.0, 5.0, shape).astype(np.float32)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -58,11 +39,11 @@ OP_CASES = [
 def test_op_sampler_step_keep_vs_spec(torch, case):
   """msd_op_sampler_step_keep at the first, a middle, the second-to-last and the last scan index: against the
   specification in float64 with its float32 evaluation as the yardstick (the plain update's criterion,
-  tests/test_gpu_fused_ops.py); free elements are msd_op_sampler_step's bits, and at i == 0 kept elements are the
-  known values' bits."""
+  tests/test_gpu_fused_ops.py); free elements are msd_op_sampler_step's bits -- the plain and the keep instance of the
+  one sampler_update text -- and at i == 0 kept elements are the known values' bits."""
   from msd_amd import inference, native
   from oracle import backend
-  spec = _sampler_spec(**case)
+  spec = helpers.sampler_spec(**case)
   cfg = inference._to_native_config(spec, msd_amd.audio_codecs.MelGAN(), 1, 'bf16x3')
   _, dc = helpers.oracle_configs(spec)
   steps = dc.sampler.schedule.num_steps
@@ -91,9 +72,9 @@ def test_op_sampler_step_keep_vs_spec(torch, case):
       pred = lambda z, time, include_conditioning, _xp=xp: _xp.asarray(oc if include_conditioning else ou)
       body = keep_spec.eval_step_keep(xp, noise, dc, 2, pred, xp.asarray(xk), keep_spec.frame_mask(xp, mask))
       outs[name] = np.asarray(body(xp.asarray(z), i), np.float64)
-    args = (_dev(torch, z), _dev(torch, oc), _dev(torch, ou) if two_pass else None, _dev(torch, nz))
+    args = (helpers.dev(torch, z), helpers.dev(torch, oc), helpers.dev(torch, ou) if two_pass else None, helpers.dev(torch, nz))
     got_t = torch.empty(shape, dtype=torch.float32, device='cuda')
-    native.op_sampler_step_keep(cfg, i, *args, _dev(torch, xk), _dev(torch, mask, np.int32), got_t)
+    native.op_sampler_step_keep(cfg, i, *args, helpers.dev(torch, xk), helpers.dev(torch, mask, np.int32), got_t)
     plain_t = torch.empty(shape, dtype=torch.float32, device='cuda')
     native.op_sampler_step(cfg, i, *args, plain_t)
     got32, plain32 = got_t.cpu().numpy(), plain_t.cpu().numpy()
@@ -115,27 +96,11 @@ def test_op_sampler_step_keep_vs_spec(torch, case):
 # --------------------------------------------------------------------------------------------------
 # models
 # --------------------------------------------------------------------------------------------------
-def _spec(preset, steps, sampler='ddpm'):
-  spec = msd_amd.config.preset(preset, num_steps=steps)
-  d = spec.diffusion
-  return dataclasses.replace(spec, diffusion=dataclasses.replace(d, sampler=dataclasses.replace(d.sampler, name=sampler)))
-
-
 _models = {}
 
 
 def _model(torch, preset='tiny_context', steps=8, sampler='ddpm'):
-  """(spec, params, model) -- one handle per configuration for the whole module."""
-  key = (preset, steps, sampler)
-  if key not in _models:
-    spec = _spec(preset, steps, sampler)
-    params = msd_amd.synthetic.init_params(spec, 3, norm_scale_jitter=0.1)
-    _models[key] = (spec, params, msd_amd.InferenceModel(params, spec, batch_size=2, **helpers.ALL_PLANES))
-  return _models[key]
-
-
-def _bits(a):
-  return np.ascontiguousarray(a, np.float32).view(np.uint32)
+  return helpers.cached_model(_models, preset, steps, sampler)
 
 
 # --------------------------------------------------------------------------------------------------
@@ -148,10 +113,10 @@ def test_zero_mask_is_the_plain_call(torch, sampler, steps, rng):
   for b, keys in ((1, dict(seed=4, segment=2)), (2, dict(seed=[4, 9], segment=[2, 0]))):
     batch = helpers.make_batch(spec, batch=b, ctx_mask='ragged')
     want, _ = model.predict(batch, rng=rng, **keys)
-    got, _ = model.predict(batch, rng=rng, keep=_known((b, 64, 128)), keep_mask=np.zeros((b, 64), np.int32), **keys)
-    np.testing.assert_array_equal(_bits(got), _bits(want))
+    got, _ = model.predict(batch, rng=rng, keep=helpers.known_mel((b, 64, 128)), keep_mask=np.zeros((b, 64), np.int32), **keys)
+    np.testing.assert_array_equal(helpers.bits(got), helpers.bits(want))
     again, _ = model.predict(batch, rng=rng, **keys)
-    np.testing.assert_array_equal(_bits(again), _bits(want))
+    np.testing.assert_array_equal(helpers.bits(again), helpers.bits(want))
 
 
 # --------------------------------------------------------------------------------------------------
@@ -160,20 +125,20 @@ def test_zero_mask_is_the_plain_call(torch, sampler, steps, rng):
 def test_kept_frames_are_returned_exactly(torch):
   spec, _, model = _model(torch)
   batch = helpers.make_batch(spec, batch=2, ctx_mask='ragged')
-  known = _known((2, 64, 128))
+  known = helpers.known_mel((2, 64, 128))
   mask = keep_spec.parity_masks(2)
   kept = mask.astype(bool)
   assert (known[kept] > 4.0).any() and (known[kept] < np.log(1e-5)).any()   # beyond the codec's range inside kept frames
   plain, _ = model.predict(batch, seed=3)
   for kw in (dict(seed=3), dict(seed=[3, 8], segment=[0, 5]), dict(seed=3, rng='threefry')):
     got, _ = model.predict(batch, keep=known, keep_mask=mask.astype(bool), **kw)
-    np.testing.assert_array_equal(_bits(got[kept]), _bits(known[kept]))
+    np.testing.assert_array_equal(helpers.bits(got[kept]), helpers.bits(known[kept]))
     assert np.isfinite(got).all() and np.abs(got[~kept] - known[~kept]).max() > 1.0
   got, _ = model.predict(batch, seed=3, keep=known, keep_mask=mask)
   assert np.abs(got[~kept] - plain[~kept]).max() > 1e-3     # the free frames saw the known ones
   # a device tensor as `keep`, and the all-ones mask: the known mel everywhere
-  full, _ = model.predict(batch, seed=3, keep=_dev(torch, known), keep_mask=np.ones((2, 64), np.int64))
-  np.testing.assert_array_equal(_bits(full), _bits(known))
+  full, _ = model.predict(batch, seed=3, keep=helpers.dev(torch, known), keep_mask=np.ones((2, 64), np.int64))
+  np.testing.assert_array_equal(helpers.bits(full), helpers.bits(known))
   with pytest.raises(ValueError):
     model.predict(batch, keep=known)
   with pytest.raises(ValueError):
@@ -198,11 +163,11 @@ def test_chain_matches_the_spec_on_the_free_frames(torch, b):
   spec, params, model = _model(torch)
   batch = helpers.make_batch(spec, batch=b, ctx_mask='ragged')
   init_z, noise = helpers.make_noise(spec, batch=b)
-  known, mask = _known((b, 64, 128)), keep_spec.parity_masks(b)
+  known, mask = helpers.known_mel((b, 64, 128)), keep_spec.parity_masks(b)
   got, _ = model.predict(batch, init_z=init_z, noise=noise, keep=known, keep_mask=mask)
   ref64, ref32 = _spec_refs(spec, params, batch, init_z, noise, known, mask)
   kept = mask.astype(bool)
-  np.testing.assert_array_equal(_bits(got[kept]), _bits(known[kept]))
+  np.testing.assert_array_equal(helpers.bits(got[kept]), helpers.bits(known[kept]))
   # the free frames only: the kept ones are exact and would dilute the fractions
   helpers.assert_fp32_class(got[~kept], ref64[~kept], ref32[~kept], 'keep b=%d' % b)
 
@@ -211,11 +176,11 @@ def test_chain_matches_the_spec_ddim_without_context(torch):
   spec, params, model = _model(torch, 'tiny', 8, 'ddim')
   batch = helpers.make_batch(spec, batch=2)
   init_z, _ = helpers.make_noise(spec, batch=2)
-  known, mask = _known((2, 64, 128)), keep_spec.parity_masks(2)
+  known, mask = helpers.known_mel((2, 64, 128)), keep_spec.parity_masks(2)
   got, _ = model.predict(batch, init_z=init_z, keep=known, keep_mask=mask)
   ref64, ref32 = _spec_refs(spec, params, batch, init_z, None, known, mask)
   kept = mask.astype(bool)
-  np.testing.assert_array_equal(_bits(got[kept]), _bits(known[kept]))
+  np.testing.assert_array_equal(helpers.bits(got[kept]), helpers.bits(known[kept]))
   helpers.assert_fp32_class(got[~kept], ref64[~kept], ref32[~kept], 'keep ddim')
 
 
@@ -225,7 +190,7 @@ def test_chain_matches_the_spec_ddim_without_context(torch):
 def test_plain_and_keep_calls_alternate_on_one_handle(torch):
   spec, params, _ = _model(torch, 'tiny_context', 10)   # (with the remainder graph)
   batch = helpers.make_batch(spec, batch=2, ctx_mask='ragged')
-  known, mask = _known((2, 64, 128)), keep_spec.parity_masks(2)
+  known, mask = helpers.known_mel((2, 64, 128)), keep_spec.parity_masks(2)
   kw = dict(seed=[6, 7], segment=[1, 2])
 
   def handle():
@@ -236,10 +201,10 @@ def test_plain_and_keep_calls_alternate_on_one_handle(torch):
           one.predict(batch, **kw)[0], one.predict(batch, keep=known, keep_mask=mask, **kw)[0]]
   fresh_plain = handle().predict(batch, **kw)[0]
   fresh_keep = handle().predict(batch, keep=known, keep_mask=mask, **kw)[0]   # keep first on this one
-  np.testing.assert_array_equal(_bits(runs[0]), _bits(runs[2]))
-  np.testing.assert_array_equal(_bits(runs[0]), _bits(fresh_plain))
-  np.testing.assert_array_equal(_bits(runs[1]), _bits(runs[3]))
-  np.testing.assert_array_equal(_bits(runs[1]), _bits(fresh_keep))
+  np.testing.assert_array_equal(helpers.bits(runs[0]), helpers.bits(runs[2]))
+  np.testing.assert_array_equal(helpers.bits(runs[0]), helpers.bits(fresh_plain))
+  np.testing.assert_array_equal(helpers.bits(runs[1]), helpers.bits(runs[3]))
+  np.testing.assert_array_equal(helpers.bits(runs[1]), helpers.bits(fresh_keep))
   assert not np.array_equal(runs[0], runs[1])
 
 
@@ -250,11 +215,11 @@ def test_regenerate_a_region_across_a_boundary(torch):
   from msd_amd import inference
   spec, _, model = _model(torch)
   toks = [msd_amd.synthetic.segment_tokens(spec, k, min_len=8, max_len=126) for k in range(3)]
-  song = _known((1, 192, 128), seed=8)
+  song = helpers.known_mel((1, 192, 128), seed=8)
   new = model.regenerate(song, toks, 40, 100, seed=12)
   assert new.shape == song.shape and new.dtype == np.float32
-  np.testing.assert_array_equal(_bits(new[:, :40]), _bits(song[:, :40]))
-  np.testing.assert_array_equal(_bits(new[:, 100:]), _bits(song[:, 100:]))   # segment 2 included: untouched
+  np.testing.assert_array_equal(helpers.bits(new[:, :40]), helpers.bits(song[:, :40]))
+  np.testing.assert_array_equal(helpers.bits(new[:, 100:]), helpers.bits(song[:, 100:]))   # segment 2 included: untouched
   assert np.abs(new[:, 40:100] - song[:, 40:100]).max() > 1.0
   # the two predict calls the plan names
   plan = inference.plan_region(192, 64, 40, 100)
@@ -266,5 +231,5 @@ def test_regenerate_a_region_across_a_boundary(torch):
   second, _ = model.predict({'encoder_input_tokens': toks[1].reshape(1, -1), 'encoder_continuous_inputs': first,
                              'encoder_continuous_mask': np.ones((1, 64), np.int32)},
                             seed=12, segment=1, keep=song[:, 64:128], keep_mask=plan[1][1][None])
-  np.testing.assert_array_equal(_bits(new[:, :64]), _bits(first))
-  np.testing.assert_array_equal(_bits(new[:, 64:128]), _bits(second))
+  np.testing.assert_array_equal(helpers.bits(new[:, :64]), helpers.bits(first))
+  np.testing.assert_array_equal(helpers.bits(new[:, 64:128]), helpers.bits(second))

@@ -11,22 +11,11 @@ import pytest
 
 import msd_amd
 from tests import helpers
+from tests.helpers import gpu_torch  # noqa: F401  (the `torch` fixture)
 
 pytestmark = pytest.mark.gpu
 
 N, B = 24, 2
-
-
-@pytest.fixture(scope='module')
-def torch():
-  import torch
-  assert torch.cuda.is_available(), 'these tests need the MI355X'
-  msd_amd.native.load()
-  return torch
-
-
-def _bits(a):
-  return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
 def _forms(spec):
@@ -60,12 +49,12 @@ def test_every_form_on_one_handle_is_the_fresh_handles_call(torch):
     fresh[name] = model.predict(batch, **kw)[0]
     assert np.isfinite(fresh[name]).all(), name
     model._get_native().close()
-  assert len({_bits(v).tobytes() for v in fresh.values()}) == len(forms)   # (seven different calls)
+  assert len({helpers.bits(v).tobytes() for v in fresh.values()}) == len(forms)   # (seven different calls)
   model = make()
   first = {name: model.predict(batch, **kw)[0] for name, kw in forms}
   model._get_native().reset_graph()
   second = {name: model.predict(batch, **kw)[0] for name, kw in reversed(forms)}
   for name, _ in forms:
-    np.testing.assert_array_equal(_bits(first[name]), _bits(fresh[name]), err_msg='a .. g, ' + name)
-    np.testing.assert_array_equal(_bits(second[name]), _bits(fresh[name]), err_msg='g .. a, ' + name)
-    np.testing.assert_array_equal(_bits(first[name]), _bits(second[name]), err_msg='both passes, ' + name)
+    np.testing.assert_array_equal(helpers.bits(first[name]), helpers.bits(fresh[name]), err_msg='a .. g, ' + name)
+    np.testing.assert_array_equal(helpers.bits(second[name]), helpers.bits(fresh[name]), err_msg='g .. a, ' + name)
+    np.testing.assert_array_equal(helpers.bits(first[name]), helpers.bits(second[name]), err_msg='both passes, ' + name)
