@@ -656,6 +656,49 @@ int msd_op_gemm_site_tiles(int precision, int site, int index, int32_t* bm, int3
  * "in_proj", "resnorm_tall_y2", "dual_qkv", "dual_out", "dual_out_dup" -- or NULL past the last site. */
 const char* msd_op_gemm_site_name(int precision, int site);
 
+/* (appended to ABI 7) One attention launch the way the DECODER fills it (msd_op_attention_ex fixes the easiest form: one
+ * segment, ldq = ldk = heads * 64, the key allocation exactly the key axis, no prefetch wave).  J = heads * 64; inputs are
+ * float32 device arrays in the caller's own layout:
+ *   q      [segs * q_rows_per_seg][ldq], head h at columns q_col + 64 h
+ *   k      [segs][k_alloc_rows][ldk], head h at columns k_col + 64 h.  The launch sees the WINDOW of k_rows rows from row
+ *          k_row0 of every segment (AttnParams::k_rows; segment stride k_alloc_rows * ldk).  k == q (self-attention: q and
+ *          k interleaved in one buffer) needs ldk == ldq, k_row0 == 0 and k_rows == k_alloc_rows == q_rows_per_seg
+ *   v      [segs][k_alloc_rows][J]; the entry builds V^T [segs][J][k_alloc_rows] with the kernel's per-16 key permutation and
+ *          launches on vt = base + k_row0, vt_ld = k_alloc_rows, vt_cols = k_rows (0 when the window is the whole allocation)
+ *   n_keys int32 [segs], 0 <= n_keys[s] <= k_rows
+ *   q_ssq  optional [segs * q_rows_per_seg][q_tiles]: un-normalised queries, as msd_op_attention_ex
+ *   o      [segs * q_rows_per_seg][J]
+ * Every 16-bit plane starts as NaN and only the columns (q) and the window (k, V^T) above are filled from the caller's data:
+ * a read outside them comes back as NaN through V^T, and so does an output row that nobody stored.
+ * prefetch_rows, prefetch_k != 0: the launch carries a weight target of two planes [prefetch_rows][prefetch_k] (two-plane
+ * precisions; prefetch_k % 64 == 0, <= 4096), so its blocks run the prefetch wave; touch_ahead (0 .. 16) and pf_late (0 / 1)
+ * are AttnParams' fields.  merge_in_launch: segs * (q_rows_per_seg / 32) * heads arrival counters, zeroed once, for all
+ * `repeats` launches.  ran_*: what the launcher's own rule (attention.h attention_launch_shape) chose -- query blocks per
+ * workgroup (1, 2, 4), prefetch wave, touch-ahead, and the power of two the key split ran as.
+ * k_row0, k_rows % 32 == 0; k_alloc_rows, ldq, ldk, q_col, k_col % 8 == 0; q_rows_per_seg % 64 == 0.  Errors as
+ * msd_op_attention_ex.  Synchronises. */
+typedef struct msd_attention_launch_args {
+  int32_t struct_size;       /* sizeof(msd_attention_launch_args) */
+  int32_t precision;         /* msd_precision */
+  int32_t qp, heads, segs, q_rows_per_seg, repeats;
+  int32_t ksplit, merge_in_launch, allow_qb4;
+  int32_t ldq, q_col;
+  int32_t ldk, k_col, k_alloc_rows, k_row0, k_rows;
+  int32_t prefetch_rows, prefetch_k, touch_ahead, pf_late;
+  int32_t q_tiles;
+  /* out: what ran */
+  int32_t ran_qb, ran_prefetch_wave, ran_touch_ahead, ran_ksplit;
+  /* operands (device) */
+  const float* q;
+  const float* k;
+  const float* v;
+  const int32_t* n_keys;
+  const float* q_ssq;
+  /* result (device, float32) */
+  float* o;
+} msd_attention_launch_args;
+int msd_op_attention_launch(msd_attention_launch_args* args, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

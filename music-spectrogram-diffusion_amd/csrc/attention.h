@@ -754,19 +754,44 @@ inline hipError_t attention_prepare() {
   return e;
 }
 
+// log2 of the key split a request for `ksplit` runs as: the largest power of two <= ksplit
+inline int attention_ksplit_log2(int ksplit) {
+  int l = 0;
+  while ((2 << l) <= ksplit) ++l;
+  return l;
+}
+
+// What a launch of `p` (ksplit already a power of two) runs on, decided in ONE place for the launcher below and for the
+// stand-alone op that reports it (standalone_ops.h msd_op_attention_launch):
+//   qb           query blocks per workgroup.  64-row blocks share K/V between two query blocks; when that leaves most of
+//                the 256 CUs without a block, 32-row blocks (twice as many) finish sooner; 128-row blocks only where the
+//                caller allows them, and never with un-normalised queries (`qs`: their row sums fill the LDS)
+//   prefetch     the launch touches its weight target: a two-plane launch that has one, on 32- or 64-row blocks (the
+//                single-plane mode never prefetches, 16 compute waves leave no room for the wave)
+//   pf_wave      ... from a wave of its own (kPfWaveAttn)
+//   touch_ahead  ... which also runs kv_touch_ahead
+struct AttnLaunchShape { int qb; bool prefetch, pf_wave, touch_ahead; };
+inline AttnLaunchShape attention_launch_shape(const AttnParams& p, int heads, int segs, int np, bool qs) {
+  const int blocks64 = heads * (p.q_rows_per_seg / 64) * p.ksplit * segs;
+  AttnLaunchShape s;
+  s.qb = attention_query_blocks((p.allow_qb4 && !qs) ? blocks64 : (blocks64 > 256 ? 256 : blocks64), p.q_rows_per_seg, np);
+  s.prefetch = np == 2 && prefetch_kind(p.pf) >= 1 && s.qb < 4;
+  s.pf_wave = kPfWaveAttn && s.prefetch;
+  s.touch_ahead = s.pf_wave && p.touch_ahead > 0;
+  return s;
+}
+
 template <int NP, int QP>
 inline void launch_attention_qp(const AttnParams& p, int heads, int segs, hipStream_t stream) {
   constexpr int NS = attention_ns<NP>();
-  // 64-row blocks share K/V between two query blocks; when that leaves most of the 256 CUs without
-  // a block, 32-row blocks (twice as many) finish sooner
-  const int blocks64 = heads * (p.q_rows_per_seg / 64) * p.ksplit * segs;
   constexpr bool QS = (QP & 4) != 0;
   constexpr int smem1 = attention_smem<NP, NS, 1, QS>(), smem2 = attention_smem<NP, NS, 2, QS>();
-  // one instantiation per prefetch kind (gemm_h16.h); the single-plane mode never prefetches
+  // one instantiation per prefetch kind (gemm_h16.h)
   constexpr int PFW = NP == 2 ? 1 : 0;   // attention launches carry at most one target
-  const bool pfw = NP == 2 && prefetch_kind(p.pf) >= 1;
+  const AttnLaunchShape shape = attention_launch_shape(p, heads, segs, NP, QS);
+  const bool pfw = shape.prefetch;
   const dim3 g1(heads, (p.q_rows_per_seg / 32) * p.ksplit, segs), g2(heads, (p.q_rows_per_seg / 64) * p.ksplit, segs);
-  const int qb = attention_query_blocks((p.allow_qb4 && !QS) ? blocks64 : (blocks64 > 256 ? 256 : blocks64), p.q_rows_per_seg, NP);
+  const int qb = shape.qb;
   if constexpr (NP == 2 && !QS) {
     if (qb == 4) {   // (no prefetch wave: the caller moved the launch's weight target elsewhere -- msd_api.hip)
       const dim3 g4(heads, (p.q_rows_per_seg / 128) * p.ksplit, segs);
@@ -789,8 +814,7 @@ inline hipError_t launch_attention(const AttnParams& p_in, int heads, int segs, 
   static const hipError_t attr = attention_prepare<NP, NS>();
   if (attr != hipSuccess) return attr;
   AttnParams p = p_in;
-  p.ksplit_log2 = 0;
-  while ((2 << p.ksplit_log2) <= p.ksplit) ++p.ksplit_log2;
+  p.ksplit_log2 = attention_ksplit_log2(p.ksplit);
   p.ksplit = 1 << p.ksplit_log2;   // a power of two (a request for 3 runs as 2): the kernel shifts, it never divides
   if constexpr (NP == 2) {
     if (p.q_ssq != nullptr && (p.q_tiles <= 0 || p.q_tiles > kAuxMaxTiles || p.q_tiles % 4)) return hipErrorInvalidValue;

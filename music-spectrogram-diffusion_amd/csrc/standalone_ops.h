@@ -1,5 +1,5 @@
 // The msd_op_* entry points: the library's building blocks one at a time, for the unit tests (tests/test_gpu_ops.py,
-// test_gpu_fused_ops.py, test_gpu_gemm_sites.py, test_gpu_keep_frames.py, test_gpu_edit_strength.py, test_gpu_few_steps.py, test_gpu_threefry.py).  Host code only, and no
+// test_gpu_fused_ops.py, test_gpu_gemm_sites.py, test_gpu_attention_forms.py (+ attention_forms.py, test_attention_forms_host.py), test_gpu_keep_frames.py, test_gpu_edit_strength.py, test_gpu_few_steps.py, test_gpu_threefry.py).  Host code only, and no
 // part of the product's paths; the file belongs to msd_api.hip alone, which includes it behind its own entry points and
 // in front of the vocoder's.
 // Every GEMM here runs through the product's dispatch (gemm / gemm_on on a site's TileTable), so its tile is an entry of
@@ -548,6 +548,126 @@ int op_sampler_step(const msd_config* cfg, int step_index, const float* z_dev, c
   }
   return sampler_op_finish(s);
 }
+
+// ---- one attention launch the way the decoder fills it (tests/test_gpu_attention_forms.py) ---------------------------
+// The caller's float32 arrays become planes that are NaN wherever the launch has no business: the operands are gathered
+// dense, split (the range flag sees the caller's values only), and scattered into their place of all-NaN planes.
+template <int NP>
+struct AttnLaunchRun : OpKit {
+  msd_attention_launch_args* g;
+
+  AttnLaunchRun(msd_attention_launch_args* g_, hipStream_t s_) : OpKit(s_, NP), g(g_) {}
+
+  // `blocks` blocks of `rows` rows of `width` floats, block b from src + b * block_stride, row pitch ld -> dense planes
+  bool gather(const float* src, size_t block_stride, int ld, int blocks, int rows, int width, Planes* out) {
+    float* dense = get<float>((size_t)blocks * rows * width);
+    if (!dense) return false;
+    for (int b = 0; b < blocks; ++b)
+      if (!ok(hipMemcpy2DAsync(dense + (size_t)b * rows * width, (size_t)width * sizeof(float), src + b * block_stride,
+                               (size_t)ld * sizeof(float), (size_t)width * sizeof(float), rows, hipMemcpyDeviceToDevice, s)))
+        return false;
+    return operand(dense, (size_t)blocks * rows * width, out);
+  }
+  // dense planes [blocks][rows][width] -> block b at off + b * block_stride, row pitch ld, of new planes of `total`
+  // elements, NaN everywhere else
+  bool scatter(const Planes& dense, size_t total, size_t off, size_t block_stride, int ld, int blocks, int rows, int width,
+               Planes* out) {
+    if (!planes(total, out, true)) return false;
+    for (int i = 0; i < np; ++i)
+      for (int b = 0; b < blocks; ++b)
+        if (!ok(hipMemcpy2DAsync(out->p[i] + off + b * block_stride, (size_t)ld * sizeof(h16_t),
+                                 dense.p[i] + (size_t)b * rows * width, (size_t)width * sizeof(h16_t),
+                                 (size_t)width * sizeof(h16_t), rows, hipMemcpyDeviceToDevice, s)))
+          return false;
+    return true;
+  }
+
+  int run() {
+    const int heads = g->heads, segs = g->segs, rows = g->q_rows_per_seg, J = heads * kHeadDim;
+    const int ka = g->k_alloc_rows, r0 = g->k_row0, kr = g->k_rows;
+    const size_t total_rows = (size_t)segs * rows;
+    const bool self = g->k == g->q;
+    // n_keys: the kernel clamps its reads into the window whatever the count says, but a count beyond the window is no launch
+    // of the decoder's
+    std::vector<int32_t> nk(segs);
+    if (!ok(hipMemcpy(nk.data(), g->n_keys, nk.size() * sizeof(int32_t), hipMemcpyDeviceToHost))) return rc;
+    for (int32_t n : nk)
+      if (n < 0 || n > kr) return MSD_ERR_INVALID_ARGUMENT;
+    if (!init_flags()) return rc;
+    ctx_model.prefetch = true;
+
+    Planes q, k, vt, o, dense;
+    if (self) {   // q | k interleaved in one buffer: split once, the whole of it is the launch's
+      if (!operand(g->q, total_rows * g->ldq, &q)) return rc;
+      k = q;
+    } else {
+      if (!gather(g->q + g->q_col, 0, g->ldq, 1, (int)total_rows, J, &dense) ||
+          !scatter(dense, total_rows * g->ldq, (size_t)g->q_col, 0, g->ldq, 1, (int)total_rows, J, &q))
+        return rc;
+      if (!gather(g->k + (size_t)r0 * g->ldk + g->k_col, (size_t)ka * g->ldk, g->ldk, segs, kr, J, &dense) ||
+          !scatter(dense, (size_t)segs * ka * g->ldk, (size_t)r0 * g->ldk + g->k_col, (size_t)ka * g->ldk, g->ldk, segs, kr, J, &k))
+        return rc;
+    }
+    {   // the window of V -> V^T [segs][J][k_rows] with the per-16 key permutation (host copy, as msd_op_attention_ex),
+        // then columns [k_row0, k_row0 + k_rows) of V^T [segs][J][k_alloc_rows]
+      std::vector<float> vh((size_t)segs * ka * J), vth((size_t)segs * J * kr);
+      if (!ok(hipMemcpy(vh.data(), g->v, vh.size() * sizeof(float), hipMemcpyDeviceToHost))) return rc;
+      for (int sg = 0; sg < segs; ++sg)
+        for (int key = 0; key < kr; ++key) {
+          const int kp = vt_key_pos(key);
+          const float* src = &vh[((size_t)sg * ka + r0 + key) * J];
+          for (int j = 0; j < J; ++j) vth[((size_t)sg * J + j) * kr + kp] = src[j];
+        }
+      float* vt32 = get<float>(vth.size());
+      if (!vt32 || !ok(hipMemcpy(vt32, vth.data(), vth.size() * sizeof(float), hipMemcpyHostToDevice)) ||
+          !operand(vt32, vth.size(), &dense) ||
+          !scatter(dense, (size_t)segs * J * ka, (size_t)r0, 0, ka, 1, segs * J, kr, &vt))
+        return rc;
+    }
+    if (!planes(total_rows * J, &o, true)) return rc;
+
+    AttnParams p;
+    arm(p);
+    p.qp = g->qp;
+    p.allow_qb4 = g->allow_qb4 != 0;
+    if (g->q_ssq) { p.q_ssq = g->q_ssq; p.q_tiles = g->q_tiles; p.q_inv_d = 1.0f / (float)(kNarrowTile * g->q_tiles); }
+    const size_t k_off = (size_t)r0 * g->ldk + g->k_col;
+    for (int i = 0; i < 2; ++i) {
+      const int j = i < NP ? i : 0;
+      p.q[i] = q.p[j] + g->q_col; p.k[i] = k.p[j] + k_off; p.vt[i] = vt.p[j] + r0; p.o[i] = o.p[j];
+    }
+    p.n_keys = g->n_keys; p.ldq = g->ldq; p.ldk = g->ldk; p.ldo = J; p.vt_ld = ka; p.q_rows_per_seg = rows;
+    p.k_seg_stride = (size_t)ka * g->ldk; p.vt_seg_stride = (size_t)J * ka; p.k_rows = kr;
+    p.vt_cols = (r0 == 0 && kr == ka) ? 0 : kr;
+    p.ksplit = g->ksplit; p.part_o = nullptr; p.part_ml = nullptr; p.total_rows = (int)total_rows;
+    p.touch_ahead = g->touch_ahead; p.pf_late = g->pf_late;
+    if (g->prefetch_rows) {
+      Planes w;
+      if (!planes((size_t)g->prefetch_rows * g->prefetch_k, &w)) return rc;
+      p.pf = prefetch_of<NP>(&ctx_model, w, g->prefetch_rows, g->prefetch_k);
+    }
+    AttnParams ran = p;   // as launch_attention will see it: the split a power of two
+    ran.ksplit = 1 << attention_ksplit_log2(p.ksplit);
+    if (ran.ksplit > 1) {
+      p.part_o = get<float>((size_t)ran.ksplit * total_rows * J);
+      p.part_ml = get<float>((size_t)ran.ksplit * total_rows * heads * 2);
+      if (!p.part_o || !p.part_ml) return rc;
+      if (g->merge_in_launch) {   // one (zeroed) arrival counter per (segment, 32-row query block, head): enough for every block shape
+        p.tickets = get<int>((size_t)segs * (rows / 32) * heads);
+        if (!p.tickets) return rc;
+      }
+    }
+    const AttnLaunchShape shape = attention_launch_shape(ran, heads, segs, NP, g->q_ssq != nullptr);
+    g->ran_qb = shape.qb; g->ran_prefetch_wave = shape.pf_wave; g->ran_touch_ahead = shape.touch_ahead; g->ran_ksplit = ran.ksplit;
+    hipError_t e = hipSuccess;
+    for (int r = 0; r < g->repeats && e == hipSuccess; ++r)   // back to back: the counters must be zero again after every launch
+      e = launch_attention<NP>(p, heads, segs, s);
+    if (e != hipSuccess) return MSD_ERR_HIP;
+    back(o, g->o, total_rows * J);
+    const int frc = finish();
+    return rc ? rc : frc;
+  }
+};
 }  // namespace
 
 extern "C" {
@@ -661,6 +781,43 @@ int msd_op_attention_ex(int precision, int qp, int ksplit, int merge_in_launch, 
   if (e != hipSuccess) return MSD_ERR_HIP;
   kit.back(o, o_dev, (size_t)n_q * J);
   return kit.finish();
+}
+
+int msd_op_attention_launch(msd_attention_launch_args* g, void* stream) {
+  if (!g || g->struct_size != (int32_t)sizeof(msd_attention_launch_args)) return MSD_ERR_INVALID_ARGUMENT;
+  g->ran_qb = g->ran_prefetch_wave = g->ran_touch_ahead = g->ran_ksplit = 0;
+  if (g->qp < 0 || g->qp > 3 || g->ksplit < 1 || g->ksplit > 8 || g->repeats < 1 || g->repeats > 1000) return MSD_ERR_INVALID_ARGUMENT;
+  if (g->heads <= 0 || g->heads > 64 || g->segs <= 0 || g->segs > 1024 || g->q_rows_per_seg <= 0 || g->q_rows_per_seg % 64 ||
+      g->q_rows_per_seg > 65536 || !g->q || !g->k || !g->v || !g->n_keys || !g->o)
+    return MSD_ERR_INVALID_ARGUMENT;
+  const int J = g->heads * kHeadDim;
+  // the window lies inside the allocation; whole 32-key blocks (the plain op's rule) from a 32-key boundary (the V^T
+  // permutation works on 16 keys, a DMA lane moves 8 elements: rows of K and of V^T start on 16 bytes)
+  if (g->k_alloc_rows <= 0 || g->k_alloc_rows > (1 << 20) || g->k_alloc_rows % 8 || g->k_rows <= 0 || g->k_rows % 32 ||
+      g->k_row0 < 0 || g->k_row0 % 32 || (int64_t)g->k_row0 + g->k_rows > g->k_alloc_rows)
+    return MSD_ERR_INVALID_ARGUMENT;
+  // the heads' columns fit the rows of q and of k
+  if (g->ldq <= 0 || g->ldq > (1 << 20) || g->ldq % 8 || g->q_col < 0 || g->q_col % 8 || (int64_t)g->q_col + J > g->ldq ||
+      g->ldk <= 0 || g->ldk > (1 << 20) || g->ldk % 8 || g->k_col < 0 || g->k_col % 8 || (int64_t)g->k_col + J > g->ldk)
+    return MSD_ERR_INVALID_ARGUMENT;
+  if (g->k == g->q && (g->ldk != g->ldq || g->k_row0 != 0 || g->k_rows != g->k_alloc_rows || g->k_rows != g->q_rows_per_seg))
+    return MSD_ERR_INVALID_ARGUMENT;
+  if (g->touch_ahead < 0 || g->touch_ahead > 16 || g->pf_late < 0 || g->pf_late > 1) return MSD_ERR_INVALID_ARGUMENT;
+  if ((g->prefetch_rows != 0) != (g->prefetch_k != 0) || g->prefetch_rows < 0 || g->prefetch_rows > (1 << 20) ||
+      g->prefetch_k < 0 || g->prefetch_k % kGemmBK || g->prefetch_k > 4096)
+    return MSD_ERR_INVALID_ARGUMENT;
+  // the kernels index rows, partials and planes with 32-bit offsets
+  const int64_t total_rows = (int64_t)g->segs * g->q_rows_per_seg, lim = 0x7FFFFFFFll;
+  if (total_rows * g->ldq > lim || (int64_t)g->segs * g->k_alloc_rows * (g->ldk > J ? g->ldk : J) > lim ||
+      total_rows * J * 8 * (int64_t)sizeof(float) > lim)
+    return MSD_ERR_INVALID_ARGUMENT;
+  if (g->q_ssq != nullptr && (g->q_tiles <= 0 || g->q_tiles > kAuxMaxTiles || g->q_tiles % 4)) return MSD_ERR_INVALID_ARGUMENT;
+  const int NP = op_planes(g->precision);
+  if (NP < 0) return MSD_ERR_UNSUPPORTED;
+  if (g->q_ssq != nullptr && NP != 2) return MSD_ERR_UNSUPPORTED;   // (un-normalised queries: two-plane kernels only)
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (NP == 2) return AttnLaunchRun<2>(g, s).run();
+  return AttnLaunchRun<1>(g, s).run();
 }
 
 int msd_op_threefry(int stage, uint64_t seed, int64_t fold, const uint32_t* bits_in_dev, float* out_dev, int64_t n,

@@ -71,7 +71,9 @@ EXPORTED_SYMBOLS = (
     # (appended to ABI 7) edit strength: per-frame release words and a part-way start of the sampler
     'msd_sample_edit', 'msd_op_sampler_step_release', 'msd_op_diffuse_to_step',
     # (appended to ABI 7) a step count and a sampler per call; the second-order multistep sampler
-    'msd_sample_steps', 'msd_op_sampler_step_multistep')
+    'msd_sample_steps', 'msd_op_sampler_step_multistep',
+    # (appended to ABI 7) one attention launch the way the decoder fills it
+    'msd_op_attention_launch')
 
 
 def divisors(n: int):
@@ -139,6 +141,15 @@ class GemmSiteArgs(ctypes.Structure):
            'ran_bm2', 'ran_bn2', 'ran_ns2', 'ran_xcd_rows2', 'step_copy')
   _PTRS = ('a', 'w', 'w_gate', 'ssq', 'bias', 'g_lo', 'g_hi', 'g2', 'pos', 'a2', 'w2', 'addend2', 'prefetch',
            'x', 'out', 'y', 'y2', 'ssq_out', 'out2')
+  _fields_ = [(n, ctypes.c_int32) for n in _INTS] + [(n, ctypes.c_void_p) for n in _PTRS]
+
+
+class AttentionLaunchArgs(ctypes.Structure):
+  """msd_attention_launch_args of include/msd_amd.h, field for field."""
+  _INTS = ('struct_size', 'precision', 'qp', 'heads', 'segs', 'q_rows_per_seg', 'repeats', 'ksplit', 'merge_in_launch',
+           'allow_qb4', 'ldq', 'q_col', 'ldk', 'k_col', 'k_alloc_rows', 'k_row0', 'k_rows', 'prefetch_rows', 'prefetch_k',
+           'touch_ahead', 'pf_late', 'q_tiles', 'ran_qb', 'ran_prefetch_wave', 'ran_touch_ahead', 'ran_ksplit')
+  _PTRS = ('q', 'k', 'v', 'n_keys', 'q_ssq', 'o')
   _fields_ = [(n, ctypes.c_int32) for n in _INTS] + [(n, ctypes.c_void_p) for n in _PTRS]
 
 
@@ -267,6 +278,8 @@ def load(planes: str = 'f16') -> ctypes.CDLL:
     lib.msd_op_gemm_site_tiles.argtypes = [i32, i32, i32, c.POINTER(c.c_int32), c.POINTER(c.c_int32), c.POINTER(c.c_int32)]
     lib.msd_op_gemm_site_name.argtypes = [i32, i32]
     lib.msd_op_gemm_site_name.restype = c.c_char_p
+  if 'msd_op_attention_launch' in present:   # (appended to ABI 7)
+    lib.msd_op_attention_launch.argtypes = [c.POINTER(AttentionLaunchArgs), vp]
   for name in present:
     fn = getattr(lib, name)
     if name not in ('msd_version', 'msd_last_error', 'msd_destroy', 'msd_vocoder_last_error', 'msd_vocoder_destroy',
@@ -580,6 +593,28 @@ def op_attention_ex(precision: str, q, k, v, o, heads: int, ksplit: int = 1, mer
                                n_keys, nv, heads, stream)
   if rc:
     raise _EXC.get(rc, RuntimeError)('msd_op_attention_ex failed (%d)' % rc)
+
+
+def op_attention_launch(precision: str, stream: int = 0, planes: Optional[str] = None, **fields) -> Dict[str, int]:
+  """One attention launch the way the decoder fills it (msd_op_attention_launch).  `fields`: the members of
+  msd_attention_launch_args by name -- integers, and device tensors for the pointers (float32; n_keys int32), kept alive
+  by the caller.  Defaults: one launch, no split, qp 0.  Returns the ran_* out-fields."""
+  lib = load(planes or plane_format(precision))
+  args = AttentionLaunchArgs()
+  args.struct_size = ctypes.sizeof(AttentionLaunchArgs)
+  args.precision = PRECISIONS[precision]
+  args.repeats = args.ksplit = 1
+  for name, value in fields.items():
+    if name in AttentionLaunchArgs._PTRS:
+      setattr(args, name, _ptr(value))
+    elif name in AttentionLaunchArgs._INTS and not name.startswith('ran_') and name != 'precision':
+      setattr(args, name, int(value))
+    else:
+      raise TypeError('msd_attention_launch_args has no input field %r' % name)
+  rc = lib.msd_op_attention_launch(ctypes.byref(args), stream)
+  if rc:
+    raise _EXC.get(rc, RuntimeError)('msd_op_attention_launch failed (msd_status %d)' % rc)
+  return {n: getattr(args, n) for n in AttentionLaunchArgs._INTS if n.startswith('ran_')}
 
 
 def _op_check(rc, what):

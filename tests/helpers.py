@@ -118,6 +118,18 @@ def cached_model(cache, preset, steps, sampler='ddpm'):
   return cache[key]
 
 
+def attention_ref(q, k, v, heads, valid, rstd=None):
+  """float64 oracle attention of [n_q, heads*64] queries on the first `valid` keys; rstd (per query row) scales the
+  queries first -- the un-normalised form's algebra."""
+  from oracle import ops
+  xp = backend.TorchBackend('float64')
+  nq = q.shape[0]
+  q64 = q.astype(np.float64) if rstd is None else q.astype(np.float64) * rstd[:, None]
+  sh = lambda x, n: xp.asarray(np.ascontiguousarray(x, np.float64).reshape(1, n, heads, 64))
+  out = ops.dot_product_attention(xp, sh(q64, nq), sh(k[:valid], valid), sh(v[:valid], valid))
+  return xp.to_numpy(out).reshape(nq, heads * 64).astype(np.float64)
+
+
 def rms(a, b):
   a = np.asarray(a, np.float64)
   b = np.asarray(b, np.float64)

@@ -2,6 +2,9 @@
 import numpy as np
 import pytest
 
+from tests.attention_forms import unnormalised_queries as _unnormalised_queries
+from tests.helpers import attention_ref as _attention_ref
+
 pytestmark = pytest.mark.gpu
 
 
@@ -265,18 +268,6 @@ def test_attention_spiked_key_forces_online_rescale(env):
   assert np.abs(o.cpu().numpy() - ref).max() < 1e-4
 
 
-def _attention_ref(q, k, v, heads, valid, rstd=None):
-  """float64 oracle attention of [n_q, heads*64] queries on the first `valid` keys; rstd (per query row) scales the
-  queries first -- the un-normalised form's algebra."""
-  from oracle import backend, ops
-  xp = backend.TorchBackend('float64')
-  nq = q.shape[0]
-  q64 = q.astype(np.float64) if rstd is None else q.astype(np.float64) * rstd[:, None]
-  sh = lambda x, n: xp.asarray(np.ascontiguousarray(x, np.float64).reshape(1, n, heads, 64))
-  out = ops.dot_product_attention(xp, sh(q64, nq), sh(k[:valid], valid), sh(v[:valid], valid))
-  return xp.to_numpy(out).reshape(nq, heads * 64).astype(np.float64)
-
-
 def _blocks64(nq, heads, ksplit):   # attention.h attention_query_blocks: 128-row blocks need > 256 64-row blocks
   return heads * (nq // 64) * ksplit
 
@@ -349,20 +340,6 @@ def test_attention_128_row_blocks_sharp_logits_and_spiked_key(env, s_std):
     err = np.abs(got[True] - ref).max() / max(1.0, np.abs(ref).max())
     print('128-row blocks, logit std %.0f, %s: max err %.2e' % (s_std, name, err))
     assert err < bound, (name, err)
-
-
-def _unnormalised_queries(rng, nq, j, d=768):
-  """(q_unnorm, ssq [nq, d / 32], rstd): queries of O(1) logits times the 1/rstd of a random residual stream x [nq, d]
-  whose row rms spans 1e-1 ... 1e3 (log-uniform), with rows 1e4 apart side by side in the first query block."""
-  rms = 10.0 ** rng.uniform(-1, 3, nq)
-  rms[:32:2], rms[1:32:2] = 0.1, 1e3
-  x = rng.standard_normal((nq, d)) * rms[:, None]
-  x = x.astype(np.float32).astype(np.float64)
-  ssq = (x * x).reshape(nq, d // 32, 32).sum(-1).astype(np.float32)
-  rstd = 1.0 / np.sqrt(ssq.astype(np.float64).sum(-1) / d + 1e-6)
-  q = (rng.standard_normal((nq, j)) * 0.35 / rstd[:, None]).astype(np.float32)
-  assert np.abs(q).max() < 65504
-  return q, ssq, rstd
 
 
 @pytest.mark.parametrize('prec', ['f16x3', 'bf16x3'])
