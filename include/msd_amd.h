@@ -211,6 +211,15 @@ typedef struct msd_config {
                                      it.  Same float32-class result, not bit-identical to the per-tile launch (another
                                      contraction of the epilogue's multiply-adds).  0 = the library's choice (on), 1 = on,
                                      2 = off */
+  /* appended to ABI 7 (msd_create also takes the struct WITHOUT this field, at ABI 6's size: it then reads as 0) */
+  int32_t touch_carrier;          /* who carries a launch's weight-prefetch touches at one song per call:
+                                     1 = one extra wave inside every compute block of the carrier launch; 2 = touch blocks
+                                     -- extra blocks behind the compute grid, on CUs the launch leaves idle, that do nothing
+                                     but touch and end: the self- and the cross-attention launches carry their targets
+                                     that way, and the cross-attention's in-block wave keeps its own K / V^T touch-ahead
+                                     only.  Bit-identical results (a touch has no reader).  0 = the library's choice (2;
+                                     DESIGN.md 6 says why).  Launches of more than one song per call, and every GEMM
+                                     carrier, keep the in-block waves. */
 } msd_config;
 
 const char* msd_version(void);
@@ -376,6 +385,11 @@ int msd_sample_steps(msd_model* m, int batch, int rng, int per_row, const uint64
 
 /* Drop the captured hipGraph of the DDPM step; the next msd_sample captures it again. */
 int msd_reset_graph(msd_model* m);
+
+/* (appended to ABI 7) msd_config.touch_carrier of a live handle: 0 = back to the library's choice, 1, 2.  The step plan
+ * -- which is the key of the captured graphs -- follows at the next sampling call; graphs of the other form stay cached
+ * until msd_reset_graph.  Not while a sampling call of this handle is in flight. */
+int msd_set_touch_carrier(msd_model* m, int32_t touch_carrier);
 
 /* One decoder call of the scan body: pred_fn(z, time=(i+1)/N, include_conditioning)
  * (models.py:373-386 -> network.py:561-573).  For parity tests and profiling.
@@ -698,6 +712,32 @@ typedef struct msd_attention_launch_args {
   float* o;
 } msd_attention_launch_args;
 int msd_op_attention_launch(msd_attention_launch_args* args, void* stream);
+
+/* (appended to ABI 7) One launch WITH A WEIGHT TARGET in either carrier form (msd_config.touch_carrier).  The op makes
+ * the target itself: two planes [target_rows][target_k] of 16-bit elements in ONE allocation of exactly their size, so
+ * the last line a touch may read ends where the allocation ends.  `prefetch*` of the launch arguments are ignored.
+ * Two-plane precisions only.  A touch has no reader: the outputs of the three forms are bit-identical. */
+typedef struct msd_carrier_args {
+  int32_t struct_size;
+  int32_t form;                   /* 0 = no target, 1 = the in-block wave, 2 = touch blocks */
+  int32_t n_touch;                /* form 2: touch blocks asked for (1 .. 1024; the launch keeps within one round of the chip) */
+  int32_t delay;                  /* form 2: counted sleep rounds in front of the touches (0 .. 64, ~0.2 us each) */
+  int32_t target_rows, target_k;  /* form != 0: rows and elements per row of one plane (k a multiple of 64, <= 4096) */
+  /* out */
+  int32_t ran_form;               /* what the launch ran: 2 only where the kernel has a touch-block form and a slot was free */
+  int32_t ran_touch_blocks;
+  int32_t ran_range_flag;         /* the half-plane range flag after the launch (0 = clean) */
+} msd_carrier_args;
+int msd_op_gemm_site_carrier(msd_gemm_site_args* args, msd_carrier_args* carrier, void* stream);
+int msd_op_attention_launch_carrier(msd_attention_launch_args* args, msd_carrier_args* carrier, void* stream);
+/* Host only, no GPU call: how a target of `target_bytes` -- rows of `row_bytes` bytes (<= 8192), `row_pitch` bytes apart,
+ * the last row ending the target -- is dealt over `waves` touching waves, by the function both device forms use.
+ * Each touch is evaluated lane by lane with the predicate the device waves use; the target is ONE plane (the device deals a
+ * two-plane target as 2 x rows rows, plane 1 behind plane 0, with the same predicate).
+ * ranges[(w * R + u) * 3 + {0, 1, 2}] = first row, rows, and 128-byte lines per row of touch u of wave w (rows 0 = nothing),
+ * R = the return value (touches per wave).  Negative: -msd_status (bad arguments, `capacity` int32 words too few, or
+ * MSD_ERR_UNSUPPORTED: more rows than the waves cover in R touches each). */
+int msd_op_touch_deal(int64_t target_bytes, int32_t row_bytes, int32_t row_pitch, int32_t waves, int32_t* ranges, int32_t capacity);
 
 #ifdef __cplusplus
 }

@@ -68,6 +68,7 @@ struct AttnParams {
                              // weights late -0.9 ... -1.2 %, the stage touches late another -0.5 ... -1.1 % from ~1150 keys,
                              // 0 at 557 (profiles/r06q_pf_place_ab*.log).  The weights still arrive a launch ahead of
                              // their GEMM.  Bit-identical (a touch has no reader).
+  int grid_y = 0;            // touch-block form (launcher): the compute grid's y extent; blocks with blockIdx.y >= grid_y touch
   int* tickets = nullptr;    // ksplit > 1, in-launch merge (round 6, attention_inlaunch_merge below): one arrival counter per
                              // (segment, query block of this launch, head), all zero between launches; nullptr = the
                              // separate attention_merge_kernel launch finishes the split
@@ -287,7 +288,11 @@ __device__ __forceinline__ void attention_inlaunch_merge(const AttnParams& p, in
 // O += V^T.P^T as one plane): 2 instead of 3 MFMAs for that product, and no hi / lo split of P.  The memory side
 // (K, V) always keeps both planes (dropping those costs 20 - 50x the error).  0 = all three products.
 // Bit 2 (QS): the queries are un-normalised, see AttnParams::q_ssq.
-template <int NP, int NS, int QB, int PF = kPfNone, int QP = 0>
+// TB: the touch-block carrier form (gemm_h16.h "Touch blocks"): the launch's weight target is touched by the blocks with
+// blockIdx.y >= p.grid_y, on CUs the compute grid leaves idle, and by nobody else.  PF then only says whether the compute
+// blocks have a prefetch wave at all -- for their own K / V^T touch-ahead (cross-attention) -- and that wave touches no
+// weights.  Every wave of a touch block touches (its extra wave included).
+template <int NP, int NS, int QB, int PF = kPfNone, int QP = 0, bool TB = false>
 __global__ void __launch_bounds__(QB * kAttKG * 64 + (kPfWaveAttn && PF != kPfNone ? 64 : 0)) attention_kernel(AttnParams p) {
   // Every multiply-add of this kernel that is MEANT to be fused is an explicit fma, and nothing else may be: left to
   // -ffp-contract=fast the instantiations contracted differently (round 6: <QB = 2, PF = 1> fused four packed
@@ -296,22 +301,33 @@ __global__ void __launch_bounds__(QB * kAttKG * 64 + (kPfWaveAttn && PF != kPfNo
 #pragma clang fp contract(off)
   static_assert(QB < 4 || PF == kPfNone, "16 compute waves fill the workgroup: no prefetch wave");
   warm_kernargs<kernarg_lines<AttnParams>()>();
+  static_assert(!TB || (QB < 4 && NP == 2), "touch blocks: the two-plane 32- and 64-row forms");
+  constexpr int WPF = TB ? kPfNone : PF;   // the weight targets the prefetch WAVE touches
+  if constexpr (TB) {
+    if ((int)blockIdx.y >= p.grid_y) {   // a touch block: no tile work, no LDS, no barrier
+      const int ty = (int)gridDim.y - p.grid_y;
+      touch_block<1>(p.pf, (int)blockIdx.x + (int)gridDim.x * ((int)blockIdx.y - p.grid_y + ty * (int)blockIdx.z),
+                     (int)gridDim.x * ty * (int)gridDim.z, p.q[0]);
+      return;
+    }
+  }
   if constexpr (kPfWaveAttn && PF != kPfNone) {
     if (threadIdx.x >= QB * kAttKG * 64) {   // the prefetch wave: a later GEMM's weights (+ this block's later K / V^T stages)
       if (p.touch_ahead <= 0) {   // weights only, and the wave ends (an ended wave does not count at s_barrier)
         const int lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-        prefetch_wave<PF>(p.pf, lin, gridDim.x * gridDim.y * gridDim.z, p.q[0]);
+        prefetch_wave<WPF>(p.pf, lin, gridDim.x * gridDim.y * gridDim.z, p.q[0]);
         return;
       }
       extern __shared__ __attribute__((aligned(16))) char smem_pf[];
-      kv_touch_ahead<NP, NS, PF>(p, smem_pf + attention_work_smem<NP, NS, QB>());
+      kv_touch_ahead<NP, NS, WPF>(p, smem_pf + attention_work_smem<NP, NS, QB>());
       return;
     }
   }
   constexpr bool Q1 = NP == 2 && (QP & 1), P1 = NP == 2 && (QP & 2), QS = (QP & 4) != 0;
   static_assert(!QS || QB < 4, "un-normalised queries: 32- and 64-row blocks only (the 128-row block fills the LDS)");
 #if MSD_TIMESTAMPS
-  const int ts_blk = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+  const int ts_gy = TB ? p.grid_y : (int)gridDim.y;   // (touch blocks stamp nothing: the compute blocks stay densely numbered)
+  const int ts_blk = blockIdx.x + gridDim.x * (blockIdx.y + ts_gy * blockIdx.z);
   constexpr int ts_cls = QB == 1 ? 4 : 5;
 #endif
   MSD_TS_BEGIN(ts_cls, ts_blk)
@@ -643,7 +659,8 @@ __global__ void __launch_bounds__(QB * kAttKG * 64 + (kPfWaveAttn && PF != kPfNo
       rc.commit(p.sat, p.sat_tag);
     } else if (p.tickets != nullptr) {
       // in-launch merge: group = (segment, query block of the launch, head); the LDS word behind the merge slab is free
-      const int heads = gridDim.x, nblk = (int)(gridDim.y >> kl2);
+      // (touch blocks sit behind grid_y: they draw no ticket and are in no group)
+      const int heads = gridDim.x, nblk = (int)((TB ? (unsigned)p.grid_y : gridDim.y) >> kl2);
       const int group = ((int)seg * nblk + blk) * heads + head;
       int* slot = reinterpret_cast<int*>(smem + QB * kAttKG * kAttWStride * 4);
       if (p.ksplit == 4) attention_inlaunch_merge<NP, 4>(p, ks, row, head, heads, d0, acc, mt, lt, group, tid, slot);
@@ -663,7 +680,7 @@ __global__ void __launch_bounds__(QB * kAttKG * 64 + (kPfWaveAttn && PF != kPfNo
   }
   prefetch_done(pf_keep);
   MSD_TS_AT(ts_cls, ts_blk, 5)
-  MSD_TS_END(ts_cls, ts_blk, gridDim.x * gridDim.y * gridDim.z)
+  MSD_TS_END(ts_cls, ts_blk, gridDim.x * ts_gy * gridDim.z)
 }
 
 // Finish a key-split attention: out[row][head*64 + d] = sum_ks O_ks e^(m_ks - m) / sum_ks l_ks e^(m_ks - m)
@@ -732,6 +749,13 @@ inline hipError_t attention_prepare_one() {
   if constexpr (QB < 4)
     b = hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<NP, NS, QB, NP == 2 ? 1 : 0, QP>),
                             hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+  if constexpr (QB < 4 && NP == 2) {   // the touch-block forms: without and with a prefetch wave (its K / V^T touch-ahead)
+    const hipError_t c = hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<NP, NS, QB, kPfNone, QP, true>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    const hipError_t d = hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<NP, NS, QB, 1, QP, true>),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+    if (b == hipSuccess) b = c != hipSuccess ? c : d;
+  }
   return a != hipSuccess ? a : b;
 }
 
@@ -770,20 +794,31 @@ inline int attention_ksplit_log2(int ksplit) {
 //                single-plane mode never prefetches, 16 compute waves leave no room for the wave)
 //   pf_wave      ... from a wave of its own (kPfWaveAttn)
 //   touch_ahead  ... which also runs kv_touch_ahead
-struct AttnLaunchShape { int qb; bool prefetch, pf_wave, touch_ahead; };
+//   touch_y      touch-block form: rows of `heads` touch blocks behind the compute grid's y extent (0 = the wave form).
+//                The target then rides on those blocks alone; the compute blocks keep a prefetch wave only for their own
+//                K / V^T touch-ahead (pf_wave && touch_ahead), none otherwise
+struct AttnLaunchShape { int qb; bool prefetch, pf_wave, touch_ahead; int touch_y; };
 inline AttnLaunchShape attention_launch_shape(const AttnParams& p, int heads, int segs, int np, bool qs) {
   const int blocks64 = heads * (p.q_rows_per_seg / 64) * p.ksplit * segs;
   AttnLaunchShape s;
   s.qb = attention_query_blocks((p.allow_qb4 && !qs) ? blocks64 : (blocks64 > 256 ? 256 : blocks64), p.q_rows_per_seg, np);
   s.prefetch = np == 2 && prefetch_kind(p.pf) >= 1 && s.qb < 4;
-  s.pf_wave = kPfWaveAttn && s.prefetch;
+  s.touch_y = 0;
+  if (s.prefetch && p.pf.touch_blocks > 0) {   // whole rows of `heads` x `segs` blocks within one round of the chip
+    const int grid = heads * (p.q_rows_per_seg / (32 * s.qb)) * p.ksplit * segs;
+    const int smem = s.qb == 1 ? (qs ? attention_smem<2, 2, 1, true>() : attention_smem<2, 2, 1, false>())
+                               : (qs ? attention_smem<2, 2, 2, true>() : attention_smem<2, 2, 2, false>());
+    s.touch_y = touch_blocks_fit(p.pf.touch_blocks, grid, smem) / (heads * segs);
+  }
+  s.pf_wave = kPfWaveAttn && s.prefetch && (s.touch_y == 0 || p.touch_ahead > 0);
   s.touch_ahead = s.pf_wave && p.touch_ahead > 0;
   return s;
 }
 
 template <int NP, int QP>
-inline void launch_attention_qp(const AttnParams& p, int heads, int segs, hipStream_t stream) {
+inline void launch_attention_qp(const AttnParams& p_in, int heads, int segs, hipStream_t stream) {
   constexpr int NS = attention_ns<NP>();
+  AttnParams p = p_in;
   constexpr bool QS = (QP & 4) != 0;
   constexpr int smem1 = attention_smem<NP, NS, 1, QS>(), smem2 = attention_smem<NP, NS, 2, QS>();
   // one instantiation per prefetch kind (gemm_h16.h)
@@ -796,6 +831,22 @@ inline void launch_attention_qp(const AttnParams& p, int heads, int segs, hipStr
     if (qb == 4) {   // (no prefetch wave: the caller moved the launch's weight target elsewhere -- msd_api.hip)
       const dim3 g4(heads, (p.q_rows_per_seg / 128) * p.ksplit, segs);
       hipLaunchKernelGGL((attention_kernel<NP, NS, 4, kPfNone, QP>), g4, dim3(4 * kAttKG * 64), (attention_smem<NP, NS, 4>()), stream, p);
+      return;
+    }
+  }
+  if constexpr (NP == 2) {
+    if (shape.touch_y > 0) {   // the touch-block form
+      const dim3 gc = qb == 1 ? g1 : g2;
+      const dim3 gt(gc.x, gc.y + shape.touch_y, gc.z);
+      const unsigned wave = shape.pf_wave ? 64 : 0;
+      p.grid_y = (int)gc.y;
+      if (qb == 1) {
+        if (wave) hipLaunchKernelGGL((attention_kernel<NP, NS, 1, 1, QP, true>), gt, dim3(kAttKG * 64 + wave), smem1, stream, p);
+        else hipLaunchKernelGGL((attention_kernel<NP, NS, 1, kPfNone, QP, true>), gt, dim3(kAttKG * 64), smem1, stream, p);
+      } else {
+        if (wave) hipLaunchKernelGGL((attention_kernel<NP, NS, 2, 1, QP, true>), gt, dim3(2 * kAttKG * 64 + wave), smem2, stream, p);
+        else hipLaunchKernelGGL((attention_kernel<NP, NS, 2, kPfNone, QP, true>), gt, dim3(2 * kAttKG * 64), smem2, stream, p);
+      }
       return;
     }
   }

@@ -59,6 +59,10 @@ constexpr int kMaxPrefetchTargets = 1;   // a launch carries at most one target 
 struct WeightPrefetch {
   PrefetchTarget t[kMaxPrefetchTargets];
   int n = 0;   // used slots
+  // Carrier form (host side; "Touch blocks" below): 0 = one extra wave in every compute block; > 0 = that many touch
+  // blocks behind the compute grid (the launcher caps it at the CUs' free resident slots; no slot left = the wave form).
+  int touch_blocks = 0;
+  int touch_delay = 0;   // touch blocks: counted s_sleep rounds in front of the touches (<= kTouchDelayMax)
   void add(const PrefetchTarget& x) { if (x.rows > 0 && n < kMaxPrefetchTargets) t[n++] = x; }
 };
 
@@ -125,6 +129,18 @@ __device__ __forceinline__ void prefetch_done(const PrefetchRegsT<PF>& keep) {
 // time to arrive before their consumer starts.  An ended wave no longer counts at s_barrier, so the compute
 // waves' barriers are unaffected once it has gone.  One wave issues what the four compute waves issued together.
 // (-1.0 % step time same-box against the in-epilogue touches, profiles/r03f_env_ab.log)
+// How a target is DEALT over the waves that touch it, in ONE function for both device forms and for the host
+// (msd_op_touch_deal): a wave-wide touch covers rpt = 64 >> lg whole rows (planes back to back: row index rows + r is row
+// r of plane 1), and touch u of dealt wave w of nw starts at row (w + nw * u) * rpt -- whole touches, block-cyclic.
+constexpr int kTouchesPerWave = 4 * kPrefetchPerThread;
+__host__ __device__ inline int touch_first_row(int w, int nw, int u, int rpt) { return (w + nw * u) * rpt; }
+// Lane (row offset `sub`, line slot `line`) of the touch that starts at row index rp0: the plane and the first row of the
+// touch in it; returns whether the lane's line lies inside the target (a lane outside touches nothing of it).
+__host__ __device__ inline bool touch_lane_in(int rp0, int sub, int line, int rows, int planes, int lpr, int* pl, int* row0) {
+  *pl = (planes == 2 && rp0 >= rows) ? 1 : 0;
+  *row0 = rp0 - *pl * rows;
+  return rp0 < rows * planes && *row0 + sub < rows && line < lpr;
+}
 constexpr bool kPfWave = true;       // GEMM launches
 constexpr bool kPfWaveAttn = true;   // attention launches
 // LDS_SINK: the touches are LDS-DMA dwords into 256 bytes of LDS nobody reads instead of loads into a
@@ -134,7 +150,7 @@ template <int PF, bool LDS_SINK = false>
 __device__ __forceinline__ void prefetch_wave(const WeightPrefetch& pf, int blk, int nblk, const void* valid,
                                               char* sink_lds = nullptr) {
   if constexpr (PF != kPfNone) {
-    constexpr int TOUCHES = 4 * kPrefetchPerThread;
+    constexpr int TOUCHES = kTouchesPerWave;
     const int lane = (int)threadIdx.x & 63;
     // ONE destination register for every touch, read-write in each asm statement and kept live to the end of the
     // wave: the compiler believes an asm output is complete when the statement ends, so a register it were free to
@@ -152,10 +168,10 @@ __device__ __forceinline__ void prefetch_wave(const WeightPrefetch& pf, int blk,
       const uint32_t lane_off = (uint32_t)sub * (uint32_t)t.row_stride + (uint32_t)line * 128u;
 #pragma unroll
       for (int u = 0; u < TOUCHES; ++u) {
-        const int rp0 = (blk + nblk * u) * rpt;
-        const int pl = (planes == 2 && rp0 >= rows) ? 1 : 0, row0 = rp0 - pl * rows;
+        const int rp0 = touch_first_row(blk, nblk, u, rpt);
+        int pl, row0;
+        const bool in = touch_lane_in(rp0, sub, line, rows, planes, lpr, &pl, &row0);
         const char* row_ptr = t.base[pl] + (size_t)row0 * t.row_stride;
-        const bool in = rp0 < rows * planes && row0 + sub < rows && line < lpr;
         const char* src = in ? row_ptr + lane_off : reinterpret_cast<const char*>(valid);
         if constexpr (LDS_SINK) {
           typedef const __attribute__((address_space(1))) void* pf_gptr_t;
@@ -170,6 +186,35 @@ __device__ __forceinline__ void prefetch_wave(const WeightPrefetch& pf, int blk,
   }
 }
 
+// Touch blocks: the same touches from BLOCKS of their own.  A launch whose compute grid leaves CUs idle (192 blocks on
+// 256 CUs) is given n_touch extra blocks behind the compute blocks (block index >= the compute grid); they do no tile
+// work: each of their waves runs prefetch_wave on its share of the target -- dealt over n_touch x waves waves instead of
+// over the compute blocks -- and ends.  No LDS access, no barrier, nothing waited for in memory (no flag, no counter,
+// no poll): the optional delay in front of the touches is a counted s_sleep loop bounded at compile time, so a touch
+// block always terminates.  The compute blocks then carry no extra wave at all: nothing of theirs waits for a touch at
+// s_endpgm.  The dynamic LDS size is launch-wide, so a touch block needs a CU with that much LDS free: the launcher
+// keeps compute + touch blocks within the resident slots of the chip (touch_blocks_fit), one round.
+constexpr int kTouchDelayMax = 64;      // rounds of s_sleep 8 (512 clocks, ~0.2 us each)
+constexpr int kLdsPerCu = 160 * 1024;   // CDNA4
+constexpr int kChipCus = 256;
+// touch blocks a launch of `grid` compute blocks with `smem` bytes of dynamic LDS may add (host)
+inline int touch_blocks_fit(int requested, int grid, int smem) {
+  const int per_cu = smem > 0 ? kLdsPerCu / smem : 8, slots = kChipCus * (per_cu < 1 ? 1 : (per_cu > 8 ? 8 : per_cu));
+  const int room = slots - grid;
+  return requested < room ? (requested > 0 ? requested : 0) : (room > 0 ? room : 0);
+}
+template <int PF>
+__device__ __forceinline__ void touch_block(const WeightPrefetch& pf, int tb, int n_touch, const void* valid) {
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), nwave = (int)blockDim.x >> 6;
+  const int rounds = pf.touch_delay < kTouchDelayMax ? pf.touch_delay : kTouchDelayMax;
+  for (int i = 0; i < rounds; ++i) __builtin_amdgcn_s_sleep(8);
+  prefetch_wave<PF>(pf, tb * nwave + wave, n_touch * nwave, valid);
+  // The wave ends HERE, with an s_endpgm of its own: left to the compiler, the touch path rejoins the compute path's exit
+  // through a flag and a conditional branch, and the listing no longer shows that nothing runs behind the touches
+  // (check_prefetch_regs.py follows both sides of every branch).
+  __builtin_amdgcn_endpgm();
+}
+
 struct GemmParams {
   const h16_t* A[2];
   const h16_t* B[2];
@@ -177,6 +222,7 @@ struct GemmParams {
   int M, N, K;
   WeightPrefetch pf;  // optional: warm a later launch's weights (see WeightPrefetch)
   int pf_nblk = 0;    // blocks that take part in the prefetch (0 = the whole grid); they are blockIdx.x < pf_nblk
+  int grid_compute = 0;   // touch-block form (launcher): the compute grid; blocks from here on are touch blocks
   int xcd_rows = 1;   // LDS-DMA kernel: the 8 XCDs form an xcd_rows x (8 / xcd_rows) grid over (M, N) tiles
   int xcd_walk_n = 0; // order in which an XCD's blocks walk its tiles
   // block -> tile map, precomputed by the launcher (TileMap::fill): the kernel used to derive it with FIVE software
@@ -543,11 +589,19 @@ __device__ __forceinline__ bool gemm_block_tile(const GemmParams& p, int b, int&
 
 constexpr int pf_threads(int pf) { return kPfWave && pf != kPfNone ? 64 : 0; }   // the prefetch wave of a launch, if any
 
-template <int NP, int BM, int BN, int NS, class Epi, int PF = kPfNone>
-__global__ void __launch_bounds__(256 + pf_threads(PF)) gemm_h16_dma_kernel(GemmParams p, Epi epi) {
+// TB: the touch-block carrier form (above): blocks of 256 threads, the compute blocks run the code of a launch without a
+// target, blocks >= p.grid_compute touch.
+template <int NP, int BM, int BN, int NS, class Epi, int PF = kPfNone, bool TB = false>
+__global__ void __launch_bounds__(256 + (TB ? 0 : pf_threads(PF))) gemm_h16_dma_kernel(GemmParams p, Epi epi) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   warm_kernargs<kernarg_lines<GemmParams, Epi>()>();
-  if constexpr (kPfWave && PF != kPfNone) {
+  if constexpr (TB) {
+    static_assert(PF != kPfNone, "touch blocks carry a target");
+    if ((int)blockIdx.x >= p.grid_compute) {
+      touch_block<PF>(p.pf, (int)blockIdx.x - p.grid_compute, (int)gridDim.x - p.grid_compute, p.B[0]);
+      return;
+    }
+  } else if constexpr (kPfWave && PF != kPfNone) {
     if (threadIdx.x >= 256) {   // the prefetch wave (only launched with pf_wave)
       prefetch_wave<PF>(p.pf, blockIdx.x, gridDim.x, p.B[0]);
       return;
@@ -555,7 +609,7 @@ __global__ void __launch_bounds__(256 + pf_threads(PF)) gemm_h16_dma_kernel(Gemm
   }
   int bm, bn;
   if (!gemm_block_tile(p, (int)blockIdx.x, bm, bn)) return;
-  gemm_tile<NP, BM, BN, NS, Epi, PF>(p, epi, bm, bn, smem);
+  gemm_tile<NP, BM, BN, NS, Epi, TB ? kPfNone : PF>(p, epi, bm, bn, smem);
 }
 
 // ----------------------------------------------------------------------------
@@ -1312,13 +1366,20 @@ template <> struct epi_may_prefetch<EpiStoreF32> : std::false_type {};
 template <int NP, int BM, int BN, int NS, class Epi>
 constexpr int gemm_h16_dma_smem() { return NS * NP * (BM + BN) * 128 + Epi::template aux_bytes<BM, BN>(); }
 
-template <int NP, int BM, int BN, int NS, class Epi, int PF>
+template <int NP, int BM, int BN, int NS, class Epi, int PF, bool TB = false>
 inline hipError_t gemm_h16_dma_prepare_one() {
   constexpr int smem = gemm_h16_dma_smem<NP, BM, BN, NS, Epi>();
   if (smem < 64 * 1024) return hipSuccess;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h16_dma_kernel<NP, BM, BN, NS, Epi, PF>),
+  return hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h16_dma_kernel<NP, BM, BN, NS, Epi, PF, TB>),
                              hipFuncAttributeMaxDynamicSharedMemorySize, smem);
 }
+
+// Which kernels have a touch-block form: the two-plane narrow tiles (32 rows) of the residual + folded-norm epilogue --
+// the cross-attention output projection, whose 192 blocks of 32 x 32 leave CUs idle at one song (measured as a carrier
+// of MLP-in's weights and not adopted: DESIGN.md 6; the form stays for msd_op_gemm_site_carrier and the next
+// measurement).  The dual, persistent and 128-row kernels fill the chip and have none.
+template <int NP, int BM, class Epi> struct gemm_has_touch_blocks : std::false_type {};
+template <> struct gemm_has_touch_blocks<2, 32, EpiResidualNorm<2, false, false>> : std::true_type {};
 
 // one-time opt-in to > 64 KiB dynamic LDS; call for every instantiation OUTSIDE stream capture
 template <int NP, int BM, int BN, int NS, class Epi>
@@ -1326,6 +1387,9 @@ inline hipError_t gemm_h16_dma_prepare() {
   hipError_t e = gemm_h16_dma_prepare_one<NP, BM, BN, NS, Epi, 0>(), r;
   if constexpr (NP == 2 && epi_may_prefetch<Epi>::value) {   // the single-plane mode never prefetches
     if ((r = gemm_h16_dma_prepare_one<NP, BM, BN, NS, Epi, 1>()) != hipSuccess) e = r;
+  }
+  if constexpr (gemm_has_touch_blocks<NP, BM, Epi>::value) {
+    if ((r = gemm_h16_dma_prepare_one<NP, BM, BN, NS, Epi, 1, true>()) != hipSuccess) e = r;
   }
   return e;
 }
@@ -1336,6 +1400,24 @@ template <int NP, class Epi>
 inline bool gemm_carries_prefetch(const GemmParams& p) {
   if constexpr (NP == 2 && epi_may_prefetch<Epi>::value) return prefetch_kind(p.pf) >= 1;   // product: the first target only
   else return false;
+}
+
+// the compute grid of a launch of p on BM x BN tiles (p.xcd_rows set) ...
+template <int BM, int BN>
+inline int gemm_h16_dma_grid(const GemmParams& p) {
+  const int rx = p.xcd_rows, cx = 8 / rx;
+  return 8 * ((p.N / BN + cx - 1) / cx) * ((p.M / BM + rx - 1) / rx);
+}
+// ... and the touch blocks it runs behind it (0 = none: the wave form, or no target).  ONE rule for the launcher and for
+// the stand-alone op that reports it.  (host only)
+template <int NP, int BM, int BN, int NS, class Epi>
+inline int gemm_touch_blocks(const GemmParams& p) {
+  if constexpr (gemm_has_touch_blocks<NP, BM, Epi>::value) {
+    if (!gemm_carries_prefetch<NP, Epi>(p) || p.pf.touch_blocks <= 0) return 0;
+    return touch_blocks_fit(p.pf.touch_blocks, gemm_h16_dma_grid<BM, BN>(p), gemm_h16_dma_smem<NP, BM, BN, NS, Epi>());
+  } else {
+    return 0;
+  }
 }
 
 template <int NP, int BM, int BN, int NS, class Epi>
@@ -1351,6 +1433,14 @@ inline hipError_t launch_gemm_h16_dma(const GemmParams& p_in, const Epi& epi, hi
 #define MSD_LAUNCH_PF(PF_) \
   hipLaunchKernelGGL((gemm_h16_dma_kernel<NP, BM, BN, NS, Epi, PF_>), dim3(grid), dim3(256 + pf_threads(PF_)), smem, stream, p, epi)
   if constexpr (NP == 2 && epi_may_prefetch<Epi>::value) {
+    if constexpr (gemm_has_touch_blocks<NP, BM, Epi>::value) {
+      const int n_touch = gemm_touch_blocks<NP, BM, BN, NS, Epi>(p);
+      if (n_touch > 0) {
+        p.grid_compute = grid;
+        hipLaunchKernelGGL((gemm_h16_dma_kernel<NP, BM, BN, NS, Epi, 1, true>), dim3(grid + n_touch), dim3(256), smem, stream, p, epi);
+        return hipGetLastError();
+      }
+    }
     if (gemm_carries_prefetch<NP, Epi>(p)) MSD_LAUNCH_PF(1);
     else MSD_LAUNCH_PF(0);
   } else {

@@ -88,6 +88,12 @@ struct EncoderW {
 
 struct TileShape { int bm, bn; };   // a GEMM tile, BM x BN (pick_tile)
 
+// msd_config.touch_carrier = 0: the library's choice (DESIGN.md 6 "Weight prefetch": the measurement that decides it)
+constexpr int kTouchCarrierDefault = 2;
+constexpr int kTouchBlocksAsk = 64;   // touch blocks a carrier launch asks for: the CUs 192 compute blocks leave idle
+constexpr int kTouchDelayCrossAttn = 16;   // sleep rounds (~0.2 us each) in front of the cross-attention's touch blocks: its
+                                           // compute blocks' first two K / V^T stages leave first (tools/ubench/attn_cold.hip)
+
 // ---- the step plan -------------------------------------------------------------------------------------------------
 // Everything one decoder evaluation decides about its launches, computed ONCE by plan_step and handed to in_proj and the
 // blocks of decoder_layers: a launch and whoever produces its operands or warms its weights read the same value.
@@ -104,6 +110,9 @@ struct StepPlan {
     int Ms, Ps;                 // rows and passes the block runs on (dup: BT, 1)
     TileShape qkv, out, out2;   // fold only: the tile of the QKV launch (both problems), of attention-out's two problems
     int warms;                  // WarmTarget: the first projection behind the block; the block warms its weights ...
+    int touch_blocks;           // ... from this many touch blocks behind the self-attention's compute grid (gemm_h16.h
+                                // "Touch blocks"; the launcher keeps the launch within one round of the chip); 0 = from
+                                // the in-block prefetch wave
     bool warm_on_out;           // ... from the attention-out launch -- the self-attention runs 128-row blocks, which
                                 // have no prefetch wave -- and not from the self-attention
     bool qb4;                   // the self-attention runs 128-row blocks (more than one round of 64-row blocks: from 3
@@ -118,6 +127,10 @@ struct StepPlan {
   // (A folded layer's launch stays on 64-row blocks whatever `cross_qb4` says -- attention.h: no 128-row kernel for
   // un-normalised queries -- and its output projection still carries the target: a single pass of 4 songs.)
   int ks[2];
+  // Touch-block carriers (one song per call, msd_config.touch_carrier): MLP-in's weights ride on this many touch blocks
+  // of the last module's cross-attention launch, behind mlp_in_touch_delay sleep rounds, and that launch's in-block wave
+  // keeps only its own K / V^T touch-ahead; 0 = on the in-block wave.
+  int mlp_in_touch_blocks, mlp_in_touch_delay;
   bool cross_qb4[2];
   bool cond0, mlp_in_on_cross_out;
 };
@@ -223,6 +236,8 @@ struct msd_model {
   bool merge_in_launch = true; // attention.h attention_inlaunch_merge (msd_config.cross_merge_in_launch = 2 turns it off)
   bool fold_q = true;          // folded cross-attention query projection (msd_config.cross_q_fold = 2 turns it off)
   bool persist_mlp_in = true;  // batched songs: persistent gated-MLP-in tile loop (msd_config.mlp_in_persistent = 2 turns it off)
+  int ran_touch_blocks[2] = {0, 0};   // touch blocks of the last self- / cross-attention launch enqueued (msd_debug_read "touch_blocks")
+  bool touch_blocks = kTouchCarrierDefault == 2;   // one song per call: weight touches from touch blocks (msd_config.touch_carrier; plan_step)
   Planes xg;                   // [Bmax T, D] x (.) gamma_cross of the layer about to run, conditional rows (EpiResidualNorm Y2)
   float* qp = nullptr;         // [Bmax T, n_cross J] (x0 (.) gamma) . Wq, the half of the projection that rides on the QKV launch
   int* att_tickets = nullptr;  // its arrival counters: [Bmax][T / 32][H], zero between launches
@@ -706,6 +721,12 @@ WeightPrefetch prefetch_of(const msd_model* m, const Planes& w, int N, int K) {
   return pf;
 }
 
+// the same target on `n` touch blocks behind its carrier's compute grid (gemm_h16.h "Touch blocks"); n = 0: the in-block wave
+inline WeightPrefetch on_touch_blocks(WeightPrefetch pf, int n, int delay = 0) {
+  pf.touch_blocks = n; pf.touch_delay = delay;
+  return pf;
+}
+
 // ---- operands and epilogues: one builder each ---------------------------------------------------------------------
 // Two single-plane conventions, kept apart: OPERAND planes at an element offset keep p[1] == nullptr when NP == 1
 // (planes_at); the OUTPUT pair of an epilogue aliases plane 0 then (out_pair).
@@ -826,6 +847,11 @@ void attention(Ctx& c, int kc, const Planes& q, int ldq, const AttnKV& kv, const
   p.allow_qb4 = qb4;
   // a key-split cross-attention merges its partials inside the launch (attention.h attention_inlaunch_merge)
   p.tickets = (kc == KC_ATTN_CROSS && ksplit > 1 && c.m->merge_in_launch) ? c.m->att_tickets : nullptr;
+  if (kc == KC_ATTN_SELF || kc == KC_ATTN_CROSS) {   // what the launcher is about to run, from its own rule
+    AttnParams q = p;
+    q.ksplit = 1 << attention_ksplit_log2(p.ksplit);
+    c.m->ran_touch_blocks[kc == KC_ATTN_CROSS] = attention_launch_shape(q, heads, segs, NP, q_ssq != nullptr).touch_y * heads * segs;
+  }
   c.begin(kc);
   c.latch(launch_attention<NP>(p, heads, segs, c.s));
   c.end(kc);
@@ -1289,6 +1315,13 @@ StepPlan plan_step(const msd_model* m, int batch, int P, bool cond0, bool dedup0
     p.cross_qb4[e] = attention_query_blocks(m->H * (T / 64) * p.ks[e] * batch, T, NP) == 4;
     if (e + 1 == m->n_cross) p.mlp_in_on_cross_out = p.cross_qb4[e];
   }
+  // Touch-block carriers: ONE song per call of a CFG step, where the attentions and the cross-attention output projection
+  // run 192 blocks on 256 CUs.  The batched paths (128-row blocks, several rounds of blocks per launch) keep the plan above.
+  if (m->touch_blocks && m->prefetch && NP == 2 && cond0 && batch == 1 && !p.cross_qb4[m->n_cross - 1]) {
+    for (int i = 0; i < 2; ++i)
+      if (!p.self[i].warm_on_out) p.self[i].touch_blocks = kTouchBlocksAsk;
+    p.mlp_in_touch_blocks = kTouchBlocksAsk; p.mlp_in_touch_delay = kTouchDelayCrossAttn;
+  }
   return p;
 }
 // S5: a CFG step computes layer 0's self-attention block once for both passes
@@ -1315,10 +1348,17 @@ EpiResidualNorm<NP> dec_residual(const msd_model* m, Gain lo, Gain hi, int split
 template <int NP>
 WeightPrefetch mlp_in_weights(const msd_model* m, int l) { return prefetch_of<NP>(m, m->dec[l].mlp.wi, 2 * m->F, m->D); }
 
+
 // Weight prefetch plan of a layer (gemm_h16.h WeightPrefetch; every producer warms a LATER GEMM's weights from a
 // wave of its own): QKV -> attention-out . self-attention -> cross-q (or MLP-in on an unconditional pass) .
 // cross-q -> cross-out . cross-attention -> MLP-in . MLP-in -> MLP-out . MLP-out -> next layer's QKV; the exceptions are
 // StepPlan's warms / warm_on_out / mlp_in_on_cross_out.
+// One song per call (msd_config.touch_carrier = 2, the library's choice; StepPlan's touch_blocks / mlp_in_touch_blocks):
+// the two attention launches run 192 blocks on 256 CUs and carry their targets on TOUCH BLOCKS behind the compute grid --
+// self-attention -> cross-q / cross-out from 5 (layer 0) or 2 x 2 rows of 12 blocks . cross-attention -> MLP-in from 5 rows
+// of 12 blocks behind kTouchDelayCrossAttn sleep rounds, while its in-block wave keeps the K / V^T touch-ahead alone.  The
+// GEMM carriers keep their waves.  (Two more moves measured slower -- MLP-in on touch blocks of the cross-attention output
+// projection, layer 0's QKV on the last MLP-out -- and live in tools/ubench/exp/touch_moves.patch: DESIGN.md 12.)
 
 // (i) self-attention block (network.py:174-193).  Layer 0 is fed by the input projection; later layers consume
 // the folded-norm planes `y` written by the previous layer's MLP output projection.
@@ -1345,7 +1385,7 @@ void self_attention_block(Ctx& c, const StepPlan& p, int l) {
                                                             : prefetch_of<NP>(m, w.wq_cross[0], J, D);
   const AttnKV kv = {planes_at<NP>(m->qk, J), 2 * J, (size_t)T * 2 * J, T, m->vt, T, (size_t)J * T, 0, m->d_nkeys_self};
   attention<NP>(c, KC_ATTN_SELF, m->qk, 2 * J, kv, m->ao, J, T, m->H, sb.Ps * p.batch, 1,
-                sb.warm_on_out ? WeightPrefetch() : pf_next, sb.qb4);
+                sb.warm_on_out ? WeightPrefetch() : on_touch_blocks(pf_next, sb.touch_blocks), sb.qb4);
   const WeightPrefetch pf_out = sb.warm_on_out ? pf_next : WeightPrefetch();
   // out-projection + residual; produces y for the cross-attention norm (conditional rows: plain gamma) and for the
   // MLP norm (unconditional rows, which skip cross-attention: S4)
@@ -1398,7 +1438,9 @@ void cross_attention_block(Ctx& c, const StepPlan& p, int l) {
     const bool warm_mlp_in = e + 1 == m->n_cross && !p.mlp_in_on_cross_out;
     // folded: module e's columns of the stacked, un-normalised queries
     attention<NP>(c, KC_ATTN_CROSS, fold ? planes_at<NP>(m->cq, (size_t)e * J) : *cq[e], fold ? nq : J, kv, *ao[e], J, T, m->H,
-                  p.batch, p.ks[e], warm_mlp_in ? mlp_in_weights<NP>(m, l) : WeightPrefetch(), true, -1, fold ? m->ssq : nullptr);
+                  p.batch, p.ks[e],
+                  warm_mlp_in ? on_touch_blocks(mlp_in_weights<NP>(m, l), p.mlp_in_touch_blocks, p.mlp_in_touch_delay) : WeightPrefetch(),
+                  true, -1, fold ? m->ssq : nullptr);
   }
   // y = x + sum_e zero_if_masked(MHA_e(...)) (network.py:199-216 / 217-235): residual adds one after the
   // other; the last one also writes the folded-norm inputs of the MLP block
@@ -1552,9 +1594,14 @@ const char* msd_last_error(const msd_model* m) { return m ? m->err.c_str() : "nu
 int msd_create(const msd_config* cfg, msd_model** out) {
   if (!cfg || !out) return MSD_ERR_INVALID_ARGUMENT;
   *out = nullptr;
-  if (cfg->struct_size != (int32_t)sizeof(msd_config)) return MSD_ERR_INVALID_ARGUMENT;
+  // (the struct as ABI 6 / 7 first had it, without the field appended since, is taken too: the field reads as 0)
+  if (cfg->struct_size != (int32_t)sizeof(msd_config) && cfg->struct_size != (int32_t)offsetof(msd_config, touch_carrier))
+    return MSD_ERR_INVALID_ARGUMENT;
   msd_model* m = new msd_model();
-  m->cfg = *cfg;
+  memset(&m->cfg, 0, sizeof(m->cfg));
+  memcpy(&m->cfg, cfg, (size_t)cfg->struct_size);
+  m->cfg.struct_size = (int32_t)sizeof(msd_config);
+  cfg = &m->cfg;
   (void)hipStreamCreateWithFlags(&m->own_stream, hipStreamNonBlocking);   // first: every fill / copy below goes through it (copy_sync)
   auto bad = [&](const char* why) {
     // keep the handle alive so the caller can read the message
@@ -1594,6 +1641,7 @@ int msd_create(const msd_config* cfg, msd_model** out) {
   if (cfg->cross_merge_in_launch < 0 || cfg->cross_merge_in_launch > 2) return bad("cross_merge_in_launch must be 0 (library default), 1 (on) or 2 (off)");
   if (cfg->cross_q_fold < 0 || cfg->cross_q_fold > 2) return bad("cross_q_fold must be 0 (library default), 1 (on) or 2 (off)");
   if (cfg->mlp_in_persistent < 0 || cfg->mlp_in_persistent > 2) return bad("mlp_in_persistent must be 0 (library default), 1 (on) or 2 (off)");
+  if (cfg->touch_carrier < 0 || cfg->touch_carrier > 2) return bad("touch_carrier must be 0 (library default), 1 (in-block waves) or 2 (touch blocks)");
   {  // schedule / model_output / logvar_type combinations are validated by building the table once
     std::vector<float> rows;
     std::string why;
@@ -1612,6 +1660,7 @@ int msd_create(const msd_config* cfg, msd_model** out) {
   m->merge_in_launch = cfg->cross_merge_in_launch != 2;
   m->fold_q = cfg->cross_q_fold != 2 && m->NP == 2;
   m->persist_mlp_in = cfg->mlp_in_persistent != 2;
+  if (cfg->touch_carrier) m->touch_blocks = cfg->touch_carrier == 2;
   {
     // Query-side planes of the decoder's attentions (attention.h QP bit 0: Q one plane, bit 1: P one plane).  Library
     // default with half planes in the two-plane mode: kDefaultQPlanes / kDefaultPPlanes (the sharp-
@@ -2288,6 +2337,13 @@ int msd_reset_graph(msd_model* m) {
   return MSD_OK;
 }
 
+int msd_set_touch_carrier(msd_model* m, int32_t touch_carrier) {
+  if (!m || touch_carrier < 0 || touch_carrier > 2) return MSD_ERR_INVALID_ARGUMENT;
+  m->cfg.touch_carrier = touch_carrier;
+  m->touch_blocks = (touch_carrier ? touch_carrier : kTouchCarrierDefault) == 2;
+  return MSD_OK;
+}
+
 int msd_decoder_pass(msd_model* m, int batch, int step_index, const float* z_dev,
                      int include_conditioning, float* eps_out_dev, void* stream) {
   if (!m) return MSD_ERR_INVALID_ARGUMENT;
@@ -2325,6 +2381,11 @@ int msd_get_schedule(const msd_model* m, float* host_out) {
 int msd_debug_read(msd_model* m, const char* buffer, float* host_out, int64_t max_elems, int64_t* n_out) {
   if (!m || !buffer || !host_out) return MSD_ERR_INVALID_ARGUMENT;
   const std::string b = buffer;
+  if (b == "touch_blocks") {   // host state, no device access: touch blocks of the last self- / cross-attention launch enqueued
+    if (n_out) *n_out = 2;
+    for (int64_t i = 0; i < 2 && i < max_elems; ++i) host_out[i] = (float)m->ran_touch_blocks[i];
+    return MSD_OK;
+  }
   const float* f32 = nullptr;
   const Planes* pl = nullptr;
   int64_t count = 0;

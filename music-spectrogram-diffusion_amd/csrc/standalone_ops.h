@@ -39,6 +39,7 @@ struct OpKit {
   msd_model ctx_model;
   Ctx c;
   unsigned* flags = nullptr;
+  unsigned range_flag = 0;   // the activation range flag as finish() read it
   std::vector<void*> owned;
 
   OpKit(hipStream_t s_, int planes_) : s(s_), np(planes_), c{&ctx_model, s_} { ctx_model.NP = planes_; }
@@ -90,6 +91,23 @@ struct OpKit {
     if (c.err == hipSuccess) gemm_on<2>(TileTable<2, TK, Epi>{}, shape_of<T>(), c, kc, p, epi);
   }
 
+  // The weight target of a carrier op (msd_op_*_carrier): two planes [rows][k] in ONE allocation of exactly their size --
+  // the last line a touch may read ends at the allocation's end -- in the form the caller asks for.  form 0: no target.
+  bool carrier_target(const msd_carrier_args* ca, WeightPrefetch* pf) {
+    *pf = WeightPrefetch();
+    if (ca->form == 0) return true;
+    void* q = nullptr;
+    const size_t plane = (size_t)ca->target_rows * ca->target_k * sizeof(h16_t);
+    if (!ok(hipMalloc(&q, 2 * plane))) return false;
+    owned.push_back(q);
+    if (!ok(hipMemsetAsync(q, 0, 2 * plane, s))) return false;
+    Planes w;
+    w.p[0] = static_cast<h16_t*>(q); w.p[1] = w.p[0] + (size_t)ca->target_rows * ca->target_k;
+    *pf = prefetch_of<2>(&ctx_model, w, ca->target_rows, ca->target_k);
+    if (ca->form == 2) { pf->touch_blocks = ca->n_touch; pf->touch_delay = ca->delay; }
+    return true;
+  }
+
   // the range flags: init_flags() before the first operand, arm() every launch that should report, finish() at the end
   bool init_flags() {
     flags = get<unsigned>(2);
@@ -103,6 +121,7 @@ struct OpKit {
     unsigned h[2] = {0, 0};
     if (hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
       return MSD_ERR_HIP;
+    range_flag = h[1];
     if (kPlaneSaturates) {
       float top;
       memcpy(&top, &h[0], sizeof(top));
@@ -134,6 +153,12 @@ const TileInfo* find_tile(const std::vector<TileInfo>& v, TileShape t) {
 template <int NP, class Epi, class... T>
 bool persistent_on(List<T...>, TileShape t, const msd_model* m, const GemmParams& p, const Epi& epi) {
   return ((T::is(t) && runs_persistent<NP, T, Epi>(m, p, epi)) || ...);
+}
+template <int NP, class Epi, class... T>
+int touch_blocks_on(List<T...>, TileShape t, const GemmParams& p) {
+  int n = 0;
+  ((T::is(t) ? (void)(n = gemm_touch_blocks<NP, T::BM, T::BN, T::NS, Epi>(p)) : (void)0), ...);
+  return n;
 }
 // the launch sites by name, from their types (msd_op_gemm_site_name)
 template <int TK, int NP> const char* site_name(Site<TK, EpiQKV<NP>>) { return "qkv"; }
@@ -178,9 +203,10 @@ template <int NP> struct SiteTiles {
 template <int NP>
 struct SiteRun : OpKit {
   msd_gemm_site_args* g;
+  msd_carrier_args* carrier;   // msd_op_gemm_site_carrier: the target and its form come from here, not from g->prefetch
   int* step = nullptr;
 
-  SiteRun(msd_gemm_site_args* g_, hipStream_t s_) : OpKit(s_, NP), g(g_) {}
+  SiteRun(msd_gemm_site_args* g_, hipStream_t s_, msd_carrier_args* ca = nullptr) : OpKit(s_, NP), g(g_), carrier(ca) {}
 
   bool bad() { rc = MSD_ERR_INVALID_ARGUMENT; return false; }
 
@@ -215,6 +241,10 @@ struct SiteRun : OpKit {
   }
   WeightPrefetch pf_target() {
     WeightPrefetch pf;
+    if (carrier) {
+      if constexpr (NP == 2) (void)carrier_target(carrier, &pf);
+      return pf;
+    }
     if (!g->prefetch) return pf;
     Planes w;
     w.p[0] = static_cast<h16_t*>(const_cast<void*>(g->prefetch));
@@ -252,6 +282,11 @@ struct SiteRun : OpKit {
     // both reports come from the predicates the launch itself uses (gemm_t, launch_gemm_h16_dma / _geglu_persist)
     g->ran_persistent = persistent_on<NP, Epi>(Tab{}, TileShape{ti->bm, ti->bn}, &ctx_model, lp, epi);
     g->ran_prefetch = g->ran_persistent ? prefetch_kind(lp.pf) >= 1 : gemm_carries_prefetch<NP, Epi>(lp);
+    if (carrier) {   // the launcher's own rule, on the tile that runs (gemm_h16.h gemm_touch_blocks)
+      const int n_touch = g->ran_persistent ? 0 : touch_blocks_on<NP, Epi>(Tab{}, TileShape{ti->bm, ti->bn}, lp);
+      carrier->ran_touch_blocks = n_touch;
+      carrier->ran_form = n_touch > 0 ? 2 : (g->ran_prefetch ? 1 : 0);
+    }
     if (forced) gemm_on<NP>(Tab{}, t, c, kc, lp, epi);
     else gemm<NP, TK>(c, kc, a, K, w, K, M, N, K, epi, align, pf);
     return ok(c.err);
@@ -456,18 +491,19 @@ struct SiteRun : OpKit {
 
 // the site of type S on the caller's arguments
 template <int NP, class S>
-int run_site(msd_gemm_site_args* g, hipStream_t s, S site) {
-  SiteRun<NP> r(g, s);
+int run_site(msd_gemm_site_args* g, hipStream_t s, S site, msd_carrier_args* ca = nullptr) {
+  SiteRun<NP> r(g, s, ca);
   if (!r.init()) return r.rc;
   r.run(site);
   const int frc = r.finish();
+  if (ca) ca->ran_range_flag = (int32_t)r.range_flag;
   return r.rc ? r.rc : frc;
 }
 // ... and the site at position g->site
 template <int NP>
-int run_gemm_site(msd_gemm_site_args* g, hipStream_t s) {
+int run_gemm_site(msd_gemm_site_args* g, hipStream_t s, msd_carrier_args* ca = nullptr) {
   int rc = MSD_ERR_INVALID_ARGUMENT;   // no such site
-  visit_site<NP>(g->site, [&](auto site) { rc = run_site<NP>(g, s, site); });
+  visit_site<NP>(g->site, [&](auto site) { rc = run_site<NP>(g, s, site, ca); });
   return rc;
 }
 // arguments of a site run that the library itself makes (msd_op_geglu, msd_op_qkv): two planes, one step, a forced tile
@@ -555,8 +591,9 @@ int op_sampler_step(const msd_config* cfg, int step_index, const float* z_dev, c
 template <int NP>
 struct AttnLaunchRun : OpKit {
   msd_attention_launch_args* g;
+  msd_carrier_args* carrier;   // msd_op_attention_launch_carrier
 
-  AttnLaunchRun(msd_attention_launch_args* g_, hipStream_t s_) : OpKit(s_, NP), g(g_) {}
+  AttnLaunchRun(msd_attention_launch_args* g_, hipStream_t s_, msd_carrier_args* ca = nullptr) : OpKit(s_, NP), g(g_), carrier(ca) {}
 
   // `blocks` blocks of `rows` rows of `width` floats, block b from src + b * block_stride, row pitch ld -> dense planes
   bool gather(const float* src, size_t block_stride, int ld, int blocks, int rows, int width, Planes* out) {
@@ -641,7 +678,9 @@ struct AttnLaunchRun : OpKit {
     p.vt_cols = (r0 == 0 && kr == ka) ? 0 : kr;
     p.ksplit = g->ksplit; p.part_o = nullptr; p.part_ml = nullptr; p.total_rows = (int)total_rows;
     p.touch_ahead = g->touch_ahead; p.pf_late = g->pf_late;
-    if (g->prefetch_rows) {
+    if (carrier) {
+      if constexpr (NP == 2) { if (!carrier_target(carrier, &p.pf)) return rc; }
+    } else if (g->prefetch_rows) {
       Planes w;
       if (!planes((size_t)g->prefetch_rows * g->prefetch_k, &w)) return rc;
       p.pf = prefetch_of<NP>(&ctx_model, w, g->prefetch_rows, g->prefetch_k);
@@ -659,15 +698,27 @@ struct AttnLaunchRun : OpKit {
     }
     const AttnLaunchShape shape = attention_launch_shape(ran, heads, segs, NP, g->q_ssq != nullptr);
     g->ran_qb = shape.qb; g->ran_prefetch_wave = shape.pf_wave; g->ran_touch_ahead = shape.touch_ahead; g->ran_ksplit = ran.ksplit;
+    if (carrier) {
+      carrier->ran_touch_blocks = shape.touch_y * heads * segs;
+      carrier->ran_form = shape.touch_y > 0 ? 2 : (shape.prefetch ? 1 : 0);
+    }
     hipError_t e = hipSuccess;
     for (int r = 0; r < g->repeats && e == hipSuccess; ++r)   // back to back: the counters must be zero again after every launch
       e = launch_attention<NP>(p, heads, segs, s);
     if (e != hipSuccess) return MSD_ERR_HIP;
     back(o, g->o, total_rows * J);
     const int frc = finish();
+    if (carrier) carrier->ran_range_flag = (int32_t)range_flag;
     return rc ? rc : frc;
   }
 };
+
+bool carrier_args_ok(const msd_carrier_args* ca) {
+  if (!ca || ca->struct_size != (int32_t)sizeof(msd_carrier_args) || ca->form < 0 || ca->form > 2) return false;
+  if (ca->form == 0) return true;
+  if (ca->target_rows <= 0 || ca->target_rows > (1 << 20) || ca->target_k <= 0 || ca->target_k % kGemmBK || ca->target_k > 4096) return false;
+  return ca->form == 1 || (ca->n_touch >= 1 && ca->n_touch <= 1024 && ca->delay >= 0 && ca->delay <= kTouchDelayMax);
+}
 }  // namespace
 
 extern "C" {
@@ -783,7 +834,7 @@ int msd_op_attention_ex(int precision, int qp, int ksplit, int merge_in_launch, 
   return kit.finish();
 }
 
-int msd_op_attention_launch(msd_attention_launch_args* g, void* stream) {
+static int attention_launch_op(msd_attention_launch_args* g, msd_carrier_args* ca, void* stream) {
   if (!g || g->struct_size != (int32_t)sizeof(msd_attention_launch_args)) return MSD_ERR_INVALID_ARGUMENT;
   g->ran_qb = g->ran_prefetch_wave = g->ran_touch_ahead = g->ran_ksplit = 0;
   if (g->qp < 0 || g->qp > 3 || g->ksplit < 1 || g->ksplit > 8 || g->repeats < 1 || g->repeats > 1000) return MSD_ERR_INVALID_ARGUMENT;
@@ -816,8 +867,50 @@ int msd_op_attention_launch(msd_attention_launch_args* g, void* stream) {
   if (NP < 0) return MSD_ERR_UNSUPPORTED;
   if (g->q_ssq != nullptr && NP != 2) return MSD_ERR_UNSUPPORTED;   // (un-normalised queries: two-plane kernels only)
   hipStream_t s = static_cast<hipStream_t>(stream);
-  if (NP == 2) return AttnLaunchRun<2>(g, s).run();
+  if (ca && NP != 2) return MSD_ERR_UNSUPPORTED;   // (the single-plane modes never carry a target)
+  if (NP == 2) return AttnLaunchRun<2>(g, s, ca).run();
   return AttnLaunchRun<1>(g, s).run();
+}
+int msd_op_attention_launch(msd_attention_launch_args* g, void* stream) { return attention_launch_op(g, nullptr, stream); }
+int msd_op_attention_launch_carrier(msd_attention_launch_args* g, msd_carrier_args* ca, void* stream) {
+  if (!carrier_args_ok(ca)) return MSD_ERR_INVALID_ARGUMENT;
+  ca->ran_form = ca->ran_touch_blocks = ca->ran_range_flag = 0;
+  return attention_launch_op(g, ca, stream);
+}
+
+// (ONE plane: a two-plane target is dealt as 2 x rows rows, plane 1 behind plane 0 -- the same predicate with planes = 2.)
+// Host only (no HIP call): how a target of `target_bytes` -- rows of `row_bytes` bytes, `row_pitch` bytes apart -- is dealt
+// over `waves` touching waves, by the function both device forms use (gemm_h16.h touch_first_row / prefetch_wave).
+// ranges[(w * kTouchesPerWave + u) * 3 + {0, 1, 2}] = first row, rows and 128-byte lines per row of touch u of wave w (rows
+// = 0: that touch covers nothing).  Returns the touches per wave (> 0), or a negative msd_status: bad arguments, a
+// `capacity` (in int32 words) too small, or a target the waves cannot cover in their kTouchesPerWave touches each.
+int msd_op_touch_deal(int64_t target_bytes, int32_t row_bytes, int32_t row_pitch, int32_t waves, int32_t* ranges, int32_t capacity) {
+  if (target_bytes <= 0 || row_bytes <= 0 || row_bytes > 64 * 128 || row_pitch < row_bytes || waves <= 0 || waves > (1 << 16) || !ranges)
+    return -MSD_ERR_INVALID_ARGUMENT;
+  if ((target_bytes - row_bytes) % row_pitch) return -MSD_ERR_INVALID_ARGUMENT;   // whole rows; the last one ends the target
+  const int64_t rows64 = (target_bytes - row_bytes) / row_pitch + 1;
+  if (rows64 > (1 << 24) || (int64_t)waves * kTouchesPerWave * 3 > capacity) return -MSD_ERR_INVALID_ARGUMENT;
+  PrefetchTarget t;
+  t.set(nullptr, nullptr, (int)rows64, row_pitch, row_bytes);
+  const int rpt = 64 >> t.lg;
+  if ((int64_t)waves * kTouchesPerWave * rpt < rows64) return -MSD_ERR_UNSUPPORTED;
+  for (int w = 0; w < waves; ++w)
+    for (int u = 0; u < kTouchesPerWave; ++u) {
+      // the 64 lanes of the touch, through the device's own predicate (gemm_h16.h touch_lane_in): lane = (sub, line)
+      const int r0 = touch_first_row(w, waves, u, rpt);
+      int first = -1, last = -1, lines = 0;
+      for (int lane = 0; lane < 64; ++lane) {
+        const int sub = lane >> t.lg, line = lane & ((1 << t.lg) - 1);
+        int pl, row0;
+        if (!touch_lane_in(r0, sub, line, t.rows, /*planes=*/1, t.lpr, &pl, &row0)) continue;
+        if (first < 0) first = row0 + sub;
+        last = row0 + sub;
+        if (row0 + sub == first) ++lines;
+      }
+      int32_t* o = ranges + ((size_t)w * kTouchesPerWave + u) * 3;
+      o[0] = first < 0 ? r0 : first; o[1] = first < 0 ? 0 : last - first + 1; o[2] = first < 0 ? t.lpr : lines;
+    }
+  return kTouchesPerWave;
 }
 
 int msd_op_threefry(int stage, uint64_t seed, int64_t fold, const uint32_t* bits_in_dev, float* out_dev, int64_t n,
@@ -1035,6 +1128,18 @@ int msd_op_gemm_site(msd_gemm_site_args* args, void* stream) {
   args->step_copy = -1;
   hipStream_t s = static_cast<hipStream_t>(stream);
   return NP == 2 ? run_gemm_site<2>(args, s) : run_gemm_site<1>(args, s);
+}
+
+int msd_op_gemm_site_carrier(msd_gemm_site_args* args, msd_carrier_args* ca, void* stream) {
+  if (!args || args->struct_size != (int32_t)sizeof(msd_gemm_site_args) || args->site < 0 || args->step < 0 ||
+      args->steps <= 0 || args->step >= args->steps || !carrier_args_ok(ca))
+    return MSD_ERR_INVALID_ARGUMENT;
+  if (op_planes(args->precision) != 2) return MSD_ERR_UNSUPPORTED;   // (the single-plane modes never carry a target)
+  args->ran_bm = args->ran_bn = args->ran_ns = args->ran_xcd_rows = args->ran_persistent = args->ran_dual = 0;
+  args->ran_prefetch = args->ran_bm2 = args->ran_bn2 = args->ran_ns2 = args->ran_xcd_rows2 = 0;
+  args->step_copy = -1;
+  ca->ran_form = ca->ran_touch_blocks = ca->ran_range_flag = 0;
+  return run_gemm_site<2>(args, static_cast<hipStream_t>(stream), ca);
 }
 
 const char* msd_op_gemm_site_name(int precision, int site) {

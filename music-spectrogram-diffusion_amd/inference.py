@@ -80,7 +80,8 @@ def _to_native_config(spec: config_lib.ModelSpec, codec: audio_codecs.AudioCodec
                       weight_prefetch: Optional[bool] = None, dedup_layer0: Optional[bool] = None,
                       cross_key_split: int = 0, keep_raw_weights: bool = False,
                       kv_touch_ahead: Optional[int] = None, cross_merge_in_launch: Optional[bool] = None,
-                      cross_q_fold: Optional[bool] = None, mlp_in_persistent: Optional[bool] = None) -> native.MsdConfig:
+                      cross_q_fold: Optional[bool] = None, mlp_in_persistent: Optional[bool] = None,
+                      touch_carrier: Optional[int] = None) -> native.MsdConfig:
   t5, d = spec.t5, spec.diffusion
   # Everything the kernels fix by construction is validated here with the
   # reference's own error type (ValueError; msd_amd.h msd_config comment).
@@ -176,6 +177,9 @@ def _to_native_config(spec: config_lib.ModelSpec, codec: audio_codecs.AudioCodec
   cfg.cross_merge_in_launch = 0 if cross_merge_in_launch is None else (1 if cross_merge_in_launch else 2)
   cfg.cross_q_fold = 0 if cross_q_fold is None else (1 if cross_q_fold else 2)
   cfg.mlp_in_persistent = 0 if mlp_in_persistent is None else (1 if mlp_in_persistent else 2)
+  if touch_carrier is not None and int(touch_carrier) < 1:   # (the library names the values it knows: msd_create)
+    raise ValueError('touch_carrier must be None (library default), 1 (in-block waves) or 2 (touch blocks)')
+  cfg.touch_carrier = 0 if touch_carrier is None else int(touch_carrier)
   return cfg
 
 
@@ -347,7 +351,7 @@ class InferenceModel(object):
                weight_prefetch: Optional[bool] = None, dedup_layer0: Optional[bool] = None,
                cross_key_split: int = 0, keep_raw_weights: bool = False, kv_touch_ahead: Optional[int] = None,
                cross_merge_in_launch: Optional[bool] = None, cross_q_fold: Optional[bool] = None,
-               mlp_in_persistent: Optional[bool] = None, rng: Optional[str] = None):
+               mlp_in_persistent: Optional[bool] = None, rng: Optional[str] = None, touch_carrier: Optional[int] = None):
     """Args mirror inference.py:71-88.
 
     gin_config: the parsed gin string (``parse_training_gin_file``) or a typed
@@ -375,6 +379,9 @@ class InferenceModel(object):
       self-attention output projection launches by exact algebra, msd_amd.h); None = the library's choice (on)
     mlp_in_persistent: batched songs (>= 4 per call): the decoder's gated-MLP input projection as one resident block per
       CU walking its tiles (register epilogue, the next tile's operands land under it); None = the library's choice (on)
+    touch_carrier: who carries the weight-prefetch touches of a one-song step: 1 = an extra wave in every compute block of
+      the carrier launch, 2 = touch blocks on the CUs the carrier leaves idle (msd_amd.h; bit-identical results); None =
+      the library's choice
     keep_raw_weights: keep the float32 staging copies of the packed matrices on the device (default: freed after
       packing -- 1.5 GB per handle at base_with_context).
     rng: the generator of a predict / predict_sequence call that does not name one: 'philox' (None: the library's own),
@@ -403,6 +410,7 @@ class InferenceModel(object):
     self.kv_touch_ahead = kv_touch_ahead
     self.cross_merge_in_launch, self.cross_q_fold = cross_merge_in_launch, cross_q_fold
     self.mlp_in_persistent = mlp_in_persistent
+    self.touch_carrier = touch_carrier
     if rng is not None and rng not in RNG_MODES:
       raise ValueError('rng must be one of %s: %r' % (RNG_MODES, rng))
     self.rng = rng or 'philox'
@@ -474,7 +482,8 @@ class InferenceModel(object):
         cfg = _to_native_config(self.spec, self.audio_codec, self.batch_size, self.precision,
                                 self.attention_query_planes, self.graph_steps, self.weight_prefetch,
                                 self.dedup_layer0, self.cross_key_split, self.keep_raw_weights, self.kv_touch_ahead,
-                                self.cross_merge_in_launch, self.cross_q_fold, self.mlp_in_persistent)
+                                self.cross_merge_in_launch, self.cross_q_fold, self.mlp_in_persistent,
+                                self.touch_carrier)
         nm = native.NativeModel(cfg)   # the library build (plane format) follows from cfg.precision
         self._stream = torch.cuda.Stream(device=self.device)
         nm.load_weights(params, stream=self._stream.cuda_stream)

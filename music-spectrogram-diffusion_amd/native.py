@@ -73,7 +73,9 @@ EXPORTED_SYMBOLS = (
     # (appended to ABI 7) a step count and a sampler per call; the second-order multistep sampler
     'msd_sample_steps', 'msd_op_sampler_step_multistep',
     # (appended to ABI 7) one attention launch the way the decoder fills it
-    'msd_op_attention_launch')
+    'msd_op_attention_launch',
+    # (appended to ABI 7) a launch with a weight target in either carrier form; how a target is dealt over the waves
+    'msd_op_gemm_site_carrier', 'msd_op_attention_launch_carrier', 'msd_op_touch_deal', 'msd_set_touch_carrier')
 
 
 def divisors(n: int):
@@ -129,7 +131,8 @@ class MsdConfig(ctypes.Structure):
       ('dedup_layer0', ctypes.c_int32), ('cross_key_split', ctypes.c_int32), ('keep_raw_weights', ctypes.c_int32),
       ('kv_touch_ahead', ctypes.c_int32),
       ('cross_merge_in_launch', ctypes.c_int32), ('cross_q_fold', ctypes.c_int32),
-      ('mlp_in_persistent', ctypes.c_int32)]
+      ('mlp_in_persistent', ctypes.c_int32),
+      ('touch_carrier', ctypes.c_int32)]   # (appended to ABI 7)
 
 
 class GemmSiteArgs(ctypes.Structure):
@@ -142,6 +145,16 @@ class GemmSiteArgs(ctypes.Structure):
   _PTRS = ('a', 'w', 'w_gate', 'ssq', 'bias', 'g_lo', 'g_hi', 'g2', 'pos', 'a2', 'w2', 'addend2', 'prefetch',
            'x', 'out', 'y', 'y2', 'ssq_out', 'out2')
   _fields_ = [(n, ctypes.c_int32) for n in _INTS] + [(n, ctypes.c_void_p) for n in _PTRS]
+
+
+class CarrierArgs(ctypes.Structure):
+  """msd_carrier_args of include/msd_amd.h, field for field."""
+  _INTS = ('struct_size', 'form', 'n_touch', 'delay', 'target_rows', 'target_k', 'ran_form', 'ran_touch_blocks',
+           'ran_range_flag')
+  _fields_ = [(n, ctypes.c_int32) for n in _INTS]
+
+
+CARRIER_FORMS = {'none': 0, 'wave': 1, 'blocks': 2}   # msd_carrier_args.form
 
 
 class AttentionLaunchArgs(ctypes.Structure):
@@ -162,8 +175,17 @@ GEMM_SITES = {'qkv': 0, 'mlp_in': 1, 'residual_square': 2, 'residual_tall': 3, '
 
 # msd_config only ever grows at its end, so an OLDER library can be driven by passing it the struct size it knows
 # (same-box A/B of a previous round's binary through MSD_AMD_LIB: tools/ab/); the newer fields are then simply not seen.
-ABI_STRUCT_SIZES = {4: MsdConfig.weight_prefetch.offset + 4, 5: MsdConfig.kv_touch_ahead.offset + 4, 6: ctypes.sizeof(MsdConfig),
-                    7: ctypes.sizeof(MsdConfig)}   # ABI 7 appends entry points only
+ABI_STRUCT_SIZES = {4: MsdConfig.weight_prefetch.offset + 4, 5: MsdConfig.kv_touch_ahead.offset + 4,
+                    6: MsdConfig.mlp_in_persistent.offset + 4,
+                    7: MsdConfig.mlp_in_persistent.offset + 4}   # ABI 7 appends entry points only ...
+
+
+def config_struct_size(lib) -> int:
+  """The msd_config size to hand to `lib`: this package's own library -- and any build that exports msd_op_touch_deal --
+  knows the field appended to ABI 7 since (touch_carrier); an older build under MSD_AMD_LIB gets the size of its ABI."""
+  if hasattr(lib, 'msd_op_touch_deal'):
+    return ctypes.sizeof(MsdConfig)
+  return ABI_STRUCT_SIZES[getattr(lib, '_msd_abi', None) or ABI_VERSION]
 
 _libs = {}
 
@@ -280,6 +302,11 @@ def load(planes: str = 'f16') -> ctypes.CDLL:
     lib.msd_op_gemm_site_name.restype = c.c_char_p
   if 'msd_op_attention_launch' in present:   # (appended to ABI 7)
     lib.msd_op_attention_launch.argtypes = [c.POINTER(AttentionLaunchArgs), vp]
+  if 'msd_op_touch_deal' in present:   # (appended to ABI 7)
+    lib.msd_op_gemm_site_carrier.argtypes = [c.POINTER(GemmSiteArgs), c.POINTER(CarrierArgs), vp]
+    lib.msd_op_attention_launch_carrier.argtypes = [c.POINTER(AttentionLaunchArgs), c.POINTER(CarrierArgs), vp]
+    lib.msd_op_touch_deal.argtypes = [i64, i32, i32, i32, c.POINTER(c.c_int32), i32]
+    lib.msd_set_touch_carrier.argtypes = [vp, i32]
   for name in present:
     fn = getattr(lib, name)
     if name not in ('msd_version', 'msd_last_error', 'msd_destroy', 'msd_vocoder_last_error', 'msd_vocoder_destroy',
@@ -324,7 +351,7 @@ class NativeModel:
     self.planes = planes
     self.cfg = cfg
     self.handle = ctypes.c_void_p()
-    cfg.struct_size = ABI_STRUCT_SIZES[getattr(self.lib, '_msd_abi', None) or ABI_VERSION]
+    cfg.struct_size = config_struct_size(self.lib)
     rc = self.lib.msd_create(ctypes.byref(cfg), ctypes.byref(self.handle))
     if rc != 0:
       msg = self.lib.msd_last_error(self.handle).decode() if self.handle else 'invalid config'
@@ -449,6 +476,10 @@ class NativeModel:
     else:
       name, rc = 'msd_sample', lib.msd_sample_rng(h, batch, kind, seed, stream_id, *draws, *tail)
     _check(lib, h, rc, name)
+
+  def set_touch_carrier(self, touch_carrier: Optional[int]):
+    """msd_config.touch_carrier of this handle from the next sampling call on (None = the library's choice, 1, 2)."""
+    _check(self.lib, self.handle, self.lib.msd_set_touch_carrier(self.handle, int(touch_carrier or 0)), 'msd_set_touch_carrier')
 
   def reset_graph(self):
     _check(self.lib, self.handle, self.lib.msd_reset_graph(self.handle), 'msd_reset_graph')
@@ -600,6 +631,14 @@ def op_attention_launch(precision: str, stream: int = 0, planes: Optional[str] =
   msd_attention_launch_args by name -- integers, and device tensors for the pointers (float32; n_keys int32), kept alive
   by the caller.  Defaults: one launch, no split, qp 0.  Returns the ran_* out-fields."""
   lib = load(planes or plane_format(precision))
+  args = _attention_launch_args(precision, fields)
+  rc = lib.msd_op_attention_launch(ctypes.byref(args), stream)
+  if rc:
+    raise _EXC.get(rc, RuntimeError)('msd_op_attention_launch failed (msd_status %d)' % rc)
+  return {n: getattr(args, n) for n in AttentionLaunchArgs._INTS if n.startswith('ran_')}
+
+
+def _attention_launch_args(precision, fields) -> AttentionLaunchArgs:
   args = AttentionLaunchArgs()
   args.struct_size = ctypes.sizeof(AttentionLaunchArgs)
   args.precision = PRECISIONS[precision]
@@ -611,10 +650,46 @@ def op_attention_launch(precision: str, stream: int = 0, planes: Optional[str] =
       setattr(args, name, int(value))
     else:
       raise TypeError('msd_attention_launch_args has no input field %r' % name)
-  rc = lib.msd_op_attention_launch(ctypes.byref(args), stream)
-  if rc:
-    raise _EXC.get(rc, RuntimeError)('msd_op_attention_launch failed (msd_status %d)' % rc)
-  return {n: getattr(args, n) for n in AttentionLaunchArgs._INTS if n.startswith('ran_')}
+  return args
+
+
+def _carrier_args(form, n_touch, delay, target_rows, target_k) -> CarrierArgs:
+  ca = CarrierArgs()
+  ca.struct_size = ctypes.sizeof(CarrierArgs)
+  ca.form = CARRIER_FORMS.get(form, form)
+  ca.n_touch, ca.delay, ca.target_rows, ca.target_k = int(n_touch), int(delay), int(target_rows), int(target_k)
+  return ca
+
+
+def op_attention_launch_carrier(precision: str, form, n_touch: int = 0, delay: int = 0, target_rows: int = 0,
+                                target_k: int = 0, stream: int = 0, **fields) -> Dict[str, int]:
+  """op_attention_launch with a weight target the op makes itself -- two planes [target_rows][target_k] in one allocation
+  of exactly their size -- carried in `form`: 'none' (no target), 'wave' (the in-block prefetch wave) or 'blocks'
+  (`n_touch` touch blocks behind the compute grid, `delay` sleep rounds in front of their touches).  The status is
+  RETURNED (key 'status', 0 = MSD_OK) next to the ran_* out-fields of both structs."""
+  lib = load(plane_format(precision))
+  args = _attention_launch_args(precision, fields)
+  ca = _carrier_args(form, n_touch, delay, target_rows, target_k)
+  rc = lib.msd_op_attention_launch_carrier(ctypes.byref(args), ctypes.byref(ca), stream)
+  out = {n: getattr(args, n) for n in AttentionLaunchArgs._INTS if n.startswith('ran_')}
+  out.update({n: getattr(ca, n) for n in CarrierArgs._INTS if n.startswith('ran_')}, status=rc)
+  return out
+
+
+def op_touch_deal(target_bytes: int, row_bytes: int, row_pitch: int, waves: int) -> np.ndarray:
+  """How a target is dealt over `waves` touching waves (msd_op_touch_deal; host only, no GPU): int32
+  [waves, touches per wave, 3] of (first row, rows, 128-byte lines per row); rows 0 = that touch covers nothing."""
+  lib = load()
+  per_wave = 12
+  while True:
+    buf = np.zeros(waves * per_wave * 3, np.int32)
+    rc = lib.msd_op_touch_deal(target_bytes, row_bytes, row_pitch, waves, buf.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), buf.size)
+    if rc == -MSD_ERR_INVALID_ARGUMENT and per_wave < 64:   # (a library that deals more touches per wave: a larger buffer)
+      per_wave *= 2
+      continue
+    if rc <= 0:
+      raise _EXC.get(-rc, RuntimeError)('msd_op_touch_deal failed (msd_status %d)' % -rc)
+    return buf[:waves * rc * 3].reshape(waves, rc, 3)
 
 
 def _op_check(rc, what):
@@ -625,7 +700,7 @@ def _op_check(rc, what):
 def op_sampler_step(cfg: MsdConfig, step_index: int, z, out_cond, out_uncond, noise, z_out, stream: int = 0):
   """One sampler update (msd_op_sampler_step).  Tensors: float32 device tensors of equal numel."""
   lib = load()
-  cfg.struct_size = ABI_STRUCT_SIZES[getattr(lib, '_msd_abi', None) or ABI_VERSION]
+  cfg.struct_size = config_struct_size(lib)
   _op_check(lib.msd_op_sampler_step(ctypes.byref(cfg), step_index, _ptr(z), _ptr(out_cond), _ptr(out_uncond),
                                     _ptr(noise), _ptr(z_out), z.numel(), stream), 'msd_op_sampler_step')
 
@@ -635,7 +710,7 @@ def op_sampler_step_keep(cfg: MsdConfig, step_index: int, z, out_cond, out_uncon
   """op_sampler_step with known frames (msd_op_sampler_step_keep): known_scaled float32 [..., frames, n_dims] in model
   units, keep_mask int32 device tensor with one flag per frame."""
   lib = load()
-  cfg.struct_size = ABI_STRUCT_SIZES[getattr(lib, '_msd_abi', None) or ABI_VERSION]
+  cfg.struct_size = config_struct_size(lib)
   n_dims = int(known_scaled.shape[-1])
   if known_scaled.numel() != z.numel() or keep_mask.numel() * n_dims != z.numel():
     raise ValueError('known_scaled must have z\'s element count and keep_mask one flag per frame of %d' % n_dims)
@@ -649,7 +724,7 @@ def op_sampler_step_release(cfg: MsdConfig, step_index: int, z, out_cond, out_un
   """op_sampler_step_keep with release words (msd_op_sampler_step_release): release int32 device tensor, one word per
   frame -- 0 = free, v >= 1 = known at scan indices >= v - 1."""
   lib = load()
-  cfg.struct_size = ABI_STRUCT_SIZES[getattr(lib, '_msd_abi', None) or ABI_VERSION]
+  cfg.struct_size = config_struct_size(lib)
   n_dims = int(known_scaled.shape[-1])
   if known_scaled.numel() != z.numel() or release.numel() * n_dims != z.numel():
     raise ValueError('known_scaled must have z\'s element count and release one word per frame of %d' % n_dims)
@@ -663,7 +738,7 @@ def op_sampler_step_multistep(cfg: MsdConfig, step_index: int, z, out_cond, out_
   """One update of the 'dpmpp_2m' sampler (msd_op_sampler_step_multistep): x0_prev float32 device tensor of z's element
   count, the previous step's pred_x0 on entry (not read when `first`) and this step's on return."""
   lib = load()
-  cfg.struct_size = ABI_STRUCT_SIZES[getattr(lib, '_msd_abi', None) or ABI_VERSION]
+  cfg.struct_size = config_struct_size(lib)
   if x0_prev.numel() != z.numel() or z_out.numel() != z.numel():
     raise ValueError('x0_prev and z_out must have z\'s element count')
   _op_check(lib.msd_op_sampler_step_multistep(ctypes.byref(cfg), step_index, _ptr(z), _ptr(out_cond), _ptr(out_uncond),
@@ -676,7 +751,7 @@ def op_diffuse_to_step(cfg: MsdConfig, step_index: int, mel, eps, z_out, z_plane
   sigma eps at step_index's noise level, z's operand planes of cfg.precision merged back to float32, and xk =
   scale_features(clip=True) of mel out.  float32 device tensors of equal numel (% 4 == 0)."""
   lib = load(_PLANES_OF[cfg.precision])
-  cfg.struct_size = ABI_STRUCT_SIZES[getattr(lib, '_msd_abi', None) or ABI_VERSION]
+  cfg.struct_size = config_struct_size(lib)
   if not (mel.numel() == eps.numel() == z_out.numel() == z_planes_out.numel() == xk_out.numel()):
     raise ValueError('mel, eps and the three outputs must have the same element count')
   _op_check(lib.msd_op_diffuse_to_step(ctypes.byref(cfg), step_index, _ptr(mel), _ptr(eps), _ptr(z_out), _ptr(z_planes_out),
@@ -745,6 +820,12 @@ def op_gemm_site(precision: str, site, stream: int = 0, planes: Optional[str] = 
   Returns the ran_* out-fields and step_copy.  `planes` names the library build to call when it is not the one
   `precision` belongs to (which that build answers with MSD_ERR_UNSUPPORTED)."""
   lib = load(planes or plane_format(precision))
+  args = _gemm_site_args(precision, site, fields)
+  _op_check(lib.msd_op_gemm_site(ctypes.byref(args), stream), 'msd_op_gemm_site')
+  return {n: getattr(args, n) for n in GemmSiteArgs._INTS if n.startswith('ran_') or n == 'step_copy'}
+
+
+def _gemm_site_args(precision, site, fields) -> GemmSiteArgs:
   args = GemmSiteArgs()
   args.struct_size = ctypes.sizeof(GemmSiteArgs)
   args.precision = PRECISIONS[precision]
@@ -757,5 +838,17 @@ def op_gemm_site(precision: str, site, stream: int = 0, planes: Optional[str] = 
       setattr(args, name, int(value))
     else:
       raise TypeError('msd_gemm_site_args has no input field %r' % name)
-  _op_check(lib.msd_op_gemm_site(ctypes.byref(args), stream), 'msd_op_gemm_site')
-  return {n: getattr(args, n) for n in GemmSiteArgs._INTS if n.startswith('ran_') or n == 'step_copy'}
+  return args
+
+
+def op_gemm_site_carrier(precision: str, site, form, n_touch: int = 0, delay: int = 0, target_rows: int = 0,
+                         target_k: int = 0, stream: int = 0, **fields) -> Dict[str, int]:
+  """op_gemm_site with a weight target the op makes itself, carried in `form` (op_attention_launch_carrier).  The status
+  is RETURNED (key 'status') next to the ran_* out-fields of both structs."""
+  lib = load(plane_format(precision))
+  args = _gemm_site_args(precision, site, fields)
+  ca = _carrier_args(form, n_touch, delay, target_rows, target_k)
+  rc = lib.msd_op_gemm_site_carrier(ctypes.byref(args), ctypes.byref(ca), stream)
+  out = {n: getattr(args, n) for n in GemmSiteArgs._INTS if n.startswith('ran_') or n == 'step_copy'}
+  out.update({n: getattr(ca, n) for n in CarrierArgs._INTS if n.startswith('ran_')}, status=rc)
+  return out

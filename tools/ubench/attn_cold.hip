@@ -32,7 +32,14 @@ int main() {
   for (int i = 0; i < 8; ++i) { hipMalloc(&wbuf[i], (size_t)2 * 4096 * 768 * 2 * 4); hipMemset(wbuf[i], 0x11, (size_t)2 * 4096 * 768 * 2 * 4); }   // (8 x 50 MB: never cache-resident)
   for (int nkeys : {557, 1136, 1701}) {
     int* nk; hipMalloc(&nk, 4); hipMemcpy(nk, &nkeys, 4, hipMemcpyHostToDevice);
-    for (int touch = -1; touch < 3; ++touch) {   // -1: no prefetch wave at all; 0: prefetch wave with a 6.3 MB weight target (what the product's launch carries: MLP-in's planes), no K / V touches; 1: + touch-ahead 2
+    // -1: no prefetch wave at all; 0: prefetch wave with a 12.6 MB weight target (MLP-in's planes), no K / V touches; 1: + touch-ahead 2;
+    // 2: ... its touches behind barrier 0 (the in-block wave form);
+    // 4 .. 7: the target on touch blocks behind the compute grid (5 rows of 12 on the 64 idle CUs), the wave keeps the K / V
+    // touch-ahead alone, 0 / 8 / 16 / 32 sleep rounds (~0.2 us each) in front of the touches
+    // (row 3 -- the K / V wave WITHOUT any weight target -- needs tools/ubench/exp/touch_moves.patch)
+    const int delays[4] = {0, 8, 16, 32};
+    for (int touch = -1; touch < 8; ++touch) {
+      if (touch == 3) continue;
       double us[2];
       for (int cold = 0; cold < 2; ++cold) {
         auto launch = [&](int it) {
@@ -42,8 +49,9 @@ int main() {
           p.n_keys = nk; p.ldq = J; p.ldk = J; p.ldo = J; p.vt_ld = kpad; p.q_rows_per_seg = nq;
           p.k_seg_stride = (size_t)kpad * J; p.vt_seg_stride = (size_t)J * kpad; p.k_rows = kpad; p.vt_cols = kpad;
           p.ksplit = nkeys > 768 ? KS : 2; p.total_rows = nq; p.part_o = part_o; p.part_ml = part_ml; p.tickets = tickets;
-          p.touch_ahead = touch > 0 ? 2 : 0; p.pf_late = touch == 2 ? 1 : 0;
-          if (touch >= 0) { PrefetchTarget t; t.set(wbuf[it % 8], wbuf[it % 8] + (size_t)4096 * 768, 4096, 768 * 2, 768 * 2); p.pf.add(t); }   // (rotating: cold like a step's weights)
+          p.touch_ahead = touch > 0 ? 2 : 0; p.pf_late = touch >= 2 ? 1 : 0;
+          if (touch >= 4) { p.pf.touch_blocks = 64; p.pf.touch_delay = delays[touch - 4]; }
+          if (touch >= 0 && touch != 3) { PrefetchTarget t; t.set(wbuf[it % 8], wbuf[it % 8] + (size_t)4096 * 768, 4096, 768 * 2, 768 * 2); p.pf.add(t); }   // (rotating: cold like a step's weights)
           launch_attention<2>(p, heads, 1, 0);
         };
         for (int i = 0; i < 50; ++i) launch(i);
@@ -53,8 +61,11 @@ int main() {
         hipEventSynchronize(e1); float ms; hipEventElapsedTime(&ms, e0, e1);
         us[cold] = ms * 1e3 / iters;
       }
+      char name[64];
+      if (touch >= 4) snprintf(name, sizeof(name), "touch blocks, delay %2d + K/V wave", delays[touch - 4]);
+      else snprintf(name, sizeof(name), "%s", touch < 0 ? "no prefetch wave" : (touch == 0 ? "prefetch wave (12.6 MB target)" : (touch == 1 ? "prefetch wave + K/V touch-ahead 2" : (touch == 2 ? "... weights behind barrier 0" : "K/V wave only, no weight target"))));
       printf("cross-attention 12 x 256 x %4d keys, %-34s: warm K/V %6.2f us   cold K/V %6.2f us   (cold - warm %5.2f)\n", nkeys,
-             touch < 0 ? "no prefetch wave" : (touch == 0 ? "prefetch wave (12.6 MB target)" : (touch == 1 ? "prefetch wave + K/V touch-ahead 2" : "... weights behind barrier 0")), us[0], us[1], us[1] - us[0]);
+             name, us[0], us[1], us[1] - us[0]);
     }
   }
   return 0;
