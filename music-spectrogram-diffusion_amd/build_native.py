@@ -51,9 +51,9 @@ def needs_build(lib: str = LIB) -> bool:
 
 
 def check_prefetch_registers(listing: str) -> str:
-  """The weight prefetch (csrc/gemm_h16.h prefetch_weights) loads from inline asm into registers the compiler does
-  not know are written late; a compiler that copied or reused one of them would produce a library that corrupts
-  its own epilogue.  check_prefetch_regs.py (next to this file) verifies the DEVICE LISTING OF THE BINARY BEING BUILT (whatever
+  """The weight prefetch (csrc/gemm_h16.h prefetch_wave / touch_block) loads from inline asm into a register the compiler
+  does not know is written late; a compiler that reused it (for the next touch's address: it did once) would produce a
+  library that faults on the GPU.  check_prefetch_regs.py (next to this file) verifies the DEVICE LISTING OF THE BINARY BEING BUILT (whatever
   ROCm version builds it); an unsafe listing fails the build."""
   tool = os.path.join(HERE, 'check_prefetch_regs.py')   # ships inside the package (ADVICE r03)
   if not os.path.exists(tool):

@@ -1,6 +1,6 @@
-"""Static check of the weight-prefetch trick (csrc/gemm_h16.h prefetch_weights): the inline-asm loads target
-registers the compiler must neither copy nor reuse before the kernel ends -- it does not know they are written
-late.  Scans a device assembly listing (hipcc -save-temps / --cuda-device-only -S) and fails if a destination
+"""Static check of the weight-prefetch trick (csrc/gemm_h16.h prefetch_wave, which the prefetch wave of a launch and
+every wave of a touch_block run): the inline-asm loads target a register the compiler must neither copy nor reuse
+before the wave ends -- it does not know it is written late.  Scans a device assembly listing (hipcc -save-temps / --cuda-device-only -S) and fails if a destination
 register of such a load can be WRITTEN again on any path from the load to the end of the kernel (a read of a
 register pair that merely contains it, e.g. a packed-math broadcast operand, is harmless: only a write could be
 overwritten by the late load).

@@ -293,7 +293,7 @@ __device__ __forceinline__ void attention_inlaunch_merge(const AttnParams& p, in
 // blocks have a prefetch wave at all -- for their own K / V^T touch-ahead (cross-attention) -- and that wave touches no
 // weights.  Every wave of a touch block touches (its extra wave included).
 template <int NP, int NS, int QB, int PF = kPfNone, int QP = 0, bool TB = false>
-__global__ void __launch_bounds__(QB * kAttKG * 64 + (kPfWaveAttn && PF != kPfNone ? 64 : 0)) attention_kernel(AttnParams p) {
+__global__ void __launch_bounds__(QB * kAttKG * 64 + (PF != kPfNone ? 64 : 0)) attention_kernel(AttnParams p) {
   // Every multiply-add of this kernel that is MEANT to be fused is an explicit fma, and nothing else may be: left to
   // -ffp-contract=fast the instantiations contracted differently (round 6: <QB = 2, PF = 1> fused four packed
   // multiply-adds fewer than <QB = 1, PF = 1> and the PF = 0 pair -- the last bit of a segment then depended on which
@@ -311,7 +311,7 @@ __global__ void __launch_bounds__(QB * kAttKG * 64 + (kPfWaveAttn && PF != kPfNo
       return;
     }
   }
-  if constexpr (kPfWaveAttn && PF != kPfNone) {
+  if constexpr (PF != kPfNone) {
     if (threadIdx.x >= QB * kAttKG * 64) {   // the prefetch wave: a later GEMM's weights (+ this block's later K / V^T stages)
       if (p.touch_ahead <= 0) {   // weights only, and the wave ends (an ended wave does not count at s_barrier)
         const int lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
@@ -600,11 +600,6 @@ __global__ void __launch_bounds__(QB * kAttKG * 64 + (kPfWaveAttn && PF != kPfNo
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // (a prologue stage beyond this block's key range may still be landing)
   __syncthreads();  // every wave is done with the K/V ring before it becomes the merge slab
   MSD_TS_AT(ts_cls, ts_blk, 3)
-  PrefetchRegsT<PF> pf_keep;   // warm a later GEMM's weights behind the merge below (gemm_h16.h WeightPrefetch)
-  {
-    const int lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-    if constexpr (!kPfWaveAttn) prefetch_weights<PF>(p.pf, lin, gridDim.x * gridDim.y * gridDim.z, p.q[0], pf_keep);
-  }
 
   // ---- merge the 4 key-group partials of each query block through LDS --------------
   // per wave: O [32 q][64 d + 4 pad] fp32, then m[32], l[32]
@@ -678,7 +673,6 @@ __global__ void __launch_bounds__(QB * kAttKG * 64 + (kPfWaveAttn && PF != kPfNo
       }
     }
   }
-  prefetch_done(pf_keep);
   MSD_TS_AT(ts_cls, ts_blk, 5)
   MSD_TS_END(ts_cls, ts_blk, gridDim.x * ts_gy * gridDim.z)
 }
@@ -792,7 +786,7 @@ inline int attention_ksplit_log2(int ksplit) {
 //                caller allows them, and never with un-normalised queries (`qs`: their row sums fill the LDS)
 //   prefetch     the launch touches its weight target: a two-plane launch that has one, on 32- or 64-row blocks (the
 //                single-plane mode never prefetches, 16 compute waves leave no room for the wave)
-//   pf_wave      ... from a wave of its own (kPfWaveAttn)
+//   pf_wave      ... from a wave of its own
 //   touch_ahead  ... which also runs kv_touch_ahead
 //   touch_y      touch-block form: rows of `heads` touch blocks behind the compute grid's y extent (0 = the wave form).
 //                The target then rides on those blocks alone; the compute blocks keep a prefetch wave only for their own
@@ -802,7 +796,7 @@ inline AttnLaunchShape attention_launch_shape(const AttnParams& p, int heads, in
   const int blocks64 = heads * (p.q_rows_per_seg / 64) * p.ksplit * segs;
   AttnLaunchShape s;
   s.qb = attention_query_blocks((p.allow_qb4 && !qs) ? blocks64 : (blocks64 > 256 ? 256 : blocks64), p.q_rows_per_seg, np);
-  s.prefetch = np == 2 && prefetch_kind(p.pf) >= 1 && s.qb < 4;
+  s.prefetch = np == 2 && p.pf.active() && s.qb < 4;
   s.touch_y = 0;
   if (s.prefetch && p.pf.touch_blocks > 0) {   // whole rows of `heads` x `segs` blocks within one round of the chip
     const int grid = heads * (p.q_rows_per_seg / (32 * s.qb)) * p.ksplit * segs;
@@ -810,7 +804,7 @@ inline AttnLaunchShape attention_launch_shape(const AttnParams& p, int heads, in
                                : (qs ? attention_smem<2, 2, 2, true>() : attention_smem<2, 2, 2, false>());
     s.touch_y = touch_blocks_fit(p.pf.touch_blocks, grid, smem) / (heads * segs);
   }
-  s.pf_wave = kPfWaveAttn && s.prefetch && (s.touch_y == 0 || p.touch_ahead > 0);
+  s.pf_wave = s.prefetch && (s.touch_y == 0 || p.touch_ahead > 0);
   s.touch_ahead = s.pf_wave && p.touch_ahead > 0;
   return s;
 }
@@ -851,10 +845,10 @@ inline void launch_attention_qp(const AttnParams& p_in, int heads, int segs, hip
     }
   }
   if (qb == 1) {
-    if (pfw) hipLaunchKernelGGL((attention_kernel<NP, NS, 1, PFW, QP>), g1, dim3(kAttKG * 64 + (kPfWaveAttn && PFW ? 64 : 0)), smem1, stream, p);
+    if (pfw) hipLaunchKernelGGL((attention_kernel<NP, NS, 1, PFW, QP>), g1, dim3(kAttKG * 64 + (PFW ? 64 : 0)), smem1, stream, p);
     else hipLaunchKernelGGL((attention_kernel<NP, NS, 1, kPfNone, QP>), g1, dim3(kAttKG * 64), smem1, stream, p);
   } else {
-    if (pfw) hipLaunchKernelGGL((attention_kernel<NP, NS, 2, PFW, QP>), g2, dim3(2 * kAttKG * 64 + (kPfWaveAttn && PFW ? 64 : 0)), smem2, stream, p);
+    if (pfw) hipLaunchKernelGGL((attention_kernel<NP, NS, 2, PFW, QP>), g2, dim3(2 * kAttKG * 64 + (PFW ? 64 : 0)), smem2, stream, p);
     else hipLaunchKernelGGL((attention_kernel<NP, NS, 2, kPfNone, QP>), g2, dim3(2 * kAttKG * 64), smem2, stream, p);
   }
 }

@@ -44,7 +44,7 @@ namespace msd {
 // cross-attention gains.)
 struct PrefetchTarget {
   const char* base[2] = {nullptr, nullptr};   // up to two planes with the same geometry
-  int rows = 0;            // rows per plane; 0 = unused slot
+  int rows = 0;            // rows per plane; 0 = no target
   int row_stride = 0;      // bytes between rows
   int lpr = 0;             // 128-byte lines to touch per row (<= 64)
   int lg = 0;              // log2 of the line slots per row (host: smallest power of two >= lpr)
@@ -55,84 +55,36 @@ struct PrefetchTarget {
     while ((1 << lg) < lpr) ++lg;
   }
 };
-constexpr int kMaxPrefetchTargets = 1;   // a launch carries at most one target (more were measured: docs/history.md)
+// A launch carries at most ONE target (more were measured: docs/history.md).
 struct WeightPrefetch {
-  PrefetchTarget t[kMaxPrefetchTargets];
-  int n = 0;   // used slots
+  PrefetchTarget t;
   // Carrier form (host side; "Touch blocks" below): 0 = one extra wave in every compute block; > 0 = that many touch
   // blocks behind the compute grid (the launcher caps it at the CUs' free resident slots; no slot left = the wave form).
   int touch_blocks = 0;
   int touch_delay = 0;   // touch blocks: counted s_sleep rounds in front of the touches (<= kTouchDelayMax)
-  void add(const PrefetchTarget& x) { if (x.rows > 0 && n < kMaxPrefetchTargets) t[n++] = x; }
+  __host__ __device__ bool active() const { return t.rows > 0; }   // does the launch carry a target?
 };
 
-// The touches are plain 4-byte loads issued from inline asm into registers nobody reads: the compiler does not
-// know they are loads, so it never waits for them (an LDS-DMA touch would be waited for in front of the
-// epilogue's first LDS read); `keep` pins the destination registers until prefetch_done() at the end of the
-// kernel, and s_endpgm waits for outstanding loads by itself.  kPrefetchPerThread touches per wave and target.
-// PF = number of targets, a template parameter: every kernel instantiation has ONE straight-line path through
-// here, so the destination registers reach prefetch_done() without a copy or a merge of values --
-// tools/check_prefetch_regs.py verifies that on the compiled listing (tests/test_prefetch_static.py).
-constexpr int kPrefetchPerThread = 3;
-template <int PF>
-struct PrefetchRegsT { uint32_t r[PF > 0 ? PF * kPrefetchPerThread : 1]; };
+// Who issues the touches.  A WAVE of its own (`prefetch_wave`): the block is launched with 64 extra threads, and that
+// wave does nothing but touch the later launch's operands and end.  Its loads are on ITS vmcnt counter, so the compute
+// waves never wait for them, and the touches leave at the start of the launch, which gives the lines the whole launch to
+// arrive before their consumer starts.  An ended wave no longer counts at s_barrier, so the compute waves' barriers are
+// unaffected once it has gone.  (Rounds 2 and 3 issued the touches from the compute waves, behind their main loop: every
+// producer then waited at s_endpgm for touches it had issued a microsecond earlier -- docs/history.md; that form lives on
+// in tools/ubench/gemm_h16_k32.h only.)  Or BLOCKS of their own on idle CUs (`touch_block`, below).
+// The touches are plain 4-byte loads issued from inline asm into a register nobody reads: the compiler does not know they
+// are loads, so it never waits for them, and s_endpgm waits for outstanding loads by itself.  check_prefetch_regs.py
+// verifies on the compiled listing that nothing else writes that register (tests/test_prefetch_static.py).
+// PF, a template parameter of every kernel that can carry a target: kPfNone, or 1 = the launch has the extra wave (or,
+// with TB, the touch blocks) -- one kernel instantiation per value, and no touch code at all in the kPfNone ones.
 enum { kPfNone = 0 };
-__host__ __device__ inline int prefetch_kind(const WeightPrefetch& pf) { return pf.n; }
 
-// blk / nblk: launch-wide index of this block and number of blocks; `valid`: any mapped device address (touched
-// by lanes that have nothing to do, so that there is no branch around a load).
-// One wave-wide touch covers 64 >> lg whole rows (lane = (row offset, line slot)): everything up to the first
-// row of a touch is wave-uniform SCALAR arithmetic and a lane adds its row offset and line.  The index math
-// sits between the main loop and the epilogue of every launch and must stay a few VALU instructions (a first
-// version with per-lane divisions cost +1 us per launch, more than the prefetch wins).  Waves are dealt
-// block-cyclically: touch u of wave w of block `blk` starts at row ((blk + nblk * u) * nwave + w) * rows-per-touch.
-template <int PF>
-__device__ __forceinline__ void prefetch_weights(const WeightPrefetch& pf, int blk, int nblk, const void* valid,
-                                                 PrefetchRegsT<PF>& keep) {
-  if constexpr (PF == kPfNone) {
-    keep.r[0] = 0;
-    return;
-  } else {
-    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), nwave = (int)blockDim.x >> 6;
-    const int lane = (int)threadIdx.x & 63;
-#pragma unroll
-    for (int k = 0; k < PF; ++k) {
-      const PrefetchTarget& t = pf.t[k];
-      const int rows = t.rows, lpr = t.lpr;
-      const int planes = t.base[1] && t.base[1] != t.base[0] ? 2 : 1;
-      const int rpt = 64 >> t.lg;                                      // rows per touch
-      const int sub = lane >> t.lg, line = lane & ((1 << t.lg) - 1);
-      const uint32_t lane_off = (uint32_t)sub * (uint32_t)t.row_stride + (uint32_t)line * 128u;
-#pragma unroll
-      for (int u = 0; u < kPrefetchPerThread; ++u) {
-        const int rp0 = ((blk + nblk * u) * nwave + wave) * rpt;       // scalar from here ...
-        const int pl = (planes == 2 && rp0 >= rows) ? 1 : 0, row0 = rp0 - pl * rows;
-        const char* row_ptr = t.base[pl] + (size_t)row0 * t.row_stride;   // ... to here
-        const bool in = rp0 < rows * planes && row0 + sub < rows && line < lpr;
-        const char* src = in ? row_ptr + lane_off : reinterpret_cast<const char*>(valid);
-        asm volatile("global_load_dword %0, %1, off ; msd_prefetch" : "=&v"(keep.r[k * kPrefetchPerThread + u]) : "v"(src) : "memory");
-      }
-    }
-  }
-}
-template <int PF>
-__device__ __forceinline__ void prefetch_done(const PrefetchRegsT<PF>& keep) {
-#pragma unroll
-  for (int u = 0; u < (PF > 0 ? PF * kPrefetchPerThread : 1); ++u) asm volatile("" ::"v"(keep.r[u]));
-}
-
-// The same touches from a wave of their own: the block is launched with 64 extra threads, and that wave does
-// nothing but touch the later launch's operands and end (`pf_wave` in the launch parameters).  Its loads are on
-// ITS vmcnt counter: the compute waves never wait for them -- the in-epilogue form above makes every producer wait
-// at s_endpgm for touches it issued a microsecond earlier (cross-attention 11.6 -> 13.3 us) -- and the
-// touches leave at the start of the launch instead of behind its main loop, which gives the lines that much more
-// time to arrive before their consumer starts.  An ended wave no longer counts at s_barrier, so the compute
-// waves' barriers are unaffected once it has gone.  One wave issues what the four compute waves issued together.
-// (-1.0 % step time same-box against the in-epilogue touches, profiles/r03f_env_ab.log)
 // How a target is DEALT over the waves that touch it, in ONE function for both device forms and for the host
-// (msd_op_touch_deal): a wave-wide touch covers rpt = 64 >> lg whole rows (planes back to back: row index rows + r is row
-// r of plane 1), and touch u of dealt wave w of nw starts at row (w + nw * u) * rpt -- whole touches, block-cyclic.
-constexpr int kTouchesPerWave = 4 * kPrefetchPerThread;
+// (msd_op_touch_deal): a wave-wide touch covers rpt = 64 >> lg whole rows (lane = (row offset, line slot); planes back to
+// back: row index rows + r is row r of plane 1), and touch u of dealt wave w of nw starts at row (w + nw * u) * rpt --
+// whole touches, block-cyclic.  Everything up to the first row of a touch is wave-uniform SCALAR arithmetic; a lane adds
+// its row offset and line (a first version with per-lane divisions cost +1 us per launch, more than the prefetch wins).
+constexpr int kTouchesPerWave = 12;   // what the four compute waves of a block issued together: 3 touches each
 __host__ __device__ inline int touch_first_row(int w, int nw, int u, int rpt) { return (w + nw * u) * rpt; }
 // Lane (row offset `sub`, line slot `line`) of the touch that starts at row index rp0: the plane and the first row of the
 // touch in it; returns whether the lane's line lies inside the target (a lane outside touches nothing of it).
@@ -141,16 +93,16 @@ __host__ __device__ inline bool touch_lane_in(int rp0, int sub, int line, int ro
   *row0 = rp0 - *pl * rows;
   return rp0 < rows * planes && *row0 + sub < rows && line < lpr;
 }
-constexpr bool kPfWave = true;       // GEMM launches
-constexpr bool kPfWaveAttn = true;   // attention launches
+// blk / nblk: index of this wave among the waves the target is dealt over, and their number; `valid`: any mapped device
+// address (touched by lanes that have nothing to do, so that there is no branch around a load).
 // LDS_SINK: the touches are LDS-DMA dwords into 256 bytes of LDS nobody reads instead of loads into a
 // register -- for a prefetch wave that goes on living behind them (attention.h kv_touch_ahead): there the register form's
 // hazard (the compiler reusing the destination once it believes the value dead) cannot be excluded by construction.
 template <int PF, bool LDS_SINK = false>
 __device__ __forceinline__ void prefetch_wave(const WeightPrefetch& pf, int blk, int nblk, const void* valid,
                                               char* sink_lds = nullptr) {
+  static_assert(PF == kPfNone || PF == 1, "a launch carries one target or none");
   if constexpr (PF != kPfNone) {
-    constexpr int TOUCHES = kTouchesPerWave;
     const int lane = (int)threadIdx.x & 63;
     // ONE destination register for every touch, read-write in each asm statement and kept live to the end of the
     // wave: the compiler believes an asm output is complete when the statement ends, so a register it were free to
@@ -158,28 +110,25 @@ __device__ __forceinline__ void prefetch_wave(const WeightPrefetch& pf, int blk,
     // v[2:3], overwritten by the returning load: a memory fault on the MI355X) must not exist.  Several loads
     // in flight to the same register are harmless: nobody reads it.
     uint32_t sink = 0;
+    const PrefetchTarget& t = pf.t;
+    const int rows = t.rows, lpr = t.lpr;
+    const int planes = t.base[1] && t.base[1] != t.base[0] ? 2 : 1;
+    const int rpt = 64 >> t.lg;
+    const int sub = lane >> t.lg, line = lane & ((1 << t.lg) - 1);
+    const uint32_t lane_off = (uint32_t)sub * (uint32_t)t.row_stride + (uint32_t)line * 128u;
 #pragma unroll
-    for (int k = 0; k < PF; ++k) {
-      const PrefetchTarget& t = pf.t[k];
-      const int rows = t.rows, lpr = t.lpr;
-      const int planes = t.base[1] && t.base[1] != t.base[0] ? 2 : 1;
-      const int rpt = 64 >> t.lg;
-      const int sub = lane >> t.lg, line = lane & ((1 << t.lg) - 1);
-      const uint32_t lane_off = (uint32_t)sub * (uint32_t)t.row_stride + (uint32_t)line * 128u;
-#pragma unroll
-      for (int u = 0; u < TOUCHES; ++u) {
-        const int rp0 = touch_first_row(blk, nblk, u, rpt);
-        int pl, row0;
-        const bool in = touch_lane_in(rp0, sub, line, rows, planes, lpr, &pl, &row0);
-        const char* row_ptr = t.base[pl] + (size_t)row0 * t.row_stride;
-        const char* src = in ? row_ptr + lane_off : reinterpret_cast<const char*>(valid);
-        if constexpr (LDS_SINK) {
-          typedef const __attribute__((address_space(1))) void* pf_gptr_t;
-          typedef __attribute__((address_space(3))) void* pf_lptr_t;
-          __builtin_amdgcn_global_load_lds((pf_gptr_t)src, (pf_lptr_t)(size_t)(unsigned)(size_t)sink_lds, 4, 0, 0);
-        } else {
-          asm volatile("global_load_dword %0, %1, off ; msd_prefetch" : "+v"(sink) : "v"(src) : "memory");
-        }
+    for (int u = 0; u < kTouchesPerWave; ++u) {
+      const int rp0 = touch_first_row(blk, nblk, u, rpt);
+      int pl, row0;
+      const bool in = touch_lane_in(rp0, sub, line, rows, planes, lpr, &pl, &row0);
+      const char* row_ptr = t.base[pl] + (size_t)row0 * t.row_stride;
+      const char* src = in ? row_ptr + lane_off : reinterpret_cast<const char*>(valid);
+      if constexpr (LDS_SINK) {
+        typedef const __attribute__((address_space(1))) void* pf_gptr_t;
+        typedef __attribute__((address_space(3))) void* pf_lptr_t;
+        __builtin_amdgcn_global_load_lds((pf_gptr_t)src, (pf_lptr_t)(size_t)(unsigned)(size_t)sink_lds, 4, 0, 0);
+      } else {
+        asm volatile("global_load_dword %0, %1, off ; msd_prefetch" : "+v"(sink) : "v"(src) : "memory");
       }
     }
     asm volatile("" ::"v"(sink));
@@ -221,7 +170,6 @@ struct GemmParams {
   int lda, ldb;
   int M, N, K;
   WeightPrefetch pf;  // optional: warm a later launch's weights (see WeightPrefetch)
-  int pf_nblk = 0;    // blocks that take part in the prefetch (0 = the whole grid); they are blockIdx.x < pf_nblk
   int grid_compute = 0;   // touch-block form (launcher): the compute grid; blocks from here on are touch blocks
   int xcd_rows = 1;   // LDS-DMA kernel: the 8 XCDs form an xcd_rows x (8 / xcd_rows) grid over (M, N) tiles
   int xcd_walk_n = 0; // order in which an XCD's blocks walk its tiles
@@ -304,7 +252,7 @@ struct GemmAcc {
 // PROLOGUE = false / REG_EPI = true (the persistent gated-MLP-in kernel below): the caller has already issued the tile's
 // first NS K-tiles and the epilogue operands (gemm_tile_issue + Epi::prefetch), and takes the accumulators back in
 // registers right behind the loop -- the ring is free from that point on (no slab), e.g. for the NEXT tile's K-tiles.
-template <int NP, int BM, int BN, int NS, class Epi, int PF = kPfNone, bool PROLOGUE = true, bool REG_EPI = false>
+template <int NP, int BM, int BN, int NS, class Epi, bool PROLOGUE = true, bool REG_EPI = false>
 __device__ __forceinline__ void gemm_tile(const GemmParams& p, const Epi& epi, int bm, int bn, char* smem,
                                           GemmAcc<BM, BN>* acc_out = nullptr, int ts_blk = -1, bool fresh = false) {
 #if MSD_TIMESTAMPS
@@ -550,10 +498,6 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const Epi& epi, i
             make_float4(acc[i][j][0] * kWScaleInv, acc[i][j][1] * kWScaleInv, acc[i][j][2] * kWScaleInv,
                         acc[i][j][3] * kWScaleInv);   // weights are packed times kWScale (common.h)
   };
-  PrefetchRegsT<PF> pf_keep;
-  // (the in-epilogue form of the weight prefetch; the product's launches carry a prefetch WAVE instead: kPfWave)
-  if constexpr (!kPfWave) prefetch_weights<PF>(p.pf, blockIdx.x, p.pf_nblk > 0 ? p.pf_nblk : (int)gridDim.x, p.B[0], pf_keep);
-  else prefetch_weights<kPfNone>(p.pf, 0, 1, nullptr, reinterpret_cast<PrefetchRegsT<kPfNone>&>(pf_keep));
   store_slab();
   epi.template stats<BM, LDS_LD>(slab, m0, tid, aux);   // row statistics next to the slab stores: one barrier
   __syncthreads();
@@ -561,7 +505,6 @@ __device__ __forceinline__ void gemm_tile(const GemmParams& p, const Epi& epi, i
   epi.template run<BM, BN, LDS_LD>(slab, m0, n0, tid, aux, /*stats_done=*/true, SatFlag{p.sat, p.sat_tag});
   MSD_TS_STAMP(BM, BN, 5)
   MSD_TS_END((ts_class<BM, BN>()), msd_ts_blk, gridDim.x)
-  prefetch_done(pf_keep);
   }
 }
 
@@ -587,7 +530,7 @@ __device__ __forceinline__ bool gemm_block_tile(const GemmParams& p, int b, int&
   return bn < tm.nbn && bm < tm.nbm;
 }
 
-constexpr int pf_threads(int pf) { return kPfWave && pf != kPfNone ? 64 : 0; }   // the prefetch wave of a launch, if any
+constexpr int pf_threads(int pf) { return pf != kPfNone ? 64 : 0; }   // the prefetch wave of a launch, if any
 
 // TB: the touch-block carrier form (above): blocks of 256 threads, the compute blocks run the code of a launch without a
 // target, blocks >= p.grid_compute touch.
@@ -601,7 +544,7 @@ __global__ void __launch_bounds__(256 + (TB ? 0 : pf_threads(PF))) gemm_h16_dma_
       touch_block<PF>(p.pf, (int)blockIdx.x - p.grid_compute, (int)gridDim.x - p.grid_compute, p.B[0]);
       return;
     }
-  } else if constexpr (kPfWave && PF != kPfNone) {
+  } else if constexpr (PF != kPfNone) {
     if (threadIdx.x >= 256) {   // the prefetch wave (only launched with pf_wave)
       prefetch_wave<PF>(p.pf, blockIdx.x, gridDim.x, p.B[0]);
       return;
@@ -609,7 +552,7 @@ __global__ void __launch_bounds__(256 + (TB ? 0 : pf_threads(PF))) gemm_h16_dma_
   }
   int bm, bn;
   if (!gemm_block_tile(p, (int)blockIdx.x, bm, bn)) return;
-  gemm_tile<NP, BM, BN, NS, Epi, TB ? kPfNone : PF>(p, epi, bm, bn, smem);
+  gemm_tile<NP, BM, BN, NS, Epi>(p, epi, bm, bn, smem);
 }
 
 // ----------------------------------------------------------------------------
@@ -1398,7 +1341,7 @@ inline hipError_t gemm_h16_dma_prepare() {
 // carry a target have none.  (host only)
 template <int NP, class Epi>
 inline bool gemm_carries_prefetch(const GemmParams& p) {
-  if constexpr (NP == 2 && epi_may_prefetch<Epi>::value) return prefetch_kind(p.pf) >= 1;   // product: the first target only
+  if constexpr (NP == 2 && epi_may_prefetch<Epi>::value) return p.pf.active();
   else return false;
 }
 
@@ -1429,7 +1372,7 @@ inline hipError_t launch_gemm_h16_dma(const GemmParams& p_in, const Epi& epi, hi
   p.map.fill(p.M, p.N, BM, BN, p.xcd_rows);
   const int rx = p.xcd_rows, cx = 8 / rx;
   const int grid = 8 * ((p.N / BN + cx - 1) / cx) * ((p.M / BM + rx - 1) / rx);
-  // one kernel instantiation per number of prefetch targets (single path: see prefetch_weights)
+  // one kernel instantiation without a prefetch wave and one with (PF, above)
 #define MSD_LAUNCH_PF(PF_) \
   hipLaunchKernelGGL((gemm_h16_dma_kernel<NP, BM, BN, NS, Epi, PF_>), dim3(grid), dim3(256 + pf_threads(PF_)), smem, stream, p, epi)
   if constexpr (NP == 2 && epi_may_prefetch<Epi>::value) {
@@ -1548,7 +1491,7 @@ __global__ void __launch_bounds__(256 + pf_threads(PF)) gemm_h16_geglu_persist_k
   static_assert(BM % 32 == 0 && BN % 64 == 0, "2 x 2 waves; whole wi_0 | wi_1 groups per wave");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   warm_kernargs<kernarg_lines<GemmParams, EpiGeglu<NP>, int>()>();
-  if constexpr (kPfWave && PF != kPfNone) {
+  if constexpr (PF != kPfNone) {
     if (threadIdx.x >= 256) {
       prefetch_wave<PF>(p.pf, blockIdx.x, gridDim.x, p.B[0]);
       return;
@@ -1585,7 +1528,7 @@ __global__ void __launch_bounds__(256 + pf_threads(PF)) gemm_h16_geglu_persist_k
   for (;;) {
     GemmAcc<BM, BN> acc;
     const int vcur = v;   // (debug builds: this tile's phase-stamp record)
-    gemm_tile<NP, BM, BN, NS, EpiGeglu<NP>, PF, /*PROLOGUE=*/false, /*REG_EPI=*/true>(p, epi, bm, bn, smem, &acc, vcur, /*fresh=*/stats_stale && vcur == (int)blockIdx.x);
+    gemm_tile<NP, BM, BN, NS, EpiGeglu<NP>, /*PROLOGUE=*/false, /*REG_EPI=*/true>(p, epi, bm, bn, smem, &acc, vcur, /*fresh=*/stats_stale && vcur == (int)blockIdx.x);
     const int m0 = bm * BM, n0 = bn * BN;
     int nbm = 0, nbn = 0;
     bool more = false;
@@ -1660,7 +1603,7 @@ inline hipError_t launch_gemm_h16_geglu_persist(const GemmParams& p_in, const Ep
   const int rx = p.xcd_rows, cx = 8 / rx;
   const int vblocks = 8 * ((p.N / BN + cx - 1) / cx) * ((p.M / BM + rx - 1) / rx);
   const int grid = vblocks < blocks ? vblocks : blocks;
-  if (prefetch_kind(p.pf) >= 1)
+  if (p.pf.active())
     hipLaunchKernelGGL((gemm_h16_geglu_persist_kernel<NP, BM, BN, NS, 1>), dim3(grid), dim3(256 + pf_threads(1)), smem, stream, p, epi, vblocks);
   else
     hipLaunchKernelGGL((gemm_h16_geglu_persist_kernel<NP, BM, BN, NS, 0>), dim3(grid), dim3(256), smem, stream, p, epi, vblocks);
@@ -1728,7 +1671,7 @@ template <int NP, int BM1, int BN1, int NS1, class Epi1, int BM2, int BN2, int N
 __global__ void __launch_bounds__(256 + pf_threads(PF)) gemm_h16_dual_kernel(GemmParams p1, Epi1 e1, GemmParams p2, Epi2 e2, int n1) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
   warm_kernargs<kernarg_lines<GemmParams, Epi1, GemmParams, Epi2, int>()>();
-  if constexpr (kPfWave && PF != kPfNone) {
+  if constexpr (PF != kPfNone) {
     if (threadIdx.x >= 256) {
       prefetch_wave<PF>(p1.pf, blockIdx.x, gridDim.x, p1.B[0]);
       return;
@@ -1737,10 +1680,10 @@ __global__ void __launch_bounds__(256 + pf_threads(PF)) gemm_h16_dual_kernel(Gem
   int bm, bn;
   if ((int)blockIdx.x < n1) {
     if (!gemm_block_tile(p1, (int)blockIdx.x, bm, bn)) return;
-    gemm_tile<NP, BM1, BN1, NS1, Epi1, PF>(p1, e1, bm, bn, smem);
+    gemm_tile<NP, BM1, BN1, NS1, Epi1>(p1, e1, bm, bn, smem);
   } else {
     if (!gemm_block_tile(p2, (int)blockIdx.x - n1, bm, bn)) return;
-    gemm_tile<NP, BM2, BN2, NS2, Epi2, PF>(p2, e2, bm, bn, smem);
+    gemm_tile<NP, BM2, BN2, NS2, Epi2>(p2, e2, bm, bn, smem);
   }
 }
 
@@ -1780,7 +1723,7 @@ inline hipError_t launch_gemm_h16_dual(const GemmParams& p1_in, const Epi1& e1, 
   p1.map.fill(p1.M, p1.N, BM1, BN1, p1.xcd_rows);
   p2.map.fill(p2.M, p2.N, BM2, BN2, p2.xcd_rows);
   const int n1 = gemm_grid_blocks(p1, BM1, BN1), n2 = gemm_grid_blocks(p2, BM2, BN2);
-  if (prefetch_kind(p1.pf) >= 1)
+  if (p1.pf.active())
     hipLaunchKernelGGL((gemm_h16_dual_kernel<NP, BM1, BN1, NS1, Epi1, BM2, BN2, NS2, Epi2, 1>), dim3(n1 + n2),
                        dim3(256 + pf_threads(1)), smem, stream, p1, e1, p2, e2, n1);
   else

@@ -709,15 +709,9 @@ void gemm_dual(Ctx& c, int kc, TileShape t1, const GemmParams& p1, const Epi1& e
 
 // Prefetch target = the packed W^T planes [N, K] of a later GEMM (gemm_h16.h PrefetchTarget)
 template <int NP>
-PrefetchTarget weights_target(const msd_model* m, const Planes& w, int N, int K) {
-  PrefetchTarget t;
-  if (m->prefetch && NP == 2) t.set(w.p[0], w.p[1], N, K * 2, K * 2);
-  return t;
-}
-template <int NP>
 WeightPrefetch prefetch_of(const msd_model* m, const Planes& w, int N, int K) {
   WeightPrefetch pf;
-  pf.add(weights_target<NP>(m, w, N, K));
+  if (m->prefetch && NP == 2) pf.t.set(w.p[0], w.p[1], N, K * 2, K * 2);
   return pf;
 }
 

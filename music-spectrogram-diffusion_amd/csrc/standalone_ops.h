@@ -27,7 +27,7 @@ template <class T> constexpr TileShape shape_of() { return {T::BM, T::BN}; }
 
 // What every op needs around its launches, in ONE place: device scratch (zeroed, freed when the op returns), operands as
 // planes of the op's plane count, the range flags, and a MINIMAL launch context -- an msd_model of which Ctx, gp_launch,
-// gemm_t and weights_target read the plane count, the range flag, the CU count and the persistent / prefetch switches;
+// gemm_t and prefetch_of read the plane count, the range flag, the CU count and the persistent / prefetch switches;
 // it has no weights, tables or buffers.
 // Range flags: device words [0] = bits of the largest packed |w| (pack_wt_kernel), [1] = the activation range flag
 // (common.h RangeCheck).  The ops fail like the model does: weights beyond the half-plane range -> MSD_ERR_UNSUPPORTED
@@ -281,7 +281,7 @@ struct SiteRun : OpKit {
     const GemmParams lp = gp_launch<NP>(c, kc, a, K, w, K, M, N, K, t.bm, pf);
     // both reports come from the predicates the launch itself uses (gemm_t, launch_gemm_h16_dma / _geglu_persist)
     g->ran_persistent = persistent_on<NP, Epi>(Tab{}, TileShape{ti->bm, ti->bn}, &ctx_model, lp, epi);
-    g->ran_prefetch = g->ran_persistent ? prefetch_kind(lp.pf) >= 1 : gemm_carries_prefetch<NP, Epi>(lp);
+    g->ran_prefetch = g->ran_persistent ? lp.pf.active() : gemm_carries_prefetch<NP, Epi>(lp);
     if (carrier) {   // the launcher's own rule, on the tile that runs (gemm_h16.h gemm_touch_blocks)
       const int n_touch = g->ran_persistent ? 0 : touch_blocks_on<NP, Epi>(Tab{}, TileShape{ti->bm, ti->bn}, lp);
       carrier->ran_touch_blocks = n_touch;
@@ -307,7 +307,7 @@ struct SiteRun : OpKit {
     g->ran_bm = i1->bm; g->ran_bn = i1->bn; g->ran_ns = i1->ns; g->ran_xcd_rows = p1.xcd_rows;
     g->ran_bm2 = i2->bm; g->ran_bn2 = i2->bn; g->ran_ns2 = i2->ns; g->ran_xcd_rows2 = p2.xcd_rows;
     g->ran_dual = 1;
-    g->ran_prefetch = prefetch_kind(p1.pf) >= 1;   // (launch_gemm_h16_dual's own test)
+    g->ran_prefetch = p1.pf.active();   // (launch_gemm_h16_dual's own test)
     gemm_dual<Pairs>(c, kc, t1, p1, e1, t2, p2, e2);
     return ok(c.err);
   }

@@ -51,7 +51,7 @@ int main() {
           p.ksplit = nkeys > 768 ? KS : 2; p.total_rows = nq; p.part_o = part_o; p.part_ml = part_ml; p.tickets = tickets;
           p.touch_ahead = touch > 0 ? 2 : 0; p.pf_late = touch >= 2 ? 1 : 0;
           if (touch >= 4) { p.pf.touch_blocks = 64; p.pf.touch_delay = delays[touch - 4]; }
-          if (touch >= 0 && touch != 3) { PrefetchTarget t; t.set(wbuf[it % 8], wbuf[it % 8] + (size_t)4096 * 768, 4096, 768 * 2, 768 * 2); p.pf.add(t); }   // (rotating: cold like a step's weights)
+          if (touch >= 0 && touch != 3) { PrefetchTarget t; t.set(wbuf[it % 8], wbuf[it % 8] + (size_t)4096 * 768, 4096, 768 * 2, 768 * 2); p.pf.t = t; }   // (rotating: cold like a step's weights)
           launch_attention<2>(p, heads, 1, 0);
         };
         for (int i = 0; i < 50; ++i) launch(i);

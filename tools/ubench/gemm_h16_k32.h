@@ -29,6 +29,51 @@ namespace msd {
 
 constexpr int kK32 = 32;   // K elements per tile: one MFMA K-step, 64-byte rows
 
+// The IN-EPILOGUE form of the weight touches (rounds 2 and 3 of the product; it left csrc/gemm_h16.h when the prefetch wave
+// and the touch blocks had replaced it everywhere, docs/history.md): the compute waves touch their share of the launch's
+// target behind their main loop.  The touches are plain 4-byte loads issued from inline asm into registers nobody reads:
+// the compiler does not know they are loads, so it never waits for them; `keep` pins the destination registers until
+// prefetch_done() at the end of the kernel, and s_endpgm waits for outstanding loads by itself.  PF (kPfNone or 1: has
+// the launch a target) is a template parameter, so every kernel instantiation has ONE straight-line path through here and
+// the destination registers reach prefetch_done() without a copy or a merge of values.
+// blk / nblk: launch-wide index of this block and number of blocks; `valid`: any mapped device address (touched by lanes
+// that have nothing to do, so that there is no branch around a load).  One wave-wide touch covers 64 >> lg whole rows
+// (lane = (row offset, line slot)); waves are dealt block-cyclically: touch u of wave w of block `blk` starts at row
+// ((blk + nblk * u) * nwave + w) * rows-per-touch -- touch_first_row / touch_lane_in of gemm_h16.h.
+constexpr int kPrefetchPerThread = 3;   // touches per wave
+template <int PF>
+struct PrefetchRegsT { uint32_t r[PF != kPfNone ? kPrefetchPerThread : 1]; };
+template <int PF>
+__device__ __forceinline__ void prefetch_weights(const WeightPrefetch& pf, int blk, int nblk, const void* valid,
+                                                 PrefetchRegsT<PF>& keep) {
+  static_assert(PF == kPfNone || PF == 1, "a launch carries one target or none");
+  if constexpr (PF == kPfNone) {
+    keep.r[0] = 0;
+  } else {
+    const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), nwave = (int)blockDim.x >> 6;
+    const int lane = (int)threadIdx.x & 63;
+    const PrefetchTarget& t = pf.t;
+    const int planes = t.base[1] && t.base[1] != t.base[0] ? 2 : 1;
+    const int rpt = 64 >> t.lg;                                      // rows per touch
+    const int sub = lane >> t.lg, line = lane & ((1 << t.lg) - 1);
+    const uint32_t lane_off = (uint32_t)sub * (uint32_t)t.row_stride + (uint32_t)line * 128u;
+#pragma unroll
+    for (int u = 0; u < kPrefetchPerThread; ++u) {
+      const int rp0 = touch_first_row(blk * nwave + wave, nblk * nwave, u, rpt);
+      int pl, row0;
+      const bool in = touch_lane_in(rp0, sub, line, t.rows, planes, t.lpr, &pl, &row0);
+      const char* row_ptr = t.base[pl] + (size_t)row0 * t.row_stride;
+      const char* src = in ? row_ptr + lane_off : reinterpret_cast<const char*>(valid);
+      asm volatile("global_load_dword %0, %1, off ; msd_prefetch" : "=&v"(keep.r[u]) : "v"(src) : "memory");
+    }
+  }
+}
+template <int PF>
+__device__ __forceinline__ void prefetch_done(const PrefetchRegsT<PF>& keep) {
+#pragma unroll
+  for (int u = 0; u < (PF != kPfNone ? kPrefetchPerThread : 1); ++u) asm volatile("" ::"v"(keep.r[u]));
+}
+
 // byte offset of chunk `c` (0..3) of `row` in a [rows][32] 16-bit LDS tile
 __device__ __forceinline__ int lds_k32_off(int row, int c) { return row * 64 + ((c ^ ((0 - (row >> 2)) & 3)) << 4); }
 
@@ -187,7 +232,7 @@ __device__ __forceinline__ void gemm_tile_k32(const GemmParams& p, const Epi& ep
 
   __syncthreads();  // all fragment reads done before the slab overwrites the ring
   // The later launch's weights are touched HERE, by the compute waves behind their main loop (the in-epilogue form
-  // of gemm_h16.h), whatever the build's prefetch mechanism: this loop needs ~340 registers, and a fifth (prefetch)
+  // above), not by a prefetch wave as in the product's kernels: this loop needs ~340 registers, and a fifth (prefetch)
   // wave in the block would halve the budget to 256 and spill (172 VGPRs to scratch when it was tried).  On 50 - 90 us
   // kernels the wait for the touches at the end is noise.
   PrefetchRegsT<PF> pf_keep;
@@ -234,7 +279,7 @@ inline hipError_t gemm_h16_k32_prepare() {
 #define MSD_K32_ATTR(PF_)                                                                                           \
   if ((r = hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_h16_k32_kernel<NP, BM, BN, NS, Epi, PF_>),        \
                                hipFuncAttributeMaxDynamicSharedMemorySize, smem)) != hipSuccess) e = r;
-  MSD_K32_ATTR(0) MSD_K32_ATTR(1) MSD_K32_ATTR(2)
+  MSD_K32_ATTR(0) MSD_K32_ATTR(1)
 #undef MSD_K32_ATTR
   return e;
 }
@@ -246,9 +291,7 @@ inline hipError_t launch_gemm_h16_k32(const GemmParams& p, const Epi& epi, hipSt
   if (attr != hipSuccess) return attr;
   const int rx = p.xcd_rows, cx = 8 / rx;
   const int grid = 8 * ((p.N / BN + cx - 1) / cx) * ((p.M / BM + rx - 1) / rx);
-  const int npf = prefetch_kind(p.pf);
-  if (npf >= 2) hipLaunchKernelGGL((gemm_h16_k32_kernel<NP, BM, BN, NS, Epi, 2>), dim3(grid), dim3(256), smem, stream, p, epi);
-  else if (npf == 1) hipLaunchKernelGGL((gemm_h16_k32_kernel<NP, BM, BN, NS, Epi, 1>), dim3(grid), dim3(256), smem, stream, p, epi);
+  if (p.pf.active()) hipLaunchKernelGGL((gemm_h16_k32_kernel<NP, BM, BN, NS, Epi, 1>), dim3(grid), dim3(256), smem, stream, p, epi);
   else hipLaunchKernelGGL((gemm_h16_k32_kernel<NP, BM, BN, NS, Epi, 0>), dim3(grid), dim3(256), smem, stream, p, epi);
   return hipGetLastError();
 }
