@@ -416,7 +416,12 @@ int msd_fill_normal_threefry(uint64_t seed, int64_t fold, float* out_dev, int64_
 int msd_get_schedule(const msd_model* m, float* host_out);
 
 /* Read an internal buffer as float (bf16 widened) into host memory, for tests.
- * Returns the element count in *n_out; copies min(count, max_elems).  Synchronises. */
+ * Returns the element count in *n_out; copies min(count, max_elems).  Synchronises.
+ * Among the buffers: the encode stage's "enc" [S_pad][D] (the LAST encoded row's encodings), "cross_k"
+ * [Ld][Bmax][S_pad][J] and "cross_vt" [Ld][Bmax][J][S_pad] (keys permuted within every 16: gemm_h16.h vt_perm16), and the
+ * load-time tables "film" [N][2 Ld][2 D], "g_table" [N][2 Ld][D] = gamma (film_scale + 1), "bw_self" [N][Ld][3 J] =
+ * film_bias_self . (Wq | Wk | Wv) and "bw_mlp" [N][Ld][2 F] = film_bias_mlp . (wi_0 | wi_1) in the gated projection's
+ * packed column order (EpiF32StoreGated). */
 int msd_debug_read(msd_model* m, const char* buffer, float* host_out, int64_t max_elems,
                    int64_t* n_out);
 

@@ -1199,9 +1199,9 @@ int encode_impl(msd_model* m, int batch, const int32_t* tokens_h, const float* c
       }
     }
     const int Sv = Lv + Cv;
-    const int Sp = round_up(Sv > 0 ? Sv : 1, 64);
-    // rows [Sv, Sp) may hold normalised padding rows of the last encoder: zero them
-    if (m->n_cross == 1 && Sp > Sv) {
+    // rows from Sv on may hold normalised padding rows of the last encoder: zero them.  (Also when Sv is a multiple of
+    // 64: one token and 63 context frames make 64 keys, and the context encoder's 64 rows, written from row 1, reach row 64.)
+    if (m->n_cross == 1 && m->S_pad > Sv) {
       for (int pl = 0; pl < NP; ++pl)
         HIP_TRY(m, hipMemsetAsync(m->enc.p[pl] + (size_t)Sv * D, 0,
                                   (size_t)(m->S_pad - Sv) * D * sizeof(h16_t), s));
@@ -2386,6 +2386,9 @@ int msd_debug_read(msd_model* m, const char* buffer, float* host_out, int64_t ma
   const int64_t Mmax = (int64_t)m->passes * m->Bmax * m->T;
   if (b == "film") { f32 = m->d_film; count = (int64_t)m->N * 2 * m->Ld * 2 * m->D; }
   else if (b == "coef") { f32 = m->d_coef; count = (int64_t)m->N * kCoefCount; }
+  else if (b == "g_table") { f32 = m->d_g; count = (int64_t)m->N * 2 * m->Ld * m->D; }
+  else if (b == "bw_self") { f32 = m->d_bw_self; count = (int64_t)m->N * m->Ld * 3 * m->J; }
+  else if (b == "bw_mlp") { f32 = m->d_bw_mlp; count = (int64_t)m->N * m->Ld * 2 * m->F; }
   else if (b == "x") { f32 = m->x; count = Mmax * m->D; }
   else if (b == "eps") { f32 = m->eps; count = Mmax * m->ND; }
   else if (b == "z") { f32 = m->z; count = (int64_t)m->Bmax * m->T * m->ND; }

@@ -498,6 +498,10 @@ class NativeModel:
     return out
 
   def debug_read(self, buffer: str, max_elems: Optional[int] = None) -> np.ndarray:
+    """An internal buffer as flat float32 (msd_debug_read; 16-bit planes merged).  The encode stage: 'enc' [S_pad, D]
+    (the last encoded row), 'cross_k' [Ld, Bmax, S_pad, J], 'cross_vt' [Ld, Bmax, J, S_pad] (keys permuted per 16).  The
+    load-time tables: 'film' [N, 2 Ld, 2 D], 'g_table' [N, 2 Ld, D], 'bw_self' [N, Ld, 3 J], 'bw_mlp' [N, Ld, 2 F] (the
+    gated projection's packed column order)."""
     n = ctypes.c_int64()
     probe = np.zeros(1, np.float32)
     _check(self.lib, self.handle,

@@ -173,6 +173,7 @@ class FastModel:
     xp, p, cfg = self.xp, self.p, self.cfg
     tokens = np.asarray(tokens)
     self.kv = []
+    self.enc = []   # per batch row (token encodings [n_tok, D] or None, context encodings [n_ctx, D] or None): for tests
     for b in range(tokens.shape[0]):
       tok_enc = ctx_enc = None
       valid = np.nonzero(tokens[b] > 0)[0]
@@ -198,6 +199,7 @@ class FastModel:
           x = x + xp.take(p['continuous_encoder/Embed_0/embedding'], xp.asint(pos))
           x = xp.take(x, xp.asint(cvalid))
           ctx_enc = self._encoder_stack('continuous_encoder', x)
+      self.enc.append((tok_enc, ctx_enc))
       # key regions, one cross-attention module each: concat_encodings = ONE region holding both encodings
       # (network.py:217-235); sum_cross_attends = a module per encoding, outputs summed (:199-216)
       if self.sum_style:
