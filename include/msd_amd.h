@@ -50,7 +50,9 @@ extern "C" {
                                       msd_sample_edit, msd_op_sampler_step_release and msd_op_diffuse_to_step (edit strength:
                                       per-frame release words and a part-way start of the sampler);
                                       msd_sample_steps, msd_op_sampler_step_multistep and MSD_SAMPLER_DPMPP_2M (a step
-                                      count per call and a second-order multistep sampler).
+                                      count per call and a second-order multistep sampler);
+                                      msd_sample_resample and msd_op_renoise (known-frame edits with RePaint resampling
+                                      jumps in the sampler scan).
                                    6: cross_merge_in_launch, cross_q_fold, mlp_in_persistent appended to msd_config.
                                    5: dedup_layer0, cross_key_split, keep_raw_weights, kv_touch_ahead appended to msd_config.
                                    4: every caller-selectable knob is a msd_config field (attn_q_planes / attn_p_planes
@@ -315,7 +317,7 @@ int msd_sample_rows(msd_model* m, int batch, int rng, const uint64_t* seeds, con
  *     pred_x0 := xk     pred_eps := predict_eps_from_x0(z_t, xk, logsnr_t)
  * and the ordinary ddpm_step / ddim_step runs: they follow the posterior q(z_s | z_t, x0 = xk), carry the noise level of
  * their step (the free frames see them through self-attention at that level) and arrive at xk at scan index 0.  init_z
- * and every noise draw are what the call without a mask makes; no resampling jumps (RePaint) are made.  out_dev gets the
+ * and every noise draw are what the call without a mask makes; resampling jumps (RePaint): msd_sample_resample.  out_dev gets the
  * CALLER's values on kept frames, bit for bit (also values outside the codec's range, which xk clips), and the sampled
  * mel on the others.  An all-zero mask gives msd_sample_rng's / msd_sample_rows' result bit for bit.
  *   per_row = 0: ONE draw over the whole array under (seeds[0], stream_ids[0]) -- msd_sample_rng's keying
@@ -351,6 +353,35 @@ int msd_sample_keep(msd_model* m, int batch, int rng, int per_row, const uint64_
 int msd_sample_edit(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
                     const float* init_z_dev, const float* noise_dev, const float* known_dev, const int32_t* release,
                     int start_step, float* out_dev, void* stream);
+
+/* (appended to ABI 7) msd_sample_edit with RESAMPLING JUMPS (RePaint, Lugmayr et al. 2022): the scan goes down a block of
+ * steps, diffuses the state back up and comes down again, so that the free frames get several chances to condition on the
+ * known frames at the same noise level.  A LEVEL is the number of steps still to run: the step with scan index i takes
+ * level i + 1 to level i, and the call starts at level S = start_step + 1.
+ *   jump, times  block k = 0, 1, ... has top S - k jump and bottom max(top - jump, 0) (the last block may be shorter).  Every
+ *                block is descended `times` times; after each descent but the last the state is diffused from the block's
+ *                bottom level s back to its top level t -- one sample of q(z_t | z_s), known and free frames alike:
+ *                    z' = fmaf(b, eps, a * z),  a = alpha_t / alpha_s,  b = sqrt(1 - a^2)
+ *                alpha = sqrt(sigmoid(logsnr)) of the SAMPLER schedule's float32 table value at the level (level L > 0: scan
+ *                index L - 1's logsnr_t; level 0: scan index 0's logsnr_s, where z holds x0); a, b computed in double and
+ *                rounded once.  The call runs times * S steps and (times - 1) ceil(S / jump) jumps.  The release words keep
+ *                their meaning in every descent: known at scan indices i >= v - 1.  jump < 1 or times < 1 is
+ *                MSD_ERR_INVALID_ARGUMENT; times == 1 is msd_sample_edit(..., noise_dev = NULL, ...) bit for bit, whatever jump.
+ *   draws        pass p = everything behind the call's p-th jump (pass 0: the call as msd_sample_edit keys it) has a key of
+ *                its own; its jump draws what that key's initial draw would be, its steps what that key's steps would draw.
+ *                MSD_RNG_PHILOX: (seed, stream_id + (p << 32)) -- eps = sub-sequence 0 (msd_fill_normal's bits), step i's
+ *                noise sub-sequence 1 + i; with times > 1 every stream_id must be < 2^32 (MSD_ERR_INVALID_ARGUMENT).
+ *                MSD_RNG_THREEFRY: key_p = fold_in(PRNGKey(seed), num_steps + p - 1), the first fold indices the plain call
+ *                does not use -- eps = normal(key_p, [batch | 1, T, n]), step i's noise normal(fold_in(key_p, i), ...).
+ *                Per-row keys: row b draws, in every pass, what its one-row call draws.  The extra draws are made on the
+ *                device, so there is no noise_dev; init_z_dev keeps its meaning for pass 0.
+ * Nothing synchronises with the host between passes: all passes' keys are uploaded once, the jump kernel installs its
+ * pass's keys and rewinds the device scan index, the descents replay msd_sample_keep's cached graphs (a jump that is a
+ * multiple of graph_steps runs on whole graphs) and the call ends with its one synchronisation.  Every other argument,
+ * check and status is msd_sample_edit's; an MSD_SAMPLER_DPMPP_2M handle stays MSD_ERR_UNSUPPORTED. */
+int msd_sample_resample(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
+                        const float* init_z_dev, const float* known_dev, const int32_t* release, int start_step, int jump,
+                        int times, float* out_dev, void* stream);
 
 /* (appended to ABI 7) A step count and a sampler PER CALL: preview in 50 steps, render in 1000, on one handle.
  *   num_steps  K: 0 = the handle's N = msd_config.num_steps; else K must DIVIDE N (MSD_ERR_INVALID_ARGUMENT otherwise, with
@@ -504,6 +535,13 @@ int msd_op_sampler_step_release(const msd_config* cfg, int step_index, const flo
  *   cfg->precision merged back to float32; n % 4 == 0.  Uses cfg->{num_steps, sampler_schedule*, feature_*, precision}. */
 int msd_op_diffuse_to_step(const msd_config* cfg, int step_index, const float* mel_dev, const float* eps_dev,
                            float* z_out_dev, float* z_planes_out_dev, float* xk_out_dev, int64_t n, void* stream);
+
+/* (appended to ABI 7) The resampling jump of msd_sample_resample on its own, with the caller's eps: z_out = fmaf(b, eps, a * z)
+ * from level from_level up to level to_level, 0 <= from_level < to_level <= cfg->num_steps (see msd_sample_resample).
+ *   z_dev, eps_dev float [n] in; z_out_dev float [n] out; z_planes_out_dev float [n]: z_out's operand planes of
+ *   cfg->precision merged back to float32; n % 4 == 0, n <= 2^31 - 1024.  Uses cfg->{num_steps, sampler_schedule*, precision}. */
+int msd_op_renoise(const msd_config* cfg, int from_level, int to_level, const float* z_dev, const float* eps_dev,
+                   float* z_out_dev, float* z_planes_out_dev, int64_t n, void* stream);
 
 /* (appended to ABI 7) One update of MSD_SAMPLER_DPMPP_2M (msd_sample_steps) at scan index step_index of cfg->num_steps:
  * x0_prev_inout_dev float [n] holds the previous step's pred_x0 on entry (not read when first != 0: D = x0_t) and this

@@ -67,8 +67,9 @@ def check_prefetch_registers(listing: str) -> str:
 # kernels that must not spill: elementwise launches on the step's critical path (the sampler once went through scratch
 # memory, csrc/elementwise.h) and the Threefry fill ...
 NO_SCRATCH_STEP_KERNELS = ('sampler_step_kernel', 'threefry_normal_kernel')
-# ... the part-way start of msd_sample_edit (csrc/keep_frames_tail.h: one pass in front of the first step) ...
-NO_SCRATCH_EDIT_KERNELS = ('diffuse_to_step_kernel',)
+# ... the part-way start of msd_sample_edit (csrc/keep_frames_tail.h: one pass in front of the first step) and the
+# resampling jump of msd_sample_resample (the same file: one pass between two descents of a block) ...
+NO_SCRATCH_EDIT_KERNELS = ('diffuse_to_step_kernel', 'renoise_kernel')
 # ... the multistep sampler form of msd_sample_steps (csrc/multistep_tail.h: the step's last launch, like the plain form) ...
 NO_SCRATCH_MULTISTEP_KERNELS = ('sampler_multistep_kernel',)
 # ... and the vocoder's elementwise kernels (csrc/vocoder.h: two of the four launches of a Griffin-Lim iteration)

@@ -509,6 +509,32 @@ void launch_diffuse_to_step(const DiffuseParams& dp, hipStream_t s);
 // flags[i] = flags[i] != 0: msd_sample_keep's "any non-zero flag = known throughout" as the release word 1
 void launch_normalize_flags(const int32_t* in, int32_t* out, int n, hipStream_t s);
 
+// A resampling jump of msd_sample_resample (keep_frames_tail.h): one sample of q(z_t | z_s) from the bottom level of a block
+// of steps back to its top, z' = fmaf(b, eps, a * z), as fp32 and operand planes.  z may be z_in (a thread reads its four
+// elements before it writes them).  eps == nullptr: drawn here under `keys`, the rows of the pass the jump opens -- what
+// that key's initial draw would be (Philox sub-sequence 0; Threefry normal(key, [B | 1, T, n])), per row of z in the
+// per-row mode, with sampler_step_kernel's row arithmetic.  The launch's last block then installs those rows in the
+// sampler's key table and sets both words of the scan index, so the steps behind it draw under the pass's key from the
+// block's top: no host round trip between passes.
+struct RenoiseParams {
+  const float* z_in;    // [n]
+  const float* eps = nullptr;   // [n] the caller's draw (msd_op_renoise), or nullptr
+  float* z;             // [n] out
+  h16_t* z_hi;          // out: operand planes of z (z_lo may be null: one-plane precisions)
+  h16_t* z_lo;
+  int n;                // % 4 == 0
+  float a, b;           // alpha_t / alpha_s and sqrt(1 - a^2) (host, double, rounded once)
+  const uint32_t* keys = nullptr;   // [rows][kRngWords] the pass's key rows (read when eps == nullptr)
+  int row_blocks = 1 << 30;         // SamplerParams::row_blocks
+  uint32_t* key_table = nullptr;    // the sampler's key table: gets key_words words of `keys`; nullptr = none
+  int key_words = 0;
+  int* step_ptr = nullptr;          // the device scan index: both words := next_step; nullptr = none
+  int next_step = 0;
+  unsigned* sat = nullptr;   // half-plane range flag (common.h RangeCheck)
+  unsigned sat_tag = 1;
+};
+void launch_renoise(const RenoiseParams& rp, hipStream_t s);
+
 // The multistep form's arguments (msd_sample_steps with MSD_SAMPLER_DPMPP_2M; kernel and launch: multistep_tail.h).  A
 // struct of its own for the keep form's reason: the plain instances' argument block stays at its two 64-byte lines.
 // Row i of the side table coef_ms: {sigma_s / sigma_t, -alpha_s expm1(-h), 1 / (2r), 0} (msd_api.hip build_multistep_rows)

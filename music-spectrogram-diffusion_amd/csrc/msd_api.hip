@@ -196,6 +196,11 @@ struct msd_model {
   // keep call (outside stream capture) and owned by the handle, so the captured keep graphs hold stable addresses
   float* keep_xk = nullptr;
   int32_t* keep_flags = nullptr;
+  // msd_sample_resample: the key rows of every pass behind a jump, [passes][batch][kRngWords], uploaded once per call (the
+  // jump kernel installs its pass's rows in d_rng_key); grown on need outside stream capture, owned by the handle
+  uint32_t* d_pass_keys = nullptr;
+  size_t pass_keys_cap = 0;            // words
+  std::vector<uint32_t> h_pass_keys;   // host staging of that upload
   // msd_sample_steps: the sampler's coefficient rows for a call of K steps (K | N), built on the first such call and kept
   // (host copy + device table; K == N is d_coef itself), and -- MSD_SAMPLER_DPMPP_2M -- the multistep side table of K and
   // the previous step's pred_x0 [Bmax][T][n]; all allocated outside stream capture and owned by the handle
@@ -1040,6 +1045,19 @@ void diffuse_coefs(float logsnr_t, float* alpha, float* sigma) {
   const double l = (double)logsnr_t;
   *alpha = (float)std::sqrt(1.0 / (1.0 + std::exp(-l)));
   *sigma = (float)std::sqrt(1.0 / (1.0 + std::exp(l)));
+}
+
+// The resampling jump's coefficients (renoise_kernel) from level `from` up to level `to` (a level = the steps still to run):
+// a = alpha_to / alpha_from, b = sqrt(1 - a^2), alpha = sqrt(sigmoid(logsnr)) of the SAMPLER schedule's float32 table value
+// at the level -- level L > 0: row L - 1's logsnr_t; level 0: row 0's logsnr_s --, in double, each rounded once
+void renoise_coefs(const std::vector<float>& rows, int from, int to, float* a, float* b) {
+  auto alpha = [&](int level) {
+    const double l = level > 0 ? (double)rows[(size_t)(level - 1) * kCoefCount + kCoefLogsnrT] : (double)rows[kCoefLogsnrS];
+    return std::sqrt(1.0 / (1.0 + std::exp(-l)));
+  };
+  const double r = alpha(to) / alpha(from);
+  *a = (float)r;
+  *b = (float)std::sqrt(std::max(1.0 - r * r, 0.0));
 }
 
 int build_tables(msd_model* m, hipStream_t s) {
@@ -2018,6 +2036,7 @@ struct SampleCall {
   const int32_t* release;        // msd_sample_edit: release words [batch, T] (host, validated by the entry point)
   int start_step;                // the scan index the call starts at: steps - 1, or msd_sample_edit's
   int steps, sampler;            // K (K | N) and the msd_sampler_kind
+  int jump = 1, times = 1;       // msd_sample_resample: every block of `jump` steps is descended `times` times (1 = no jump)
 };
 
 static SampleKeys sample_keys(int per_row, const uint64_t* seeds, const uint64_t* stream_ids) {
@@ -2084,6 +2103,11 @@ static int check_call(msd_model* m, const SampleCall& c) {
   if (c.rng != MSD_RNG_PHILOX && c.rng != MSD_RNG_THREEFRY) return fail(m, MSD_ERR_INVALID_ARGUMENT, "unknown rng %d", c.rng);
   if (c.known && (c.steps != m->N || c.sampler == MSD_SAMPLER_DPMPP_2M))
     return fail(m, MSD_ERR_UNSUPPORTED, "known frames run on the handle's own step count with ddpm or ddim (no multistep history across a release)");
+  if (c.jump < 1 || c.times < 1) return fail(m, MSD_ERR_INVALID_ARGUMENT, "resampling needs jump >= 1 and times >= 1 (got %d, %d)", c.jump, c.times);
+  if (c.times > 1 && c.rng == MSD_RNG_PHILOX)   // pass p draws under (seed, stream_id + (p << 32))
+    for (int b = 0; b < (c.keys.per_row() ? c.batch : 1); ++b)
+      if (c.keys.stream_of(b) >> 32)
+        return fail(m, MSD_ERR_INVALID_ARGUMENT, "a call with resampling needs stream_id < 2^32 (row %d: %llu)", b, (unsigned long long)c.keys.stream_of(b));
   if (!m->encoded) return fail(m, MSD_ERR_BAD_STATE, "msd_encode has not run");
   if (c.batch != m->encoded_batch) return fail(m, MSD_ERR_INVALID_ARGUMENT, "batch %d != encoded batch %d", c.batch, m->encoded_batch);
   if (!c.out) return fail(m, MSD_ERR_INVALID_ARGUMENT, "out is null");
@@ -2218,6 +2242,69 @@ static int replay(msd_model* m, const msd_model::StepGraphs& g, int steps, hipSt
   return MSD_OK;
 }
 
+// msd_sample_resample: the key rows of passes 1 .. P of the call (pass p = everything behind its p-th jump; pass 0 is the
+// call as arm_scan keys it), P = (times - 1) ceil(steps / jump), as one upload in front of the call's steps.
+//   Philox    (seed, stream_id + (p << 32)): the jump draws sub-sequence 0, step i sub-sequence 1 + i
+//   Threefry  key_p = fold_in(PRNGKey(seed), N + p - 1), the first fold indices the plain call leaves unused: the jump draws
+//             normal(key_p, ...), step i normal(fold_in(key_p, i), ...) -- the sampler kernel folds i into the table's key
+static int upload_pass_keys(msd_model* m, const SampleCall& c, int steps, hipStream_t s) {
+  const size_t passes = (size_t)(c.times - 1) * (size_t)((steps - 1) / c.jump + 1);   // (no steps + jump: jump may be INT_MAX, "one block")
+  const size_t words = passes * c.batch * kRngWords;
+  if (words > m->pass_keys_cap) {   // (the stream is idle: the last call ended with its synchronisation)
+    if (m->d_pass_keys) {
+      auto it = std::find(m->allocs.begin(), m->allocs.end(), static_cast<void*>(m->d_pass_keys));
+      if (it != m->allocs.end()) m->allocs.erase(it);
+      (void)hipFree(m->d_pass_keys);
+      m->d_pass_keys = nullptr; m->pass_keys_cap = 0;
+    }
+    if (int rc = dalloc(m, &m->d_pass_keys, words)) return rc;
+    m->pass_keys_cap = words;
+  }
+  m->h_pass_keys.resize(words);   // a member: the copy below may still read it when this returns
+  for (size_t p = 1; p <= passes; ++p)
+    for (int b = 0; b < c.batch; ++b) {
+      uint32_t* row = &m->h_pass_keys[((p - 1) * c.batch + b) * kRngWords];
+      if (c.rng == MSD_RNG_PHILOX) {   // the pass in the stream id's upper word
+        fill_rng_key(row, c.rng, c.keys.seed_of(b), c.keys.stream_of(b) + ((uint64_t)p << 32), c.keys.per_row());
+      } else {   // the pass folded into the Threefry key words (the stream id does not enter this generator's key)
+        fill_rng_key(row, c.rng, c.keys.seed_of(b), c.keys.stream_of(b), c.keys.per_row());
+        uint32_t f0 = 0u, f1 = (uint32_t)(m->N + p - 1);
+        threefry2x32(row[kRngTfKey0], row[kRngTfKey1], f0, f1);
+        row[kRngTfKey0] = f0; row[kRngTfKey1] = f1;
+      }
+    }
+  HIP_TRY(m, hipMemcpyAsync(m->d_pass_keys, m->h_pass_keys.data(), words * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+  return MSD_OK;
+}
+
+// The steps of a call with resampling jumps (RePaint): blocks of c.jump steps from level `steps` down (a level = the steps
+// still to run; the last block may be shorter), every block descended c.times times; after each descent but the last
+// the state is diffused from the block's bottom level back to its top (renoise_kernel, which also installs the next
+// pass's keys and rewinds the scan index).  times * steps steps and (times - 1) ceil(steps / jump) jumps, all enqueued.
+static int replay_resampled(msd_model* m, const SampleCall& c, const msd_model::StepGraphs& g, int steps, hipStream_t s) {
+  const int n = c.batch * m->T * m->ND;
+  int pass = 0;
+  for (int top = steps; top > 0; top -= std::min(top, c.jump)) {
+    const int bottom = std::max(top - c.jump, 0);
+    for (int r = 0; r < c.times; ++r) {
+      if (int rc = replay(m, g, top - bottom, s)) return rc;
+      if (r == c.times - 1) break;
+      ++pass;
+      RenoiseParams rp;
+      rp.z_in = m->z; rp.z = m->z; rp.z_hi = m->zp.p[0]; rp.z_lo = m->NP == 2 ? m->zp.p[1] : nullptr; rp.n = n;
+      renoise_coefs(m->h_coef, bottom, top, &rp.a, &rp.b);
+      rp.keys = m->d_pass_keys + (size_t)(pass - 1) * c.batch * kRngWords;
+      if (m->T * m->ND % kRngRowBlock == 0) rp.row_blocks = m->T * m->ND / kRngRowBlock;   // (enqueue_step's)
+      rp.key_table = m->d_rng_key; rp.key_words = c.batch * kRngWords;
+      rp.step_ptr = m->d_step; rp.next_step = top - 1;
+      rp.sat = m->d_sat; rp.sat_tag = (unsigned)KC_SAMPLER + 1u;
+      launch_renoise(rp, s);
+      HIP_TRY(m, hipGetLastError());
+    }
+  }
+  return MSD_OK;
+}
+
 // z -> the caller's mel units; kept frames: the caller's own values, not a round trip through model units
 static int unscale(msd_model* m, const SampleCall& c, hipStream_t s) {
   const int64_t n = (int64_t)c.batch * m->T * m->ND;
@@ -2241,10 +2328,19 @@ static int sample_body(msd_model* m, const SampleCall& c) {
   }
   if (int rc = arm_range(m, s)) return rc;
   if (int rc = write_initial_state(m, c, s)) return rc;
+  if (c.times > 1)
+    if (int rc = upload_pass_keys(m, c, steps, s)) return rc;
   if (int rc = arm_scan(m, c.batch, c.rng, c.keys, c.noise, c.start_step, /*reset_tickets=*/true, s)) return rc;
   msd_model::StepGraphs* g = nullptr;
-  if (int rc = find_graphs(m, view, plan_cfg_step(m, c.batch), steps, s, &g)) return rc;
-  if (int rc = replay(m, *g, steps, s)) return rc;
+  if (c.times == 1) {
+    if (int rc = find_graphs(m, view, plan_cfg_step(m, c.batch), steps, s, &g)) return rc;
+    if (int rc = replay(m, *g, steps, s)) return rc;
+  } else {
+    // (the single-step graph: needed as soon as one block is no whole number of graphs)
+    const bool singles = c.jump % m->graph_steps || steps % c.jump % m->graph_steps;
+    if (int rc = find_graphs(m, view, plan_cfg_step(m, c.batch), singles ? 1 : m->graph_steps, s, &g)) return rc;
+    if (int rc = replay_resampled(m, c, *g, steps, s)) return rc;
+  }
   if (int rc = unscale(m, c, s)) return rc;
   // ONE stream synchronisation ends the call (tens of microseconds against a ~1 s segment); behind it the half-plane range flag is read: a bad run fails THIS call
   return check_range(m, s, "msd_sample");
@@ -2280,10 +2376,10 @@ int msd_sample_keep(msd_model* m, int batch, int rng, int per_row, const uint64_
   return sample_body(m, c);
 }
 
-int msd_sample_edit(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
-                    const float* init_z_dev, const float* noise_dev, const float* known_dev, const int32_t* release,
-                    int start_step, float* out_dev, void* stream) {
-  if (!m) return MSD_ERR_INVALID_ARGUMENT;
+// msd_sample_edit's checks and its call (msd_sample_resample shares them)
+static int edit_call(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
+                     const float* init_z_dev, const float* noise_dev, const float* known_dev, const int32_t* release,
+                     int start_step, float* out_dev, void* stream, SampleCall* out) {
   if (!seeds) return fail(m, MSD_ERR_INVALID_ARGUMENT, "seeds is null");
   if (!known_dev || !release) return fail(m, MSD_ERR_INVALID_ARGUMENT, "known mel or release words are null");
   if (batch < 1 || batch > m->Bmax) return fail(m, MSD_ERR_INVALID_ARGUMENT, "batch %d outside [1, %d]", batch, m->Bmax);
@@ -2302,6 +2398,26 @@ int msd_sample_edit(msd_model* m, int batch, int rng, int per_row, const uint64_
   }
   SampleCall c = plain_call(m, batch, rng, sample_keys(per_row, seeds, stream_ids), init_z_dev, noise_dev, out_dev, stream);
   c.known = known_dev; c.release = release; c.start_step = start_step;
+  *out = c;
+  return MSD_OK;
+}
+
+int msd_sample_edit(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
+                    const float* init_z_dev, const float* noise_dev, const float* known_dev, const int32_t* release,
+                    int start_step, float* out_dev, void* stream) {
+  if (!m) return MSD_ERR_INVALID_ARGUMENT;
+  SampleCall c;
+  if (int rc = edit_call(m, batch, rng, per_row, seeds, stream_ids, init_z_dev, noise_dev, known_dev, release, start_step, out_dev, stream, &c)) return rc;
+  return sample_body(m, c);
+}
+
+int msd_sample_resample(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
+                        const float* init_z_dev, const float* known_dev, const int32_t* release, int start_step, int jump,
+                        int times, float* out_dev, void* stream) {
+  if (!m) return MSD_ERR_INVALID_ARGUMENT;
+  SampleCall c;
+  if (int rc = edit_call(m, batch, rng, per_row, seeds, stream_ids, init_z_dev, nullptr, known_dev, release, start_step, out_dev, stream, &c)) return rc;
+  c.jump = jump; c.times = times;   // (checked with the rest of the call: check_call)
   return sample_body(m, c);
 }
 

@@ -989,6 +989,30 @@ int msd_op_diffuse_to_step(const msd_config* cfg, int step_index, const float* m
   return kit.finish();
 }
 
+int msd_op_renoise(const msd_config* cfg, int from_level, int to_level, const float* z_dev, const float* eps_dev,
+                   float* z_out_dev, float* z_planes_out_dev, int64_t n, void* stream) {
+  if (!cfg || cfg->struct_size != (int32_t)sizeof(msd_config) || !z_dev || !eps_dev || !z_out_dev || !z_planes_out_dev ||
+      n <= 0 || n % 4 || n > 0x7FFFFFFFll - 1023 || from_level < 0 || to_level <= from_level || to_level > cfg->num_steps)
+    return MSD_ERR_INVALID_ARGUMENT;   // (n: the last block's element index, blocks of 1024, stays an int)
+  const int NP = op_planes(cfg->precision);
+  if (NP < 0) return MSD_ERR_UNSUPPORTED;
+  std::vector<float> rows;
+  std::string why;
+  if (!build_coef_rows(*cfg, &rows, &why)) return MSD_ERR_INVALID_ARGUMENT;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  OpKit kit(s, NP);
+  Planes zp;
+  if (!kit.init_flags() || !kit.planes((size_t)n, &zp)) return MSD_ERR_HIP;
+  RenoiseParams rp;   // (no keys, no key table, no scan index: the caller's eps, and nothing armed behind the jump)
+  rp.z_in = z_dev; rp.eps = eps_dev; rp.z = z_out_dev; rp.z_hi = zp.p[0]; rp.z_lo = zp.p[1]; rp.n = (int)n;
+  renoise_coefs(rows, from_level, to_level, &rp.a, &rp.b);
+  kit.arm(rp);
+  launch_renoise(rp, s);
+  if (hipGetLastError() != hipSuccess) return MSD_ERR_HIP;
+  kit.back(zp, z_planes_out_dev, (size_t)n);
+  return kit.finish();
+}
+
 // x_out = x_in + a . w1 ;  h_out = (RMSNorm(x_out; gamma) (.) (film_scale + 1) + film_bias) . w2
 // folded != 0: the product's path -- EpiResidualNorm (y = x (.) g planes + partial sums of squares)
 // then a consumer GEMM whose epilogue applies rstd and the tabulated bias.W2;

@@ -212,6 +212,7 @@ def _load_checkpoint(path, spec: config_lib.ModelSpec) -> Tuple[Dict[str, np.nda
 
 RNG_MODES = ('philox', 'threefry', 'jax')
 plan_steps = native.plan_steps   # (num_steps, steps) -> (row_offset, stride) of a few-step call; ValueError names the divisors
+plan_resample = native.plan_resample   # (start_step, jump, times) -> the steps and jumps of a call with resampling, in order
 
 
 def plan_region(n_frames: int, segment_frames: int, start: int, stop: int):
@@ -319,11 +320,24 @@ class SampleCall:
   start_step: Optional[int] = None
   steps: Optional[int] = None
   sampler: Optional[str] = None
+  resample: Optional[Tuple[int, int]] = None   # (jump, times) of a known-frame call with resampling jumps; None = none
 
 
-def plan_call(keep, keep_mask, strength, steps, sampler, b: int, t: int, n: int, num_steps: int) -> SampleCall:
-  """predict's keep / keep_mask / strength / steps / sampler, checked and planned once.  Pure: no device; every
-  ValueError predict raises for them is raised here."""
+def plan_call(keep, keep_mask, strength, steps, sampler, b: int, t: int, n: int, num_steps: int, resample=None,
+              noise=None) -> SampleCall:
+  """predict's keep / keep_mask / strength / steps / sampler / resample, checked and planned once (noise: only because
+  resample may not be combined with it).  Pure: no device; every ValueError predict raises for them is raised here, but for
+  resample with rng='jax', which predict raises once it knows the call's generator."""
+  if resample is not None:
+    jump, times = native.check_resample(resample)
+    if steps is not None or sampler is not None:
+      raise ValueError('resample= cannot be combined with steps= / sampler= (few-step edits are not built)')
+    if keep is None:
+      raise ValueError('resample= needs keep: resampling jumps harmonise the free frames with known ones')
+    if noise is not None:
+      raise ValueError('resample= cannot be combined with noise=: the draws of the jumps and of the passes behind them are made on the device')
+    call = plan_call(keep, keep_mask, strength, None, None, b, t, n, num_steps)
+    return dataclasses.replace(call, resample=(jump, times))   # (times == 1: the library makes no jump; the same bits)
   if steps is not None or sampler is not None:
     if keep is not None or keep_mask is not None or strength is not None:
       raise ValueError('steps= / sampler= cannot be combined with keep= / keep_mask= / strength= (few-step edits are not built)')
@@ -514,7 +528,8 @@ class InferenceModel(object):
   def predict(self, batch: Mapping[str, Any], seed: Union[int, Sequence[int]] = 0,
               segment: Union[int, Sequence[int]] = 0,
               init_z=None, noise=None, return_torch: bool = False, rng: Optional[str] = None,
-              keep=None, keep_mask=None, strength=None, steps: Optional[int] = None, sampler: Optional[str] = None):
+              keep=None, keep_mask=None, strength=None, steps: Optional[int] = None, sampler: Optional[str] = None,
+              resample=None):
     """Predict one batch of 256-frame segments.
 
     batch: the model features of inference.py:113-136 (NumPy arrays or torch
@@ -550,7 +565,18 @@ class InferenceModel(object):
       max f - 1 from the known mel diffused to that step's noise level (with the call's own initial draw) and costs
       max f steps, not N.  Frames named by keep_mask (optional here) get strength 0.  strength == 1 - keep_mask
       is the keep_mask call, bit for bit.  The network was never trained on known frames; the schedule is per frame
-      (no per-bin map) and the scan makes no resampling jumps.  strength without keep is a ValueError.
+      (no per-bin map); resampling jumps are `resample`'s.  strength without keep is a ValueError.
+    resample (jump, times), with keep (and keep_mask or strength): RePaint resampling jumps in the scan
+      (msd_sample_resample, plan_resample).  The scan goes down `jump` steps, diffuses the state back up those steps --
+      known and free frames alike, one sample of q(z_t | z_s) -- and comes down again, `times` descents per block: the free
+      frames get several chances to condition on the known ones at the same noise level instead of one pass in which the
+      known region is imposed from outside.  A call costs times x its steps plus (times - 1) ceil(steps / jump) jump
+      launches, all enqueued at once.  Every pass behind a jump has a generator key of its own ('philox': segment +
+      (p << 32), so segment < 2^32; 'threefry': fold_in(PRNGKey(seed), N + p - 1)), per row under per-row keys; init_z
+      keeps its meaning for the first pass.  The draws are made on the device: not with noise= nor rng='jax'; not
+      with steps= / sampler=; resample without keep, or a jump or times that is no integer >= 1, is a ValueError too, all
+      raised before any device work.  None and (jump, 1) are the call without it, bit for bit.  On synthetic weights
+      nothing measures whether the result sounds better; the network was still never trained on known frames.
     steps (K) / sampler ('ddpm', 'ddim', 'dpmpp_2m'): a step count and a sampler for THIS call, on the same handle
       (msd_sample_steps) -- a preview in 50 steps, the rendering in all N.  K must divide the model's N (plan_steps; a
       ValueError names the divisors).  The call is the scan of a model configured with num_steps = K -- times (j + 1) / K,
@@ -565,9 +591,12 @@ class InferenceModel(object):
     Returns (decodes float32 [B,T,n] in mel units, scores float32 [B] zeros).
     """
     call = plan_call(keep, keep_mask, strength, steps, sampler, np.shape(batch['encoder_input_tokens'])[0], self.targets_length,
-                     self.audio_codec.n_dims, self.spec.diffusion.sampler.schedule.num_steps)
+                     self.audio_codec.n_dims, self.spec.diffusion.sampler.schedule.num_steps, resample, noise)
     if rng is None:
       rng = self.rng
+    if resample is not None and rng == 'jax':
+      raise ValueError("resample= cannot be combined with rng='jax' (host draws): the draws of the jumps and of the passes "
+                       "behind them are made on the device; use 'philox' or 'threefry'")
     try:
       return self._predict_once(batch, seed, segment, init_z, noise, return_torch, rng, call)
     except native.RangeError:
@@ -752,7 +781,7 @@ class InferenceModel(object):
     return out.to(self.device)
 
   def vary(self, song, segments_tokens: Sequence[np.ndarray], strength, seed: int = 0, always_mask_context: bool = False,
-           rng: Optional[str] = None, return_torch: bool = False):
+           rng: Optional[str] = None, return_torch: bool = False, resample=None):
     """A variation of a rendering: the same song at a chosen distance.
 
     song float32 [1, K * T, n] (mel units; NumPy or a device tensor), K == len(segments_tokens).  strength: a float in
@@ -760,10 +789,13 @@ class InferenceModel(object):
     strength=...), keyed (seed, segment index) as predict_sequence keys it; its context is the NEW previous segment, as
     in predict_sequence.  A segment costs round(max strength * N) steps, not N: it starts part-way down the scan from its
     old frames diffused to that noise level.  strength 1.0 is predict_sequence, bit for bit; frames of strength 0 are
-    the input's, bit for bit.  Returns the new song [1, K * T, n] (NumPy; ``return_torch``: the device tensor)."""
+    the input's, bit for bit.  resample = (jump, times): predict's, for every segment.  Returns the new song
+    [1, K * T, n] (NumPy; ``return_torch``: the device tensor)."""
     torch = self._torch
     t = self.targets_length
     self._check_song(song, segments_tokens)
+    if resample is not None:
+      native.check_resample(resample)
     frames = np.shape(song)[1]
     s = np.asarray(_to_numpy(strength), np.float64)
     if s.shape not in ((), (frames,), (1, frames)):
@@ -771,13 +803,14 @@ class InferenceModel(object):
     s = np.broadcast_to(s.reshape(-1) if s.ndim else s, (frames,))
     new = _to_device(torch, song, self.device, torch.float32).clone()
     for k, toks in enumerate(segments_tokens):
-      out = self._edit_segment(new, k, toks, always_mask_context, seed, rng, strength=s[None, k * t:(k + 1) * t])
+      out = self._edit_segment(new, k, toks, always_mask_context, seed, rng, strength=s[None, k * t:(k + 1) * t],
+                               **({} if resample is None else {'resample': resample}))
       new[:, k * t:(k + 1) * t] = out[:1]
     return new if return_torch else new.cpu().numpy()
 
   def regenerate(self, song, segments_tokens: Sequence[np.ndarray], start_frame: int, stop_frame: int, seed: int = 0,
                  always_mask_context: bool = False, rng: Optional[str] = None, return_torch: bool = False,
-                 blend_frames: int = 0):
+                 blend_frames: int = 0, resample=None):
     """Sample the frames [start_frame, stop_frame) of a song again and keep the rest.
 
     song float32 [1, K * T, n] (mel units; NumPy or a device tensor), K == len(segments_tokens), the tokens of ALL its
@@ -793,8 +826,12 @@ class InferenceModel(object):
     blend_frames = F > 0 softens the seams: the F frames on either side of the region are released to the sampler for
     the last part of the scan only -- strength 1 - d / (F + 1) at distance d (region_strength; predict(strength=)) --,
     across segment boundaries; segments that only this ramp touches are sampled too.  Frames beyond the ramp, and ramp
-    frames whose share rounds to no step at all, are the input's bit for bit.  0 is the hard edge above, unchanged."""
+    frames whose share rounds to no step at all, are the input's bit for bit.  0 is the hard edge above, unchanged.
+
+    resample = (jump, times): predict's resampling jumps (RePaint) for every segment that is sampled; None = none."""
     torch = self._torch
+    if resample is not None:
+      native.check_resample(resample)
     t, n = self.targets_length, self.audio_codec.n_dims
     if len(np.shape(song)) != 3 or np.shape(song)[0] != 1 or np.shape(song)[2] != n:
       raise ValueError('song must be [1, frames, %d]: got %r' % (n, tuple(np.shape(song))))
@@ -809,7 +846,8 @@ class InferenceModel(object):
     new = _to_device(torch, song, self.device, torch.float32).clone()
     for k, row in plan:
       out = self._edit_segment(new, k, segments_tokens[k], always_mask_context, seed, rng,
-                               **({'strength': row[None]} if soft else {'keep_mask': row[None]}))
+                               **({'strength': row[None]} if soft else {'keep_mask': row[None]}),
+                               **({} if resample is None else {'resample': resample}))
       free = torch.as_tensor(row > 0.0 if soft else row == 0, device=self.device)
       new[0, k * t:(k + 1) * t][free] = out[0][free]   # (the other frames of `out` are the song's already)
     return new if return_torch else new.cpu().numpy()

@@ -75,11 +75,54 @@ EXPORTED_SYMBOLS = (
     # (appended to ABI 7) one attention launch the way the decoder fills it
     'msd_op_attention_launch',
     # (appended to ABI 7) a launch with a weight target in either carrier form; how a target is dealt over the waves
-    'msd_op_gemm_site_carrier', 'msd_op_attention_launch_carrier', 'msd_op_touch_deal', 'msd_set_touch_carrier')
+    'msd_op_gemm_site_carrier', 'msd_op_attention_launch_carrier', 'msd_op_touch_deal', 'msd_set_touch_carrier',
+    # (appended to ABI 7) known-frame edits with resampling jumps (RePaint) in the sampler scan
+    'msd_sample_resample', 'msd_op_renoise')
 
 
 def divisors(n: int):
   return [k for k in range(1, n + 1) if n % k == 0]
+
+
+def _check_ints(*named):
+  """(name, value, lowest) triples: a ValueError unless every value is an integer (no bool) >= its lowest."""
+  for name, v, lo in named:
+    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < lo:
+      raise ValueError('%s must be an integer >= %d: %r' % (name, lo, v))
+
+
+def plan_resample(start_step: int, jump: int, times: int):
+  """The schedule of a call with resampling jumps (RePaint; msd_sample_resample) as a list of operations, in order:
+  ('steps', top, bottom) -- the steps with scan indices top - 1 .. bottom -- and ('jump', bottom, top, p) -- the state
+  diffused from level `bottom` back to level `top`, the call's p-th jump (p = 1, 2, ...; everything behind it is pass p).
+  A level is the number of steps still to run; the call starts at level S = start_step + 1.  Block k has top S - k jump and
+  bottom max(top - jump, 0); every block is descended `times` times with a jump after each descent but the last.
+  times * S steps, (times - 1) ceil(S / jump) jumps; times == 1 is the plain descent whatever jump.  No device needed.
+  jump and times must be integers >= 1 and start_step an integer >= -1: anything else is a ValueError."""
+  _check_ints(('start_step', start_step, -1), ('jump', jump, 1), ('times', times, 1))
+  level, jump, times = int(start_step) + 1, int(jump), int(times)
+  ops, p = [], 0
+  while level > 0:
+    bottom = max(level - jump, 0)
+    for r in range(times):
+      ops.append(('steps', level, bottom))
+      if r < times - 1:
+        p += 1
+        ops.append(('jump', bottom, level, p))
+    level = bottom
+  return ops
+
+
+def check_resample(resample):
+  """resample=(jump, times) of sample / predict -> (int jump, int times); a ValueError unless it is a pair of integers >= 1."""
+  try:
+    jump, times = resample
+  except (TypeError, ValueError):
+    raise ValueError('resample must be a (jump, times) pair: %r' % (resample,))
+  _check_ints(('jump', jump, 1), ('times', times, 1))
+  if jump > 0x7FFFFFFF or times > 0x7FFFFFFF:   # (the entry point takes C ints; a jump beyond the call's steps is one block)
+    raise ValueError('jump and times must fit a 32-bit int: %r' % (resample,))
+  return int(jump), int(times)
 
 
 def plan_steps(num_steps: int, steps: int):
@@ -261,6 +304,9 @@ def load(planes: str = 'f16') -> ctypes.CDLL:
   if 'msd_sample_steps' in present:   # (appended to ABI 7)
     lib.msd_sample_steps.argtypes = [vp, i32, i32, i32, c.POINTER(u64), c.POINTER(u64), vp, vp, i32, i32, vp, vp]
     lib.msd_op_sampler_step_multistep.argtypes = [c.POINTER(MsdConfig), i32, vp, vp, vp, vp, i32, vp, i64, vp]
+  if 'msd_sample_resample' in present:   # (appended to ABI 7)
+    lib.msd_sample_resample.argtypes = [vp, i32, i32, i32, c.POINTER(u64), c.POINTER(u64), vp, vp, vp, i32, i32, i32, vp, vp]
+    lib.msd_op_renoise.argtypes = [c.POINTER(MsdConfig), i32, i32, vp, vp, vp, vp, i64, vp]
   if 'msd_fill_normal_threefry' in present:
     lib.msd_fill_normal_threefry.argtypes = [u64, i64, vp, i64, vp]
   if 'msd_op_threefry' in present:
@@ -415,7 +461,8 @@ class NativeModel:
 
   def sample(self, batch: int, out, seed: int = 0, stream_id: int = 0, init_z=None,
              noise=None, stream: int = 0, rng: str = 'philox', keep=None, keep_mask=None, release=None,
-             start_step: Optional[int] = None, steps: Optional[int] = None, sampler: Optional[str] = None):
+             start_step: Optional[int] = None, steps: Optional[int] = None, sampler: Optional[str] = None,
+             resample=None):
     """rng: the generator of the draws that are not given -- 'philox' (the library's own, keyed by seed and stream_id)
     or 'threefry' (the reference's jax.random draws for PRNGKey(seed), made on the device; stream_id is ignored).
 
@@ -434,8 +481,27 @@ class NativeModel:
 
     steps (K, a divisor of the handle's num_steps; None = all of them) / sampler ('ddpm', 'ddim', 'dpmpp_2m'; None = the
     handle's): a step count and a sampler for THIS call (msd_sample_steps); noise is then [K, batch, T, n].  Not with
-    keep / release."""
+    keep / release.
+
+    resample (jump, times), with keep: resampling jumps (RePaint; msd_sample_resample, plan_resample) -- every block of
+    `jump` steps is descended `times` times, the state diffused back up in between under a key of the pass's own.  The
+    extra draws are made on the device: not with noise, nor with steps / sampler.  keep_mask is taken as release words
+    (1 = known throughout).  times == 1 makes no jump: msd_sample_resample then returns the bits of the call without
+    resample, like None."""
     few, edit = steps is not None or sampler is not None, release is not None
+    if resample is not None:
+      jump, times = check_resample(resample)
+      if keep is None:
+        raise ValueError('resample needs keep: resampling jumps harmonise free frames with known ones')
+      if few:
+        raise ValueError('resample cannot be combined with steps / sampler')
+      if noise is not None:
+        raise ValueError('resample cannot be combined with noise: the jumps\' and the later passes\' draws are made on the device')
+      if not edit:   # msd_sample_keep's flags as release words (host): any non-zero flag = known throughout = 1
+        if keep_mask is None:
+          raise ValueError('keep and keep_mask go together')
+        flags = keep_mask.detach().cpu().numpy() if hasattr(keep_mask, 'detach') else np.asarray(keep_mask)
+        release, keep_mask, edit = np.ascontiguousarray(flags != 0, dtype=np.int32), None, True
     # (1) what the call may not combine or name
     if rng not in RNGS:
       raise ValueError('rng must be one of %s: %r' % (sorted(RNGS), rng))
@@ -464,6 +530,10 @@ class NativeModel:
     if few:
       name, rc = 'msd_sample_steps', lib.msd_sample_steps(h, batch, kind, int(per_row), *keys, *draws, int(steps or 0),
                                                           -1 if sampler is None else SAMPLERS[sampler], *tail)
+    elif edit and resample is not None:
+      start = self.cfg.num_steps - 1 if start_step is None else int(start_step)
+      name, rc = 'msd_sample_resample', lib.msd_sample_resample(h, batch, kind, int(per_row), *keys, _ptr(init_z), _ptr(keep),
+                                                                _ptr(release), start, jump, times, *tail)
     elif edit:
       start = self.cfg.num_steps - 1 if start_step is None else int(start_step)
       name, rc = 'msd_sample_edit', lib.msd_sample_edit(h, batch, kind, int(per_row), *keys, *draws, _ptr(keep), _ptr(release), start, *tail)
@@ -760,6 +830,18 @@ def op_diffuse_to_step(cfg: MsdConfig, step_index: int, mel, eps, z_out, z_plane
     raise ValueError('mel, eps and the three outputs must have the same element count')
   _op_check(lib.msd_op_diffuse_to_step(ctypes.byref(cfg), step_index, _ptr(mel), _ptr(eps), _ptr(z_out), _ptr(z_planes_out),
                                        _ptr(xk_out), mel.numel(), stream), 'msd_op_diffuse_to_step')
+
+
+def op_renoise(cfg: MsdConfig, from_level: int, to_level: int, z, eps, z_out, z_planes_out, stream: int = 0):
+  """The resampling jump of msd_sample_resample on its own (msd_op_renoise): z_out = fmaf(b, eps, a * z) from level
+  from_level up to level to_level (a = alpha_to / alpha_from, b = sqrt(1 - a^2)) and z_out's operand planes of
+  cfg.precision merged back to float32.  float32 device tensors of equal numel (% 4 == 0)."""
+  lib = load(_PLANES_OF[cfg.precision])
+  cfg.struct_size = config_struct_size(lib)
+  if not (z.numel() == eps.numel() == z_out.numel() == z_planes_out.numel()):
+    raise ValueError('z, eps and the two outputs must have the same element count')
+  _op_check(lib.msd_op_renoise(ctypes.byref(cfg), from_level, to_level, _ptr(z), _ptr(eps), _ptr(z_out), _ptr(z_planes_out),
+                               z.numel(), stream), 'msd_op_renoise')
 
 
 def op_residual_norm_gemm(folded: bool, x_in, a, w1, gamma, film_scale, film_bias, w2, x_out, h_out,

@@ -9,6 +9,7 @@ beam/evaluation.py:161-223) on the MI355X path.
       [--wav song.wav [--vocoder-iters 32]] [--context-audio earlier.wav]
       [--regenerate START:STOP [--blend FRAMES] (--edit-mel old_mel.npy | --edit-audio old.wav)]
       [--vary STRENGTH (--edit-mel old_mel.npy | --edit-audio old.wav)]
+      [--resample JUMP:TIMES]   (with --regenerate or --vary)
 
 --wav writes 16-bit PCM mono at 16 kHz from the device vocoder: Griffin-Lim over the codec's STFT, a stand-in for the
 reference's SoundStream decoder (which is not built).  --context-audio continues a recording: its last 256 frames are
@@ -28,6 +29,11 @@ of the scan only, less the farther they lie from the region (InferenceModel.rege
 --vary STRENGTH (0 .. 1) renders a variation of the old rendering: every segment starts part-way down the scan from its old
 frames at the matching noise level and runs round(STRENGTH * steps) steps -- 1 is a fresh rendering, 0 the old one
 (InferenceModel.vary).  An SDEdit-style restart: the network was never trained on known frames.
+
+--resample JUMP:TIMES (with --regenerate or --vary) adds RePaint resampling jumps to the edit: the scan goes down JUMP
+steps, diffuses the state back up and comes down again, TIMES descents per block, so that the sampled frames get several
+chances to fit the kept ones at each noise level; a segment costs TIMES x its steps (InferenceModel.predict(resample=)).
+Not with --rng jax (the extra draws are made on the device).
 
 --steps K renders every segment in K steps (K divides --num-steps; the model keeps its num-steps tables, so the same
 process could render in all of them next) and --sampler names the sampler of the run: dpmpp_2m is the second-order
@@ -85,6 +91,8 @@ def main(argv=None) -> int:
                   help='with --regenerate: release this many frames on either side of the region part-way (soft seams)')
   ap.add_argument('--vary', type=float, default=None, metavar='STRENGTH',
                   help='a variation of --edit-mel / --edit-audio at this distance, 0 .. 1 (1 = a fresh rendering)')
+  ap.add_argument('--resample', default=None, metavar='JUMP:TIMES',
+                  help='with --regenerate / --vary: RePaint resampling jumps -- every block of JUMP steps is descended TIMES times')
   ap.add_argument('--edit-mel', default=None, metavar='OLD.npy', help='the old rendering as mel frames [frames, 128]')
   ap.add_argument('--edit-audio', default=None, metavar='OLD.wav',
                   help='the old rendering as a 16 kHz PCM recording (encoded on the device)')
@@ -109,6 +117,16 @@ def main(argv=None) -> int:
     ap.error('--blend FRAMES (>= 0) goes with --regenerate')
   if (args.steps is not None or args.sampler) and (args.regenerate or args.vary is not None):
     ap.error('--steps / --sampler do not go with --regenerate / --vary (few-step edits are not built)')
+
+  if args.resample is not None:
+    if not (args.regenerate or args.vary is not None):
+      ap.error('--resample JUMP:TIMES goes with --regenerate or --vary: resampling jumps fit sampled frames to known ones')
+    if args.rng == 'jax':
+      ap.error("--resample does not go with --rng jax: the jumps' draws are made on the device (philox or threefry)")
+    try:
+      args.resample = resample_pair(args.resample)
+    except ValueError as e:
+      ap.error(str(e))
 
   import msd_amd
   from msd_amd.frontend import midi_io, tokenizer
@@ -175,6 +193,10 @@ def main(argv=None) -> int:
         part = (words[0] > 1)
         print('  blend %d, segment %d: %d frames released part-way, %d of %d steps'
               % (args.blend, k, int(part.sum()), start_step + 1, steps))
+    if args.resample is not None:
+      run = steps if args.vary is None else vary_steps   # (plan_resample's counts, without the list)
+      jump, times = args.resample
+      print('resample %d:%d: %d steps and %d jumps per full segment' % (jump, times, times * run, (times - 1) * -(-run // jump)))
     edit = (old, start, stop)
   if args.dry_run:
     return 0
@@ -220,6 +242,17 @@ def _write_outputs(args, model, mel_dev, mel):
              '' if gain == 1.0 else ' (peak-normalised, gain %.3f)' % gain), file=sys.stderr)
 
 
+def resample_pair(text: str):
+  """'JUMP:TIMES' -> (jump, times), both integers >= 1; anything else is a ValueError."""
+  try:
+    jump, times = (int(v) for v in text.split(':'))
+  except ValueError:
+    raise ValueError('--resample wants JUMP:TIMES, two integers: %r' % (text,))
+  if jump < 1 or times < 1:
+    raise ValueError('--resample wants JUMP >= 1 and TIMES >= 1: %r' % (text,))
+  return jump, times
+
+
 def region_frames(text: str, frame_rate: float):
   """'START:STOP' in seconds -> (start_frame, stop_frame), rounded OUTWARD to whole frames of 1 / frame_rate seconds
   (a time that is a whole frame up to 1e-6 frames is that frame)."""
@@ -250,11 +283,13 @@ def _regenerate(args, model, segments, edit, ns, cfg) -> int:
     song = model.vocoder.encode(np.asarray(old, np.float32)[None], return_torch=True)
   song = pad_to_segments(song, len(segments) * cfg.segment_frames, model.audio_codec.pad_value)
   t0 = time.perf_counter()
+  kw = {} if getattr(args, 'resample', None) is None else dict(resample=tuple(args.resample))
   if args.vary is not None:
     mel_dev = model.vary(song, segments, args.vary, seed=args.seed, always_mask_context=args.always_mask_context,
-                         rng=args.rng, return_torch=True)
+                         rng=args.rng, return_torch=True, **kw)
   else:
-    kw = dict(blend_frames=args.blend) if args.blend else {}
+    if args.blend:
+      kw['blend_frames'] = args.blend
     mel_dev = model.regenerate(song, segments, start, stop, seed=args.seed, always_mask_context=args.always_mask_context,
                                rng=args.rng, return_torch=True, **kw)
   frames = int(np.ceil(ns.total_time * cfg.frame_rate))
