@@ -115,7 +115,7 @@ constexpr int attention_smem() { return attention_work_smem<NP, NS, QB>() + (QB 
 //                             its two-stage ring (2.5 - 3 us per stage, whatever the rows), so 12 x 4 x songs blocks in 1.5
 //                             rounds (8 songs: 384) cost 1.5 block lifetimes where 192 blocks of 128 rows cost one; no
 //                             prefetch wave fits beside 16 waves -- the host gives the launch's weight target to a neighbour
-__host__ __device__ inline int attention_query_blocks(int blocks64, int q_rows_per_seg, int np) {
+__host__ __device__ constexpr int attention_query_blocks(int blocks64, int q_rows_per_seg, int np) {
   if (blocks64 < 128) return 1;
   if (np == 2 && blocks64 > 256 && q_rows_per_seg % 128 == 0) return 4;
   return 2;
@@ -733,44 +733,77 @@ __global__ void __launch_bounds__(256) attention_merge_kernel(AttnParams p, int 
   MSD_TS_END(6, blockIdx.x, gridDim.x)
 }
 
-template <int NP, int NS, int QB, int QP>
-inline hipError_t attention_prepare_one() {
-  constexpr int smem = attention_smem<NP, NS, QB, (QP & 4) != 0>();
-  if (smem < 64 * 1024) return hipSuccess;
-  const hipError_t a = hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<NP, NS, QB, kPfNone, QP>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-  hipError_t b = hipSuccess;
-  if constexpr (QB < 4)
-    b = hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<NP, NS, QB, NP == 2 ? 1 : 0, QP>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-  if constexpr (QB < 4 && NP == 2) {   // the touch-block forms: without and with a prefetch wave (its K / V^T touch-ahead)
-    const hipError_t c = hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<NP, NS, QB, kPfNone, QP, true>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    const hipError_t d = hipFuncSetAttribute(reinterpret_cast<const void*>(attention_kernel<NP, NS, QB, 1, QP, true>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, smem);
-    if (b == hipSuccess) b = c != hipSuccess ? c : d;
-  }
-  return a != hipSuccess ? a : b;
-}
-
 // NS: LDS ring depth (NP = 2: one stage is 64 KiB -> NS = 2; NP = 1: 32 KiB -> NS = 3)
 template <int NP>
 constexpr int attention_ns() { return (NP == 2) ? 2 : 3; }
 
-template <int NP, int NS = attention_ns<NP>()>
-inline hipError_t attention_prepare() {
-  hipError_t e = hipSuccess, r;
-#define MSD_ATT_PREP(QB_, QP_) if ((r = attention_prepare_one<NP, NS, QB_, QP_>()) != hipSuccess) e = r;
-  MSD_ATT_PREP(1, 0) MSD_ATT_PREP(2, 0)
-  if constexpr (NP == 2) {
-    MSD_ATT_PREP(1, 1) MSD_ATT_PREP(2, 1) MSD_ATT_PREP(1, 2) MSD_ATT_PREP(2, 2) MSD_ATT_PREP(1, 3) MSD_ATT_PREP(2, 3)
-    MSD_ATT_PREP(4, 0) MSD_ATT_PREP(4, 1) MSD_ATT_PREP(4, 2) MSD_ATT_PREP(4, 3)
-    MSD_ATT_PREP(1, 4) MSD_ATT_PREP(2, 4) MSD_ATT_PREP(1, 5) MSD_ATT_PREP(2, 5) MSD_ATT_PREP(1, 6) MSD_ATT_PREP(2, 6)
-    MSD_ATT_PREP(1, 7) MSD_ATT_PREP(2, 7)
-  }
-#undef MSD_ATT_PREP
-  return e;
+// ---- the instance table -----------------------------------------------------------------------------------------
+// The ONLY place that names an instance of attention_kernel: (QB query blocks per workgroup, QP query-side switches), in
+// up to four forms -- plain, with a prefetch wave, and each of the two on a grid with touch blocks behind it.
+// attention_prepare opts every form of every entry into its dynamic LDS, launch_attention finds the entry of the
+// (qb, qp) its rule chose, and the static_assert below holds the list to exactly what that rule can reach.  The order of
+// the list is the order the kernels stand in the code object (within an entry: plain, wave, touch blocks, touch blocks +
+// wave): set_func_attrs (msd_api.hip) is the first function to name them, through attention_prepare.  Placement alone
+// moves a segment by 0.5 - 1 % (keep_frames_tail.h): a new entry goes where its kernels should land, and the device
+// listing is compared with the one before.
+template <int QB_, int QP_>
+struct AttnInst {
+  static constexpr int QB = QB_, QP = QP_;
+  static constexpr bool QS = (QP_ & 4) != 0;   // un-normalised queries: the block's rows of q_ssq are staged in LDS too
+  // the prefetch-wave and touch-block forms: two planes only, and no wave fits beside the 16 compute waves of QB = 4
+  template <int NP> static constexpr bool has_forms() { return NP == 2 && QB_ < 4; }
+  template <int NP> static constexpr int smem() { return attention_smem<NP, attention_ns<NP>(), QB_, QS>(); }
+  template <int NP, bool WAVE, bool TB> static constexpr auto kernel() { return attention_kernel<NP, attention_ns<NP>(), QB_, WAVE ? 1 : kPfNone, QP_, TB>; }
+};
+template <int NP>
+using AttnInstances = decltype(
+    List<AttnInst<1, 0>, AttnInst<2, 0>>{} +
+    list_if<NP == 2, List<AttnInst<1, 1>, AttnInst<2, 1>, AttnInst<1, 2>, AttnInst<2, 2>, AttnInst<1, 3>, AttnInst<2, 3>,
+                          AttnInst<4, 0>, AttnInst<4, 1>, AttnInst<4, 2>, AttnInst<4, 3>,
+                          AttnInst<1, 4>, AttnInst<2, 4>, AttnInst<1, 5>, AttnInst<2, 5>, AttnInst<1, 6>, AttnInst<2, 6>,
+                          AttnInst<1, 7>, AttnInst<2, 7>>>{});
+
+// the 64-row blocks attention_query_blocks sees: one round of the chip at most, unless the launch may run on 128-row blocks
+constexpr int attention_blocks_seen(int blocks64, bool allow_qb4, bool qs) { return (allow_qb4 && !qs) ? blocks64 : (blocks64 > 256 ? 256 : blocks64); }
+// can launch_attention<NP> ask for (qb, qp)?  qp: what it forms (NP = 2: two plane bits | 4 with q_ssq; NP = 1: 0); qb:
+// what attention_query_blocks returns for some launch of that qp (every block count up to two rounds, both row parities)
+template <int NP>
+constexpr bool attention_reachable(int qb, int qp) {
+  for (int blocks64 = 1; blocks64 <= 512 && qp < (NP == 2 ? 8 : 1); ++blocks64)
+    for (int rows : {64, 128})
+      for (bool allow : {false, true})
+        if (attention_query_blocks(attention_blocks_seen(blocks64, allow, (qp & 4) != 0), rows, NP) == qb) return true;
+  return false;
 }
+template <int NP, class... I>
+constexpr bool attention_table_exact(List<I...>) {
+  for (int qb = 0; qb <= 4; ++qb)
+    for (int qp = 0; qp < 8; ++qp)
+      if (((I::QB == qb && I::QP == qp ? 1 : 0) + ...) != (attention_reachable<NP>(qb, qp) ? 1 : 0)) return false;
+  return true;
+}
+static_assert(attention_table_exact<1>(AttnInstances<1>{}) && attention_table_exact<2>(AttnInstances<2>{}),
+              "AttnInstances must list every (qb, qp) launch_attention can reach once, and nothing it cannot");
+
+// LDS bytes of the table's instances of `qb` query blocks, with (`qs`) or without un-normalised queries
+template <int NP, class... I>
+constexpr int attention_inst_smem(List<I...>, int qb, bool qs) {
+  int smem = 0;
+  ((I::QB == qb && I::QS == qs ? smem = I::template smem<NP>() : 0), ...);
+  return smem;
+}
+
+template <int NP, class I>
+inline hipError_t attention_prepare_one() {
+  const auto opt_in = [](auto k) { return hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, I::template smem<NP>()); };
+  if constexpr (I::template has_forms<NP>())
+    return first_error(opt_in(I::template kernel<NP, false, false>()), opt_in(I::template kernel<NP, true, false>()),
+                       opt_in(I::template kernel<NP, false, true>()), opt_in(I::template kernel<NP, true, true>()));
+  else return opt_in(I::template kernel<NP, false, false>());
+}
+
+template <int NP, class... I>
+inline hipError_t attention_prepare(List<I...>) { return first_error(attention_prepare_one<NP, I>()...); }
 
 // log2 of the key split a request for `ksplit` runs as: the largest power of two <= ksplit
 inline int attention_ksplit_log2(int ksplit) {
@@ -795,13 +828,12 @@ struct AttnLaunchShape { int qb; bool prefetch, pf_wave, touch_ahead; int touch_
 inline AttnLaunchShape attention_launch_shape(const AttnParams& p, int heads, int segs, int np, bool qs) {
   const int blocks64 = heads * (p.q_rows_per_seg / 64) * p.ksplit * segs;
   AttnLaunchShape s;
-  s.qb = attention_query_blocks((p.allow_qb4 && !qs) ? blocks64 : (blocks64 > 256 ? 256 : blocks64), p.q_rows_per_seg, np);
+  s.qb = attention_query_blocks(attention_blocks_seen(blocks64, p.allow_qb4 != 0, qs), p.q_rows_per_seg, np);
   s.prefetch = np == 2 && p.pf.active() && s.qb < 4;
   s.touch_y = 0;
   if (s.prefetch && p.pf.touch_blocks > 0) {   // whole rows of `heads` x `segs` blocks within one round of the chip
     const int grid = heads * (p.q_rows_per_seg / (32 * s.qb)) * p.ksplit * segs;
-    const int smem = s.qb == 1 ? (qs ? attention_smem<2, 2, 1, true>() : attention_smem<2, 2, 1, false>())
-                               : (qs ? attention_smem<2, 2, 2, true>() : attention_smem<2, 2, 2, false>());
+    const int smem = attention_inst_smem<2>(AttnInstances<2>{}, s.qb, qs);   // (a launch that prefetches has two planes)
     s.touch_y = touch_blocks_fit(p.pf.touch_blocks, grid, smem) / (heads * segs);
   }
   s.pf_wave = s.prefetch && (s.touch_y == 0 || p.touch_ahead > 0);
@@ -809,73 +841,39 @@ inline AttnLaunchShape attention_launch_shape(const AttnParams& p, int heads, in
   return s;
 }
 
-template <int NP, int QP>
-inline void launch_attention_qp(const AttnParams& p_in, int heads, int segs, hipStream_t stream) {
-  constexpr int NS = attention_ns<NP>();
-  AttnParams p = p_in;
-  constexpr bool QS = (QP & 4) != 0;
-  constexpr int smem1 = attention_smem<NP, NS, 1, QS>(), smem2 = attention_smem<NP, NS, 2, QS>();
-  // one instantiation per prefetch kind (gemm_h16.h)
-  constexpr int PFW = NP == 2 ? 1 : 0;   // attention launches carry at most one target
-  const AttnLaunchShape shape = attention_launch_shape(p, heads, segs, NP, QS);
-  const bool pfw = shape.prefetch;
-  const dim3 g1(heads, (p.q_rows_per_seg / 32) * p.ksplit, segs), g2(heads, (p.q_rows_per_seg / 64) * p.ksplit, segs);
-  const int qb = shape.qb;
-  if constexpr (NP == 2 && !QS) {
-    if (qb == 4) {   // (no prefetch wave: the caller moved the launch's weight target elsewhere -- msd_api.hip)
-      const dim3 g4(heads, (p.q_rows_per_seg / 128) * p.ksplit, segs);
-      hipLaunchKernelGGL((attention_kernel<NP, NS, 4, kPfNone, QP>), g4, dim3(4 * kAttKG * 64), (attention_smem<NP, NS, 4>()), stream, p);
-      return;
+// Launches p on instance I in the form `shape` asks for
+template <int NP, class I>
+inline void launch_attention_inst(const AttnLaunchShape& shape, AttnParams p, int heads, int segs, hipStream_t stream) {
+  dim3 grid(heads, (p.q_rows_per_seg / (32 * I::QB)) * p.ksplit, segs);
+  const auto launch = [&](auto k) { hipLaunchKernelGGL(k, grid, dim3(I::QB * kAttKG * 64 + (shape.pf_wave ? 64 : 0)), (I::template smem<NP>()), stream, p); };
+  if constexpr (I::template has_forms<NP>()) {
+    if (shape.touch_y > 0) {   // the touch-block form: rows of touch blocks behind the compute grid's y extent
+      p.grid_y = (int)grid.y;
+      grid.y += shape.touch_y;
+      return shape.pf_wave ? launch(I::template kernel<NP, true, true>()) : launch(I::template kernel<NP, false, true>());
     }
+    if (shape.pf_wave) return launch(I::template kernel<NP, true, false>());
   }
-  if constexpr (NP == 2) {
-    if (shape.touch_y > 0) {   // the touch-block form
-      const dim3 gc = qb == 1 ? g1 : g2;
-      const dim3 gt(gc.x, gc.y + shape.touch_y, gc.z);
-      const unsigned wave = shape.pf_wave ? 64 : 0;
-      p.grid_y = (int)gc.y;
-      if (qb == 1) {
-        if (wave) hipLaunchKernelGGL((attention_kernel<NP, NS, 1, 1, QP, true>), gt, dim3(kAttKG * 64 + wave), smem1, stream, p);
-        else hipLaunchKernelGGL((attention_kernel<NP, NS, 1, kPfNone, QP, true>), gt, dim3(kAttKG * 64), smem1, stream, p);
-      } else {
-        if (wave) hipLaunchKernelGGL((attention_kernel<NP, NS, 2, 1, QP, true>), gt, dim3(2 * kAttKG * 64 + wave), smem2, stream, p);
-        else hipLaunchKernelGGL((attention_kernel<NP, NS, 2, kPfNone, QP, true>), gt, dim3(2 * kAttKG * 64), smem2, stream, p);
-      }
-      return;
-    }
-  }
-  if (qb == 1) {
-    if (pfw) hipLaunchKernelGGL((attention_kernel<NP, NS, 1, PFW, QP>), g1, dim3(kAttKG * 64 + (PFW ? 64 : 0)), smem1, stream, p);
-    else hipLaunchKernelGGL((attention_kernel<NP, NS, 1, kPfNone, QP>), g1, dim3(kAttKG * 64), smem1, stream, p);
-  } else {
-    if (pfw) hipLaunchKernelGGL((attention_kernel<NP, NS, 2, PFW, QP>), g2, dim3(2 * kAttKG * 64 + (PFW ? 64 : 0)), smem2, stream, p);
-    else hipLaunchKernelGGL((attention_kernel<NP, NS, 2, kPfNone, QP>), g2, dim3(2 * kAttKG * 64), smem2, stream, p);
-  }
+  launch(I::template kernel<NP, false, false>());
+}
+// ... on the table's entry of (shape.qb, qp); false: the table has none
+template <int NP, class... I>
+inline bool launch_attention_on(List<I...>, int qp, const AttnLaunchShape& shape, const AttnParams& p, int heads, int segs, hipStream_t stream) {
+  return ((I::QB == shape.qb && I::QP == qp && (launch_attention_inst<NP, I>(shape, p, heads, segs, stream), true)) || ...);
 }
 
 template <int NP>
 inline hipError_t launch_attention(const AttnParams& p_in, int heads, int segs, hipStream_t stream) {
-  constexpr int NS = attention_ns<NP>();
-  static const hipError_t attr = attention_prepare<NP, NS>();
+  static const hipError_t attr = attention_prepare<NP>(AttnInstances<NP>{});
   if (attr != hipSuccess) return attr;
   AttnParams p = p_in;
   p.ksplit_log2 = attention_ksplit_log2(p.ksplit);
   p.ksplit = 1 << p.ksplit_log2;   // a power of two (a request for 3 runs as 2): the kernel shifts, it never divides
-  if constexpr (NP == 2) {
-    if (p.q_ssq != nullptr && (p.q_tiles <= 0 || p.q_tiles > kAuxMaxTiles || p.q_tiles % 4)) return hipErrorInvalidValue;
-    switch ((p.qp & 3) | (p.q_ssq != nullptr ? 4 : 0)) {
-      case 1: launch_attention_qp<NP, 1>(p, heads, segs, stream); break;
-      case 2: launch_attention_qp<NP, 2>(p, heads, segs, stream); break;
-      case 3: launch_attention_qp<NP, 3>(p, heads, segs, stream); break;
-      case 4: launch_attention_qp<NP, 4>(p, heads, segs, stream); break;
-      case 5: launch_attention_qp<NP, 5>(p, heads, segs, stream); break;
-      case 6: launch_attention_qp<NP, 6>(p, heads, segs, stream); break;
-      case 7: launch_attention_qp<NP, 7>(p, heads, segs, stream); break;
-      default: launch_attention_qp<NP, 0>(p, heads, segs, stream); break;
-    }
-  } else {
-    launch_attention_qp<NP, 0>(p, heads, segs, stream);
-  }
+  const bool qs = NP == 2 && p.q_ssq != nullptr;
+  if (qs && (p.q_tiles <= 0 || p.q_tiles > kAuxMaxTiles || p.q_tiles % 4)) return hipErrorInvalidValue;
+  const int qp = NP == 2 ? (p.qp & 3) | (qs ? 4 : 0) : 0;
+  if (!launch_attention_on<NP>(AttnInstances<NP>{}, qp, attention_launch_shape(p, heads, segs, NP, qs), p, heads, segs, stream))
+    return hipErrorInvalidValue;
   if (p.ksplit > 1 && p.tickets == nullptr) {
     const int items = p.total_rows * heads * 8;
     const dim3 mg((items + 255) / 256), mb(256);

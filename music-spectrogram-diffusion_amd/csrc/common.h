@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 // (The measured-and-rejected kernels of rounds 2 - 4 and their environment switches are frozen, with the sources they
 // were built from, under tools/ubench/exp/; nothing here depends on that directory.)
@@ -145,5 +146,13 @@ __device__ __forceinline__ float gelu_tanh(float x) {
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.4426950408889634f); }
 
 __device__ __forceinline__ float swishf(float x) { return x / (1.0f + __expf(-x)); }
+
+// Host side: a list of types, what the kernel-instance tables are written as (msd_api.hip: the GEMM tile table;
+// attention.h: the attention instances), and the first error of a run of prepare calls
+template <class... T> struct List {};
+template <class... A, class... B> constexpr List<A..., B...> operator+(List<A...>, List<B...>) { return {}; }
+template <bool C, class L> using list_if = std::conditional_t<C, L, List<>>;
+template <class X, class... T> constexpr bool in_list(List<T...>) { return (std::is_same<X, T>::value || ...); }
+template <class... E> hipError_t first_error(E... e) { hipError_t r = hipSuccess; ((r = r != hipSuccess ? r : e), ...); return r; }
 
 }  // namespace msd

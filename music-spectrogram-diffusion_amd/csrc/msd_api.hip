@@ -554,12 +554,7 @@ TileShape pick_tile(int M, int N, int align, bool wide48 = false, int K = 0) {
 // ---- the tile table ---------------------------------------------------------------------------------------------
 // The ONLY place that names a GEMM tile (BM x BN, ring depth NS).  Dispatch (gemm, gemm_dual) walks a list in order and
 // takes the entry of the shape pick_tile chose, the LAST entry otherwise; prepare_gemms opts every entry of every launch
-// site into its dynamic LDS.  A new tile is one line here (and a pick_tile rule that returns its shape).
-template <class... T> struct List {};
-template <class... A, class... B> constexpr List<A..., B...> operator+(List<A...>, List<B...>) { return {}; }
-template <bool C, class L> using list_if = std::conditional_t<C, L, List<>>;
-template <class X, class... T> constexpr bool in_list(List<T...>) { return (std::is_same<X, T>::value || ...); }
-
+// site into its dynamic LDS.  A new tile is one line here (and a pick_tile rule that returns its shape).  (List: common.h)
 template <int BM_, int BN_, int NS_> struct Tile {
   static constexpr int BM = BM_, BN = BN_, NS = NS_;
   static bool is(TileShape t) { return t.bm == BM_ && t.bn == BN_; }
@@ -645,7 +640,6 @@ void gemm_t(Ctx& c, int kc, const GemmParams& p, const Epi& epi) {
 
 // One-time opt-in to > 64 KiB dynamic LDS of everything gemm_t / gemm_dual may launch: every tile of every launch site.
 // Called OUTSIDE stream capture (set_func_attrs).
-template <class... E> hipError_t first_error(E... e) { hipError_t r = hipSuccess; ((r = r != hipSuccess ? r : e), ...); return r; }
 template <int NP, class T, class Epi>
 hipError_t prepare_tile() {
   if constexpr (kHasPersistentForm<NP, T, Epi>)
@@ -671,8 +665,8 @@ hipError_t prepare_gemms() {
 // names a GEMM or attention kernel: the compiler emits kernels in the order they are first named, and the code of
 // gemm_h16_dma_kernel<2, 128, 96, 2, EpiQKV<2>> was seen to differ (equivalent address arithmetic) with its place in the module
 void set_func_attrs() {
-  (void)attention_prepare<1, 3>();
-  (void)attention_prepare<2, 2>();
+  (void)attention_prepare<1>(AttnInstances<1>{});
+  (void)attention_prepare<2>(AttnInstances<2>{});
   (void)prepare_gemms<1>();
   (void)prepare_gemms<2>();
 }

@@ -16,8 +16,8 @@ def _mirror_query_blocks(blocks64, q_rows_per_seg, planes):
 
 
 def _mirror_launch_qb(case):
-  """... and launch_attention_qp's argument to it: the launch's 64-row blocks, capped at one round of the chip unless the
-  caller allows 128-row blocks and the queries are normalised."""
+  """... and attention_launch_shape's argument to it (attention_blocks_seen): the launch's 64-row blocks, capped at one
+  round of the chip unless the caller allows 128-row blocks and the queries are normalised."""
   ks = 1
   while 2 * ks <= case.ksplit: ks *= 2
   blocks64 = case.heads * (case.rows // 64) * ks * case.segs
