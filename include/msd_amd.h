@@ -52,7 +52,10 @@ extern "C" {
                                       msd_sample_steps, msd_op_sampler_step_multistep and MSD_SAMPLER_DPMPP_2M (a step
                                       count per call and a second-order multistep sampler);
                                       msd_sample_resample and msd_op_renoise (known-frame edits with RePaint resampling
-                                      jumps in the sampler scan).
+                                      jumps in the sampler scan);
+                                      msd_sample_guided, msd_op_sampler_step_guided and
+                                      msd_op_sampler_step_multistep_guided (a guidance weight per call or per row, applied
+                                      in an interval of the scan).
                                    6: cross_merge_in_launch, cross_q_fold, mlp_in_persistent appended to msd_config.
                                    5: dedup_layer0, cross_key_split, keep_raw_weights, kv_touch_ahead appended to msd_config.
                                    4: every caller-selectable knob is a msd_config field (attn_q_planes / attn_p_planes
@@ -414,6 +417,32 @@ int msd_sample_steps(msd_model* m, int batch, int rng, int per_row, const uint64
                      const float* init_z_dev, const float* noise_dev, int num_steps, int sampler,
                      float* out_dev, void* stream);
 
+/* (appended to ABI 7) The classifier-free guidance weight PER CALL, per row, and in a limited interval of the scan: what
+ * msd_config.cfg_weight fixes for the life of a handle becomes an argument, on one handle and one set of graphs.
+ *   weights_host  n_weights finite host floats; n_weights = 1 (every row) or batch (row b takes weights_host[b])
+ *   guide_lo, guide_hi   scan indices of the call's K steps, 0 <= guide_lo < guide_hi <= K; 0, 0 = the whole scan [0, K)
+ *   num_steps, sampler   msd_sample_steps' (0 / -1 = the handle's own); the other arguments are that call's too
+ * Row b at scan index i is eval_step.body (diffusion_utils.py:397-452) with eval_condition_weight = w[b] where
+ * guide_lo <= i < guide_hi and with eval_condition_weight = 1 elsewhere (Kynkaanniemi et al. 2024, "Applying guidance in a
+ * limited interval improves sample and distribution quality in diffusion models").  The == 1 branch is the reference's: ONE
+ * decoder pass, no combine, pred_x0 not recomputed from eps at the sampler schedule.  A row whose weight is exactly 1
+ * follows that branch inside the interval as well, so row b of any call is its one-row call.  MSD_SAMPLER_DPMPP_2M keeps
+ * its x0_prev history through the interval's edges.
+ *   How: inside the interval the step is the handle's two-pass step with the sampler's guided kernels, which read the
+ *   row's weight from a device table the handle owns (uploaded per call next to the key table), so one captured graph
+ *   serves every weight vector; a scalar weight w gives the bits of a handle created with cfg_weight = w.  Outside it the
+ *   step runs the one-pass plan (msd_decoder_pass's) with the kernels the library always had: half the rows in every
+ *   launch.  Up to three runs of steps (above guide_hi, inside, below guide_lo), each whole graphs plus single steps,
+ *   replay without a host round trip; the call ends with its one synchronisation and range check.  All weights == 1
+ *   runs K one-pass steps.
+ * Not built: known frames (msd_sample_keep / _edit / _resample take no guidance), per-frame weights, and handles created
+ * with cfg_weight == 1 (they hold one pass's buffers: MSD_ERR_UNSUPPORTED -- create the handle with any weight != 1).
+ * Per-row weights need targets_length * n_dims % 1024 == 0 (MSD_ERR_UNSUPPORTED otherwise), as per-row keys do. */
+int msd_sample_guided(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
+                      const float* init_z_dev, const float* noise_dev, int num_steps, int sampler,
+                      const float* weights_host, int n_weights, int guide_lo, int guide_hi, float* out_dev,
+                      void* stream);
+
 /* Drop the captured hipGraph of the DDPM step; the next msd_sample captures it again. */
 int msd_reset_graph(msd_model* m);
 
@@ -550,6 +579,19 @@ int msd_op_renoise(const msd_config* cfg, int from_level, int to_level, const fl
 int msd_op_sampler_step_multistep(const msd_config* cfg, int step_index, const float* z_dev,
                                   const float* out_cond_dev, const float* out_uncond_dev,
                                   float* x0_prev_inout_dev, int first, float* z_out_dev, int64_t n, void* stream);
+
+/* (appended to ABI 7) msd_op_sampler_step / msd_op_sampler_step_multistep in the GUIDED form (msd_sample_guided's update):
+ * the arrays are `rows` rows of n / rows elements, and row b is combined with weights_host[b] (host floats, finite) in
+ * cfg->cfg_weight's place; a row whose weight is exactly 1 takes the cond_wt == 1 branch.  Row b holds the bits of the
+ * plain op on that row with cfg_weight = weights_host[b].  out_uncond_dev is required whatever cfg->cfg_weight is;
+ * (n / rows) % 1024 == 0 (a block of the kernel reads one weight); else as the plain ops. */
+int msd_op_sampler_step_guided(const msd_config* cfg, int step_index, const float* z_dev,
+                               const float* out_cond_dev, const float* out_uncond_dev, const float* noise_dev,
+                               const float* weights_host, int rows, float* z_out_dev, int64_t n, void* stream);
+int msd_op_sampler_step_multistep_guided(const msd_config* cfg, int step_index, const float* z_dev,
+                                         const float* out_cond_dev, const float* out_uncond_dev,
+                                         float* x0_prev_inout_dev, int first, const float* weights_host, int rows,
+                                         float* z_out_dev, int64_t n, void* stream);
 
 /* x_out = x_in + a.w1 ; h_out = (RMSNorm(x_out; gamma) (.) (film_scale+1) + film_bias) . w2
  * (layers.py:632-666 + the Dense that follows).  folded=1: the decoder's folded-norm epilogues

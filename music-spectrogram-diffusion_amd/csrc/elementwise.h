@@ -296,6 +296,23 @@ struct SamplerKeepParams : SamplerParams {
   int n_dims = 0;                // elements per frame, % 4 == 0: a thread's four elements lie in one frame
 };
 
+// The guided form's arguments (msd_sample_guided): the classifier-free guidance weight of this block's row of z comes from a
+// device table, indexed as the key table is (block x reads row x / row_blocks), so ONE captured graph serves every weight
+// vector.  A struct of its own again: 128 bytes, the plain instances' block stays at its 120.  The launch always carries
+// both passes of the model output (passes == 2); a row whose weight is exactly 1 takes the reference's `== 1` branch
+// (no combine, pred_x0 not recomputed, the unconditional pass not read) -- block-uniform, a block never straddles rows.
+struct SamplerGuidedParams : SamplerParams {
+  const float* row_wt = nullptr;   // [rows] eval_condition_weight per row of z
+};
+// What sampler_update reads in a guided launch: the launch's arguments with the row's weight in cond_wt's place, and one
+// pass where that weight is 1.  The update's text, operations and order are untouched: the weight is its operand.
+__device__ __forceinline__ SamplerParams with_row_weight(const SamplerParams& p, float w) {
+  SamplerParams q = p;
+  q.cond_wt = w;
+  q.passes = w != 1.0f ? 2 : 1;
+  return q;
+}
+
 // The update's arithmetic is ONE text, and the operation order is that text: contraction is off, every fused
 // multiply-add is an fmaf written here, and every form of the update -- plain, keep, the multistep form's x0 -- is an
 // instance of sampler_update below.  ("A zero keep mask is the plain call, bit for bit" is a statement about rounding:
@@ -388,7 +405,8 @@ __device__ __forceinline__ void publish_next_step(const SamplerParams& p, int i)
 template <int MODE, class P = SamplerParams>
 __global__ void __launch_bounds__(256) sampler_step_kernel(P p) {
   constexpr bool KEEP = std::is_same<P, SamplerKeepParams>::value;
-  static_assert(KEEP || std::is_same<P, SamplerParams>::value, "SamplerParams or SamplerKeepParams");
+  constexpr bool GUIDED = std::is_same<P, SamplerGuidedParams>::value;
+  static_assert(KEEP || GUIDED || std::is_same<P, SamplerParams>::value, "SamplerParams, SamplerKeepParams or SamplerGuidedParams");
   warm_kernargs<kernarg_lines<P>()>();
   // step_from_slot1: the step's first kernel (in_proj) copied the index to slot 1 and nobody else
   // reads slot 0 any more in this step, so this launch may decrement slot 0 itself
@@ -407,6 +425,8 @@ __global__ void __launch_bounds__(256) sampler_step_kernel(P p) {
   u32x4 rk0 = rkp[0], rk1 = rkp[1];
   static_assert(kRngKind == 4 && kRngTfKey0 == 5 && kRngTfKey1 == 6 && kRngPerRow == 7, "rk1 = {kind, Threefry key, mode}");
   asm volatile("" : "+v"(noise), "+v"(rk0), "+v"(rk1));
+  float wt = 1.0f;   // the guided form: this row's weight, fetched with the key row (the address is the block index's too)
+  if constexpr (GUIDED) wt = p.row_wt[row];
   const int idx = (blockIdx.x * 256 + threadIdx.x) * 4;
   if (idx < p.n) {
     // Loads that do not depend on the scan index go out first; the coefficient row (20 floats = five 16-byte loads,
@@ -416,7 +436,11 @@ __global__ void __launch_bounds__(256) sampler_step_kernel(P p) {
     const f32x4 zz = *reinterpret_cast<const f32x4*>(p.z + idx);
     const f32x4 ec = *reinterpret_cast<const f32x4*>(p.eps + idx);
     f32x4 eu = {0.f, 0.f, 0.f, 0.f}, nz = {0.f, 0.f, 0.f, 0.f};
-    if (p.passes == 2) eu = *reinterpret_cast<const f32x4*>(p.eps + p.n + idx);
+    if constexpr (GUIDED) {
+      if (wt != 1.0f) eu = *reinterpret_cast<const f32x4*>(p.eps + p.n + idx);   // (the same in every lane)
+    } else {
+      if (p.passes == 2) eu = *reinterpret_cast<const f32x4*>(p.eps + p.n + idx);
+    }
     f32x4 xk = {0.f, 0.f, 0.f, 0.f};
     int kf = 0;
     if constexpr (KEEP) {
@@ -452,9 +476,15 @@ __global__ void __launch_bounds__(256) sampler_step_kernel(P p) {
 #pragma unroll
     for (int k = 0; k < kCoefCount; ++k) c[k] = cr[k >> 2][k & 3];
     f32x4 out;
+    if constexpr (GUIDED) {
+      const SamplerParams q = with_row_weight(p, wt);
 #pragma unroll
-    for (int k = 0; k < 4; ++k)
-      out[k] = sampler_update<MODE, KEEP ? kFormKeep : kFormPlain>(p, c, i, zz[k], ec[k], eu[k], nz[k], xk[k], kf != 0);
+      for (int k = 0; k < 4; ++k) out[k] = sampler_update<MODE, kFormPlain>(q, c, i, zz[k], ec[k], eu[k], nz[k]);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        out[k] = sampler_update<MODE, KEEP ? kFormKeep : kFormPlain>(p, c, i, zz[k], ec[k], eu[k], nz[k], xk[k], kf != 0);
+    }
     *reinterpret_cast<f32x4*>(p.z + idx) = out;
     if (p.z_hi) {
       uint32_t h[2], l[2];
@@ -545,6 +575,12 @@ struct SamplerMultistepParams : SamplerParams {
   int first_step = -1;             // the scan index the call starts at (no history there)
 };
 void launch_sampler_step(const SamplerMultistepParams& sp, hipStream_t s);
+// ... and their guided forms (SamplerGuidedParams above; kernels' instances and launches: guided_tail.h)
+struct SamplerMultistepGuidedParams : SamplerMultistepParams {
+  const float* row_wt = nullptr;   // [rows], as SamplerGuidedParams::row_wt
+};
+void launch_sampler_step(const SamplerGuidedParams& sp, hipStream_t s);
+void launch_sampler_step(const SamplerMultistepGuidedParams& sp, hipStream_t s);
 
 // g[step][slot][k] = gamma[k] * (film_scale[step][slot][k] + 1): the column multiplier of a
 // FiLM-modulated RMSNorm, tabulated for every step (folded-norm GEMM epilogues, gemm_h16.h)

@@ -192,6 +192,11 @@ struct msd_model {
   const float** d_noise_slot = nullptr;
   uint32_t* d_rng_key = nullptr;       // [Bmax] rows of {seed_lo, seed_hi, stream_lo, stream_hi, generator kind, PRNGKey(seed) words, per-row mode} of the current msd_sample: one row per row of z (elementwise.h SamplerParams::rng_key, kRng*)
   std::vector<uint32_t> h_rng_key;     // host staging of the rows just uploaded
+  // msd_sample_guided: the guidance weight of every row of z, [Bmax] floats beside the key table (elementwise.h
+  // SamplerGuidedParams::row_wt), uploaded per call; allocated by the first guided call (outside stream capture) and owned by
+  // the handle, so the captured guided graphs hold a stable address and serve every weight vector
+  float* d_row_wt = nullptr;
+  std::vector<float> h_row_wt;         // host staging of that upload
   // msd_sample_keep: the known mel in model units [Bmax][T][n] and its frame flags [Bmax][T]; allocated by the first
   // keep call (outside stream capture) and owned by the handle, so the captured keep graphs hold stable addresses
   float* keep_xk = nullptr;
@@ -230,7 +235,9 @@ struct msd_model {
   // never replays a keep graph, nor the other way round.
   // `steps`, `sampler`: msd_sample_steps' graphs bake another view of the step-indexed tables and maybe another sampler
   // kernel in; the handle's own (N, cfg.sampler) is the key every other entry point looks up, as it always did.
-  struct GraphKey { StepPlan plan; int steps, sampler, keep; };   // ONE key, compared bytewise (find_graphs)
+  // `guided`: msd_sample_guided's two-pass graphs launch the sampler's guided form (the row weights come from d_row_wt);
+  // its one-pass steps replay plain graphs of the one-pass plan.  (An int like its neighbours: no padding bytes.)
+  struct GraphKey { StepPlan plan; int steps, sampler, keep, guided; };   // ONE key, compared bytewise (find_graphs)
   static_assert(std::has_unique_object_representations<GraphKey>::value, "GraphKey (StepPlan included) must not have padding bytes");
   struct StepGraphs { GraphKey key; hipGraphExec_t exec = nullptr, exec1 = nullptr; };
   std::vector<StepGraphs> graphs;
@@ -420,6 +427,7 @@ struct StepView {
   const float* coef_ms = nullptr;   // [K][kMsCount], MSD_SAMPLER_DPMPP_2M only
   int sampler = 0;                  // msd_sampler_kind
   bool keep = false;                // the sampler's keep form on the handle's known-frame buffers (msd_sample_keep / _edit)
+  bool guided = false;              // the sampler's guided form on the handle's row-weight table (msd_sample_guided)
 };
 
 struct Ctx {
@@ -1562,11 +1570,18 @@ void enqueue_step(Ctx& c, const StepPlan& p) {
   c.begin(KC_SAMPLER);
   sp.step_from_slot1 = 1;
   if (sampler == MSD_SAMPLER_DPMPP_2M) {   // (never with keep: check_call refuses the pair)
-    SamplerMultistepParams mp;
+    SamplerMultistepGuidedParams mp;
     static_cast<SamplerParams&>(mp) = sp;
     mp.x0_prev = m->x0_prev; mp.coef_ms = c.v.coef_ms;
     mp.first_step = c.v.steps - 1;
-    launch_sampler_step(mp, c.s);
+    mp.row_wt = m->d_row_wt;
+    if (c.v.guided) launch_sampler_step(mp, c.s);
+    else launch_sampler_step(static_cast<const SamplerMultistepParams&>(mp), c.s);
+  } else if (c.v.guided) {   // (never with keep either: msd_sample_guided takes no known frames)
+    SamplerGuidedParams gp;
+    static_cast<SamplerParams&>(gp) = sp;
+    gp.row_wt = m->d_row_wt;
+    launch_sampler_step(gp, c.s);
   } else if (c.v.keep) {
     sp.xk = m->keep_xk; sp.keep = m->keep_flags; sp.n_dims = m->ND;
     launch_sampler_step(sp, c.s);
@@ -2031,6 +2046,10 @@ struct SampleCall {
   int start_step;                // the scan index the call starts at: steps - 1, or msd_sample_edit's
   int steps, sampler;            // K (K | N) and the msd_sampler_kind
   int jump = 1, times = 1;       // msd_sample_resample: every block of `jump` steps is descended `times` times (1 = no jump)
+  // msd_sample_guided: row b combines with weights[n_weights == 1 ? 0 : b] at scan indices in [guide_lo, guide_hi) and
+  // takes the cond_wt == 1 branch (one decoder pass) outside; null = the handle's own weight at every step, as ever
+  const float* weights = nullptr;   // host
+  int n_weights = 0, guide_lo = 0, guide_hi = 0;
 };
 
 static SampleKeys sample_keys(int per_row, const uint64_t* seeds, const uint64_t* stream_ids) {
@@ -2108,6 +2127,8 @@ static int check_call(msd_model* m, const SampleCall& c) {
   const int64_t row_n = (int64_t)m->T * m->ND;
   if (c.keys.per_row() && row_n % kRngRowBlock)   // a block of the sampler launch would straddle two rows' keys
     return fail(m, MSD_ERR_UNSUPPORTED, "per-row keys need targets_length * n_dims %% %d == 0 (got %lld)", (int)kRngRowBlock, (long long)row_n);
+  if (c.weights && c.n_weights > 1 && row_n % kRngRowBlock)   // ... or two rows' weights
+    return fail(m, MSD_ERR_UNSUPPORTED, "per-row guidance weights need targets_length * n_dims %% %d == 0 (got %lld)", (int)kRngRowBlock, (long long)row_n);
   if (c.known && m->ND % 4)   // a thread of the sampler holds four consecutive elements and ONE frame flag
     return fail(m, MSD_ERR_UNSUPPORTED, "kept frames need n_dims %% 4 == 0 (got %d)", m->ND);
   return MSD_OK;
@@ -2210,7 +2231,7 @@ static int capture_steps(msd_model* m, const StepView& view, const StepPlan& pla
 // scan index lives in device memory, so the same graph serves every position); a second, single-step graph covers what
 // a call of view.steps steps, or this call of run_steps, leaves over.
 static int find_graphs(msd_model* m, const StepView& view, const StepPlan& plan, int run_steps, hipStream_t s, msd_model::StepGraphs** out) {
-  const msd_model::GraphKey key = {plan, view.steps, view.sampler, view.keep};
+  const msd_model::GraphKey key = {plan, view.steps, view.sampler, view.keep, view.guided};
   msd_model::StepGraphs* g = nullptr;
   for (auto& e : m->graphs)
     if (memcmp(&e.key, &key, sizeof(key)) == 0) g = &e;
@@ -2299,6 +2320,45 @@ static int replay_resampled(msd_model* m, const SampleCall& c, const msd_model::
   return MSD_OK;
 }
 
+// The steps of a call with guidance in an interval of the scan (msd_sample_guided): up to three runs of steps -- one-pass
+// above guide_hi, guided inside [guide_lo, guide_hi), one-pass below guide_lo -- each whole graphs plus singles.  The scan
+// index runs on in device memory across them (both plans publish it the same way) and so do z, its planes and the multistep
+// form's x0_prev; nothing synchronises with the host in between.
+// The call needs TWO sets of graphs at once, and find_graphs hands out a pointer into m->graphs that its next call may
+// invalidate (push_back moves the entries; a full cache is reset, which destroys the graphs).  So room for every set that
+// is missing is made BEFORE the first lookup -- no reset can follow -- and each set is held by value: the executable
+// graphs' handles, which a push_back does not touch.
+static bool graphs_cached(const msd_model* m, const StepView& view, const StepPlan& plan) {
+  const msd_model::GraphKey key = {plan, view.steps, view.sampler, view.keep, view.guided};
+  for (const auto& e : m->graphs)
+    if (memcmp(&e.key, &key, sizeof(key)) == 0) return true;
+  return false;
+}
+static int replay_guided(msd_model* m, const SampleCall& c, const StepView& view, int steps, hipStream_t s) {
+  const int runs[3] = {steps - c.guide_hi, c.guide_hi - c.guide_lo, c.guide_lo};   // one-pass, guided, one-pass
+  StepView one = view, two = view;
+  one.guided = false; two.guided = true;
+  const StepPlan plan1 = plan_step(m, c.batch, 1, true, false), plan2 = plan_cfg_step(m, c.batch);
+  const bool need1 = runs[0] + runs[2] > 0, need2 = runs[1] > 0;
+  const size_t missing = (size_t)(need1 && !graphs_cached(m, one, plan1)) + (size_t)(need2 && !graphs_cached(m, two, plan2));
+  if (missing && m->graphs.size() + missing > 8) (void)msd_reset_graph(m);
+  msd_model::StepGraphs g1, g2;
+  msd_model::StepGraphs* g = nullptr;
+  const int gs = m->graph_steps;
+  if (need1) {   // (the single-step graph: needed as soon as one of the two runs is no whole number of graphs)
+    if (int rc = find_graphs(m, one, plan1, (runs[0] % gs || runs[2] % gs) ? 1 : gs, s, &g)) return rc;
+    g1 = *g;
+  }
+  if (need2) {
+    if (int rc = find_graphs(m, two, plan2, runs[1], s, &g)) return rc;
+    g2 = *g;
+  }
+  for (int r = 0; r < 3; ++r)
+    if (runs[r] > 0)
+      if (int rc = replay(m, r == 1 ? g2 : g1, runs[r], s)) return rc;
+  return MSD_OK;
+}
+
 // z -> the caller's mel units; kept frames: the caller's own values, not a round trip through model units
 static int unscale(msd_model* m, const SampleCall& c, hipStream_t s) {
   const int64_t n = (int64_t)c.batch * m->T * m->ND;
@@ -2324,9 +2384,16 @@ static int sample_body(msd_model* m, const SampleCall& c) {
   if (int rc = write_initial_state(m, c, s)) return rc;
   if (c.times > 1)
     if (int rc = upload_pass_keys(m, c, steps, s)) return rc;
+  if (c.weights) {   // the row weights travel next to the key table (arm_scan ends with the stream idle)
+    m->h_row_wt.assign((size_t)m->Bmax, c.weights[0]);   // a member: the copy may still read it when this returns
+    for (int b = 0; b < c.batch && c.n_weights > 1; ++b) m->h_row_wt[b] = c.weights[b];
+    HIP_TRY(m, hipMemcpyAsync(m->d_row_wt, m->h_row_wt.data(), m->h_row_wt.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  }
   if (int rc = arm_scan(m, c.batch, c.rng, c.keys, c.noise, c.start_step, /*reset_tickets=*/true, s)) return rc;
   msd_model::StepGraphs* g = nullptr;
-  if (c.times == 1) {
+  if (c.weights) {
+    if (int rc = replay_guided(m, c, view, steps, s)) return rc;
+  } else if (c.times == 1) {
     if (int rc = find_graphs(m, view, plan_cfg_step(m, c.batch), steps, s, &g)) return rc;
     if (int rc = replay(m, *g, steps, s)) return rc;
   } else {
@@ -2428,6 +2495,41 @@ int msd_sample_steps(msd_model* m, int batch, int rng, int per_row, const uint64
   SampleCall c = plain_call(m, batch, rng, sample_keys(per_row, seeds, stream_ids), init_z_dev, noise_dev, out_dev, stream);
   if (num_steps > 0) { c.steps = num_steps; c.start_step = num_steps - 1; }   // (the handle's own are (N, cfg.sampler), however they were named)
   if (sampler >= 0) c.sampler = sampler;
+  return sample_body(m, c);
+}
+
+int msd_sample_guided(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
+                      const float* init_z_dev, const float* noise_dev, int num_steps, int sampler, const float* weights_host,
+                      int n_weights, int guide_lo, int guide_hi, float* out_dev, void* stream) {
+  if (!m) return MSD_ERR_INVALID_ARGUMENT;
+  if (!seeds) return fail(m, MSD_ERR_INVALID_ARGUMENT, "seeds is null");
+  if (batch < 1 || batch > m->Bmax) return fail(m, MSD_ERR_INVALID_ARGUMENT, "batch %d outside [1, %d]", batch, m->Bmax);
+  if (num_steps < 0 || (num_steps > 0 && m->N % num_steps))
+    return fail(m, MSD_ERR_INVALID_ARGUMENT, "num_steps %d does not divide the handle's %d steps; it takes 0 (= %d) or one of %s",
+                num_steps, m->N, m->N, divisors_of(m->N).c_str());
+  if (sampler != -1 && sampler != MSD_SAMPLER_DDPM && sampler != MSD_SAMPLER_DDIM && sampler != MSD_SAMPLER_DPMPP_2M)
+    return fail(m, MSD_ERR_INVALID_ARGUMENT, "Unknown sampler type: %d", sampler);
+  if (!weights_host || (n_weights != 1 && n_weights != batch))
+    return fail(m, MSD_ERR_INVALID_ARGUMENT, "guidance takes 1 weight or one per row (%d), got %d", batch, weights_host ? n_weights : 0);
+  bool all_one = true;
+  for (int b = 0; b < n_weights; ++b) {
+    if (!std::isfinite(weights_host[b])) return fail(m, MSD_ERR_INVALID_ARGUMENT, "guidance weight %d is not finite", b);
+    all_one = all_one && weights_host[b] == 1.0f;
+  }
+  const int K = num_steps > 0 ? num_steps : m->N;
+  if (guide_lo == 0 && guide_hi == 0) guide_hi = K;   // the whole scan
+  if (guide_lo < 0 || guide_lo >= guide_hi || guide_hi > K)
+    return fail(m, MSD_ERR_INVALID_ARGUMENT, "guidance interval [%d, %d) is not inside the call's scan indices [0, %d)", guide_lo, guide_hi, K);
+  if (m->passes == 1)   // (a weight-1 handle has buffers for one pass only)
+    return fail(m, MSD_ERR_UNSUPPORTED, "a handle created with cfg_weight 1 holds one pass's buffers and takes no per-call guidance: "
+                "create the handle with any weight != 1");
+  if (!m->d_row_wt)
+    if (int rc = dalloc(m, &m->d_row_wt, (size_t)m->Bmax)) return rc;
+  SampleCall c = plain_call(m, batch, rng, sample_keys(per_row, seeds, stream_ids), init_z_dev, noise_dev, out_dev, stream);
+  c.steps = K; c.start_step = K - 1;
+  if (sampler >= 0) c.sampler = sampler;
+  c.weights = weights_host; c.n_weights = n_weights; c.guide_lo = guide_lo; c.guide_hi = guide_hi;
+  if (all_one) c.guide_lo = c.guide_hi = 0;   // every row follows the cond_wt == 1 branch: no guided step, K one-pass steps
   return sample_body(m, c);
 }
 
@@ -2715,3 +2817,4 @@ int msd_vocoder_decode(msd_vocoder* v, int batch, int n_frames, const float* log
 
 #include "keep_frames_tail.h"   // last on purpose: see the file
 #include "multistep_tail.h"     // ... and behind it, for the same reason
+#include "guided_tail.h"        // ... and the guided instances behind those

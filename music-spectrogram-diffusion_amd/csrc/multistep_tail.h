@@ -18,18 +18,28 @@
 #pragma once
 #include "elementwise.h"
 namespace msd {
-template <int MODE>
-__global__ void __launch_bounds__(256) sampler_multistep_kernel(SamplerMultistepParams p) {
+// P = SamplerMultistepGuidedParams: the guided form (guided_tail.h) -- this block's row weight from the device table in
+// cond_wt's place, the difference under `if constexpr` as in sampler_step_kernel.
+template <int MODE, class P = SamplerMultistepParams>
+__global__ void __launch_bounds__(256) sampler_multistep_kernel(P p) {
 #pragma clang fp contract(off)
-  warm_kernargs<kernarg_lines<SamplerMultistepParams>()>();
+  constexpr bool GUIDED = std::is_same<P, SamplerMultistepGuidedParams>::value;
+  static_assert(GUIDED || std::is_same<P, SamplerMultistepParams>::value, "SamplerMultistepParams or SamplerMultistepGuidedParams");
+  warm_kernargs<kernarg_lines<P>()>();
   const int i = p.step_from_slot1 ? p.step_ptr[1] : p.step_ptr[0];
+  float wt = 1.0f;
+  if constexpr (GUIDED) wt = p.row_wt[blockIdx.x / (uint32_t)p.row_blocks];
   const int idx = (blockIdx.x * 256 + threadIdx.x) * 4;
   if (idx < p.n) {
     // as in sampler_step_kernel: what does not depend on the scan index goes out first, the rows behind the index
     const f32x4 zz = *reinterpret_cast<const f32x4*>(p.z + idx);
     const f32x4 ec = *reinterpret_cast<const f32x4*>(p.eps + idx);
     f32x4 eu = {0.f, 0.f, 0.f, 0.f}, xp = {0.f, 0.f, 0.f, 0.f};
-    if (p.passes == 2) eu = *reinterpret_cast<const f32x4*>(p.eps + p.n + idx);
+    if constexpr (GUIDED) {
+      if (wt != 1.0f) eu = *reinterpret_cast<const f32x4*>(p.eps + p.n + idx);   // (the same in every lane)
+    } else {
+      if (p.passes == 2) eu = *reinterpret_cast<const f32x4*>(p.eps + p.n + idx);
+    }
     const bool first = i == p.first_step;   // (the same in every lane) no history yet: x0_prev is not read
     if (!first) xp = *reinterpret_cast<const f32x4*>(p.x0_prev + idx);
     f32x4 cr[5];
@@ -39,9 +49,14 @@ __global__ void __launch_bounds__(256) sampler_multistep_kernel(SamplerMultistep
 #pragma unroll
     for (int k = 0; k < kCoefCount; ++k) c[k] = cr[k >> 2][k & 3];
     f32x4 out, x0v;
+    // what sampler_update reads: the launch's own arguments, or -- guided -- those with the row's weight
+    const auto& up = [&]() -> decltype(auto) {
+      if constexpr (GUIDED) return with_row_weight(p, wt);
+      else return (p);
+    }();
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-      const float x0 = sampler_update<MODE, kFormX0>(p, c, i, zz[k], ec[k], eu[k]);
+      const float x0 = sampler_update<MODE, kFormX0>(up, c, i, zz[k], ec[k], eu[k]);
       const float d = first ? x0 : fmaf(ms[kMsHist], x0 - xp[k], x0);
       const float zs = fmaf(ms[kMsZ], zz[k], ms[kMsD] * d);
       x0v[k] = x0;

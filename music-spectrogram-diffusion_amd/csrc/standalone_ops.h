@@ -517,13 +517,15 @@ msd_gemm_site_args forced_site_args(TileShape tile, int M, int N, int K) {
 // What the sampler ops share, in ONE place: the argument checks, the coefficient rows of cfg (handed back: the multistep
 // entry derives its side table from them), the staged operands -- the passes of the model output side by side, z copied
 // into z_out (the kernel updates in place), the scan index in both slots -- and the SamplerParams every form starts from
-// (no draw, no planes).  Each entry adds its form's fields on top.
+// (no draw, no planes).  Each entry adds its form's fields on top.  both_passes: the guided forms stage the unconditional
+// output whatever cfg->cfg_weight is (their weights come from a table).
 int sampler_op_base(OpKit& kit, const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
-                    const float* out_uncond_dev, float* z_out_dev, int64_t n, SamplerParams* sp, std::vector<float>* rows) {
+                    const float* out_uncond_dev, float* z_out_dev, int64_t n, SamplerParams* sp, std::vector<float>* rows,
+                    bool both_passes = false) {
   if (!cfg || cfg->struct_size != (int32_t)sizeof(msd_config) || !z_dev || !out_cond_dev || !z_out_dev ||
       n <= 0 || n % 4 || n > 0x7FFFFFFFll || step_index < 0 || step_index >= cfg->num_steps)
     return MSD_ERR_INVALID_ARGUMENT;
-  const int passes = cfg->cfg_weight != 1.0f ? 2 : 1;
+  const int passes = (both_passes || cfg->cfg_weight != 1.0f) ? 2 : 1;
   if (passes == 2 && !out_uncond_dev) return MSD_ERR_INVALID_ARGUMENT;
   std::string why;
   if (!build_coef_rows(*cfg, rows, &why)) return MSD_ERR_INVALID_ARGUMENT;
@@ -583,6 +585,21 @@ int op_sampler_step(const msd_config* cfg, int step_index, const float* z_dev, c
     launch_sampler_step(static_cast<const SamplerParams&>(sp), s);
   }
   return sampler_op_finish(s);
+}
+
+// The guided forms' row weights: `rows` finite host floats, one per row of n / rows elements, each a whole number of the
+// sampler's blocks (a block reads ONE weight); uploaded to kit scratch.  row_blocks = blocks per row.
+int guided_op_weights(OpKit& kit, const float* weights_host, int rows, int64_t n, const float** table, int* row_blocks) {
+  if (!weights_host || rows < 1 || n <= 0 || n % rows || (n / rows) % kRngRowBlock) return MSD_ERR_INVALID_ARGUMENT;
+  for (int b = 0; b < rows; ++b)
+    if (!std::isfinite(weights_host[b])) return MSD_ERR_INVALID_ARGUMENT;
+  float* w = kit.get<float>((size_t)rows);
+  if (!w) return MSD_ERR_HIP;
+  if (hipMemcpyAsync(w, weights_host, (size_t)rows * sizeof(float), hipMemcpyHostToDevice, kit.s) != hipSuccess ||
+      hipStreamSynchronize(kit.s) != hipSuccess)
+    return MSD_ERR_HIP;
+  *table = w; *row_blocks = (int)(n / rows / kRngRowBlock);
+  return MSD_OK;
 }
 
 // ---- one attention launch the way the decoder fills it (tests/test_gpu_attention_forms.py) ---------------------------
@@ -954,6 +971,48 @@ int msd_op_sampler_step_multistep(const msd_config* cfg, int step_index, const f
   std::vector<float> rows, ms;
   if (const int rc = sampler_op_base(kit, cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, z_out_dev, n, &sp, &rows)) return rc;
   build_multistep_rows(rows, &ms);
+  float* coef_ms = kit.get<float>(ms.size());
+  if (!coef_ms) return MSD_ERR_HIP;
+  if (hipMemcpyAsync(coef_ms, ms.data(), ms.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return MSD_ERR_HIP;
+  sp.x0_prev = x0_prev_inout_dev; sp.coef_ms = coef_ms; sp.first_step = first ? step_index : -1;
+  launch_sampler_step(sp, s);
+  return sampler_op_finish(s);
+}
+
+int msd_op_sampler_step_guided(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
+                               const float* out_uncond_dev, const float* noise_dev, const float* weights_host, int rows,
+                               float* z_out_dev, int64_t n, void* stream) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  OpKit kit(s, 1);
+  SamplerGuidedParams sp;
+  std::vector<float> coef_rows;
+  if (const int rc = guided_op_weights(kit, weights_host, rows, n, &sp.row_wt, &sp.row_blocks)) return rc;
+  if (const int rc = sampler_op_base(kit, cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, z_out_dev, n, &sp, &coef_rows, /*both_passes=*/true)) return rc;
+  float* noise = kit.get<float>((size_t)n);   // one step's draw (zeros) when the caller gives none
+  const float** slot = kit.get<const float*>(1);
+  uint32_t* key = kit.get<uint32_t>((size_t)rows * kRngWords);   // fetched up front, used or not: one (zero) row per row of z
+  if (!noise || !slot || !key) return MSD_ERR_HIP;
+  const float* base = (noise_dev ? noise_dev : noise) - (size_t)step_index * n;   // (op_sampler_step's)
+  if (hipMemcpyAsync(slot, &base, sizeof(base), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    return MSD_ERR_HIP;
+  sp.noise_slot = slot; sp.rng_key = key; sp.ddim = cfg->sampler == MSD_SAMPLER_DDIM;
+  launch_sampler_step(sp, s);
+  return sampler_op_finish(s);
+}
+
+int msd_op_sampler_step_multistep_guided(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
+                                         const float* out_uncond_dev, float* x0_prev_inout_dev, int first,
+                                         const float* weights_host, int rows, float* z_out_dev, int64_t n, void* stream) {
+  if (!x0_prev_inout_dev) return MSD_ERR_INVALID_ARGUMENT;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  OpKit kit(s, 1);
+  SamplerMultistepGuidedParams sp;   // (noise_slot / rng_key stay null: the form makes no draw and reads neither)
+  std::vector<float> coef_rows, ms;
+  if (const int rc = guided_op_weights(kit, weights_host, rows, n, &sp.row_wt, &sp.row_blocks)) return rc;
+  if (const int rc = sampler_op_base(kit, cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, z_out_dev, n, &sp, &coef_rows, /*both_passes=*/true)) return rc;
+  build_multistep_rows(coef_rows, &ms);
   float* coef_ms = kit.get<float>(ms.size());
   if (!coef_ms) return MSD_ERR_HIP;
   if (hipMemcpyAsync(coef_ms, ms.data(), ms.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||

@@ -276,6 +276,35 @@ def plan_strength(strength, num_steps: int):
   return np.ascontiguousarray(words), int(f.max()) - 1
 
 
+def plan_guidance(guidance, guidance_interval, b: int, num_steps_of_call: int, model_weight: float):
+  """predict's guidance / guidance_interval -> (weights float32 [b] | None, g_lo, g_hi): row r of the call combines with
+  weights[r] at scan indices g_lo <= i < g_hi of its K = num_steps_of_call steps and runs the weight-1 branch (one decoder
+  pass) at the others.  guidance: a finite float or [b] of them; None = the model's weight.  guidance_interval (lo, hi):
+  fractions of diffusion time with 0 <= lo < hi <= 1, g = floor(x * K + 0.5) (plan_strength's rounding); None = (0, K); an
+  interval that rounds to no step is a ValueError.  weights is None for THE CALL AS IT WAS -- the model's weight (or None)
+  as a scalar, over the whole scan -- which runs the entry points and kernels it always ran.  Pure: no device."""
+  if isinstance(num_steps_of_call, bool) or int(num_steps_of_call) != num_steps_of_call or num_steps_of_call < 1:
+    raise ValueError('num_steps must be a positive integer: %r' % (num_steps_of_call,))
+  k = int(num_steps_of_call)
+  scalar = guidance is None or np.ndim(guidance) == 0
+  w = native.check_guidance(model_weight if guidance is None else _to_numpy(guidance) if np.ndim(guidance) else guidance, b)
+  g_lo, g_hi = 0, k
+  if guidance_interval is not None:
+    try:
+      lo, hi = (float(x) for x in guidance_interval)
+    except (TypeError, ValueError):
+      raise ValueError('guidance_interval must be (lo, hi), two floats: %r' % (guidance_interval,))
+    if not 0.0 <= lo < hi <= 1.0:   # (a NaN fails every comparison)
+      raise ValueError('guidance_interval needs 0 <= lo < hi <= 1 (fractions of diffusion time): %r' % (guidance_interval,))
+    g_lo, g_hi = int(np.floor(lo * k + 0.5)), int(np.floor(hi * k + 0.5))
+    if g_lo == g_hi:
+      raise ValueError('guidance_interval %r holds none of the call\'s %d steps (both ends round to scan index %d)'
+                       % (guidance_interval, k, g_lo))
+  if scalar and (g_lo, g_hi) == (0, k) and np.float32(w[0]) == np.float32(model_weight):
+    return None, g_lo, g_hi
+  return np.ascontiguousarray(np.broadcast_to(np.asarray(w, np.float32), (b,))), g_lo, g_hi
+
+
 def check_strength(strength, flags, b: int, t: int):
   """predict's strength -- a scalar, [b] or [b, t] -- as float64 [b, t], with 0 on the frames `flags` (int [b, t] or None)
   names.  A shape that is none of the three is a ValueError; the values are plan_strength's to check."""
@@ -321,13 +350,32 @@ class SampleCall:
   steps: Optional[int] = None
   sampler: Optional[str] = None
   resample: Optional[Tuple[int, int]] = None   # (jump, times) of a known-frame call with resampling jumps; None = none
+  guidance: Any = None                         # the call's guidance weight(s): a float, or one per row; None = the model's, as ever
+  guide_range: Optional[Tuple[int, int]] = None   # the scan indices [g_lo, g_hi) it is applied at; None = all
 
 
 def plan_call(keep, keep_mask, strength, steps, sampler, b: int, t: int, n: int, num_steps: int, resample=None,
-              noise=None) -> SampleCall:
-  """predict's keep / keep_mask / strength / steps / sampler / resample, checked and planned once (noise: only because
-  resample may not be combined with it).  Pure: no device; every ValueError predict raises for them is raised here, but for
-  resample with rng='jax', which predict raises once it knows the call's generator."""
+              noise=None, guidance=None, guidance_interval=None, model_weight: Optional[float] = None) -> SampleCall:
+  """predict's keep / keep_mask / strength / steps / sampler / resample / guidance / guidance_interval, checked and
+  planned once (noise: only because resample may not be combined with it; model_weight: the model's own guidance weight,
+  needed once either guidance argument is given).  Pure: no device; every ValueError predict raises for them is raised
+  here, but for resample with rng='jax', which predict raises once it knows the call's generator."""
+  if guidance is not None or guidance_interval is not None:
+    if keep is not None or keep_mask is not None or strength is not None or resample is not None:
+      raise ValueError('guidance= / guidance_interval= cannot be combined with keep= / keep_mask= / strength= / resample= '
+                       '(guided edits are not built)')
+    call = plan_call(None, None, None, steps, sampler, b, t, n, num_steps)
+    if model_weight is None:
+      raise ValueError('guidance= / guidance_interval= need the model\'s own weight (model_weight)')
+    if model_weight == 1.0:
+      raise ValueError('this model was created with guidance weight 1 and holds one pass\'s buffers: per-call guidance needs '
+                       'a model created with any weight != 1')
+    k = num_steps if call.steps is None else call.steps
+    weights, g_lo, g_hi = plan_guidance(guidance, guidance_interval, b, k, model_weight)
+    if weights is None:   # the call as it was
+      return call
+    w = [float(x) for x in weights]
+    return dataclasses.replace(call, guidance=w[0] if len(set(w)) == 1 else w, guide_range=(g_lo, g_hi))
   if resample is not None:
     jump, times = native.check_resample(resample)
     if steps is not None or sampler is not None:
@@ -529,7 +577,7 @@ class InferenceModel(object):
               segment: Union[int, Sequence[int]] = 0,
               init_z=None, noise=None, return_torch: bool = False, rng: Optional[str] = None,
               keep=None, keep_mask=None, strength=None, steps: Optional[int] = None, sampler: Optional[str] = None,
-              resample=None):
+              resample=None, guidance=None, guidance_interval=None):
     """Predict one batch of 256-frame segments.
 
     batch: the model features of inference.py:113-136 (NumPy arrays or torch
@@ -588,10 +636,24 @@ class InferenceModel(object):
       1000-step DDIM result than DDIM, and nothing is known about a trained checkpoint.  None / None is the call as it always was, bit for bit.
       NOT with keep / keep_mask / strength (nor on vary / regenerate): edits on a coarse schedule, and multistep history
       across a frame's release, are a separate piece of work -- a ValueError in this version.
+    guidance (a float, or [B] floats: row b takes guidance[b]) / guidance_interval ((lo, hi), 0 <= lo < hi <= 1,
+      fractions of diffusion time): the classifier-free guidance weight of THIS call in the model's
+      eval_condition_weight's place, on the same handle and graphs (plan_guidance, msd_sample_guided) -- a sweep of B
+      weights over one set of tokens is one batched call with equal keys.  With an interval the combine is applied only
+      at scan indices floor(lo K + 0.5) <= i < floor(hi K + 0.5) of the call's K steps (Kynkaanniemi et al. 2024);
+      every other step is the reference's weight-1 branch: ONE decoder pass, half the rows in every launch.  A row
+      whose weight is exactly 1 takes that branch at every step, so row b is always its one-row call; a scalar weight
+      w gives the bits of a model created with weight w.  An interval alone uses the model's weight.  With every seed /
+      segment / rng / init_z / noise form and with steps= / sampler= ('dpmpp_2m' keeps its history across the
+      interval's edges).  None, or the model's own weight, over the whole scan is the call as it always was, bit for
+      bit.  NOT with keep / keep_mask / strength / resample, no per-frame weights, and not on a model created with
+      weight 1 (it holds one pass's buffers): ValueErrors, raised before any device work, as are a non-finite weight,
+      a wrong length and an interval that is out of order, outside [0, 1] or rounds to no step.
     Returns (decodes float32 [B,T,n] in mel units, scores float32 [B] zeros).
     """
     call = plan_call(keep, keep_mask, strength, steps, sampler, np.shape(batch['encoder_input_tokens'])[0], self.targets_length,
-                     self.audio_codec.n_dims, self.spec.diffusion.sampler.schedule.num_steps, resample, noise)
+                     self.audio_codec.n_dims, self.spec.diffusion.sampler.schedule.num_steps, resample, noise,
+                     guidance, guidance_interval, self.spec.diffusion.classifier_free_guidance.eval_condition_weight)
     if rng is None:
       rng = self.rng
     if resample is not None and rng == 'jax':
@@ -700,7 +762,7 @@ class InferenceModel(object):
                        always_mask_context: bool = False, init_context: Optional[np.ndarray] = None,
                        first_segment_index: int = 0, return_timing: bool = False, rng: Optional[str] = None,
                        return_torch: bool = False, batch_segments: int = 1, steps: Optional[int] = None,
-                       sampler: Optional[str] = None):
+                       sampler: Optional[str] = None, guidance: Optional[float] = None, guidance_interval=None):
     """Synthesize a whole song: segments of int32 [inputs_length] (or [1, L]).
 
     Segment 0 runs with context zeros + mask 0 (beam/evaluation.py:195-198);
@@ -721,8 +783,13 @@ class InferenceModel(object):
     but the first (the loop leaves out its first segment the same way).
 
     ``steps`` / ``sampler``: predict's, for every segment of the song (the batched form included).
+
+    ``guidance`` (ONE weight for the song: a scalar) / ``guidance_interval``: predict's, for every segment as well.
     """
-    few = {k: v for k, v in (('steps', steps), ('sampler', sampler)) if v is not None}
+    if guidance is not None and (isinstance(guidance, bool) or np.ndim(guidance) != 0):
+      raise ValueError('predict_sequence takes one guidance weight for the song (a scalar): %r' % (guidance,))
+    few = {k: v for k, v in (('steps', steps), ('sampler', sampler), ('guidance', guidance),
+                             ('guidance_interval', guidance_interval)) if v is not None}
     if batch_segments != 1:
       return self._predict_sequence_batched(segments_tokens, seed, always_mask_context, init_context,
                                             first_segment_index, return_timing, rng, return_torch, batch_segments, few)

@@ -77,7 +77,39 @@ EXPORTED_SYMBOLS = (
     # (appended to ABI 7) a launch with a weight target in either carrier form; how a target is dealt over the waves
     'msd_op_gemm_site_carrier', 'msd_op_attention_launch_carrier', 'msd_op_touch_deal', 'msd_set_touch_carrier',
     # (appended to ABI 7) known-frame edits with resampling jumps (RePaint) in the sampler scan
-    'msd_sample_resample', 'msd_op_renoise')
+    'msd_sample_resample', 'msd_op_renoise',
+    # (appended to ABI 7) a guidance weight per call or per row, applied in an interval of the scan
+    'msd_sample_guided', 'msd_op_sampler_step_guided', 'msd_op_sampler_step_multistep_guided')
+
+
+def check_guidance(guidance, batch: int):
+  """guidance of a call over `batch` rows -> its weights as a list of 1 or `batch` Python floats (the values float32
+  holds); a ValueError for anything that is not a finite number or `batch` of them."""
+  if isinstance(guidance, bool):
+    raise ValueError('guidance must be a number or %d numbers, not a bool' % batch)
+  try:
+    w = np.asarray(guidance, dtype=np.float64)
+  except (TypeError, ValueError):
+    raise ValueError('guidance must be a number or %d numbers: %r' % (batch, guidance))
+  if w.ndim > 1 or (w.ndim == 1 and w.size != batch):
+    raise ValueError('guidance must be a number or one per row (%d): got shape %s' % (batch, tuple(w.shape)))
+  with np.errstate(over='ignore'):   # (a weight beyond float32 becomes inf and is refused below)
+    w32 = w.astype(np.float32).reshape(-1)
+  if not np.all(np.isfinite(w32)):
+    raise ValueError('guidance must be finite (in float32): %r' % (guidance,))
+  return [float(x) for x in w32]
+
+
+def check_guide_range(guide_range, num_steps: int):
+  """(g_lo, g_hi), scan indices of a call of num_steps steps -> two ints with 0 <= g_lo < g_hi <= num_steps."""
+  try:
+    g_lo, g_hi = guide_range
+  except (TypeError, ValueError):
+    raise ValueError('guide_range must be (g_lo, g_hi): %r' % (guide_range,))
+  _check_ints(('g_lo', g_lo, 0), ('g_hi', g_hi, 1))
+  if not g_lo < g_hi <= num_steps:
+    raise ValueError('guide_range needs 0 <= g_lo < g_hi <= %d: got (%d, %d)' % (num_steps, g_lo, g_hi))
+  return int(g_lo), int(g_hi)
 
 
 def divisors(n: int):
@@ -307,6 +339,11 @@ def load(planes: str = 'f16') -> ctypes.CDLL:
   if 'msd_sample_resample' in present:   # (appended to ABI 7)
     lib.msd_sample_resample.argtypes = [vp, i32, i32, i32, c.POINTER(u64), c.POINTER(u64), vp, vp, vp, i32, i32, i32, vp, vp]
     lib.msd_op_renoise.argtypes = [c.POINTER(MsdConfig), i32, i32, vp, vp, vp, vp, i64, vp]
+  if 'msd_sample_guided' in present:   # (appended to ABI 7)
+    fp = c.POINTER(c.c_float)
+    lib.msd_sample_guided.argtypes = [vp, i32, i32, i32, c.POINTER(u64), c.POINTER(u64), vp, vp, i32, i32, fp, i32, i32, i32, vp, vp]
+    lib.msd_op_sampler_step_guided.argtypes = [c.POINTER(MsdConfig), i32, vp, vp, vp, vp, fp, i32, vp, i64, vp]
+    lib.msd_op_sampler_step_multistep_guided.argtypes = [c.POINTER(MsdConfig), i32, vp, vp, vp, vp, i32, fp, i32, vp, i64, vp]
   if 'msd_fill_normal_threefry' in present:
     lib.msd_fill_normal_threefry.argtypes = [u64, i64, vp, i64, vp]
   if 'msd_op_threefry' in present:
@@ -462,7 +499,7 @@ class NativeModel:
   def sample(self, batch: int, out, seed: int = 0, stream_id: int = 0, init_z=None,
              noise=None, stream: int = 0, rng: str = 'philox', keep=None, keep_mask=None, release=None,
              start_step: Optional[int] = None, steps: Optional[int] = None, sampler: Optional[str] = None,
-             resample=None):
+             resample=None, guidance=None, guide_range=None):
     """rng: the generator of the draws that are not given -- 'philox' (the library's own, keyed by seed and stream_id)
     or 'threefry' (the reference's jax.random draws for PRNGKey(seed), made on the device; stream_id is ignored).
 
@@ -487,7 +524,20 @@ class NativeModel:
     `jump` steps is descended `times` times, the state diffused back up in between under a key of the pass's own.  The
     extra draws are made on the device: not with noise, nor with steps / sampler.  keep_mask is taken as release words
     (1 = known throughout).  times == 1 makes no jump: msd_sample_resample then returns the bits of the call without
-    resample, like None."""
+    resample, like None.
+
+    guidance (a finite float, or `batch` of them: row b takes guidance[b]) / guide_range ((g_lo, g_hi), scan indices of
+    the call's K steps with 0 <= g_lo < g_hi <= K; None = all of them): the classifier-free guidance weight of THIS call
+    in the handle's cfg_weight's place, applied at scan indices in [g_lo, g_hi) only; every other step -- and a row whose
+    weight is exactly 1 -- runs the reference's weight-1 branch, one decoder pass (msd_sample_guided).  guide_range alone
+    takes the handle's weight.  With steps / sampler, every rng and key form, init_z / noise; not with keep / release /
+    resample, nor on a handle created with cfg_weight 1."""
+    if guidance is not None or guide_range is not None:
+      if keep is not None or keep_mask is not None or release is not None or start_step is not None or resample is not None:
+        raise ValueError('guidance / guide_range cannot be combined with keep / keep_mask / release / start_step / resample')
+      weights = check_guidance(self.cfg.cfg_weight if guidance is None else guidance, batch)
+      k_call = self.cfg.num_steps if steps is None else steps
+      g_lo, g_hi = (0, 0) if guide_range is None else check_guide_range(guide_range, k_call)
     few, edit = steps is not None or sampler is not None, release is not None
     if resample is not None:
       jump, times = check_resample(resample)
@@ -527,7 +577,12 @@ class NativeModel:
     keys = (ctypes.c_uint64 * len(seeds))(*seeds), (ctypes.c_uint64 * len(seeds))(*stream_ids)
     # (3) the entry point
     lib, h, kind, draws, tail = self.lib, self.handle, RNGS[rng], (_ptr(init_z), _ptr(noise)), (_ptr(out), stream)
-    if few:
+    if guidance is not None or guide_range is not None:
+      w = (ctypes.c_float * len(weights))(*weights)
+      name, rc = 'msd_sample_guided', lib.msd_sample_guided(h, batch, kind, int(per_row), *keys, *draws, int(steps or 0),
+                                                            -1 if sampler is None else SAMPLERS[sampler], w, len(weights),
+                                                            g_lo, g_hi, *tail)
+    elif few:
       name, rc = 'msd_sample_steps', lib.msd_sample_steps(h, batch, kind, int(per_row), *keys, *draws, int(steps or 0),
                                                           -1 if sampler is None else SAMPLERS[sampler], *tail)
     elif edit and resample is not None:
@@ -805,6 +860,30 @@ def op_sampler_step_release(cfg: MsdConfig, step_index: int, z, out_cond, out_un
   _op_check(lib.msd_op_sampler_step_release(ctypes.byref(cfg), step_index, _ptr(z), _ptr(out_cond), _ptr(out_uncond),
                                             _ptr(noise), _ptr(known_scaled), _ptr(release), n_dims, _ptr(z_out), z.numel(),
                                             stream), 'msd_op_sampler_step_release')
+
+
+def op_sampler_step_guided(cfg: MsdConfig, step_index: int, z, out_cond, out_uncond, noise, weights, z_out, stream: int = 0):
+  """op_sampler_step in the guided form (msd_op_sampler_step_guided): z is [rows, ...] and row b combines with weights[b]
+  (host floats) in cfg.cfg_weight's place; a row's element count must be a multiple of 1024."""
+  lib = load()
+  cfg.struct_size = config_struct_size(lib)
+  w = (ctypes.c_float * len(weights))(*[float(x) for x in weights])
+  _op_check(lib.msd_op_sampler_step_guided(ctypes.byref(cfg), step_index, _ptr(z), _ptr(out_cond), _ptr(out_uncond),
+                                           _ptr(noise), w, len(weights), _ptr(z_out), z.numel(), stream),
+            'msd_op_sampler_step_guided')
+  return z_out
+
+
+def op_sampler_step_multistep_guided(cfg: MsdConfig, step_index: int, z, out_cond, out_uncond, x0_prev, first: bool, weights,
+                                     z_out, stream: int = 0):
+  """op_sampler_step_multistep in the guided form (msd_op_sampler_step_multistep_guided); weights as op_sampler_step_guided."""
+  lib = load()
+  cfg.struct_size = config_struct_size(lib)
+  w = (ctypes.c_float * len(weights))(*[float(x) for x in weights])
+  _op_check(lib.msd_op_sampler_step_multistep_guided(ctypes.byref(cfg), step_index, _ptr(z), _ptr(out_cond), _ptr(out_uncond),
+                                                     _ptr(x0_prev), int(bool(first)), w, len(weights), _ptr(z_out), z.numel(),
+                                                     stream), 'msd_op_sampler_step_multistep_guided')
+  return z_out
 
 
 def op_sampler_step_multistep(cfg: MsdConfig, step_index: int, z, out_cond, out_uncond, x0_prev, first: bool, z_out,

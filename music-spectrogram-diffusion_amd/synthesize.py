@@ -10,6 +10,7 @@ beam/evaluation.py:161-223) on the MI355X path.
       [--regenerate START:STOP [--blend FRAMES] (--edit-mel old_mel.npy | --edit-audio old.wav)]
       [--vary STRENGTH (--edit-mel old_mel.npy | --edit-audio old.wav)]
       [--resample JUMP:TIMES]   (with --regenerate or --vary)
+      [--guidance W] [--guidance-interval LO:HI]
 
 --wav writes 16-bit PCM mono at 16 kHz from the device vocoder: Griffin-Lim over the codec's STFT, a stand-in for the
 reference's SoundStream decoder (which is not built).  --context-audio continues a recording: its last 256 frames are
@@ -39,6 +40,11 @@ Not with --rng jax (the extra draws are made on the device).
 process could render in all of them next) and --sampler names the sampler of the run: dpmpp_2m is the second-order
 DPM-Solver++(2M), deterministic after the initial draw.  Not with --regenerate / --vary.
 
+--guidance W renders this run with the classifier-free guidance weight W in the model's (--cfg-weight) place, on the same
+model; --guidance-interval LO:HI (fractions of diffusion time, 0 <= LO < HI <= 1) applies the guidance only inside that
+part of the scan, and every step outside it runs one decoder pass instead of two (InferenceModel.predict(guidance=,
+guidance_interval=)).  Not with --regenerate / --vary, nor with --cfg-weight 1.
+
 --dry-run tokenises only (no GPU): prints the segment / token statistics the synthesis would see, and with --regenerate
 the plan: the segments touched and the frames each keeps."""
 from __future__ import annotations
@@ -64,6 +70,10 @@ def main(argv=None) -> int:
   ap.add_argument('--sampler', choices=['ddpm', 'ddim', 'dpmpp_2m'], default=None,
                   help="the sampler of this run (default: the configuration's); 'dpmpp_2m' = DPM-Solver++(2M), second order")
   ap.add_argument('--cfg-weight', type=float, default=5.0)
+  ap.add_argument('--guidance', type=float, default=None, metavar='W',
+                  help='the guidance weight of this run (default: the model\'s, --cfg-weight)')
+  ap.add_argument('--guidance-interval', default=None, metavar='LO:HI',
+                  help='apply the guidance only in this part of the scan (fractions of diffusion time); one decoder pass outside')
   ap.add_argument('--seed', type=int, default=0)
   ap.add_argument('--rng', choices=['philox', 'threefry', 'jax'], default='philox',
                   help="'threefry': the reference's jax.random draws for --seed, made on the device; 'jax': the same on the host")
@@ -117,6 +127,13 @@ def main(argv=None) -> int:
     ap.error('--blend FRAMES (>= 0) goes with --regenerate')
   if (args.steps is not None or args.sampler) and (args.regenerate or args.vary is not None):
     ap.error('--steps / --sampler do not go with --regenerate / --vary (few-step edits are not built)')
+  if (args.guidance is not None or args.guidance_interval is not None) and (args.regenerate or args.vary is not None):
+    ap.error('--guidance / --guidance-interval do not go with --regenerate / --vary (guided edits are not built)')
+  if args.guidance_interval is not None:
+    try:
+      args.guidance_interval = interval_pair(args.guidance_interval)
+    except ValueError as e:
+      ap.error(str(e))
 
   if args.resample is not None:
     if not (args.regenerate or args.vary is not None):
@@ -144,6 +161,17 @@ def main(argv=None) -> int:
     few['steps'] = args.steps
   if args.sampler:
     few['sampler'] = args.sampler
+  if args.guidance is not None or args.guidance_interval is not None:
+    from msd_amd import inference
+    k = spec.diffusion.sampler.schedule.num_steps if args.steps is None else args.steps
+    w = spec.diffusion.classifier_free_guidance.eval_condition_weight
+    try:
+      if w == 1.0:
+        raise ValueError('a model with --cfg-weight 1 holds one pass\'s buffers: give it any other weight')
+      inference.plan_guidance(args.guidance, args.guidance_interval, 1, k, w)
+    except ValueError as e:
+      ap.error('--guidance / --guidance-interval: %s' % e)
+    few.update({k_: v for k_, v in (('guidance', args.guidance), ('guidance_interval', args.guidance_interval)) if v is not None})
   ns = midi_io.midi_file_to_note_sequence(args.midi)
   cfg = tokenizer.FrontendConfig.from_spec(spec)
   t0 = time.perf_counter()
@@ -251,6 +279,17 @@ def resample_pair(text: str):
   if jump < 1 or times < 1:
     raise ValueError('--resample wants JUMP >= 1 and TIMES >= 1: %r' % (text,))
   return jump, times
+
+
+def interval_pair(text: str):
+  """'LO:HI' -> (lo, hi), floats with 0 <= lo < hi <= 1; anything else is a ValueError."""
+  try:
+    lo, hi = (float(v) for v in text.split(':'))
+  except ValueError:
+    raise ValueError('--guidance-interval wants LO:HI, two numbers: %r' % (text,))
+  if not 0.0 <= lo < hi <= 1.0:
+    raise ValueError('--guidance-interval wants 0 <= LO < HI <= 1: %r' % (text,))
+  return lo, hi
 
 
 def region_frames(text: str, frame_rate: float):
