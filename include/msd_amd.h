@@ -824,6 +824,68 @@ int msd_op_attention_launch_carrier(msd_attention_launch_args* args, msd_carrier
  * MSD_ERR_UNSUPPORTED: more rows than the waves cover in R touches each). */
 int msd_op_touch_deal(int64_t target_bytes, int32_t row_bytes, int32_t row_pitch, int32_t waves, int32_t* ranges, int32_t capacity);
 
+/* ---- the denoising loss (appended to ABI 7): how well a mel fits the encoded tokens --------------------------------------
+ * The evaluation loss of the reference (models.py loss_fn over diffusion_utils.get_diffusion_training_input and
+ * calculate_loss) at time indices of the handle's own grid, on the device, with no host round trip between evaluations.
+ * One EVALUATION at index i (row i of the handle's step tables, time (i + 1) / num_steps, as msd_decoder_pass), for the
+ * rows of the encoded batch:
+ *   x0    = scale_features(target, clip=True)                      the context path's expression and bits
+ *   z_t   = fmaf(sigma, eps, alpha * x0)                           (alpha, sigma) = sqrt(sigmoid(+-logsnr)) of the TRAIN
+ *                                                                  schedule at the index (msd_get_schedule word 7), computed
+ *                                                                  in double and rounded once -- not the sampler schedule
+ *                                                                  of msd_sample_edit's part-way start
+ *   eps   = eps_dev[j] (the j-th entry of the call's time list), or drawn under the call's keys: MSD_RNG_PHILOX
+ *           sub-sequence 1 + i of (seed, stream_id) = msd_fill_normal(seed, stream_id, 1 + i, ...); MSD_RNG_THREEFRY
+ *           normal(fold_in(PRNGKey(seed), i), [batch | 1, T, n]) = msd_fill_normal_threefry(seed, i, ...); per-row keys as
+ *           in msd_sample_rows.  The draw is a function of the index: an index that appears twice in one call draws the SAME
+ *           eps twice, and its two output rows are equal.
+ *   o     = one decoder pass on z_t, conditional (MSD_LOSS_COND) or unconditional (MSD_LOSS_UNCOND), or both passes in the
+ *           two-pass plan of a guided step (MSD_LOSS_BOTH; MSD_ERR_UNSUPPORTED on a handle created with cfg_weight 1).
+ *           Dropout is off: this is an evaluation (the reference's loss_fn passes enable_dropout=True even in eval; that
+ *           quirk is not restated), and loss_fn's own draws of the time and of the condition drop are the caller's business.
+ *   (eps_hat, x0_hat) = the model-output conversion of the sampler, at the train schedule's log-SNR, for every pass
+ *   element loss = |d| (MSD_LOSS_L1) or d * d (MSD_LOSS_L2) of d_x0 = x0_hat - x0 (MSD_LOSS_X0), d_eps = eps_hat - eps
+ *           (MSD_LOSS_EPS), the larger of the two (MSD_LOSS_MAX_X0_EPS; a NaN stays a NaN) or eps loss + x0 loss
+ *           (MSD_LOSS_X0_AND_EPS), times mask[b, t] (float, any value; NULL = ones)
+ *   out_dev[j][pass][b][t] = the sum over the frame's n_dims elements, float32: a thread sums its four consecutive
+ *           elements left to right, the frame's n_dims / 4 thread sums are added as a pairwise tree (level s = 1, 2, 4, ...:
+ *           thread t with t % 2s == 0 adds the sum of thread t + s).  passes = 2 for MSD_LOSS_BOTH (0 = conditional), else 1.
+ *           Sums over frames, rows and times are the caller's, in whatever precision it likes.
+ * times_host: n_times >= 1 indices in [0, num_steps), any order, repeats allowed.  loss_type / loss_norm are arguments of
+ * the call, not of msd_config.  Needs msd_encode; batch must be the encoded batch; n_dims % 4 == 0 and 1024 % n_dims == 0
+ * (MSD_ERR_UNSUPPORTED otherwise; every shipped configuration has 128); per-row keys need targets_length * n_dims % 1024 == 0.
+ * Every refusal comes before any device work, names the offending value and leaves the handle usable.  The call ends
+ * with one synchronisation and the half-plane range check (MSD_ERR_RANGE).  It overwrites the sampler's state (z, the scan
+ * index, the key table), which every sampling call writes afresh; its captured graphs are the handle's (msd_reset_graph
+ * drops them) and are kept apart from the step graphs. */
+enum { MSD_LOSS_COND = 0, MSD_LOSS_UNCOND = 1, MSD_LOSS_BOTH = 2 };
+enum { MSD_LOSS_X0 = 0, MSD_LOSS_EPS = 1, MSD_LOSS_MAX_X0_EPS = 2, MSD_LOSS_X0_AND_EPS = 3 };
+enum { MSD_LOSS_L1 = 0, MSD_LOSS_L2 = 1 };
+typedef struct msd_loss_args {
+  int32_t struct_size;         /* sizeof(msd_loss_args) */
+  int32_t batch;               /* rows; = the encoded batch */
+  int32_t rng;                 /* MSD_RNG_*: the generator of eps when eps_dev is NULL */
+  int32_t per_row;             /* 0: seeds[0] / stream_ids[0] key one draw over [batch, T, n]; else one key per row */
+  const uint64_t* seeds;       /* host [per_row ? batch : 1] */
+  const uint64_t* stream_ids;  /* host, same length, or NULL = zeros */
+  const float* target_dev;     /* [batch, T, n] the mel, mel units */
+  const float* mask_dev;       /* [batch, T] float, or NULL = ones */
+  const float* eps_dev;        /* [n_times][batch, T, n], or NULL = drawn */
+  const int32_t* times_host;   /* [n_times] time indices */
+  int32_t n_times;
+  int32_t conditioning;        /* MSD_LOSS_COND / _UNCOND / _BOTH */
+  int32_t loss_type;           /* MSD_LOSS_X0 / _EPS / _MAX_X0_EPS / _X0_AND_EPS */
+  int32_t loss_norm;           /* MSD_LOSS_L1 / _L2 */
+  float* out_dev;              /* [n_times][passes][batch][T] */
+} msd_loss_args;
+int msd_loss(msd_model* m, const msd_loss_args* args, void* stream);
+/* The loss kernel alone (unit test): out_dev[n / n_dims] = the per-frame loss of ONE pass's model output o_dev at step_index
+ * of cfg's tables, over the caller's z, x0 (model units), eps and mask (float [n / n_dims] or NULL), all device [n].
+ * n % n_dims == 0, n_dims as above.  Synchronises. */
+int msd_op_diffusion_loss(const msd_config* cfg, int step_index, int loss_type, int loss_norm, const float* o_dev,
+                          const float* z_dev, const float* x0_dev, const float* eps_dev, const float* mask_dev, int n_dims,
+                          float* out_dev, int64_t n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -582,6 +582,54 @@ struct SamplerMultistepGuidedParams : SamplerMultistepParams {
 void launch_sampler_step(const SamplerGuidedParams& sp, hipStream_t s);
 void launch_sampler_step(const SamplerMultistepGuidedParams& sp, hipStream_t s);
 
+// The denoising loss (msd_loss; kernels and launches: loss_tail.h).  What changes from call to call -- the caller's buffers,
+// the loss form, the time list -- lives in ONE device struct the handle owns, so a captured (diffuse, decoder, loss) graph
+// serves every call; `cursor` is the position in the time list, double-buffered like the scan index: loss_diffuse_kernel
+// reads word 0 and its last block copies it to word 1, diffusion_loss_kernel reads word 1 and its last block writes
+// word 0 := word 1 + 1 -- nobody reads the word a launch writes.
+enum { kLossX0 = 0, kLossEps, kLossMaxX0Eps, kLossX0AndEps };   // = MSD_LOSS_X0 ...
+enum { kLossL1 = 0, kLossL2 };                                   // = MSD_LOSS_L1, _L2
+enum { kLossTimeAlpha = 0, kLossTimeSigma, kLossTimeIndex, kLossTimePad, kLossTimeWords };   // a row of LossCall::times
+struct LossCall {
+  const float* target;   // [n] the caller's mel, mel units (loss_diffuse_kernel)
+  const float* mask;     // [n / n_dims] float, or nullptr = ones
+  const float* eps;      // [n_times][n] the caller's draws, or nullptr = drawn in both kernels
+  float* out;            // [n_times][passes][n / n_dims]
+  const float* times;    // [n_times][kLossTimeWords]: {alpha, sigma, bits of the time index i, 0}
+  int32_t type, norm;    // kLoss*
+  int32_t cursor[2];
+};
+static_assert(sizeof(LossCall) == 56, "five pointers and four words");
+struct LossDiffuseParams {
+  LossCall* call;
+  float* x0;            // [n] out: scale_features(clip=True) of the target
+  float* z;             // [n] out
+  h16_t* z_hi;          // out: operand planes of z (z_lo may be null: one-plane precisions)
+  h16_t* z_lo;
+  const uint32_t* keys; // [rows][kRngWords] (SamplerParams::rng_key)
+  int row_blocks = 1 << 30;   // SamplerParams::row_blocks
+  int n;                // % 4 == 0
+  float fmin, fmax;     // the codec's range
+  int* step_ptr = nullptr;   // the device scan index: both words := i; nullptr = none
+  unsigned* sat = nullptr;   // half-plane range flag (common.h RangeCheck)
+  unsigned sat_tag = 1;
+};
+struct LossParams {
+  LossCall* call;
+  const float* o;       // [passes][n] the model output
+  const float* z;       // [n]
+  const float* x0;      // [n]
+  const float* coef;    // [N][kCoefCount]
+  const uint32_t* keys; // as above
+  int row_blocks = 1 << 30;
+  int n;                // per pass; % n_dims == 0
+  int passes;           // 1 or 2
+  int n_dims;           // % 4 == 0, 1024 % n_dims == 0: a frame is n_dims / 4 consecutive threads of one block
+  int model_output = kOutEps;
+};
+void launch_loss_diffuse(const LossDiffuseParams& p, hipStream_t s);
+void launch_diffusion_loss(const LossParams& p, hipStream_t s);
+
 // g[step][slot][k] = gamma[k] * (film_scale[step][slot][k] + 1): the column multiplier of a
 // FiLM-modulated RMSNorm, tabulated for every step (folded-norm GEMM epilogues, gemm_h16.h)
 __global__ void build_g_kernel(const float* film, const float* gamma, float* g, int n_steps, int slots,

@@ -212,6 +212,15 @@ struct msd_model {
   struct StepTables { std::vector<float> h_coef; float* coef = nullptr; float* coef_ms = nullptr; };
   std::map<int, StepTables> step_tables;
   float* x0_prev = nullptr;
+  // msd_loss: the target in model units [Bmax][T][n], the per-call words of the two loss kernels (elementwise.h LossCall) and
+  // the call's time rows [n_times][kLossTimeWords]; allocated on first use (outside stream capture) and owned by the handle,
+  // so the captured loss graphs hold stable addresses.  The time rows are reached THROUGH the call words: they may grow.
+  float* loss_x0 = nullptr;
+  LossCall* d_loss_call = nullptr;
+  LossCall h_loss_call = {};           // host staging of that upload
+  float* d_loss_times = nullptr;
+  size_t loss_times_cap = 0;           // floats
+  std::vector<float> h_loss_times;
   int* d_step = nullptr;       // [2]
   int* d_nkeys_self = nullptr; // [passes*Bmax] = T
   int* d_nkeys_cross = nullptr;// [n_cross][Bmax] valid keys per key region and song
@@ -241,6 +250,11 @@ struct msd_model {
   static_assert(std::has_unique_object_representations<GraphKey>::value, "GraphKey (StepPlan included) must not have padding bytes");
   struct StepGraphs { GraphKey key; hipGraphExec_t exec = nullptr, exec1 = nullptr; };
   std::vector<StepGraphs> graphs;
+  // msd_loss's graphs: ONE evaluation (diffuse, decoder pass(es), loss) per plan -- the conditional, the unconditional
+  // and the two-pass plan differ bytewise -- in a list of their own, so that they neither evict nor alter a cached set of step
+  // graphs; msd_reset_graph drops both lists.
+  struct LossGraph { StepPlan plan; hipGraphExec_t exec = nullptr; };
+  std::vector<LossGraph> loss_graphs;
   int graph_steps = 8;              // DDPM steps per graph launch (msd_config.graph_steps; 1 -> 4 -> 10: 1.2000 -> 1.1963 -> 1.1955 ms/step)
   bool prefetch = true;        // producers warm the next GEMM's weights (msd_config.weight_prefetch; default: by model size)
   bool dedup_layer0 = true;    // S5 (decoder_layers); msd_config.dedup_layer0 = 2 turns it off for A/B and bitwise tests
@@ -2540,6 +2554,9 @@ int msd_reset_graph(msd_model* m) {
     if (e.exec1) (void)hipGraphExecDestroy(e.exec1);
   }
   m->graphs.clear();
+  for (auto& e : m->loss_graphs)
+    if (e.exec) (void)hipGraphExecDestroy(e.exec);
+  m->loss_graphs.clear();
   return MSD_OK;
 }
 
@@ -2570,6 +2587,127 @@ int msd_decoder_pass(msd_model* m, int batch, int step_index, const float* z_dev
   if (c.err != hipSuccess) return fail(m, MSD_ERR_HIP, "decoder pass failed: %s", hipGetErrorString(c.err));
   HIP_TRY(m, hipMemcpyAsync(eps_out_dev, m->eps, n * sizeof(float), hipMemcpyDeviceToDevice, s));
   return check_range(m, s, "msd_decoder_pass");   // synchronises
+}
+
+// ---- msd_loss: the denoising loss at time indices of the handle's grid (kernels: loss_tail.h) --------------------------
+// One evaluation = (loss_diffuse_kernel, decoder_eval(publish_step = false), diffusion_loss_kernel), captured once per plan
+// and replayed once per time: the time rows, the cursor and the keys live in device memory.
+static int enqueue_loss_eval(msd_model* m, const StepPlan& plan, hipStream_t s) {
+  const int n = plan.batch * m->T * m->ND;
+  const int row_blocks = m->T * m->ND % kRngRowBlock == 0 ? m->T * m->ND / kRngRowBlock : 1 << 30;   // (enqueue_step's)
+  LossDiffuseParams dp;
+  dp.call = m->d_loss_call; dp.x0 = m->loss_x0; dp.z = m->z;
+  dp.z_hi = m->zp.p[0]; dp.z_lo = m->NP == 2 ? m->zp.p[1] : nullptr;
+  dp.keys = m->d_rng_key; dp.row_blocks = row_blocks; dp.n = n;
+  dp.fmin = m->cfg.feature_min; dp.fmax = m->cfg.feature_max;
+  dp.step_ptr = m->d_step; dp.sat = m->d_sat; dp.sat_tag = (unsigned)KC_SAMPLER + 1u;
+  Ctx c{m, s};
+  c.begin(KC_SAMPLER);
+  launch_loss_diffuse(dp, s);
+  c.end(KC_SAMPLER);
+  decoder_eval(c, plan, /*publish_step=*/false);
+  LossParams lp;
+  lp.call = m->d_loss_call; lp.o = m->eps; lp.z = m->z; lp.x0 = m->loss_x0; lp.coef = m->d_coef;
+  lp.keys = m->d_rng_key; lp.row_blocks = row_blocks; lp.n = n; lp.passes = plan.P; lp.n_dims = m->ND;
+  lp.model_output = m->cfg.model_output;
+  c.begin(KC_SAMPLER);
+  launch_diffusion_loss(lp, s);
+  c.end(KC_SAMPLER);
+  if (c.err != hipSuccess) return fail(m, MSD_ERR_HIP, "loss evaluation failed: %s", hipGetErrorString(c.err));
+  return MSD_OK;
+}
+
+static int find_loss_graph(msd_model* m, const StepPlan& plan, hipStream_t s, hipGraphExec_t* out) {
+  for (auto& e : m->loss_graphs)
+    if (memcmp(&e.plan, &plan, sizeof(plan)) == 0) { *out = e.exec; return MSD_OK; }
+  if (m->loss_graphs.size() >= 6) {   // (a handle that cycles through more shapes than that re-captures; the step graphs stay)
+    for (auto& e : m->loss_graphs) (void)hipGraphExecDestroy(e.exec);
+    m->loss_graphs.clear();
+  }
+  hipGraph_t graph = nullptr;
+  HIP_TRY(m, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+  const int rc = enqueue_loss_eval(m, plan, s);
+  const hipError_t ce = hipStreamEndCapture(s, &graph);
+  if (ce != hipSuccess || rc) {
+    if (graph) (void)hipGraphDestroy(graph);
+    return rc ? rc : fail(m, MSD_ERR_HIP, "loss graph capture failed: %s", hipGetErrorString(ce));
+  }
+  msd_model::LossGraph g;
+  memcpy(&g.plan, &plan, sizeof(plan));
+  const hipError_t ie = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(graph);
+  if (ie != hipSuccess) return fail(m, MSD_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie));
+  m->loss_graphs.push_back(g);
+  *out = g.exec;
+  return MSD_OK;
+}
+
+int msd_loss(msd_model* m, const msd_loss_args* a, void* stream) {
+  if (!m) return MSD_ERR_INVALID_ARGUMENT;
+  if (!a || a->struct_size != (int32_t)sizeof(msd_loss_args))
+    return fail(m, MSD_ERR_INVALID_ARGUMENT, "msd_loss_args.struct_size %d != %d", a ? a->struct_size : 0, (int)sizeof(msd_loss_args));
+  // every refusal in front of any device work
+  if (!m->encoded) return fail(m, MSD_ERR_BAD_STATE, "msd_encode has not run");
+  if (a->batch != m->encoded_batch) return fail(m, MSD_ERR_INVALID_ARGUMENT, "batch %d != encoded batch %d", a->batch, m->encoded_batch);
+  if (a->rng != MSD_RNG_PHILOX && a->rng != MSD_RNG_THREEFRY) return fail(m, MSD_ERR_INVALID_ARGUMENT, "unknown rng %d", a->rng);
+  if (a->conditioning != MSD_LOSS_COND && a->conditioning != MSD_LOSS_UNCOND && a->conditioning != MSD_LOSS_BOTH)
+    return fail(m, MSD_ERR_INVALID_ARGUMENT, "unknown conditioning %d", a->conditioning);
+  if (a->loss_type < MSD_LOSS_X0 || a->loss_type > MSD_LOSS_X0_AND_EPS) return fail(m, MSD_ERR_INVALID_ARGUMENT, "Unknown diffusion loss_type: %d", a->loss_type);
+  if (a->loss_norm != MSD_LOSS_L1 && a->loss_norm != MSD_LOSS_L2) return fail(m, MSD_ERR_INVALID_ARGUMENT, "Unknown diffusion loss norm: %d", a->loss_norm);
+  if (a->n_times < 1) return fail(m, MSD_ERR_INVALID_ARGUMENT, "n_times %d < 1", a->n_times);
+  if (!a->times_host || !a->target_dev || !a->out_dev || !a->seeds)
+    return fail(m, MSD_ERR_INVALID_ARGUMENT, "times_host, target_dev, out_dev or seeds is null");
+  for (int j = 0; j < a->n_times; ++j)
+    if (a->times_host[j] < 0 || a->times_host[j] >= m->N)
+      return fail(m, MSD_ERR_INVALID_ARGUMENT, "time index %d (entry %d) outside [0, %d)", a->times_host[j], j, m->N);
+  if (m->ND % 4 || 1024 % m->ND)
+    return fail(m, MSD_ERR_UNSUPPORTED, "the loss needs n_dims %% 4 == 0 and 1024 %% n_dims == 0 (got %d)", m->ND);
+  const int64_t row_n = (int64_t)m->T * m->ND;
+  if (a->per_row && row_n % kRngRowBlock)
+    return fail(m, MSD_ERR_UNSUPPORTED, "per-row keys need targets_length * n_dims %% %d == 0 (got %lld)", (int)kRngRowBlock, (long long)row_n);
+  if (a->conditioning == MSD_LOSS_BOTH && m->passes == 1)
+    return fail(m, MSD_ERR_UNSUPPORTED, "a handle created with cfg_weight 1 holds one pass's buffers and takes conditioning %d or %d, not both (%d): "
+                "create the handle with any weight != 1", (int)MSD_LOSS_COND, (int)MSD_LOSS_UNCOND, (int)MSD_LOSS_BOTH);
+  // the handle's buffers, each on its own (a call after a failed allocation tries again for the one that is missing)
+  if (!m->loss_x0)
+    if (int rc = dalloc(m, &m->loss_x0, (size_t)m->Bmax * m->T * m->ND)) return rc;
+  if (!m->d_loss_call)
+    if (int rc = dalloc(m, &m->d_loss_call, 1)) return rc;
+  const size_t time_words = (size_t)a->n_times * kLossTimeWords;
+  if (time_words > m->loss_times_cap) {   // (the stream is idle: the last call ended with its synchronisation)
+    if (m->d_loss_times) {
+      auto it = std::find(m->allocs.begin(), m->allocs.end(), static_cast<void*>(m->d_loss_times));
+      if (it != m->allocs.end()) m->allocs.erase(it);
+      (void)hipFree(m->d_loss_times);
+      m->d_loss_times = nullptr; m->loss_times_cap = 0;
+    }
+    if (int rc = dalloc(m, &m->d_loss_times, time_words)) return rc;
+    m->loss_times_cap = time_words;
+  }
+  hipStream_t s;
+  if (int rc = choose_stream(m, stream, &s)) return rc;
+  if (int rc = arm_range(m, s)) return rc;
+  // the call's words: the time rows ((alpha, sigma) of the TRAIN schedule's log-SNR at the index, in double, rounded once),
+  // the caller's buffers and the loss form, the cursor at 0; members: the copies below may still read them on return
+  m->h_loss_times.assign(time_words, 0.f);
+  for (int j = 0; j < a->n_times; ++j) {
+    float* row = &m->h_loss_times[(size_t)j * kLossTimeWords];
+    const int32_t i = a->times_host[j];
+    diffuse_coefs(m->h_coef[(size_t)i * kCoefCount + kCoefMLogsnr], &row[kLossTimeAlpha], &row[kLossTimeSigma]);
+    memcpy(&row[kLossTimeIndex], &i, sizeof(i));
+  }
+  HIP_TRY(m, hipMemcpyAsync(m->d_loss_times, m->h_loss_times.data(), time_words * sizeof(float), hipMemcpyHostToDevice, s));
+  m->h_loss_call = LossCall{a->target_dev, a->mask_dev, a->eps_dev, a->out_dev, m->d_loss_times, a->loss_type, a->loss_norm, {0, 0}};
+  HIP_TRY(m, hipMemcpyAsync(m->d_loss_call, &m->h_loss_call, sizeof(LossCall), hipMemcpyHostToDevice, s));
+  HIP_TRY(m, upload_rng_keys(m, a->batch, a->rng, sample_keys(a->per_row, a->seeds, a->stream_ids), s));
+  HIP_TRY(m, hipMemsetAsync(m->att_tickets, 0, (size_t)m->att_ticket_count * sizeof(int), s));
+  // (no synchronisation here: every upload above reads a member of the handle, which outlives the call)
+  const StepPlan plan = a->conditioning == MSD_LOSS_BOTH ? plan_cfg_step(m, a->batch)
+                                                         : plan_step(m, a->batch, 1, a->conditioning == MSD_LOSS_COND, false);
+  hipGraphExec_t exec = nullptr;
+  if (int rc = find_loss_graph(m, plan, s, &exec)) return rc;
+  for (int j = 0; j < a->n_times; ++j) HIP_TRY(m, hipGraphLaunch(exec, s));
+  return check_range(m, s, "msd_loss");   // the call's single synchronisation
 }
 
 int msd_get_schedule(const msd_model* m, float* host_out) {
@@ -2604,6 +2742,7 @@ int msd_debug_read(msd_model* m, const char* buffer, float* host_out, int64_t ma
   else if (b == "x") { f32 = m->x; count = Mmax * m->D; }
   else if (b == "eps") { f32 = m->eps; count = Mmax * m->ND; }
   else if (b == "z") { f32 = m->z; count = (int64_t)m->Bmax * m->T * m->ND; }
+  else if (b == "loss_x0" && m->loss_x0) { f32 = m->loss_x0; count = (int64_t)m->Bmax * m->T * m->ND; }
   else if (b == "ssq") { f32 = m->ssq; count = Mmax * (m->D / kNarrowTile); }
   else if (b == "y") { pl = &m->y; count = Mmax * m->D; }
   else if (b == "qk") { pl = &m->qk; count = Mmax * 2 * m->J; }
@@ -2818,3 +2957,4 @@ int msd_vocoder_decode(msd_vocoder* v, int batch, int n_frames, const float* log
 #include "keep_frames_tail.h"   // last on purpose: see the file
 #include "multistep_tail.h"     // ... and behind it, for the same reason
 #include "guided_tail.h"        // ... and the guided instances behind those
+#include "loss_tail.h"          // ... and the two kernels of msd_loss behind everything

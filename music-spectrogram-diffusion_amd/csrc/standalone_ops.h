@@ -1072,6 +1072,40 @@ int msd_op_renoise(const msd_config* cfg, int from_level, int to_level, const fl
   return kit.finish();
 }
 
+// diffusion_loss_kernel alone (tests/test_gpu_loss.py): one pass, the caller's eps, a one-row time list at cursor 0
+int msd_op_diffusion_loss(const msd_config* cfg, int step_index, int loss_type, int loss_norm, const float* o_dev,
+                          const float* z_dev, const float* x0_dev, const float* eps_dev, const float* mask_dev, int n_dims,
+                          float* out_dev, int64_t n, void* stream) {
+  if (!cfg || cfg->struct_size != (int32_t)sizeof(msd_config) || !o_dev || !z_dev || !x0_dev || !eps_dev || !out_dev ||
+      n_dims <= 0 || n <= 0 || n % n_dims || n > 0x7FFFFFFFll - 1023 || step_index < 0 || step_index >= cfg->num_steps ||
+      loss_type < MSD_LOSS_X0 || loss_type > MSD_LOSS_X0_AND_EPS || (loss_norm != MSD_LOSS_L1 && loss_norm != MSD_LOSS_L2))
+    return MSD_ERR_INVALID_ARGUMENT;   // (n: the last block's element index, blocks of 1024, stays an int)
+  if (n_dims % 4 || 1024 % n_dims) return MSD_ERR_UNSUPPORTED;
+  std::vector<float> rows;
+  std::string why;
+  if (!build_coef_rows(*cfg, &rows, &why)) return MSD_ERR_INVALID_ARGUMENT;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  OpKit kit(s, 1);
+  float* coef = kit.get<float>(rows.size());
+  float* times = kit.get<float>(kLossTimeWords);
+  LossCall* call = kit.get<LossCall>(1);
+  if (!coef || !times || !call) return MSD_ERR_HIP;
+  float row[kLossTimeWords] = {0.f, 0.f, 0.f, 0.f};
+  const int32_t i = step_index;
+  memcpy(&row[kLossTimeIndex], &i, sizeof(i));
+  const LossCall lc = {nullptr, mask_dev, eps_dev, out_dev, times, loss_type, loss_norm, {0, 0}};
+  if (hipMemcpyAsync(coef, rows.data(), rows.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(times, row, sizeof(row), hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(call, &lc, sizeof(lc), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
+    return MSD_ERR_HIP;
+  LossParams lp;   // (no keys: the caller's eps)
+  lp.call = call; lp.o = o_dev; lp.z = z_dev; lp.x0 = x0_dev; lp.coef = coef; lp.keys = nullptr; lp.n = (int)n; lp.passes = 1;
+  lp.n_dims = n_dims; lp.model_output = cfg->model_output;
+  launch_diffusion_loss(lp, s);
+  if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return MSD_ERR_HIP;
+  return MSD_OK;
+}
+
 // x_out = x_in + a . w1 ;  h_out = (RMSNorm(x_out; gamma) (.) (film_scale + 1) + film_bias) . w2
 // folded != 0: the product's path -- EpiResidualNorm (y = x (.) g planes + partial sums of squares)
 // then a consumer GEMM whose epilogue applies rstd and the tabulated bias.W2;

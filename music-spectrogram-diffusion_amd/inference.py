@@ -213,6 +213,7 @@ def _load_checkpoint(path, spec: config_lib.ModelSpec) -> Tuple[Dict[str, np.nda
 RNG_MODES = ('philox', 'threefry', 'jax')
 plan_steps = native.plan_steps   # (num_steps, steps) -> (row_offset, stride) of a few-step call; ValueError names the divisors
 plan_resample = native.plan_resample   # (start_step, jump, times) -> the steps and jumps of a call with resampling, in order
+plan_loss_times = native.plan_loss_times   # (num_steps, times) -> the time indices of a loss call: K -> the stratified grid
 
 
 def plan_region(n_frames: int, segment_frames: int, start: int, stop: int):
@@ -756,6 +757,146 @@ class InferenceModel(object):
         z, nz = jax_random.reference_noise(sd, (1, t, n), steps)
         drawn[sd] = (torch.as_tensor(z).to(self.device), torch.as_tensor(nz).to(self.device))
     return (torch.cat([drawn[sd][0] for sd in seeds], dim=0), torch.cat([drawn[sd][1] for sd in seeds], dim=1))
+
+  # -- the denoising loss: how well a mel fits a set of tokens (models.py loss_fn as an evaluation) ---------------
+  def loss(self, batch: Mapping[str, Any], times=16, seed: Union[int, Sequence[int]] = 0,
+           segment: Union[int, Sequence[int]] = 0, rng: Optional[str] = None, conditioning: str = 'cond',
+           loss_type: Optional[str] = None, loss_norm: Optional[str] = None, eps=None):
+    """The reference's evaluation loss (models.py loss_fn over diffusion_utils.get_diffusion_training_input and
+    calculate_loss) of a given mel under a given set of tokens, at time indices of the model's own step grid, on the device
+    (msd_loss): diffuse the target to the time, run ONE decoder pass, compare the prediction with the noise and the
+    target per element, mask and sum.
+
+    batch: predict's features plus ``decoder_target_tokens`` (the mel, [B, T, n], mel units) and optionally
+      ``decoder_target_mask`` ([B, T], any float; default ones) -- loss_fn's names.
+    times: an integer K (1 <= K <= N: the stratified grid of plan_loss_times) or a sequence of time indices in [0, N);
+      index i is time (i + 1) / N.  The reference draws ONE random time per row; an average over a fixed grid is the
+      evaluation of the same expectation with no noise from the choice of times.
+    seed / segment / rng: the keys of the eps draws, as in predict ('philox' or 'threefry'; per-row sequences work the
+      same way; not 'jax': pass eps= instead).  The draw at index i is a function of (key, i): an index that appears
+      twice draws the same eps twice.  eps [K, B, T, n]: explicit draws instead.
+    conditioning: 'cond' (the tokens and the context as encoded), 'uncond' (the sampler's unconditional pass), or 'both'
+      (the two passes of a guided step in one batched launch; not on a model created with weight 1).
+    loss_type ('x0', 'eps', 'max_x0_eps', 'x0_and_eps') / loss_norm ('l1', 'l2'): calculate_loss's; None = the spec's
+      (eps / l1 for every shipped configuration).  Dropout is off: this is an evaluation.
+    Returns a dict of float64 NumPy values, sums taken on the host from the device's per-frame float32 sums:
+      'loss' [passes] the sum over masked elements, mean over times; 'per_row' [passes, B]; 'per_frame' [passes, B, T];
+      'per_time' [K, passes, B]; 'times' the indices; 'target_frames' the sum of the mask.
+    The range fallback repeats the call on the bfloat16-plane build, as predict does.  Argument errors are ValueErrors
+    raised before any device work."""
+    n_steps = self.spec.diffusion.sampler.schedule.num_steps
+    idx = native.plan_loss_times(n_steps, times)
+    if rng is None:
+      rng = self.rng
+    if rng == 'jax' and eps is None:
+      raise ValueError("loss() draws eps on the device: rng must be 'philox' or 'threefry' (or pass eps=), not 'jax'")
+    if rng not in RNG_MODES:
+      raise ValueError('rng must be one of %s: %r' % (RNG_MODES, rng))
+    if conditioning not in native.LOSS_CONDITIONINGS:
+      raise ValueError('conditioning must be one of %s: %r' % (sorted(native.LOSS_CONDITIONINGS), conditioning))
+    if conditioning == 'both' and self.spec.diffusion.classifier_free_guidance.eval_condition_weight == 1.0:
+      raise ValueError("conditioning='both' needs a model created with a guidance weight != 1 (a weight-1 model holds one pass's buffers)")
+    loss_type = getattr(self.spec.diffusion, 'loss_type', 'eps') if loss_type is None else loss_type
+    loss_norm = getattr(self.spec.diffusion, 'loss_norm', 'l1') if loss_norm is None else loss_norm
+    if loss_type not in native.LOSS_TYPES:
+      raise ValueError('Unknown diffusion loss_type: %r (one of %s)' % (loss_type, sorted(native.LOSS_TYPES)))
+    if loss_norm not in native.LOSS_NORMS:
+      raise ValueError('Unknown diffusion loss norm: %r (one of %s)' % (loss_norm, sorted(native.LOSS_NORMS)))
+    if 'decoder_target_tokens' not in batch:
+      raise ValueError("loss() needs batch['decoder_target_tokens']: the mel to score, [batch, %d, %d]"
+                       % (self.targets_length, self.audio_codec.n_dims))
+    b, t, n = np.shape(batch['encoder_input_tokens'])[0], self.targets_length, self.audio_codec.n_dims
+    if tuple(np.shape(batch['decoder_target_tokens'])) != (b, t, n):
+      raise ValueError('decoder_target_tokens must be [batch, %d, %d] = %r: got %r'
+                       % (t, n, (b, t, n), tuple(np.shape(batch['decoder_target_tokens']))))
+    mask = batch.get('decoder_target_mask')
+    if mask is not None and tuple(np.shape(mask)) != (b, t):
+      raise ValueError('decoder_target_mask must be [batch, %d]: got %r' % (t, tuple(np.shape(mask))))
+    if eps is not None and tuple(np.shape(eps)) != (len(idx), b, t, n):
+      raise ValueError('eps must be [times, batch, %d, %d] = %r: got %r' % (t, n, (len(idx), b, t, n), tuple(np.shape(eps))))
+    args = (batch, idx, seed, segment, rng, conditioning, loss_type, loss_norm, eps)
+    try:
+      return self._loss_once(*args)
+    except native.RangeError:
+      if not (self.range_fallback and self.precision in ('f16x3', 'f16')):
+        raise
+      import warnings
+      new = 'bf16x3' if self.precision == 'f16x3' else 'bf16'
+      warnings.warn("an activation left the half-plane range (|x| > 65504): switching this model from precision "
+                    "'%s' to '%s' (bfloat16 planes) and repeating the call" % (self.precision, new), RuntimeWarning)
+      self.precision = new
+      if self._native is not None:
+        self._native.close()
+      self._native = None
+      return self._loss_once(*args)
+
+  def _loss_once(self, batch, idx, seed, segment, rng, conditioning, loss_type, loss_norm, eps):
+    torch = self._torch
+    nm = self._get_native()
+    dev = self.device
+    tokens = _to_numpy(batch['encoder_input_tokens'])
+    if tokens.dtype.kind not in 'iu':
+      raise ValueError('Input type must be an integer or unsigned integer.')
+    tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+    b = tokens.shape[0]
+    if tokens.ndim != 2 or tokens.shape[1] != self.inputs_length:
+      raise ValueError('encoder_input_tokens must be [batch, %d]' % self.inputs_length)
+    if b > self.batch_size:
+      raise ValueError('batch %d exceeds batch_size %d' % (b, self.batch_size))
+    t, n = self.targets_length, self.audio_codec.n_dims
+    passes = 2 if conditioning == 'both' else 1
+    with torch.cuda.device(dev):
+      self._stream.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.device(dev), torch.cuda.stream(self._stream):
+      s = self._stream.cuda_stream
+      ctx = cmask = None
+      if self.targets_context_length is not None:
+        ctx = _to_device(torch, batch['encoder_continuous_inputs'], dev, torch.float32)
+        if tuple(ctx.shape) != (b, self.targets_context_length, n):
+          raise ValueError('encoder_continuous_inputs must be [batch, %d, %d]' % (self.targets_context_length, n))
+        cmask = np.ascontiguousarray(_to_numpy(batch['encoder_continuous_mask']), dtype=np.int32)
+        if cmask.shape != (b, self.targets_context_length):
+          raise ValueError('encoder_continuous_mask must be [batch, %d]' % self.targets_context_length)
+      nm.encode(b, tokens, ctx, cmask, stream=s)
+      target = _to_device(torch, batch['decoder_target_tokens'], dev, torch.float32).contiguous()
+      mask = batch.get('decoder_target_mask')
+      mask_d = None if mask is None else _to_device(torch, mask, dev, torch.float32).contiguous()
+      eps_d = None if eps is None else _to_device(torch, eps, dev, torch.float32).contiguous()
+      out = torch.empty((len(idx), passes, b, t), dtype=torch.float32, device=dev)
+      if not (np.isscalar(seed) and np.isscalar(segment)):
+        seed, segment = native.row_keys(b, seed, segment)
+      nm.loss(b, target, out, idx, seed=seed, stream_id=segment, rng='threefry' if rng == 'threefry' else 'philox',
+              conditioning=conditioning, loss_type=loss_type, loss_norm=loss_norm, mask=mask_d, eps=eps_d, stream=s)
+      self._stream.synchronize()
+    frames = out.cpu().numpy().astype(np.float64)   # [K, passes, B, T]
+    per_time = frames.sum(axis=3)
+    per_frame = frames.mean(axis=0)
+    per_row = per_frame.sum(axis=2)
+    return {'loss': per_row.sum(axis=1), 'per_row': per_row, 'per_frame': per_frame, 'per_time': per_time,
+            'times': list(idx),
+            'target_frames': float(b * t) if mask is None else float(np.asarray(_to_numpy(mask), np.float64).sum())}
+
+  def score_sequence(self, song, segments_tokens: Sequence[np.ndarray], times=16, seed: int = 0,
+                     conditioning: str = 'cond', always_mask_context: bool = False, rng: Optional[str] = None):
+    """The denoising loss of a whole song under its tokens, teacher-forced: segment k of `song` ([1, K * T, n], mel units;
+    NumPy or a device tensor) is scored by loss() with segment k - 1 OF THE GIVEN SONG as context (zeros and mask 0 for
+    segment 0 and ``always_mask_context``), keyed (seed, k); ``rng``: loss()'s ('philox' or 'threefry'; None = the model's).
+    Returns {'per_frame': [passes, K * T], 'per_segment':
+    [passes, K], 'loss': [passes], 'times'}: per-frame losses (mean over times) and their sums, float64."""
+    t = self.targets_length
+    self._check_song(song, segments_tokens)
+    idx = native.plan_loss_times(self.spec.diffusion.sampler.schedule.num_steps, times)
+    torch = self._torch
+    mel = _to_device(torch, song, self.device, torch.float32)
+    frames = []
+    for k, toks in enumerate(segments_tokens):
+      no_ctx = always_mask_context or k == 0 or self.targets_context_length is None
+      batch = self._segment_batch(toks, None if no_ctx else mel[:, (k - 1) * t:k * t].clone(), no_ctx)
+      batch['decoder_target_tokens'] = mel[:, k * t:(k + 1) * t].clone()
+      frames.append(self.loss(batch, times=idx, seed=seed, segment=k, rng=rng, conditioning=conditioning)['per_frame'][:, 0])
+    per_frame = np.concatenate(frames, axis=1)
+    per_segment = np.stack([f.sum(axis=1) for f in frames], axis=1)
+    return {'per_frame': per_frame, 'per_segment': per_segment, 'loss': per_segment.sum(axis=1), 'times': idx}
 
   # -- InferSong.process segment loop (beam/evaluation.py:161-223) ---------------------
   def predict_sequence(self, segments_tokens: Sequence[np.ndarray], seed: int = 0,

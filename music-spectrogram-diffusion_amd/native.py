@@ -79,7 +79,50 @@ EXPORTED_SYMBOLS = (
     # (appended to ABI 7) known-frame edits with resampling jumps (RePaint) in the sampler scan
     'msd_sample_resample', 'msd_op_renoise',
     # (appended to ABI 7) a guidance weight per call or per row, applied in an interval of the scan
-    'msd_sample_guided', 'msd_op_sampler_step_guided', 'msd_op_sampler_step_multistep_guided')
+    'msd_sample_guided', 'msd_op_sampler_step_guided', 'msd_op_sampler_step_multistep_guided',
+    # (appended to ABI 7) the denoising loss of a mel under the encoded tokens
+    'msd_loss', 'msd_op_diffusion_loss')
+
+
+LOSS_CONDITIONINGS = {'cond': 0, 'uncond': 1, 'both': 2}   # MSD_LOSS_COND, _UNCOND, _BOTH
+LOSS_TYPES = {'x0': 0, 'eps': 1, 'max_x0_eps': 2, 'x0_and_eps': 3}   # MSD_LOSS_X0 ... (diffusion_utils.calculate_loss's names)
+LOSS_NORMS = {'l1': 0, 'l2': 1}
+
+
+def plan_loss_times(num_steps: int, times):
+  """The time indices of a loss call on a handle of N = num_steps steps (index i = row i of the step tables, time
+  (i + 1) / N).  An integer K with 1 <= K <= N gives the stratified grid i_j = ((2 j + 1) N) // (2 K), j = 0 .. K - 1: the
+  middle of each of K equal strata, strictly increasing, every index for K == N.  A sequence gives its own entries, each an
+  integer in [0, N), in the given order, repeats allowed.  Anything else is a ValueError.  No device needed."""
+  if isinstance(num_steps, (bool, np.bool_)) or not isinstance(num_steps, (int, np.integer)) or num_steps < 1:
+    raise ValueError('num_steps must be a positive integer: %r' % (num_steps,))
+  n = int(num_steps)
+  if isinstance(times, (bool, np.bool_)):
+    raise ValueError('times must be an integer in [1, %d] or a sequence of time indices, not a bool' % n)
+  if isinstance(times, (int, np.integer)):
+    k = int(times)
+    if not 1 <= k <= n:
+      raise ValueError('times = %d is outside [1, %d] (the model\'s steps)' % (k, n))
+    return [((2 * j + 1) * n) // (2 * k) for j in range(k)]
+  try:
+    idx = list(times)
+  except TypeError:
+    raise ValueError('times must be an integer in [1, %d] or a sequence of time indices: %r' % (n, times))
+  if not idx:
+    raise ValueError('times is empty: a loss call needs at least one time index')
+  for i in idx:
+    if isinstance(i, (bool, np.bool_)) or not isinstance(i, (int, np.integer)) or not 0 <= i < n:
+      raise ValueError('time index %r is not an integer in [0, %d)' % (i, n))
+  return [int(i) for i in idx]
+
+
+class LossArgs(ctypes.Structure):
+  """msd_loss_args of include/msd_amd.h, field for field."""
+  _fields_ = [(n, ctypes.c_int32) for n in ('struct_size', 'batch', 'rng', 'per_row')] + [
+      ('seeds', ctypes.POINTER(ctypes.c_uint64)), ('stream_ids', ctypes.POINTER(ctypes.c_uint64)),
+      ('target_dev', ctypes.c_void_p), ('mask_dev', ctypes.c_void_p), ('eps_dev', ctypes.c_void_p),
+      ('times_host', ctypes.POINTER(ctypes.c_int32))] + [
+          (n, ctypes.c_int32) for n in ('n_times', 'conditioning', 'loss_type', 'loss_norm')] + [('out_dev', ctypes.c_void_p)]
 
 
 def check_guidance(guidance, batch: int):
@@ -344,6 +387,9 @@ def load(planes: str = 'f16') -> ctypes.CDLL:
     lib.msd_sample_guided.argtypes = [vp, i32, i32, i32, c.POINTER(u64), c.POINTER(u64), vp, vp, i32, i32, fp, i32, i32, i32, vp, vp]
     lib.msd_op_sampler_step_guided.argtypes = [c.POINTER(MsdConfig), i32, vp, vp, vp, vp, fp, i32, vp, i64, vp]
     lib.msd_op_sampler_step_multistep_guided.argtypes = [c.POINTER(MsdConfig), i32, vp, vp, vp, vp, i32, fp, i32, vp, i64, vp]
+  if 'msd_loss' in present:   # (appended to ABI 7)
+    lib.msd_loss.argtypes = [vp, c.POINTER(LossArgs), vp]
+    lib.msd_op_diffusion_loss.argtypes = [c.POINTER(MsdConfig), i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, i64, vp]
   if 'msd_fill_normal_threefry' in present:
     lib.msd_fill_normal_threefry.argtypes = [u64, i64, vp, i64, vp]
   if 'msd_op_threefry' in present:
@@ -601,6 +647,41 @@ class NativeModel:
     else:
       name, rc = 'msd_sample', lib.msd_sample_rng(h, batch, kind, seed, stream_id, *draws, *tail)
     _check(lib, h, rc, name)
+
+  def loss(self, batch: int, target, out, times, seed=0, stream_id=0, rng: str = 'philox', conditioning: str = 'cond',
+           loss_type: str = 'eps', loss_norm: str = 'l1', mask=None, eps=None, stream: int = 0):
+    """The denoising loss of `target` (float32 device tensor [batch, T, n], mel units) under the encoded tokens
+    (msd_loss), per frame: out (float32 device tensor [len(times), passes, batch, T]; passes = 2 for conditioning 'both' --
+    0 = conditional --, else 1).  times: time indices in [0, num_steps) (plan_loss_times).  mask: float32 device
+    [batch, T] or None = ones; eps: float32 device [len(times), batch, T, n] or None = drawn under (seed, stream_id) with
+    `rng`, scalars or one per row as in sample().  A time index that appears twice draws the same eps twice.  loss_type /
+    loss_norm: diffusion_utils.calculate_loss's names.  Argument errors are raised before the library is called."""
+    if rng not in RNGS:
+      raise ValueError('rng must be one of %s: %r' % (sorted(RNGS), rng))
+    if conditioning not in LOSS_CONDITIONINGS:
+      raise ValueError('conditioning must be one of %s: %r' % (sorted(LOSS_CONDITIONINGS), conditioning))
+    if loss_type not in LOSS_TYPES:
+      raise ValueError('Unknown diffusion loss_type: %r (one of %s)' % (loss_type, sorted(LOSS_TYPES)))
+    if loss_norm not in LOSS_NORMS:
+      raise ValueError('Unknown diffusion loss norm: %r (one of %s)' % (loss_norm, sorted(LOSS_NORMS)))
+    idx = plan_loss_times(self.cfg.num_steps, times)
+    per_row = not (np.isscalar(seed) and np.isscalar(stream_id))
+    seeds, stream_ids = row_keys(batch if per_row else 1, seed, stream_id)
+    passes = 2 if conditioning == 'both' else 1
+    frames = batch * self.cfg.targets_length
+    for name, t, want in (('target', target, frames * self.cfg.n_dims), ('out', out, len(idx) * passes * frames),
+                          ('mask', mask, frames), ('eps', eps, len(idx) * frames * self.cfg.n_dims)):
+      if t is None and name in ('mask', 'eps'):
+        continue
+      if t is None or int(np.prod(tuple(t.shape))) != want:
+        raise ValueError('%s must hold %d float32 values: got %s' % (name, want, None if t is None else tuple(t.shape)))
+    a = LossArgs()
+    a.struct_size, a.batch, a.rng, a.per_row = ctypes.sizeof(LossArgs), batch, RNGS[rng], int(per_row)
+    a.seeds, a.stream_ids = (ctypes.c_uint64 * len(seeds))(*seeds), (ctypes.c_uint64 * len(seeds))(*stream_ids)
+    a.target_dev, a.mask_dev, a.eps_dev, a.out_dev = _ptr(target), _ptr(mask), _ptr(eps), _ptr(out)
+    a.times_host, a.n_times = (ctypes.c_int32 * len(idx))(*idx), len(idx)
+    a.conditioning, a.loss_type, a.loss_norm = LOSS_CONDITIONINGS[conditioning], LOSS_TYPES[loss_type], LOSS_NORMS[loss_norm]
+    _check(self.lib, self.handle, self.lib.msd_loss(self.handle, ctypes.byref(a), stream), 'msd_loss')
 
   def set_touch_carrier(self, touch_carrier: Optional[int]):
     """msd_config.touch_carrier of this handle from the next sampling call on (None = the library's choice, 1, 2)."""
@@ -909,6 +990,18 @@ def op_diffuse_to_step(cfg: MsdConfig, step_index: int, mel, eps, z_out, z_plane
     raise ValueError('mel, eps and the three outputs must have the same element count')
   _op_check(lib.msd_op_diffuse_to_step(ctypes.byref(cfg), step_index, _ptr(mel), _ptr(eps), _ptr(z_out), _ptr(z_planes_out),
                                        _ptr(xk_out), mel.numel(), stream), 'msd_op_diffuse_to_step')
+
+
+def op_diffusion_loss(cfg: MsdConfig, step_index: int, loss_type: str, loss_norm: str, o, z, x0, eps, mask, out, n_dims: int,
+                      stream: int = 0):
+  """diffusion_loss_kernel alone (msd_op_diffusion_loss): out [n / n_dims] = the per-frame loss of one pass's model output o
+  at step_index of cfg's tables over the caller's z, x0 (model units), eps and mask (float [n / n_dims] or None); float32
+  device tensors."""
+  lib = load(_PLANES_OF.get(cfg.precision, 'f16'))
+  cfg.struct_size = config_struct_size(lib)
+  _op_check(lib.msd_op_diffusion_loss(ctypes.byref(cfg), step_index, LOSS_TYPES[loss_type], LOSS_NORMS[loss_norm], _ptr(o),
+                                      _ptr(z), _ptr(x0), _ptr(eps), _ptr(mask), n_dims, _ptr(out), z.numel(), stream),
+            'msd_op_diffusion_loss')
 
 
 def op_renoise(cfg: MsdConfig, from_level: int, to_level: int, z, eps, z_out, z_planes_out, stream: int = 0):

@@ -11,6 +11,14 @@ beam/evaluation.py:161-223) on the MI355X path.
       [--vary STRENGTH (--edit-mel old_mel.npy | --edit-audio old.wav)]
       [--resample JUMP:TIMES]   (with --regenerate or --vary)
       [--guidance W] [--guidance-interval LO:HI]
+  python -m msd_amd.synthesize song.mid (--score MEL.npy | --score-audio REC.wav) [--score-times K]
+      [--score-conditioning cond|uncond|both]
+
+--score MEL.npy / --score-audio REC.wav sample nothing: they print the denoising loss of the given mel (a recording goes
+through the device Audio2Mel) under the MIDI file's tokens as one JSON object with per-segment sums (a mel that ends inside a
+segment is padded with the codec's pad value: 'loss_given_frames' is the sum without the padding) -- segment k scored with
+segment k - 1 of the GIVEN mel as context, at --score-times K time indices spread over the model's steps
+(InferenceModel.score_sequence).  No --out.
 
 --wav writes 16-bit PCM mono at 16 kHz from the device vocoder: Griffin-Lim over the codec's STFT, a stand-in for the
 reference's SoundStream decoder (which is not built).  --context-audio continues a recording: its last 256 frames are
@@ -106,9 +114,33 @@ def main(argv=None) -> int:
   ap.add_argument('--edit-mel', default=None, metavar='OLD.npy', help='the old rendering as mel frames [frames, 128]')
   ap.add_argument('--edit-audio', default=None, metavar='OLD.wav',
                   help='the old rendering as a 16 kHz PCM recording (encoded on the device)')
+  ap.add_argument('--score', default=None, metavar='MEL.npy',
+                  help='no sampling: the denoising loss of these mel frames [frames, 128] under the MIDI file\'s tokens, per '
+                       'segment, as one JSON object on stdout')
+  ap.add_argument('--score-audio', default=None, metavar='REC.wav',
+                  help='--score for a 16 kHz PCM recording (encoded on the device)')
+  ap.add_argument('--score-times', type=int, default=16, metavar='K',
+                  help='with --score / --score-audio: time indices per segment, a stratified grid over the model\'s steps')
+  ap.add_argument('--score-conditioning', choices=['cond', 'uncond', 'both'], default='cond',
+                  help="with --score / --score-audio: the decoder pass(es) that are scored")
   ap.add_argument('--on-too-long', choices=['error', 'truncate'], default='error')
   ap.add_argument('--dry-run', action='store_true')
   args = ap.parse_args(argv)
+  scoring = bool(args.score or args.score_audio)
+  if args.score and args.score_audio:
+    ap.error('--score and --score-audio are two sources of the same thing: give one')
+  if scoring and (args.out or args.wav):
+    ap.error('--score / --score-audio sample nothing: no --out / --wav')
+  if scoring and (args.regenerate or args.vary is not None or args.edit_mel or args.edit_audio or args.resample is not None):
+    ap.error('--score / --score-audio do not go with --regenerate / --vary / --edit-mel / --edit-audio / --resample')
+  if scoring and (args.steps is not None or args.sampler or args.guidance is not None or args.guidance_interval is not None
+                  or args.batch_segments != 1 or args.context_audio):
+    ap.error('--score / --score-audio sample nothing: no --steps / --sampler / --guidance / --guidance-interval / '
+             '--batch-segments / --context-audio')
+  if scoring and args.rng == 'jax':
+    ap.error("--score / --score-audio draw on the device: --rng philox or threefry")
+  if not scoring and (args.score_times != 16 or args.score_conditioning != 'cond'):
+    ap.error('--score-times / --score-conditioning go with --score MEL.npy or --score-audio REC.wav')
   if args.regenerate and args.vary is not None:
     ap.error('--regenerate and --vary are two edits: give one')
   if args.regenerate and not (args.edit_mel or args.edit_audio):
@@ -172,6 +204,14 @@ def main(argv=None) -> int:
     except ValueError as e:
       ap.error('--guidance / --guidance-interval: %s' % e)
     few.update({k_: v for k_, v in (('guidance', args.guidance), ('guidance_interval', args.guidance_interval)) if v is not None})
+  if scoring:
+    from msd_amd import native
+    try:
+      native.plan_loss_times(spec.diffusion.sampler.schedule.num_steps, args.score_times)
+      if args.score_conditioning == 'both' and spec.diffusion.classifier_free_guidance.eval_condition_weight == 1.0:
+        raise ValueError('a model with --cfg-weight 1 holds one pass\'s buffers: --score-conditioning cond or uncond')
+    except ValueError as e:
+      ap.error('--score-times / --score-conditioning: %s' % e)
   ns = midi_io.midi_file_to_note_sequence(args.midi)
   cfg = tokenizer.FrontendConfig.from_spec(spec)
   t0 = time.perf_counter()
@@ -226,10 +266,31 @@ def main(argv=None) -> int:
       jump, times = args.resample
       print('resample %d:%d: %d steps and %d jumps per full segment' % (jump, times, times * run, (times - 1) * -(-run // jump)))
     edit = (old, start, stop)
+  score_mel = None
+  if scoring:   # the mel's shape and length against the MIDI file's segments, before any device work
+    from msd_amd import audio_codecs, vocoder
+    codec = audio_codecs.get_codec(spec.audio_codec)
+    try:
+      if args.score:
+        score_mel = np.load(args.score)
+        score_mel = score_mel[0] if score_mel.ndim == 3 and score_mel.shape[0] == 1 else score_mel
+        if score_mel.ndim != 2 or score_mel.shape[1] != codec.n_dims:
+          raise ValueError('%s must hold mel frames [frames, %d]: got %r' % (args.score, codec.n_dims, score_mel.shape))
+        got = score_mel.shape[0]
+      else:
+        score_mel = vocoder.read_wav(args.score_audio, codec.sample_rate)
+        got = -(-score_mel.size // codec.hop_size)
+      if got > len(segments) * cfg.segment_frames:
+        raise ValueError('the mel to score has %d frames, the MIDI file only %d (%d segments)'
+                         % (got, len(segments) * cfg.segment_frames, len(segments)))
+    except (ValueError, OSError) as e:
+      ap.error(str(e))
   if args.dry_run:
     return 0
   model = msd_amd.InferenceModel(args.checkpoint, spec, batch_size=max(args.batch_segments, 1), precision=args.precision,
                                  range_fallback=args.range_fallback)
+  if scoring:
+    return _score(args, model, segments, score_mel, cfg)
   try:   # (before any sampling, and before the context recording is read)
     model.check_batch_segments(args.batch_segments, args.always_mask_context, args.context_audio)
   except ValueError as e:
@@ -253,6 +314,30 @@ def main(argv=None) -> int:
            1.0 / timing['predictions_seconds_per_audio_second'] if timing['predictions_seconds_per_audio_second'] == timing['predictions_seconds_per_audio_second'] else float('nan')),
         file=sys.stderr)
   _write_outputs(args, model, mel_dev, mel)
+  return 0
+
+
+def _score(args, model, segments, mel, cfg) -> int:
+  """--score / --score-audio: InferenceModel.score_sequence of the given mel (the recording's frames made on the device,
+  as --edit-audio's), padded to whole segments with the codec's pad value.  'loss' / 'per_segment' sum over whole segments,
+  the padding's frames included (the decoder sees them either way); 'loss_given_frames' sums the frames that were given."""
+  import json
+  torch = model._torch
+  if args.score:
+    song = torch.as_tensor(np.ascontiguousarray(mel, np.float32)).to(model.device)[None]
+  else:
+    song = model.vocoder.encode(np.asarray(mel, np.float32)[None], return_torch=True)
+  given = int(song.shape[1])
+  song = pad_to_segments(song, len(segments) * cfg.segment_frames, model.audio_codec.pad_value)
+  t0 = time.perf_counter()
+  res = model.score_sequence(song, segments, times=args.score_times, seed=args.seed, conditioning=args.score_conditioning,
+                             always_mask_context=args.always_mask_context, rng=args.rng)
+  passes = ['cond', 'uncond'] if args.score_conditioning == 'both' else [args.score_conditioning]
+  print(json.dumps({'segments': len(segments), 'frames': given, 'times': [int(i) for i in res['times']],
+                    'conditioning': args.score_conditioning, 'seconds': round(time.perf_counter() - t0, 4),
+                    'loss': {p: float(res['loss'][k]) for k, p in enumerate(passes)},
+                    'loss_given_frames': {p: float(res['per_frame'][k, :given].sum()) for k, p in enumerate(passes)},
+                    'per_segment': {p: [float(v) for v in res['per_segment'][k]] for k, p in enumerate(passes)}}))
   return 0
 
 
