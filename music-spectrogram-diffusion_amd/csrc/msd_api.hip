@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <map>
 #include <string>
 #include <unordered_map>
@@ -134,7 +135,34 @@ struct StepPlan {
   bool cross_qb4[2];
   bool cond0, mlp_in_on_cross_out;
 };
-// (captured step graphs are looked up by comparing plans bytewise, msd_model::GraphKey: no padding bytes -- group its bools in fours)
+// (captured graphs are looked up by comparing plans bytewise, GraphCache: no padding bytes -- group its bools in fours)
+
+// Instantiated graphs of a handle under keys that are compared bytewise, at most Cap of them.  The handle keeps two, the
+// step graphs and msd_loss's, so that neither evicts the other's entries.  A deque: an entry stays where it is when
+// another is inserted, so a caller may hold several entries at once -- as long as it makes room for all it will insert
+// BEFORE its first lookup (make_room: a cache without that room is emptied, which destroys every graph in it).
+template <class Key, size_t Cap>
+struct GraphCache {
+  static_assert(std::has_unique_object_representations<Key>::value, "a graph key (StepPlan included) must not have padding bytes");
+  struct Entry { Key key; hipGraphExec_t exec = nullptr, exec1 = nullptr; };
+  std::deque<Entry> entries;
+  Entry* find(const Key& key) {
+    for (Entry& e : entries)
+      if (memcmp(&e.key, &key, sizeof(Key)) == 0) return &e;
+    return nullptr;
+  }
+  void make_room(size_t n) {   // (a handle that cycles through more shapes than Cap re-captures)
+    if (entries.size() + n > Cap) clear();
+  }
+  Entry* insert(const Entry& e) { entries.push_back(e); return &entries.back(); }
+  void clear() {
+    for (Entry& e : entries) {
+      if (e.exec) (void)hipGraphExecDestroy(e.exec);
+      if (e.exec1) (void)hipGraphExecDestroy(e.exec1);
+    }
+    entries.clear();
+  }
+};
 
 
 struct Profiler {
@@ -192,29 +220,31 @@ struct msd_model {
   const float** d_noise_slot = nullptr;
   uint32_t* d_rng_key = nullptr;       // [Bmax] rows of {seed_lo, seed_hi, stream_lo, stream_hi, generator kind, PRNGKey(seed) words, per-row mode} of the current msd_sample: one row per row of z (elementwise.h SamplerParams::rng_key, kRng*)
   std::vector<uint32_t> h_rng_key;     // host staging of the rows just uploaded
+  // The buffers from here to d_loss_times are made by the first call that needs them (`ensure`) or grown by a call that
+  // needs more (`grow`, those with a capacity beside them), outside stream capture, and owned by the handle.
   // msd_sample_guided: the guidance weight of every row of z, [Bmax] floats beside the key table (elementwise.h
-  // SamplerGuidedParams::row_wt), uploaded per call; allocated by the first guided call (outside stream capture) and owned by
-  // the handle, so the captured guided graphs hold a stable address and serve every weight vector
+  // SamplerGuidedParams::row_wt), uploaded per call; the captured guided graphs hold a stable address and serve every
+  // weight vector
   float* d_row_wt = nullptr;
   std::vector<float> h_row_wt;         // host staging of that upload
-  // msd_sample_keep: the known mel in model units [Bmax][T][n] and its frame flags [Bmax][T]; allocated by the first
-  // keep call (outside stream capture) and owned by the handle, so the captured keep graphs hold stable addresses
+  // msd_sample_keep: the known mel in model units [Bmax][T][n] and its frame flags [Bmax][T]; the captured keep graphs hold
+  // stable addresses
   float* keep_xk = nullptr;
   int32_t* keep_flags = nullptr;
   // msd_sample_resample: the key rows of every pass behind a jump, [passes][batch][kRngWords], uploaded once per call (the
-  // jump kernel installs its pass's rows in d_rng_key); grown on need outside stream capture, owned by the handle
+  // jump kernel installs its pass's rows in d_rng_key, outside the captured graphs: the buffer may move when it grows)
   uint32_t* d_pass_keys = nullptr;
   size_t pass_keys_cap = 0;            // words
   std::vector<uint32_t> h_pass_keys;   // host staging of that upload
   // msd_sample_steps: the sampler's coefficient rows for a call of K steps (K | N), built on the first such call and kept
   // (host copy + device table; K == N is d_coef itself), and -- MSD_SAMPLER_DPMPP_2M -- the multistep side table of K and
-  // the previous step's pred_x0 [Bmax][T][n]; all allocated outside stream capture and owned by the handle
+  // the previous step's pred_x0 [Bmax][T][n] (make_step_view builds the tables)
   struct StepTables { std::vector<float> h_coef; float* coef = nullptr; float* coef_ms = nullptr; };
   std::map<int, StepTables> step_tables;
   float* x0_prev = nullptr;
   // msd_loss: the target in model units [Bmax][T][n], the per-call words of the two loss kernels (elementwise.h LossCall) and
-  // the call's time rows [n_times][kLossTimeWords]; allocated on first use (outside stream capture) and owned by the handle,
-  // so the captured loss graphs hold stable addresses.  The time rows are reached THROUGH the call words: they may grow.
+  // the call's time rows [n_times][kLossTimeWords]; the captured loss graphs hold stable addresses.  The time rows are
+  // reached THROUGH the call words: they may grow.
   float* loss_x0 = nullptr;
   LossCall* d_loss_call = nullptr;
   LossCall h_loss_call = {};           // host staging of that upload
@@ -246,15 +276,16 @@ struct msd_model {
   // kernel in; the handle's own (N, cfg.sampler) is the key every other entry point looks up, as it always did.
   // `guided`: msd_sample_guided's two-pass graphs launch the sampler's guided form (the row weights come from d_row_wt);
   // its one-pass steps replay plain graphs of the one-pass plan.  (An int like its neighbours: no padding bytes.)
-  struct GraphKey { StepPlan plan; int steps, sampler, keep, guided; };   // ONE key, compared bytewise (find_graphs)
-  static_assert(std::has_unique_object_representations<GraphKey>::value, "GraphKey (StepPlan included) must not have padding bytes");
-  struct StepGraphs { GraphKey key; hipGraphExec_t exec = nullptr, exec1 = nullptr; };
-  std::vector<StepGraphs> graphs;
-  // msd_loss's graphs: ONE evaluation (diffuse, decoder pass(es), loss) per plan -- the conditional, the unconditional
-  // and the two-pass plan differ bytewise -- in a list of their own, so that they neither evict nor alter a cached set of step
-  // graphs; msd_reset_graph drops both lists.
-  struct LossGraph { StepPlan plan; hipGraphExec_t exec = nullptr; };
-  std::vector<LossGraph> loss_graphs;
+  // An entry: `exec` runs graph_steps steps, `exec1` one (captured on first need).  find_graphs looks up and captures.
+  struct GraphKey { StepPlan plan; int steps, sampler, keep, guided; };   // ONE key, compared bytewise (GraphCache)
+  using StepGraphCache = GraphCache<GraphKey, 8>;
+  using StepGraphs = StepGraphCache::Entry;
+  StepGraphCache graphs;
+  // msd_loss's graphs: ONE evaluation (diffuse, decoder pass(es), loss) per plan in `exec` -- the conditional, the
+  // unconditional and the two-pass plan differ bytewise -- in a cache of their own, so that they neither evict nor alter a
+  // cached set of step graphs; msd_reset_graph empties both.
+  using LossGraphCache = GraphCache<StepPlan, 6>;
+  LossGraphCache loss_graphs;
   int graph_steps = 8;              // DDPM steps per graph launch (msd_config.graph_steps; 1 -> 4 -> 10: 1.2000 -> 1.1963 -> 1.1955 ms/step)
   bool prefetch = true;        // producers warm the next GEMM's weights (msd_config.weight_prefetch; default: by model size)
   bool dedup_layer0 = true;    // S5 (decoder_layers); msd_config.dedup_layer0 = 2 turns it off for A/B and bitwise tests
@@ -332,6 +363,26 @@ int palloc(msd_model* m, Planes* pl, size_t count) {
     int rc = dalloc(m, &pl->p[i], count);
     if (rc) return rc;
   }
+  return MSD_OK;
+}
+
+// The handle's lazily made device buffers, both outside stream capture.  ensure: allocated (zeroed) by the first call
+// that needs it, each buffer on its own -- a call after a failed allocation tries again for the one that is missing.
+template <class Tp>
+int ensure(msd_model* m, Tp** p, size_t count) { return *p ? MSD_OK : dalloc(m, p, count); }
+// grow: a buffer of *cap elements that a call needing more frees and allocates anew (the stream is idle then: every call
+// that uses one ends with its synchronisation); no captured graph holds such a buffer's address
+template <class Tp>
+int grow(msd_model* m, Tp** p, size_t* cap, size_t count) {
+  if (count <= *cap) return MSD_OK;
+  if (*p) {
+    auto it = std::find(m->allocs.begin(), m->allocs.end(), static_cast<void*>(*p));
+    if (it != m->allocs.end()) m->allocs.erase(it);
+    (void)hipFree(*p);
+    *p = nullptr; *cap = 0;
+  }
+  if (int rc = dalloc(m, p, count)) return rc;
+  *cap = count;
   return MSD_OK;
 }
 
@@ -1565,6 +1616,19 @@ void decoder_eval(Ctx& c, const StepPlan& p, bool publish_step) {
 // z (fp32) -> bf16 planes, after z was written from outside the sampler kernel
 void split_z(msd_model* m, int64_t n, hipStream_t s) { split(m->z, m->zp, n, s, m->d_sat, (unsigned)KC_SAMPLER + 1u); }
 
+// ... and every kernel that writes z itself writes the planes and the range flag with it: the handle's z as the output of
+// P -- SamplerParams and the structs derived from it, DiffuseParams, RenoiseParams, LossDiffuseParams (elementwise.h)
+template <class P>
+void z_out(P& p, const msd_model* m, unsigned sat_tag = (unsigned)KC_SAMPLER + 1u) {
+  p.z = m->z;
+  p.z_hi = m->zp.p[0];
+  p.z_lo = m->NP == 2 ? m->zp.p[1] : nullptr;
+  p.sat = m->d_sat; p.sat_tag = sat_tag;
+}
+// blocks of kRngRowBlock elements per [T, n] row of z (SamplerParams::row_blocks); a row that is no whole number of them
+// keeps every block on row 0 of the key table, and the per-row calls are refused (check_encoded_call)
+int row_blocks_of(const msd_model* m) { return m->T * m->ND % kRngRowBlock == 0 ? m->T * m->ND / kRngRowBlock : 1 << 30; }
+
 // one DDPM step of the CFG sampler: the decoder on plan_cfg_step's plan, then the sampler update
 // c.v: the call's view of the step-indexed tables, its coefficient rows, its sampler and whether that runs in its keep form
 void enqueue_step(Ctx& c, const StepPlan& p) {
@@ -1572,15 +1636,13 @@ void enqueue_step(Ctx& c, const StepPlan& p) {
   decoder_eval(c, p, /*publish_step=*/true);
   const int sampler = c.v.sampler;
   SamplerKeepParams sp;
-  sp.eps = m->eps; sp.z = m->z; sp.noise_slot = m->d_noise_slot; sp.coef = c.v.coef; sp.rng_key = m->d_rng_key;
+  sp.eps = m->eps; sp.noise_slot = m->d_noise_slot; sp.coef = c.v.coef; sp.rng_key = m->d_rng_key;
   sp.step_ptr = m->d_step; sp.n = p.batch * m->T * m->ND; sp.passes = p.P;
-  if (m->T * m->ND % kRngRowBlock == 0) sp.row_blocks = m->T * m->ND / kRngRowBlock;   // (else: table row 0 only, msd_sample_rows refuses)
+  sp.row_blocks = row_blocks_of(m);
   sp.cond_wt = m->cfg.cfg_weight; sp.clip_x0 = m->cfg.clip_x0;
   sp.ddim = sampler == MSD_SAMPLER_DDIM;
   sp.model_output = m->cfg.model_output;
-  sp.z_hi = m->zp.p[0];
-  sp.z_lo = m->NP == 2 ? m->zp.p[1] : nullptr;
-  sp.sat = m->d_sat; sp.sat_tag = (unsigned)KC_SAMPLER + 1u;
+  z_out(sp, m);
   c.begin(KC_SAMPLER);
   sp.step_from_slot1 = 1;
   if (sampler == MSD_SAMPLER_DPMPP_2M) {   // (never with keep: check_call refuses the pair)
@@ -1605,6 +1667,23 @@ void enqueue_step(Ctx& c, const StepPlan& p) {
   c.end(KC_SAMPLER);
 }
 
+// One stream capture (thread-local) on s: whatever `enqueue` puts on the stream -- it returns a status, its message set --
+// instantiated as *out.  The hipGraph_t is destroyed on every path; `what` names the capture in the message.
+template <class Enqueue>
+int capture_graph(msd_model* m, hipStream_t s, const char* what, hipGraphExec_t* out, Enqueue enqueue) {
+  hipGraph_t graph = nullptr;
+  HIP_TRY(m, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
+  const int rc = enqueue();
+  const hipError_t ce = hipStreamEndCapture(s, &graph);
+  if (ce != hipSuccess || rc) {
+    if (graph) (void)hipGraphDestroy(graph);
+    return rc ? rc : fail(m, MSD_ERR_HIP, "%s capture failed: %s", what, hipGetErrorString(ce));
+  }
+  const hipError_t ie = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
+  (void)hipGraphDestroy(graph);
+  if (ie != hipSuccess) { *out = nullptr; return fail(m, MSD_ERR_HIP, "%s: hipGraphInstantiate: %s", what, hipGetErrorString(ie)); }
+  return MSD_OK;
+}
 
 }  // namespace
 
@@ -2090,10 +2169,10 @@ static std::string divisors_of(int n) {
 // x0_prev.  Runs outside stream capture; every allocation is the handle's.
 static int make_step_view(msd_model* m, int K, int sampler, bool keep, StepView* v) {
   const int N = m->N;
-  if (keep && !m->keep_xk)
-    if (int rc = dalloc(m, &m->keep_xk, (size_t)m->Bmax * m->T * m->ND)) return rc;
-  if (keep && !m->keep_flags)
-    if (int rc = dalloc(m, &m->keep_flags, (size_t)m->Bmax * m->T)) return rc;
+  if (keep) {
+    if (int rc = ensure(m, &m->keep_xk, (size_t)m->Bmax * m->T * m->ND)) return rc;
+    if (int rc = ensure(m, &m->keep_flags, (size_t)m->Bmax * m->T)) return rc;
+  }
   *v = StepView();
   v->steps = K; v->mul = N / K; v->off = N / K - 1; v->coef = m->d_coef; v->sampler = sampler; v->keep = keep;
   // (the kernels index base + step * stride in 64 bits; the stride itself travels as an int)
@@ -2119,15 +2198,25 @@ static int make_step_view(msd_model* m, int K, int sampler, bool keep, StepView*
       HIP_TRY(m, copy_sync(m, t.coef_ms, ms.data(), ms.size() * sizeof(float), hipMemcpyHostToDevice));
     }
     v->coef_ms = t.coef_ms;
-    if (!m->x0_prev)
-      if (int rc = dalloc(m, &m->x0_prev, (size_t)m->Bmax * m->T * m->ND)) return rc;
+    if (int rc = ensure(m, &m->x0_prev, (size_t)m->Bmax * m->T * m->ND)) return rc;
   }
+  return MSD_OK;
+}
+
+// What every call that runs the decoder on the encoded state refuses, sampling or loss: no encoded state, another batch
+// than the encoded one, an unknown generator, per-row keys on rows that are no whole number of the sampler's blocks
+static int check_encoded_call(msd_model* m, int batch, int rng, bool per_row) {
+  if (!m->encoded) return fail(m, MSD_ERR_BAD_STATE, "msd_encode has not run");
+  if (batch != m->encoded_batch) return fail(m, MSD_ERR_INVALID_ARGUMENT, "batch %d != encoded batch %d", batch, m->encoded_batch);
+  if (rng != MSD_RNG_PHILOX && rng != MSD_RNG_THREEFRY) return fail(m, MSD_ERR_INVALID_ARGUMENT, "unknown rng %d", rng);
+  const int64_t row_n = (int64_t)m->T * m->ND;
+  if (per_row && row_n % kRngRowBlock)   // a block of the sampler launch would straddle two rows' keys
+    return fail(m, MSD_ERR_UNSUPPORTED, "per-row keys need targets_length * n_dims %% %d == 0 (got %lld)", (int)kRngRowBlock, (long long)row_n);
   return MSD_OK;
 }
 
 // ---- the phases of a sampling call, in the order sample_body runs them ---------------------------------------------
 static int check_call(msd_model* m, const SampleCall& c) {
-  if (c.rng != MSD_RNG_PHILOX && c.rng != MSD_RNG_THREEFRY) return fail(m, MSD_ERR_INVALID_ARGUMENT, "unknown rng %d", c.rng);
   if (c.known && (c.steps != m->N || c.sampler == MSD_SAMPLER_DPMPP_2M))
     return fail(m, MSD_ERR_UNSUPPORTED, "known frames run on the handle's own step count with ddpm or ddim (no multistep history across a release)");
   if (c.jump < 1 || c.times < 1) return fail(m, MSD_ERR_INVALID_ARGUMENT, "resampling needs jump >= 1 and times >= 1 (got %d, %d)", c.jump, c.times);
@@ -2135,13 +2224,10 @@ static int check_call(msd_model* m, const SampleCall& c) {
     for (int b = 0; b < (c.keys.per_row() ? c.batch : 1); ++b)
       if (c.keys.stream_of(b) >> 32)
         return fail(m, MSD_ERR_INVALID_ARGUMENT, "a call with resampling needs stream_id < 2^32 (row %d: %llu)", b, (unsigned long long)c.keys.stream_of(b));
-  if (!m->encoded) return fail(m, MSD_ERR_BAD_STATE, "msd_encode has not run");
-  if (c.batch != m->encoded_batch) return fail(m, MSD_ERR_INVALID_ARGUMENT, "batch %d != encoded batch %d", c.batch, m->encoded_batch);
+  if (int rc = check_encoded_call(m, c.batch, c.rng, c.keys.per_row())) return rc;
   if (!c.out) return fail(m, MSD_ERR_INVALID_ARGUMENT, "out is null");
   const int64_t row_n = (int64_t)m->T * m->ND;
-  if (c.keys.per_row() && row_n % kRngRowBlock)   // a block of the sampler launch would straddle two rows' keys
-    return fail(m, MSD_ERR_UNSUPPORTED, "per-row keys need targets_length * n_dims %% %d == 0 (got %lld)", (int)kRngRowBlock, (long long)row_n);
-  if (c.weights && c.n_weights > 1 && row_n % kRngRowBlock)   // ... or two rows' weights
+  if (c.weights && c.n_weights > 1 && row_n % kRngRowBlock)   // a block of the sampler launch would straddle two rows' weights
     return fail(m, MSD_ERR_UNSUPPORTED, "per-row guidance weights need targets_length * n_dims %% %d == 0 (got %lld)", (int)kRngRowBlock, (long long)row_n);
   if (c.known && m->ND % 4)   // a thread of the sampler holds four consecutive elements and ONE frame flag
     return fail(m, MSD_ERR_UNSUPPORTED, "kept frames need n_dims %% 4 == 0 (got %d)", m->ND);
@@ -2185,11 +2271,10 @@ static int write_initial_state(msd_model* m, const SampleCall& c, hipStream_t s)
     // part-way start (msd_sample_edit): z holds the call's initial draw eps; one pass makes xk and z = alpha xk + sigma eps
     // at the start index's noise level, with z's planes and the range flag (what split_z does for the plain start)
     DiffuseParams dp;
-    dp.mel = c.known; dp.eps = m->z; dp.xk = m->keep_xk; dp.z = m->z;
-    dp.z_hi = m->zp.p[0]; dp.z_lo = m->NP == 2 ? m->zp.p[1] : nullptr;
+    dp.mel = c.known; dp.eps = m->z; dp.xk = m->keep_xk;
+    z_out(dp, m);
     dp.n = (int)n; dp.fmin = m->cfg.feature_min; dp.fmax = m->cfg.feature_max;
     diffuse_coefs(m->h_coef[(size_t)c.start_step * kCoefCount + kCoefLogsnrT], &dp.alpha, &dp.sigma);
-    dp.sat = m->d_sat; dp.sat_tag = (unsigned)KC_SAMPLER + 1u;
     launch_diffuse_to_step(dp, s);
     HIP_TRY(m, hipGetLastError());
   }
@@ -2225,38 +2310,31 @@ static int arm_scan(msd_model* m, int batch, int rng, const SampleKeys& keys, co
 
 // `steps` consecutive steps of the view's form, captured on s and instantiated
 static int capture_steps(msd_model* m, const StepView& view, const StepPlan& plan, int steps, hipStream_t s, hipGraphExec_t* out) {
-  hipGraph_t graph = nullptr;
-  HIP_TRY(m, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-  Ctx c{m, s};
-  c.v = view;
-  for (int k = 0; k < steps; ++k) enqueue_step(c, plan);
-  hipError_t ce = hipStreamEndCapture(s, &graph);
-  if (ce != hipSuccess || c.err != hipSuccess) {
-    if (graph) (void)hipGraphDestroy(graph);
-    return fail(m, MSD_ERR_HIP, "graph capture failed: %s / %s", hipGetErrorString(ce), hipGetErrorString(c.err));
-  }
-  hipError_t ie = hipGraphInstantiate(out, graph, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(graph);
-  if (ie != hipSuccess) { *out = nullptr; return fail(m, MSD_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie)); }
-  return MSD_OK;
+  return capture_graph(m, s, "step graph", out, [&] {
+    Ctx c{m, s};
+    c.v = view;
+    for (int k = 0; k < steps; ++k) enqueue_step(c, plan);
+    return c.err == hipSuccess ? MSD_OK : fail(m, MSD_ERR_HIP, "step graph capture failed: %s", hipGetErrorString(c.err));
+  });
+}
+
+static msd_model::GraphKey step_graph_key(const StepView& view, const StepPlan& plan) {
+  return {plan, view.steps, view.sampler, view.keep, view.guided};
 }
 
 // The graphs of (plan, view), from the handle's cache or captured now.  One graph = `graph_steps` consecutive steps (the
 // scan index lives in device memory, so the same graph serves every position); a second, single-step graph covers what
 // a call of view.steps steps, or this call of run_steps, leaves over.
 static int find_graphs(msd_model* m, const StepView& view, const StepPlan& plan, int run_steps, hipStream_t s, msd_model::StepGraphs** out) {
-  const msd_model::GraphKey key = {plan, view.steps, view.sampler, view.keep, view.guided};
-  msd_model::StepGraphs* g = nullptr;
-  for (auto& e : m->graphs)
-    if (memcmp(&e.key, &key, sizeof(key)) == 0) g = &e;
+  const msd_model::GraphKey key = step_graph_key(view, plan);
+  msd_model::StepGraphs* g = m->graphs.find(key);
   if (__builtin_expect(!g, 0)) {   // (a capture is the rare path; said so, the compiler keeps it out of line as it was inside the one long function)
-    if (m->graphs.size() >= 8) (void)msd_reset_graph(m);   // (a handle that cycles through more shapes than that re-captures)
+    m->graphs.make_room(1);
     msd_model::StepGraphs ng = {key};
     if (int rc = capture_steps(m, view, plan, m->graph_steps, s, &ng.exec)) return rc;
     if (m->graph_steps > 1 && view.steps % m->graph_steps)
       if (int rc = capture_steps(m, view, plan, 1, s, &ng.exec1)) { (void)hipGraphExecDestroy(ng.exec); return rc; }
-    m->graphs.push_back(ng);
-    g = &m->graphs.back();
+    g = m->graphs.insert(ng);
   }
   // (msd_sample_edit's part-way start on a handle whose N is a whole number of graphs: on first need, in the same entry)
   if (m->graph_steps > 1 && run_steps % m->graph_steps && !g->exec1)
@@ -2279,16 +2357,7 @@ static int replay(msd_model* m, const msd_model::StepGraphs& g, int steps, hipSt
 static int upload_pass_keys(msd_model* m, const SampleCall& c, int steps, hipStream_t s) {
   const size_t passes = (size_t)(c.times - 1) * (size_t)((steps - 1) / c.jump + 1);   // (no steps + jump: jump may be INT_MAX, "one block")
   const size_t words = passes * c.batch * kRngWords;
-  if (words > m->pass_keys_cap) {   // (the stream is idle: the last call ended with its synchronisation)
-    if (m->d_pass_keys) {
-      auto it = std::find(m->allocs.begin(), m->allocs.end(), static_cast<void*>(m->d_pass_keys));
-      if (it != m->allocs.end()) m->allocs.erase(it);
-      (void)hipFree(m->d_pass_keys);
-      m->d_pass_keys = nullptr; m->pass_keys_cap = 0;
-    }
-    if (int rc = dalloc(m, &m->d_pass_keys, words)) return rc;
-    m->pass_keys_cap = words;
-  }
+  if (int rc = grow(m, &m->d_pass_keys, &m->pass_keys_cap, words)) return rc;
   m->h_pass_keys.resize(words);   // a member: the copy below may still read it when this returns
   for (size_t p = 1; p <= passes; ++p)
     for (int b = 0; b < c.batch; ++b) {
@@ -2320,13 +2389,13 @@ static int replay_resampled(msd_model* m, const SampleCall& c, const msd_model::
       if (r == c.times - 1) break;
       ++pass;
       RenoiseParams rp;
-      rp.z_in = m->z; rp.z = m->z; rp.z_hi = m->zp.p[0]; rp.z_lo = m->NP == 2 ? m->zp.p[1] : nullptr; rp.n = n;
+      rp.z_in = m->z; rp.n = n;
+      z_out(rp, m);
       renoise_coefs(m->h_coef, bottom, top, &rp.a, &rp.b);
       rp.keys = m->d_pass_keys + (size_t)(pass - 1) * c.batch * kRngWords;
-      if (m->T * m->ND % kRngRowBlock == 0) rp.row_blocks = m->T * m->ND / kRngRowBlock;   // (enqueue_step's)
+      rp.row_blocks = row_blocks_of(m);
       rp.key_table = m->d_rng_key; rp.key_words = c.batch * kRngWords;
       rp.step_ptr = m->d_step; rp.next_step = top - 1;
-      rp.sat = m->d_sat; rp.sat_tag = (unsigned)KC_SAMPLER + 1u;
       launch_renoise(rp, s);
       HIP_TRY(m, hipGetLastError());
     }
@@ -2338,38 +2407,26 @@ static int replay_resampled(msd_model* m, const SampleCall& c, const msd_model::
 // above guide_hi, guided inside [guide_lo, guide_hi), one-pass below guide_lo -- each whole graphs plus singles.  The scan
 // index runs on in device memory across them (both plans publish it the same way) and so do z, its planes and the multistep
 // form's x0_prev; nothing synchronises with the host in between.
-// The call needs TWO sets of graphs at once, and find_graphs hands out a pointer into m->graphs that its next call may
-// invalidate (push_back moves the entries; a full cache is reset, which destroys the graphs).  So room for every set that
-// is missing is made BEFORE the first lookup -- no reset can follow -- and each set is held by value: the executable
-// graphs' handles, which a push_back does not touch.
-static bool graphs_cached(const msd_model* m, const StepView& view, const StepPlan& plan) {
-  const msd_model::GraphKey key = {plan, view.steps, view.sampler, view.keep, view.guided};
-  for (const auto& e : m->graphs)
-    if (memcmp(&e.key, &key, sizeof(key)) == 0) return true;
-  return false;
-}
+// The call needs TWO sets of graphs at once, and a full cache is emptied in front of a capture, which destroys the graphs in
+// it.  So room for every set that is missing is made BEFORE the first lookup -- no emptying can follow -- and both sets
+// are held where they lie: an insertion leaves the cache's other entries in place (GraphCache).
 static int replay_guided(msd_model* m, const SampleCall& c, const StepView& view, int steps, hipStream_t s) {
   const int runs[3] = {steps - c.guide_hi, c.guide_hi - c.guide_lo, c.guide_lo};   // one-pass, guided, one-pass
   StepView one = view, two = view;
   one.guided = false; two.guided = true;
   const StepPlan plan1 = plan_step(m, c.batch, 1, true, false), plan2 = plan_cfg_step(m, c.batch);
   const bool need1 = runs[0] + runs[2] > 0, need2 = runs[1] > 0;
-  const size_t missing = (size_t)(need1 && !graphs_cached(m, one, plan1)) + (size_t)(need2 && !graphs_cached(m, two, plan2));
-  if (missing && m->graphs.size() + missing > 8) (void)msd_reset_graph(m);
-  msd_model::StepGraphs g1, g2;
-  msd_model::StepGraphs* g = nullptr;
+  m->graphs.make_room((size_t)(need1 && !m->graphs.find(step_graph_key(one, plan1))) +
+                      (size_t)(need2 && !m->graphs.find(step_graph_key(two, plan2))));
+  msd_model::StepGraphs *g1 = nullptr, *g2 = nullptr;
   const int gs = m->graph_steps;
-  if (need1) {   // (the single-step graph: needed as soon as one of the two runs is no whole number of graphs)
-    if (int rc = find_graphs(m, one, plan1, (runs[0] % gs || runs[2] % gs) ? 1 : gs, s, &g)) return rc;
-    g1 = *g;
-  }
-  if (need2) {
-    if (int rc = find_graphs(m, two, plan2, runs[1], s, &g)) return rc;
-    g2 = *g;
-  }
+  if (need1)   // (the single-step graph: needed as soon as one of the two runs is no whole number of graphs)
+    if (int rc = find_graphs(m, one, plan1, (runs[0] % gs || runs[2] % gs) ? 1 : gs, s, &g1)) return rc;
+  if (need2)
+    if (int rc = find_graphs(m, two, plan2, runs[1], s, &g2)) return rc;
   for (int r = 0; r < 3; ++r)
     if (runs[r] > 0)
-      if (int rc = replay(m, r == 1 ? g2 : g1, runs[r], s)) return rc;
+      if (int rc = replay(m, r == 1 ? *g2 : *g1, runs[r], s)) return rc;
   return MSD_OK;
 }
 
@@ -2496,11 +2553,10 @@ int msd_sample_resample(msd_model* m, int batch, int rng, int per_row, const uin
   return sample_body(m, c);
 }
 
-int msd_sample_steps(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
-                     const float* init_z_dev, const float* noise_dev, int num_steps, int sampler, float* out_dev,
-                     void* stream) {
-  if (!m) return MSD_ERR_INVALID_ARGUMENT;
-  if (!seeds) return fail(m, MSD_ERR_INVALID_ARGUMENT, "seeds is null");
+// msd_sample_steps' checks of the step count and the sampler, and its call (msd_sample_guided shares them); seeds: not null
+static int steps_call(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
+                      const float* init_z_dev, const float* noise_dev, int num_steps, int sampler, float* out_dev,
+                      void* stream, SampleCall* out) {
   if (num_steps < 0 || (num_steps > 0 && m->N % num_steps))
     return fail(m, MSD_ERR_INVALID_ARGUMENT, "num_steps %d does not divide the handle's %d steps; it takes 0 (= %d) or one of %s",
                 num_steps, m->N, m->N, divisors_of(m->N).c_str());
@@ -2509,6 +2565,17 @@ int msd_sample_steps(msd_model* m, int batch, int rng, int per_row, const uint64
   SampleCall c = plain_call(m, batch, rng, sample_keys(per_row, seeds, stream_ids), init_z_dev, noise_dev, out_dev, stream);
   if (num_steps > 0) { c.steps = num_steps; c.start_step = num_steps - 1; }   // (the handle's own are (N, cfg.sampler), however they were named)
   if (sampler >= 0) c.sampler = sampler;
+  *out = c;
+  return MSD_OK;
+}
+
+int msd_sample_steps(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
+                     const float* init_z_dev, const float* noise_dev, int num_steps, int sampler, float* out_dev,
+                     void* stream) {
+  if (!m) return MSD_ERR_INVALID_ARGUMENT;
+  if (!seeds) return fail(m, MSD_ERR_INVALID_ARGUMENT, "seeds is null");
+  SampleCall c;
+  if (int rc = steps_call(m, batch, rng, per_row, seeds, stream_ids, init_z_dev, noise_dev, num_steps, sampler, out_dev, stream, &c)) return rc;
   return sample_body(m, c);
 }
 
@@ -2518,11 +2585,8 @@ int msd_sample_guided(msd_model* m, int batch, int rng, int per_row, const uint6
   if (!m) return MSD_ERR_INVALID_ARGUMENT;
   if (!seeds) return fail(m, MSD_ERR_INVALID_ARGUMENT, "seeds is null");
   if (batch < 1 || batch > m->Bmax) return fail(m, MSD_ERR_INVALID_ARGUMENT, "batch %d outside [1, %d]", batch, m->Bmax);
-  if (num_steps < 0 || (num_steps > 0 && m->N % num_steps))
-    return fail(m, MSD_ERR_INVALID_ARGUMENT, "num_steps %d does not divide the handle's %d steps; it takes 0 (= %d) or one of %s",
-                num_steps, m->N, m->N, divisors_of(m->N).c_str());
-  if (sampler != -1 && sampler != MSD_SAMPLER_DDPM && sampler != MSD_SAMPLER_DDIM && sampler != MSD_SAMPLER_DPMPP_2M)
-    return fail(m, MSD_ERR_INVALID_ARGUMENT, "Unknown sampler type: %d", sampler);
+  SampleCall c;
+  if (int rc = steps_call(m, batch, rng, per_row, seeds, stream_ids, init_z_dev, noise_dev, num_steps, sampler, out_dev, stream, &c)) return rc;
   if (!weights_host || (n_weights != 1 && n_weights != batch))
     return fail(m, MSD_ERR_INVALID_ARGUMENT, "guidance takes 1 weight or one per row (%d), got %d", batch, weights_host ? n_weights : 0);
   bool all_one = true;
@@ -2530,18 +2594,14 @@ int msd_sample_guided(msd_model* m, int batch, int rng, int per_row, const uint6
     if (!std::isfinite(weights_host[b])) return fail(m, MSD_ERR_INVALID_ARGUMENT, "guidance weight %d is not finite", b);
     all_one = all_one && weights_host[b] == 1.0f;
   }
-  const int K = num_steps > 0 ? num_steps : m->N;
+  const int K = c.steps;
   if (guide_lo == 0 && guide_hi == 0) guide_hi = K;   // the whole scan
   if (guide_lo < 0 || guide_lo >= guide_hi || guide_hi > K)
     return fail(m, MSD_ERR_INVALID_ARGUMENT, "guidance interval [%d, %d) is not inside the call's scan indices [0, %d)", guide_lo, guide_hi, K);
   if (m->passes == 1)   // (a weight-1 handle has buffers for one pass only)
     return fail(m, MSD_ERR_UNSUPPORTED, "a handle created with cfg_weight 1 holds one pass's buffers and takes no per-call guidance: "
                 "create the handle with any weight != 1");
-  if (!m->d_row_wt)
-    if (int rc = dalloc(m, &m->d_row_wt, (size_t)m->Bmax)) return rc;
-  SampleCall c = plain_call(m, batch, rng, sample_keys(per_row, seeds, stream_ids), init_z_dev, noise_dev, out_dev, stream);
-  c.steps = K; c.start_step = K - 1;
-  if (sampler >= 0) c.sampler = sampler;
+  if (int rc = ensure(m, &m->d_row_wt, (size_t)m->Bmax)) return rc;
   c.weights = weights_host; c.n_weights = n_weights; c.guide_lo = guide_lo; c.guide_hi = guide_hi;
   if (all_one) c.guide_lo = c.guide_hi = 0;   // every row follows the cond_wt == 1 branch: no guided step, K one-pass steps
   return sample_body(m, c);
@@ -2549,13 +2609,7 @@ int msd_sample_guided(msd_model* m, int batch, int rng, int per_row, const uint6
 
 int msd_reset_graph(msd_model* m) {
   if (!m) return MSD_ERR_INVALID_ARGUMENT;
-  for (auto& e : m->graphs) {
-    if (e.exec) (void)hipGraphExecDestroy(e.exec);
-    if (e.exec1) (void)hipGraphExecDestroy(e.exec1);
-  }
   m->graphs.clear();
-  for (auto& e : m->loss_graphs)
-    if (e.exec) (void)hipGraphExecDestroy(e.exec);
   m->loss_graphs.clear();
   return MSD_OK;
 }
@@ -2594,13 +2648,12 @@ int msd_decoder_pass(msd_model* m, int batch, int step_index, const float* z_dev
 // and replayed once per time: the time rows, the cursor and the keys live in device memory.
 static int enqueue_loss_eval(msd_model* m, const StepPlan& plan, hipStream_t s) {
   const int n = plan.batch * m->T * m->ND;
-  const int row_blocks = m->T * m->ND % kRngRowBlock == 0 ? m->T * m->ND / kRngRowBlock : 1 << 30;   // (enqueue_step's)
   LossDiffuseParams dp;
-  dp.call = m->d_loss_call; dp.x0 = m->loss_x0; dp.z = m->z;
-  dp.z_hi = m->zp.p[0]; dp.z_lo = m->NP == 2 ? m->zp.p[1] : nullptr;
-  dp.keys = m->d_rng_key; dp.row_blocks = row_blocks; dp.n = n;
+  dp.call = m->d_loss_call; dp.x0 = m->loss_x0;
+  z_out(dp, m);
+  dp.keys = m->d_rng_key; dp.row_blocks = row_blocks_of(m); dp.n = n;
   dp.fmin = m->cfg.feature_min; dp.fmax = m->cfg.feature_max;
-  dp.step_ptr = m->d_step; dp.sat = m->d_sat; dp.sat_tag = (unsigned)KC_SAMPLER + 1u;
+  dp.step_ptr = m->d_step;
   Ctx c{m, s};
   c.begin(KC_SAMPLER);
   launch_loss_diffuse(dp, s);
@@ -2608,7 +2661,7 @@ static int enqueue_loss_eval(msd_model* m, const StepPlan& plan, hipStream_t s) 
   decoder_eval(c, plan, /*publish_step=*/false);
   LossParams lp;
   lp.call = m->d_loss_call; lp.o = m->eps; lp.z = m->z; lp.x0 = m->loss_x0; lp.coef = m->d_coef;
-  lp.keys = m->d_rng_key; lp.row_blocks = row_blocks; lp.n = n; lp.passes = plan.P; lp.n_dims = m->ND;
+  lp.keys = m->d_rng_key; lp.row_blocks = dp.row_blocks; lp.n = n; lp.passes = plan.P; lp.n_dims = m->ND;
   lp.model_output = m->cfg.model_output;
   c.begin(KC_SAMPLER);
   launch_diffusion_loss(lp, s);
@@ -2618,27 +2671,14 @@ static int enqueue_loss_eval(msd_model* m, const StepPlan& plan, hipStream_t s) 
 }
 
 static int find_loss_graph(msd_model* m, const StepPlan& plan, hipStream_t s, hipGraphExec_t* out) {
-  for (auto& e : m->loss_graphs)
-    if (memcmp(&e.plan, &plan, sizeof(plan)) == 0) { *out = e.exec; return MSD_OK; }
-  if (m->loss_graphs.size() >= 6) {   // (a handle that cycles through more shapes than that re-captures; the step graphs stay)
-    for (auto& e : m->loss_graphs) (void)hipGraphExecDestroy(e.exec);
-    m->loss_graphs.clear();
+  msd_model::LossGraphCache::Entry* g = m->loss_graphs.find(plan);
+  if (!g) {
+    m->loss_graphs.make_room(1);   // (the step graphs stay)
+    msd_model::LossGraphCache::Entry ng = {plan};
+    if (int rc = capture_graph(m, s, "loss graph", &ng.exec, [&] { return enqueue_loss_eval(m, plan, s); })) return rc;
+    g = m->loss_graphs.insert(ng);
   }
-  hipGraph_t graph = nullptr;
-  HIP_TRY(m, hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal));
-  const int rc = enqueue_loss_eval(m, plan, s);
-  const hipError_t ce = hipStreamEndCapture(s, &graph);
-  if (ce != hipSuccess || rc) {
-    if (graph) (void)hipGraphDestroy(graph);
-    return rc ? rc : fail(m, MSD_ERR_HIP, "loss graph capture failed: %s", hipGetErrorString(ce));
-  }
-  msd_model::LossGraph g;
-  memcpy(&g.plan, &plan, sizeof(plan));
-  const hipError_t ie = hipGraphInstantiate(&g.exec, graph, nullptr, nullptr, 0);
-  (void)hipGraphDestroy(graph);
-  if (ie != hipSuccess) return fail(m, MSD_ERR_HIP, "hipGraphInstantiate: %s", hipGetErrorString(ie));
-  m->loss_graphs.push_back(g);
-  *out = g.exec;
+  *out = g->exec;
   return MSD_OK;
 }
 
@@ -2647,9 +2687,7 @@ int msd_loss(msd_model* m, const msd_loss_args* a, void* stream) {
   if (!a || a->struct_size != (int32_t)sizeof(msd_loss_args))
     return fail(m, MSD_ERR_INVALID_ARGUMENT, "msd_loss_args.struct_size %d != %d", a ? a->struct_size : 0, (int)sizeof(msd_loss_args));
   // every refusal in front of any device work
-  if (!m->encoded) return fail(m, MSD_ERR_BAD_STATE, "msd_encode has not run");
-  if (a->batch != m->encoded_batch) return fail(m, MSD_ERR_INVALID_ARGUMENT, "batch %d != encoded batch %d", a->batch, m->encoded_batch);
-  if (a->rng != MSD_RNG_PHILOX && a->rng != MSD_RNG_THREEFRY) return fail(m, MSD_ERR_INVALID_ARGUMENT, "unknown rng %d", a->rng);
+  if (int rc = check_encoded_call(m, a->batch, a->rng, a->per_row != 0)) return rc;
   if (a->conditioning != MSD_LOSS_COND && a->conditioning != MSD_LOSS_UNCOND && a->conditioning != MSD_LOSS_BOTH)
     return fail(m, MSD_ERR_INVALID_ARGUMENT, "unknown conditioning %d", a->conditioning);
   if (a->loss_type < MSD_LOSS_X0 || a->loss_type > MSD_LOSS_X0_AND_EPS) return fail(m, MSD_ERR_INVALID_ARGUMENT, "Unknown diffusion loss_type: %d", a->loss_type);
@@ -2662,28 +2700,14 @@ int msd_loss(msd_model* m, const msd_loss_args* a, void* stream) {
       return fail(m, MSD_ERR_INVALID_ARGUMENT, "time index %d (entry %d) outside [0, %d)", a->times_host[j], j, m->N);
   if (m->ND % 4 || 1024 % m->ND)
     return fail(m, MSD_ERR_UNSUPPORTED, "the loss needs n_dims %% 4 == 0 and 1024 %% n_dims == 0 (got %d)", m->ND);
-  const int64_t row_n = (int64_t)m->T * m->ND;
-  if (a->per_row && row_n % kRngRowBlock)
-    return fail(m, MSD_ERR_UNSUPPORTED, "per-row keys need targets_length * n_dims %% %d == 0 (got %lld)", (int)kRngRowBlock, (long long)row_n);
   if (a->conditioning == MSD_LOSS_BOTH && m->passes == 1)
     return fail(m, MSD_ERR_UNSUPPORTED, "a handle created with cfg_weight 1 holds one pass's buffers and takes conditioning %d or %d, not both (%d): "
                 "create the handle with any weight != 1", (int)MSD_LOSS_COND, (int)MSD_LOSS_UNCOND, (int)MSD_LOSS_BOTH);
   // the handle's buffers, each on its own (a call after a failed allocation tries again for the one that is missing)
-  if (!m->loss_x0)
-    if (int rc = dalloc(m, &m->loss_x0, (size_t)m->Bmax * m->T * m->ND)) return rc;
-  if (!m->d_loss_call)
-    if (int rc = dalloc(m, &m->d_loss_call, 1)) return rc;
   const size_t time_words = (size_t)a->n_times * kLossTimeWords;
-  if (time_words > m->loss_times_cap) {   // (the stream is idle: the last call ended with its synchronisation)
-    if (m->d_loss_times) {
-      auto it = std::find(m->allocs.begin(), m->allocs.end(), static_cast<void*>(m->d_loss_times));
-      if (it != m->allocs.end()) m->allocs.erase(it);
-      (void)hipFree(m->d_loss_times);
-      m->d_loss_times = nullptr; m->loss_times_cap = 0;
-    }
-    if (int rc = dalloc(m, &m->d_loss_times, time_words)) return rc;
-    m->loss_times_cap = time_words;
-  }
+  if (int rc = ensure(m, &m->loss_x0, (size_t)m->Bmax * m->T * m->ND)) return rc;
+  if (int rc = ensure(m, &m->d_loss_call, 1)) return rc;
+  if (int rc = grow(m, &m->d_loss_times, &m->loss_times_cap, time_words)) return rc;
   hipStream_t s;
   if (int rc = choose_stream(m, stream, &s)) return rc;
   if (int rc = arm_range(m, s)) return rc;

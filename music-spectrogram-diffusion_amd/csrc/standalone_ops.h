@@ -58,6 +58,12 @@ struct OpKit {
     owned.push_back(q);
     return static_cast<Tp*>(q);
   }
+  // n host elements as new scratch; synchronises (the source may be a temporary).  nullptr on failure.
+  template <class Tp> Tp* put(const Tp* host, size_t n) {
+    Tp* q = get<Tp>(n);
+    const bool done = q && ok(hipMemcpyAsync(q, host, n * sizeof(Tp), hipMemcpyHostToDevice, s)) && ok(hipStreamSynchronize(s));
+    return done ? q : nullptr;
+  }
 
   // zeroed planes (one when np == 1: p[1] stays null, the operand convention); `nan`: every element a NaN instead
   bool planes(size_t n, Planes* out, bool nan = false) {
@@ -117,6 +123,11 @@ struct OpKit {
   unsigned* absmax() const { return flags; }
   unsigned* sat() const { return flags ? flags + 1 : nullptr; }
   template <class P> void arm(P& p) const { p.sat = sat(); p.sat_tag = 1; }
+  // z and planes `zp` of this kit as the output of p, armed: the product's filler (z_out) on the kit's own context
+  template <class P> void z_out_to(P& p, float* z, const Planes& zp) {
+    ctx_model.z = z; ctx_model.zp = zp;
+    z_out(p, &ctx_model, 1u);
+  }
   int finish() {   // synchronises
     unsigned h[2] = {0, 0};
     if (hipMemcpyAsync(h, flags, sizeof(h), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
@@ -514,92 +525,102 @@ msd_gemm_site_args forced_site_args(TileShape tile, int M, int N, int K) {
   return g;
 }
 
-// What the sampler ops share, in ONE place: the argument checks, the coefficient rows of cfg (handed back: the multistep
-// entry derives its side table from them), the staged operands -- the passes of the model output side by side, z copied
-// into z_out (the kernel updates in place), the scan index in both slots -- and the SamplerParams every form starts from
-// (no draw, no planes).  Each entry adds its form's fields on top.  both_passes: the guided forms stage the unconditional
-// output whatever cfg->cfg_weight is (their weights come from a table).
-int sampler_op_base(OpKit& kit, const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
-                    const float* out_uncond_dev, float* z_out_dev, int64_t n, SamplerParams* sp, std::vector<float>* rows,
-                    bool both_passes = false) {
+// The form of a stand-alone sampler launch, as its entry point (msd_op_sampler_step*) describes it: the forms combine as
+// the product's do (enqueue_step) -- guided with either update, known frames with the plain update only.
+struct SamplerOpForm {
+  const float* noise = nullptr;      // the plain update's draw of this step; NULL = zeros.  (The multistep update draws nothing.)
+  const float* known = nullptr;      // != NULL: the keep form on the known mel in model units, with
+  const int32_t* keep = nullptr;     // ... its frames' release words, or -- flags -- msd_sample_keep's flags (any non-zero =
+  int n_dims = 0;                    //     known throughout)
+  bool flags = false;
+  float* x0_prev = nullptr;          // != NULL: the multistep update with this history, at the call's first step or not
+  int first = 0;
+  bool guided = false;               // the guided form: `rows` finite host weights, one per row of n / rows elements, each
+  const float* weights = nullptr;    // a whole number of the sampler's blocks (a block reads ONE weight)
+  int rows = 0;
+};
+
+// One launch of the sampler update on the caller's arrays, in form f.  What the forms share, in ONE place: the argument
+// checks, the coefficient rows of cfg, the staged operands -- the passes of the model output side by side (the guided forms
+// stage the unconditional output whatever cfg->cfg_weight is: their weights come from a table), z copied into z_out (the
+// kernel updates in place), the scan index in both slots -- and the SamplerParams every form starts from (no planes).
+// Then the draw (noise, slot, key rows) or the multistep side table, staged once each, and the launch of the form's arguments.
+int op_sampler_step(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
+                    const float* out_uncond_dev, float* z_out_dev, int64_t n, void* stream, const SamplerOpForm& f) {
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  OpKit kit(s, 1);
+  SamplerMultistepGuidedParams sp;   // the widest form's arguments; the other forms' are its bases
+  if (f.guided) {
+    if (!f.weights || f.rows < 1 || n <= 0 || n % f.rows || (n / f.rows) % kRngRowBlock) return MSD_ERR_INVALID_ARGUMENT;
+    for (int b = 0; b < f.rows; ++b)
+      if (!std::isfinite(f.weights[b])) return MSD_ERR_INVALID_ARGUMENT;
+    sp.row_wt = kit.put(f.weights, (size_t)f.rows);
+    if (!sp.row_wt) return MSD_ERR_HIP;
+    sp.row_blocks = (int)(n / f.rows / kRngRowBlock);
+  }
   if (!cfg || cfg->struct_size != (int32_t)sizeof(msd_config) || !z_dev || !out_cond_dev || !z_out_dev ||
       n <= 0 || n % 4 || n > 0x7FFFFFFFll || step_index < 0 || step_index >= cfg->num_steps)
     return MSD_ERR_INVALID_ARGUMENT;
-  const int passes = (both_passes || cfg->cfg_weight != 1.0f) ? 2 : 1;
+  const int passes = (f.guided || cfg->cfg_weight != 1.0f) ? 2 : 1;
   if (passes == 2 && !out_uncond_dev) return MSD_ERR_INVALID_ARGUMENT;
+  std::vector<float> rows, ms;
   std::string why;
-  if (!build_coef_rows(*cfg, rows, &why)) return MSD_ERR_INVALID_ARGUMENT;
-  hipStream_t s = kit.s;
-  float* coef = kit.get<float>(rows->size());
-  float* eps = kit.get<float>((size_t)passes * n);
-  int* step = kit.get<int>(2);
-  if (!coef || !eps || !step) return MSD_ERR_HIP;
+  if (!build_coef_rows(*cfg, &rows, &why)) return MSD_ERR_INVALID_ARGUMENT;
   const int st[2] = {step_index, step_index};
-  if (hipMemcpyAsync(coef, rows->data(), rows->size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(eps, out_cond_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+  float* eps = kit.get<float>((size_t)passes * n);
+  sp.coef = kit.put(rows.data(), rows.size());
+  sp.step_ptr = kit.put(st, 2);
+  if (!eps || !sp.coef || !sp.step_ptr) return MSD_ERR_HIP;
+  if (hipMemcpyAsync(eps, out_cond_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
       (passes == 2 && hipMemcpyAsync(eps + n, out_uncond_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) ||
       hipMemcpyAsync(z_out_dev, z_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
-      hipMemcpyAsync(step, st, sizeof(st), hipMemcpyHostToDevice, s) != hipSuccess ||
       hipStreamSynchronize(s) != hipSuccess)
     return MSD_ERR_HIP;
-  sp->eps = eps; sp->z = z_out_dev; sp->noise_slot = nullptr; sp->coef = coef; sp->step_ptr = step;
-  sp->n = (int)n; sp->passes = passes; sp->cond_wt = cfg->cfg_weight; sp->clip_x0 = cfg->clip_x0;
-  sp->ddim = 0; sp->model_output = cfg->model_output;
-  sp->z_hi = nullptr; sp->z_lo = nullptr; sp->step_from_slot1 = 1;
-  return MSD_OK;
-}
-int sampler_op_finish(hipStream_t s) {
-  if (hipGetLastError() != hipSuccess) return MSD_ERR_HIP;
-  return hipStreamSynchronize(s) == hipSuccess ? MSD_OK : MSD_ERR_HIP;
-}
-
-// one launch of the sampler update on the caller's arrays; known_scaled_dev != NULL: the keep form, keep_mask_dev its
-// frames' release words, or -- flags -- msd_sample_keep's flags (any non-zero = known throughout)
-int op_sampler_step(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
-                    const float* out_uncond_dev, const float* noise_dev, const float* known_scaled_dev,
-                    const int32_t* keep_mask_dev, int n_dims, float* z_out_dev, int64_t n, void* stream, bool flags = false) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  OpKit kit(s, 1);
-  SamplerKeepParams sp;
-  std::vector<float> rows;
-  if (const int rc = sampler_op_base(kit, cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, z_out_dev, n, &sp, &rows)) return rc;
-  float* noise = kit.get<float>((size_t)n);   // one step's draw (zeros) when the caller gives none
-  const float** slot = kit.get<const float*>(1);
-  uint32_t* key = kit.get<uint32_t>(kRngWords);   // the kernel fetches the words of its own draw up front, used or not (table row 0: SamplerParams::row_blocks' default)
-  if (!noise || !slot || !key) return MSD_ERR_HIP;
-  // the kernel indexes noise as base + i * n: hand it base = draw - i * n
-  const float* base = (noise_dev ? noise_dev : noise) - (size_t)step_index * n;
-  if (hipMemcpyAsync(slot, &base, sizeof(base), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-    return MSD_ERR_HIP;
-  sp.noise_slot = slot; sp.rng_key = key; sp.ddim = cfg->sampler == MSD_SAMPLER_DDIM;
-  if (known_scaled_dev) {
-    sp.xk = known_scaled_dev; sp.keep = keep_mask_dev; sp.n_dims = n_dims;
-    if (flags) {
-      int32_t* words = kit.get<int32_t>((size_t)(n / n_dims));
+  sp.eps = eps; sp.z = z_out_dev; sp.noise_slot = nullptr;
+  sp.n = (int)n; sp.passes = passes; sp.cond_wt = cfg->cfg_weight; sp.clip_x0 = cfg->clip_x0;
+  sp.ddim = 0; sp.model_output = cfg->model_output;
+  sp.z_hi = nullptr; sp.z_lo = nullptr; sp.step_from_slot1 = 1;
+  if (f.x0_prev) {   // (noise_slot / rng_key stay null: the form makes no draw and reads neither)
+    build_multistep_rows(rows, &ms);
+    sp.coef_ms = kit.put(ms.data(), ms.size());
+    if (!sp.coef_ms) return MSD_ERR_HIP;
+    sp.x0_prev = f.x0_prev; sp.first_step = f.first ? step_index : -1;
+  } else {
+    float* noise = kit.get<float>((size_t)n);   // one step's draw (zeros) when the caller gives none
+    // the kernel fetches the words of its own draw up front, used or not: one (zero) row per row of z (not guided: table
+    // row 0 only, SamplerParams::row_blocks' default)
+    sp.rng_key = kit.get<uint32_t>((size_t)(f.guided ? f.rows : 1) * kRngWords);
+    if (!noise || !sp.rng_key) return MSD_ERR_HIP;
+    // the kernel indexes noise as base + i * n: hand it base = draw - i * n
+    const float* base = (f.noise ? f.noise : noise) - (size_t)step_index * n;
+    sp.noise_slot = kit.put(&base, 1);
+    if (!sp.noise_slot) return MSD_ERR_HIP;
+    sp.ddim = cfg->sampler == MSD_SAMPLER_DDIM;
+  }
+  if (f.x0_prev) {
+    if (f.guided) launch_sampler_step(sp, s);
+    else launch_sampler_step(static_cast<const SamplerMultistepParams&>(sp), s);
+  } else if (f.guided) {
+    SamplerGuidedParams gp;
+    static_cast<SamplerParams&>(gp) = sp;
+    gp.row_wt = sp.row_wt;
+    launch_sampler_step(gp, s);
+  } else if (f.known) {
+    SamplerKeepParams kp;
+    static_cast<SamplerParams&>(kp) = sp;
+    kp.xk = f.known; kp.keep = f.keep; kp.n_dims = f.n_dims;
+    if (f.flags) {
+      int32_t* words = kit.get<int32_t>((size_t)(n / f.n_dims));
       if (!words) return MSD_ERR_HIP;
-      launch_normalize_flags(keep_mask_dev, words, (int)(n / n_dims), s);
-      sp.keep = words;
+      launch_normalize_flags(f.keep, words, (int)(n / f.n_dims), s);
+      kp.keep = words;
     }
-    launch_sampler_step(sp, s);
+    launch_sampler_step(kp, s);
   } else {
     launch_sampler_step(static_cast<const SamplerParams&>(sp), s);
   }
-  return sampler_op_finish(s);
-}
-
-// The guided forms' row weights: `rows` finite host floats, one per row of n / rows elements, each a whole number of the
-// sampler's blocks (a block reads ONE weight); uploaded to kit scratch.  row_blocks = blocks per row.
-int guided_op_weights(OpKit& kit, const float* weights_host, int rows, int64_t n, const float** table, int* row_blocks) {
-  if (!weights_host || rows < 1 || n <= 0 || n % rows || (n / rows) % kRngRowBlock) return MSD_ERR_INVALID_ARGUMENT;
-  for (int b = 0; b < rows; ++b)
-    if (!std::isfinite(weights_host[b])) return MSD_ERR_INVALID_ARGUMENT;
-  float* w = kit.get<float>((size_t)rows);
-  if (!w) return MSD_ERR_HIP;
-  if (hipMemcpyAsync(w, weights_host, (size_t)rows * sizeof(float), hipMemcpyHostToDevice, kit.s) != hipSuccess ||
-      hipStreamSynchronize(kit.s) != hipSuccess)
-    return MSD_ERR_HIP;
-  *table = w; *row_blocks = (int)(n / rows / kRngRowBlock);
-  return MSD_OK;
+  if (hipGetLastError() != hipSuccess) return MSD_ERR_HIP;
+  return hipStreamSynchronize(s) == hipSuccess ? MSD_OK : MSD_ERR_HIP;
 }
 
 // ---- one attention launch the way the decoder fills it (tests/test_gpu_attention_forms.py) ---------------------------
@@ -936,11 +957,13 @@ int msd_op_threefry(int stage, uint64_t seed, int64_t fold, const uint32_t* bits
   return threefry_fill(stage, seed, fold, bits_in_dev, out_dev, n, static_cast<hipStream_t>(stream));
 }
 
+// the sampler update's entry points: each checks what only it takes and names its form (op_sampler_step)
 int msd_op_sampler_step(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
                         const float* out_uncond_dev, const float* noise_dev, float* z_out_dev, int64_t n,
                         void* stream) {
-  return op_sampler_step(cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, noise_dev, nullptr, nullptr, 0, z_out_dev,
-                         n, stream);
+  SamplerOpForm f;
+  f.noise = noise_dev;
+  return op_sampler_step(cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, z_out_dev, n, stream, f);
 }
 
 int msd_op_sampler_step_keep(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
@@ -948,8 +971,9 @@ int msd_op_sampler_step_keep(const msd_config* cfg, int step_index, const float*
                              const int32_t* keep_mask_dev, int n_dims, float* z_out_dev, int64_t n, void* stream) {
   if (!known_scaled_dev || !keep_mask_dev || n_dims <= 0 || n_dims % 4 || n <= 0 || n % n_dims)
     return MSD_ERR_INVALID_ARGUMENT;
-  return op_sampler_step(cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, noise_dev, known_scaled_dev, keep_mask_dev,
-                         n_dims, z_out_dev, n, stream, /*flags=*/true);
+  SamplerOpForm f;
+  f.noise = noise_dev; f.known = known_scaled_dev; f.keep = keep_mask_dev; f.n_dims = n_dims; f.flags = true;
+  return op_sampler_step(cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, z_out_dev, n, stream, f);
 }
 
 int msd_op_sampler_step_release(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
@@ -957,70 +981,35 @@ int msd_op_sampler_step_release(const msd_config* cfg, int step_index, const flo
                                 const int32_t* release_dev, int n_dims, float* z_out_dev, int64_t n, void* stream) {
   if (!known_scaled_dev || !release_dev || n_dims <= 0 || n_dims % 4 || n <= 0 || n % n_dims)
     return MSD_ERR_INVALID_ARGUMENT;
-  return op_sampler_step(cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, noise_dev, known_scaled_dev, release_dev,
-                         n_dims, z_out_dev, n, stream);
+  SamplerOpForm f;
+  f.noise = noise_dev; f.known = known_scaled_dev; f.keep = release_dev; f.n_dims = n_dims;
+  return op_sampler_step(cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, z_out_dev, n, stream, f);
 }
 
 int msd_op_sampler_step_multistep(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
                                   const float* out_uncond_dev, float* x0_prev_inout_dev, int first, float* z_out_dev,
                                   int64_t n, void* stream) {
   if (!x0_prev_inout_dev) return MSD_ERR_INVALID_ARGUMENT;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  OpKit kit(s, 1);
-  SamplerMultistepParams sp;   // (noise_slot / rng_key stay null: the form makes no draw and reads neither)
-  std::vector<float> rows, ms;
-  if (const int rc = sampler_op_base(kit, cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, z_out_dev, n, &sp, &rows)) return rc;
-  build_multistep_rows(rows, &ms);
-  float* coef_ms = kit.get<float>(ms.size());
-  if (!coef_ms) return MSD_ERR_HIP;
-  if (hipMemcpyAsync(coef_ms, ms.data(), ms.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess)
-    return MSD_ERR_HIP;
-  sp.x0_prev = x0_prev_inout_dev; sp.coef_ms = coef_ms; sp.first_step = first ? step_index : -1;
-  launch_sampler_step(sp, s);
-  return sampler_op_finish(s);
+  SamplerOpForm f;
+  f.x0_prev = x0_prev_inout_dev; f.first = first;
+  return op_sampler_step(cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, z_out_dev, n, stream, f);
 }
 
 int msd_op_sampler_step_guided(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
                                const float* out_uncond_dev, const float* noise_dev, const float* weights_host, int rows,
                                float* z_out_dev, int64_t n, void* stream) {
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  OpKit kit(s, 1);
-  SamplerGuidedParams sp;
-  std::vector<float> coef_rows;
-  if (const int rc = guided_op_weights(kit, weights_host, rows, n, &sp.row_wt, &sp.row_blocks)) return rc;
-  if (const int rc = sampler_op_base(kit, cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, z_out_dev, n, &sp, &coef_rows, /*both_passes=*/true)) return rc;
-  float* noise = kit.get<float>((size_t)n);   // one step's draw (zeros) when the caller gives none
-  const float** slot = kit.get<const float*>(1);
-  uint32_t* key = kit.get<uint32_t>((size_t)rows * kRngWords);   // fetched up front, used or not: one (zero) row per row of z
-  if (!noise || !slot || !key) return MSD_ERR_HIP;
-  const float* base = (noise_dev ? noise_dev : noise) - (size_t)step_index * n;   // (op_sampler_step's)
-  if (hipMemcpyAsync(slot, &base, sizeof(base), hipMemcpyHostToDevice, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess)
-    return MSD_ERR_HIP;
-  sp.noise_slot = slot; sp.rng_key = key; sp.ddim = cfg->sampler == MSD_SAMPLER_DDIM;
-  launch_sampler_step(sp, s);
-  return sampler_op_finish(s);
+  SamplerOpForm f;
+  f.noise = noise_dev; f.guided = true; f.weights = weights_host; f.rows = rows;
+  return op_sampler_step(cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, z_out_dev, n, stream, f);
 }
 
 int msd_op_sampler_step_multistep_guided(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
                                          const float* out_uncond_dev, float* x0_prev_inout_dev, int first,
                                          const float* weights_host, int rows, float* z_out_dev, int64_t n, void* stream) {
   if (!x0_prev_inout_dev) return MSD_ERR_INVALID_ARGUMENT;
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  OpKit kit(s, 1);
-  SamplerMultistepGuidedParams sp;   // (noise_slot / rng_key stay null: the form makes no draw and reads neither)
-  std::vector<float> coef_rows, ms;
-  if (const int rc = guided_op_weights(kit, weights_host, rows, n, &sp.row_wt, &sp.row_blocks)) return rc;
-  if (const int rc = sampler_op_base(kit, cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, z_out_dev, n, &sp, &coef_rows, /*both_passes=*/true)) return rc;
-  build_multistep_rows(coef_rows, &ms);
-  float* coef_ms = kit.get<float>(ms.size());
-  if (!coef_ms) return MSD_ERR_HIP;
-  if (hipMemcpyAsync(coef_ms, ms.data(), ms.size() * sizeof(float), hipMemcpyHostToDevice, s) != hipSuccess ||
-      hipStreamSynchronize(s) != hipSuccess)
-    return MSD_ERR_HIP;
-  sp.x0_prev = x0_prev_inout_dev; sp.coef_ms = coef_ms; sp.first_step = first ? step_index : -1;
-  launch_sampler_step(sp, s);
-  return sampler_op_finish(s);
+  SamplerOpForm f;
+  f.x0_prev = x0_prev_inout_dev; f.first = first; f.guided = true; f.weights = weights_host; f.rows = rows;
+  return op_sampler_step(cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, z_out_dev, n, stream, f);
 }
 
 int msd_op_diffuse_to_step(const msd_config* cfg, int step_index, const float* mel_dev, const float* eps_dev,
@@ -1038,10 +1027,10 @@ int msd_op_diffuse_to_step(const msd_config* cfg, int step_index, const float* m
   Planes zp;
   if (!kit.init_flags() || !kit.planes((size_t)n, &zp)) return MSD_ERR_HIP;
   DiffuseParams dp;
-  dp.mel = mel_dev; dp.eps = eps_dev; dp.xk = xk_out_dev; dp.z = z_out_dev; dp.z_hi = zp.p[0]; dp.z_lo = zp.p[1];
+  dp.mel = mel_dev; dp.eps = eps_dev; dp.xk = xk_out_dev;
+  kit.z_out_to(dp, z_out_dev, zp);
   dp.n = (int)n; dp.fmin = cfg->feature_min; dp.fmax = cfg->feature_max;
   diffuse_coefs(rows[(size_t)step_index * kCoefCount + kCoefLogsnrT], &dp.alpha, &dp.sigma);
-  kit.arm(dp);
   launch_diffuse_to_step(dp, s);
   if (hipGetLastError() != hipSuccess) return MSD_ERR_HIP;
   kit.back(zp, z_planes_out_dev, (size_t)n);
@@ -1063,9 +1052,9 @@ int msd_op_renoise(const msd_config* cfg, int from_level, int to_level, const fl
   Planes zp;
   if (!kit.init_flags() || !kit.planes((size_t)n, &zp)) return MSD_ERR_HIP;
   RenoiseParams rp;   // (no keys, no key table, no scan index: the caller's eps, and nothing armed behind the jump)
-  rp.z_in = z_dev; rp.eps = eps_dev; rp.z = z_out_dev; rp.z_hi = zp.p[0]; rp.z_lo = zp.p[1]; rp.n = (int)n;
+  rp.z_in = z_dev; rp.eps = eps_dev; rp.n = (int)n;
+  kit.z_out_to(rp, z_out_dev, zp);
   renoise_coefs(rows, from_level, to_level, &rp.a, &rp.b);
-  kit.arm(rp);
   launch_renoise(rp, s);
   if (hipGetLastError() != hipSuccess) return MSD_ERR_HIP;
   kit.back(zp, z_planes_out_dev, (size_t)n);
