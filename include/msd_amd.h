@@ -55,7 +55,8 @@ extern "C" {
                                       jumps in the sampler scan);
                                       msd_sample_guided, msd_op_sampler_step_guided and
                                       msd_op_sampler_step_multistep_guided (a guidance weight per call or per row, applied
-                                      in an interval of the scan).
+                                      in an interval of the scan); msd_loss and msd_op_diffusion_loss;
+                                      msd_invert and msd_op_invert_step (deterministic DDIM inversion).
                                    6: cross_merge_in_launch, cross_q_fold, mlp_in_persistent appended to msd_config.
                                    5: dedup_layer0, cross_key_split, keep_raw_weights, kv_touch_ahead appended to msd_config.
                                    4: every caller-selectable knob is a msd_config field (attn_q_planes / attn_p_planes
@@ -885,6 +886,48 @@ int msd_loss(msd_model* m, const msd_loss_args* args, void* stream);
 int msd_op_diffusion_loss(const msd_config* cfg, int step_index, int loss_type, int loss_norm, const float* o_dev,
                           const float* z_dev, const float* x0_dev, const float* eps_dev, const float* mask_dev, int n_dims,
                           float* out_dev, int64_t n, void* stream);
+
+/* ---- deterministic DDIM inversion (appended to ABI 7): from a mel and the encoded tokens to the noise that renders it -----
+ * A call of K steps (K | num_steps) has levels 0 .. K; level l has time l / K, logsnr_l of the SAMPLER schedule, alpha_l =
+ * sqrt(sigmoid(logsnr_l)) and sigma_l = sqrt(sigmoid(-logsnr_l)).  Level 0 is scale_features(mel, clip=True) (the context
+ * path's expression and bits); step i = 0 .. K - 1 takes level i to level i + 1 with ONE decoder evaluation of the state it
+ * has, at the UPPER level's time (i + 1) / K (table row (i + 1) num_steps / K - 1, as scan index i of msd_sample_steps), and
+ * no draw:
+ *   eps  = the model output -> eps at the TRAIN schedule's log-SNR (the sampler's conversion), combined as
+ *          w eps_cond + (1 - w) eps_uncond when the row's weight w != 1 (two rounded products and a sum)
+ *   z_up = fmaf(b_i, eps, a_i * z)      a_i = alpha_{i+1} / alpha_i, b_i = sigma_{i+1} - a_i sigma_i  (i >= 1)
+ *                                       a_0 = alpha_1, b_0 = sigma_1   (the mirror of "scan index 0 returns x0")
+ * a and b are computed in double from the float32 log-SNRs of the call's K coefficient rows and rounded once.  This is the
+ * exact inverse of the DDIM step of msd_sample_steps(MSD_SAMPLER_DDIM, K) with eps frozen -- taken at the state below, not
+ * above -- where the train and the sampler schedule agree at the time; with a linear sampler schedule, or different train
+ * and sampler schedules, the step is what these lines say.  msd_config.clip_x0 is IGNORED: the clip is not invertible where
+ * it binds.  out_dev is z at level K: float32 [batch, T, n] in MODEL units (not unscaled), an init_z_dev for msd_sample_steps.
+ * num_steps: 0 = the handle's; K must divide it.  weights_host / n_weights: NULL or 0 = weight 1 for every row; else 1 or
+ * `batch` finite floats, per-row weights need targets_length * n_dims % 1024 == 0.  Every weight == 1 runs the one-pass plan
+ * (half the rows in every launch); a handle created with cfg_weight 1 holds one pass's buffers and takes nothing else
+ * (MSD_ERR_UNSUPPORTED).  Needs msd_encode; batch must be the encoded batch.  Every refusal comes before any device work
+ * and leaves the handle usable.  The call ends with one synchronisation and the half-plane range check (MSD_ERR_RANGE).
+ * It overwrites the sampler's state (z, the scan index, the key table, the row weights), which every sampling call writes
+ * afresh; its graphs live in the handle's step-graph cache under a key of their own.
+ * NOT built: fixed-point refinement of a step, stopping below level K, inversion under DDPM noise or the multistep sampler,
+ * known frames, per-frame weights, K that does not divide num_steps. */
+typedef struct msd_invert_args {
+  int32_t struct_size;         /* sizeof(msd_invert_args) */
+  int32_t batch;               /* rows; = the encoded batch */
+  const float* mel_dev;        /* [batch, T, n] the mel, mel units */
+  int32_t num_steps;           /* K; 0 = the handle's */
+  int32_t n_weights;           /* 0, 1 or batch */
+  const float* weights_host;   /* [n_weights] guidance weights, or NULL = 1 */
+  float* out_dev;              /* [batch, T, n] z at level K, model units */
+} msd_invert_args;
+int msd_invert(msd_model* m, const msd_invert_args* args, void* stream);
+/* One inversion update alone (unit test): z_out_dev = fmaf(b, eps, a * z_dev) at step_index of cfg's tables (cfg->num_steps
+ * is the call's K) from the model outputs of the passes, row r of `rows` rows of n / rows elements (a multiple of 1024)
+ * with weights_host[r]; z_planes_out_dev = z_out's operand planes of cfg->precision merged back to float32.
+ * out_uncond_dev may be NULL if and only if every weight is 1.  cfg->cfg_weight and cfg->clip_x0 are not read.  Synchronises. */
+int msd_op_invert_step(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
+                       const float* out_uncond_dev, const float* weights_host, int rows, float* z_out_dev,
+                       float* z_planes_out_dev, int64_t n, void* stream);
 
 #ifdef __cplusplus
 }

@@ -27,7 +27,7 @@ LIBS = {'f16': (LIB, []), 'bf16': (os.path.join(CSRC, 'libmsd_amd_bf16.so'), ['-
 EXP_SRC = os.path.join(EXP, 'src_r04')   # round 4's sources with the experiments still inside
 EXP_LIBS = {'exp': (LIB_EXP, ['-DMSD_EXPERIMENTS=1'])}
 SOURCES = ['msd_api.hip']
-HEADERS = ['common.h', 'phase_stamps.h', 'gemm_h16.h', 'gemm_f32.h', 'attention.h', 'elementwise.h', 'keep_frames_tail.h', 'multistep_tail.h', 'guided_tail.h', 'loss_tail.h', 'standalone_ops.h', 'vocoder.h',
+HEADERS = ['common.h', 'phase_stamps.h', 'gemm_h16.h', 'gemm_f32.h', 'attention.h', 'elementwise.h', 'keep_frames_tail.h', 'multistep_tail.h', 'guided_tail.h', 'loss_tail.h', 'invert_tail.h', 'standalone_ops.h', 'vocoder.h',
            os.path.join('..', '..', 'include', 'msd_amd.h')]
 EXP_HEADERS = ['chain.h', 'gemm_h16_exp.h', 'gemm_splitk_exchange.inc', 'gemm_h16_pair.h', 'gemm_h16_wide.h', 'gemm_h16_ls.h']
 
@@ -77,7 +77,9 @@ NO_SCRATCH_VOCODER_KERNELS = ('voc_pad_signal_kernel', 'voc_exp_kernel', 'voc_lo
                               'voc_phase_kernel', 'voc_magnitude_kernel')
 # ... and the two kernels of msd_loss (csrc/loss_tail.h: around the decoder pass of every evaluation)
 NO_SCRATCH_LOSS_KERNELS = ('loss_diffuse_kernel', 'diffusion_loss_kernel')
-NO_SCRATCH_KERNELS = NO_SCRATCH_STEP_KERNELS + NO_SCRATCH_EDIT_KERNELS + NO_SCRATCH_MULTISTEP_KERNELS + NO_SCRATCH_VOCODER_KERNELS + NO_SCRATCH_LOSS_KERNELS   # what build() checks in every product listing
+# ... and the inversion form of msd_invert (csrc/invert_tail.h: the step's last launch, like the plain form; three instances)
+NO_SCRATCH_INVERT_KERNELS = ('sampler_invert_kernel',)
+NO_SCRATCH_KERNELS = NO_SCRATCH_STEP_KERNELS + NO_SCRATCH_EDIT_KERNELS + NO_SCRATCH_MULTISTEP_KERNELS + NO_SCRATCH_VOCODER_KERNELS + NO_SCRATCH_LOSS_KERNELS + NO_SCRATCH_INVERT_KERNELS   # what build() checks in every product listing
 
 
 def check_no_scratch(listing: str, kernels=NO_SCRATCH_STEP_KERNELS) -> str:

@@ -346,8 +346,10 @@ __device__ __forceinline__ void convert_model_output(const float (&c)[kCoefCount
 // FORM: kFormPlain = the step; kFormKeep = the step with KNOWN frames (msd_sample_keep): on a kept element (kf, xk = its
 // known value in model units), after the CFG combine and the clip, pred_x0 := xk and pred_eps := predict_eps_from_x0(z_t,
 // xk, logsnr_t) -- the clip branch's expression -- so the element follows the posterior q(z_s | z_t, x0 = xk) and arrives
-// at xk at i == 0; kFormX0 = pred_x0 alone (converted, combined, clipped), what the multistep form steps from.
-enum { kFormPlain = 0, kFormKeep, kFormX0 };
+// at xk at i == 0; kFormX0 = pred_x0 alone (converted, combined, clipped), what the multistep form steps from; kFormEps =
+// pred_eps alone, converted and combined and NOT clipped (p.clip_x0 is not read), what the inversion steps from
+// (invert_tail.h).
+enum { kFormPlain = 0, kFormKeep, kFormX0, kFormEps };
 template <int MODE, int FORM>
 __device__ __forceinline__ float sampler_update(const SamplerParams& p, const float (&c)[kCoefCount], int i, float z,
                                                 float o_c, float o_u, float nz = 0.f, float xk = 0.f, bool kf = false) {
@@ -360,6 +362,7 @@ __device__ __forceinline__ float sampler_update(const SamplerParams& p, const fl
     eps = p.cond_wt * eps + (1.0f - p.cond_wt) * eps_u;
     x0 = c[kCoefX0Scale] * fmaf(-eps, c[kCoefX0Eps], z);
   }
+  if constexpr (FORM == kFormEps) return eps;
   // jnp.clip semantics: a NaN stays a NaN (fminf / fmaxf would turn it into a bound and hide a poisoned input --
   // the half-plane range flag sees Inf but not NaN: v_max3_f32 drops NaN operands)
   if constexpr (FORM == kFormX0) {
@@ -581,6 +584,17 @@ struct SamplerMultistepGuidedParams : SamplerMultistepParams {
 };
 void launch_sampler_step(const SamplerGuidedParams& sp, hipStream_t s);
 void launch_sampler_step(const SamplerMultistepGuidedParams& sp, hipStream_t s);
+
+// The inversion's arguments (msd_invert; kernel and launch: invert_tail.h): one deterministic DDIM step UP the scan, from
+// level i to level i + 1.  A struct of its own once more: the plain instances' argument block stays at its 120 bytes.
+// Row i of the side table coef_inv: {a, b, 0, 0} of z_up = fmaf(b, eps, a * z) (msd_api.hip build_invert_rows).  The row
+// weights are read as SamplerGuidedParams::row_wt is; the form makes no draw: noise_slot and rng_key are not read.
+enum { kInvA = 0, kInvB, kInvPad0, kInvPad1, kInvCount };
+struct SamplerInvertParams : SamplerParams {
+  const float* row_wt = nullptr;     // [rows] eval_condition_weight per row of z; a weight of exactly 1 reads one pass
+  const float* coef_inv = nullptr;   // [K][kInvCount]
+};
+void launch_sampler_invert(const SamplerInvertParams& sp, hipStream_t s);
 
 // The denoising loss (msd_loss; kernels and launches: loss_tail.h).  What changes from call to call -- the caller's buffers,
 // the loss form, the time list -- lives in ONE device struct the handle owns, so a captured (diffuse, decoder, loss) graph

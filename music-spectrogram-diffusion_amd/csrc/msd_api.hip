@@ -238,8 +238,8 @@ struct msd_model {
   std::vector<uint32_t> h_pass_keys;   // host staging of that upload
   // msd_sample_steps: the sampler's coefficient rows for a call of K steps (K | N), built on the first such call and kept
   // (host copy + device table; K == N is d_coef itself), and -- MSD_SAMPLER_DPMPP_2M -- the multistep side table of K and
-  // the previous step's pred_x0 [Bmax][T][n] (make_step_view builds the tables)
-  struct StepTables { std::vector<float> h_coef; float* coef = nullptr; float* coef_ms = nullptr; };
+  // the previous step's pred_x0 [Bmax][T][n] (make_step_view builds the tables); msd_invert: the inversion's side table of K
+  struct StepTables { std::vector<float> h_coef; float* coef = nullptr; float* coef_ms = nullptr; float* coef_inv = nullptr; };
   std::map<int, StepTables> step_tables;
   float* x0_prev = nullptr;
   // msd_loss: the target in model units [Bmax][T][n], the per-call words of the two loss kernels (elementwise.h LossCall) and
@@ -276,8 +276,9 @@ struct msd_model {
   // kernel in; the handle's own (N, cfg.sampler) is the key every other entry point looks up, as it always did.
   // `guided`: msd_sample_guided's two-pass graphs launch the sampler's guided form (the row weights come from d_row_wt);
   // its one-pass steps replay plain graphs of the one-pass plan.  (An int like its neighbours: no padding bytes.)
+  // `invert`: msd_invert's graphs launch the inversion kernel, which counts the scan index up.
   // An entry: `exec` runs graph_steps steps, `exec1` one (captured on first need).  find_graphs looks up and captures.
-  struct GraphKey { StepPlan plan; int steps, sampler, keep, guided; };   // ONE key, compared bytewise (GraphCache)
+  struct GraphKey { StepPlan plan; int steps, sampler, keep, guided, invert; };   // ONE key, compared bytewise (GraphCache)
   using StepGraphCache = GraphCache<GraphKey, 8>;
   using StepGraphs = StepGraphCache::Entry;
   StepGraphCache graphs;
@@ -493,6 +494,8 @@ struct StepView {
   int sampler = 0;                  // msd_sampler_kind
   bool keep = false;                // the sampler's keep form on the handle's known-frame buffers (msd_sample_keep / _edit)
   bool guided = false;              // the sampler's guided form on the handle's row-weight table (msd_sample_guided)
+  bool invert = false;              // the inversion form: the scan index counts up (msd_invert; kernel: invert_tail.h)
+  const float* coef_inv = nullptr;  // [K][kInvCount], the inversion form only
 };
 
 struct Ctx {
@@ -1106,6 +1109,24 @@ void build_multistep_rows(const std::vector<float>& rows, std::vector<float>* ou
   }
 }
 
+// The inversion's side table (invert_tail.h, kInv*) from the K rows of build_coef_rows: with alpha = sqrt(sigmoid(logsnr)) and
+// sigma = sqrt(sigmoid(-logsnr)) of the SAMPLER schedule's float32 table values -- level i + 1: row i's logsnr_t, level i: row
+// i's logsnr_s -- {a, b} = {alpha_{i+1} / alpha_i, sigma_{i+1} - a sigma_i} for i >= 1 and {alpha_1, sigma_1} for row 0 (the
+// mirror of "scan index 0 returns x0"), in double, rounded once.
+void build_invert_rows(const std::vector<float>& rows, std::vector<float>* out) {
+  const int K = (int)(rows.size() / kCoefCount);
+  out->assign((size_t)K * kInvCount, 0.f);
+  for (int i = 0; i < K; ++i) {
+    const double lt = rows[(size_t)i * kCoefCount + kCoefLogsnrT], ls = rows[(size_t)i * kCoefCount + kCoefLogsnrS];
+    const double alpha_t = std::sqrt(1.0 / (1.0 + std::exp(-lt))), sigma_t = std::sqrt(1.0 / (1.0 + std::exp(lt)));
+    const double alpha_s = std::sqrt(1.0 / (1.0 + std::exp(-ls))), sigma_s = std::sqrt(1.0 / (1.0 + std::exp(ls)));
+    const double a = i == 0 ? alpha_t : alpha_t / alpha_s;
+    float* c = &(*out)[(size_t)i * kInvCount];
+    c[kInvA] = (float)a;
+    c[kInvB] = (float)(i == 0 ? sigma_t : sigma_t - a * sigma_s);
+  }
+}
+
 // The part-way start's coefficients (diffuse_to_step_kernel): alpha = sqrt(sigmoid(logsnr_t)), sigma = sqrt(sigmoid(-logsnr_t))
 // of a row's sampler log-SNR, in double, rounded once
 void diffuse_coefs(float logsnr_t, float* alpha, float* sigma) {
@@ -1645,7 +1666,12 @@ void enqueue_step(Ctx& c, const StepPlan& p) {
   z_out(sp, m);
   c.begin(KC_SAMPLER);
   sp.step_from_slot1 = 1;
-  if (sampler == MSD_SAMPLER_DPMPP_2M) {   // (never with keep: check_call refuses the pair)
+  if (c.v.invert) {   // (msd_invert: no draw, no known frames; the row weights decide the passes it reads)
+    SamplerInvertParams ip;
+    static_cast<SamplerParams&>(ip) = sp;
+    ip.row_wt = m->d_row_wt; ip.coef_inv = c.v.coef_inv;
+    launch_sampler_invert(ip, c.s);
+  } else if (sampler == MSD_SAMPLER_DPMPP_2M) {   // (never with keep: check_call refuses the pair)
     SamplerMultistepGuidedParams mp;
     static_cast<SamplerParams&>(mp) = sp;
     mp.x0_prev = m->x0_prev; mp.coef_ms = c.v.coef_ms;
@@ -2143,6 +2169,8 @@ struct SampleCall {
   // takes the cond_wt == 1 branch (one decoder pass) outside; null = the handle's own weight at every step, as ever
   const float* weights = nullptr;   // host
   int n_weights = 0, guide_lo = 0, guide_hi = 0;
+  // msd_invert: the caller's mel [batch, T, n] (device); the scan starts at index 0 from it and counts up.  null = a sampling call
+  const float* invert_mel = nullptr;
 };
 
 static SampleKeys sample_keys(int per_row, const uint64_t* seeds, const uint64_t* stream_ids) {
@@ -2166,8 +2194,9 @@ static std::string divisors_of(int n) {
 // The view of a call of K steps with `sampler` (K | N, a known kind) in the keep form or not, every field filled, with what
 // it needs built on first use: the known-frame buffers (each on its own, so that a call after a failed allocation tries
 // again for the one that is missing), the K-row coefficient table (K == N: the handle's own), the multistep side table,
-// x0_prev.  Runs outside stream capture; every allocation is the handle's.
-static int make_step_view(msd_model* m, int K, int sampler, bool keep, StepView* v) {
+// x0_prev; `invert`: the inversion form (msd_invert) with its side table and the row-weight table.  Runs outside stream
+// capture; every allocation is the handle's.
+static int make_step_view(msd_model* m, int K, int sampler, bool keep, StepView* v, bool invert = false) {
   const int N = m->N;
   if (keep) {
     if (int rc = ensure(m, &m->keep_xk, (size_t)m->Bmax * m->T * m->ND)) return rc;
@@ -2179,7 +2208,8 @@ static int make_step_view(msd_model* m, int K, int sampler, bool keep, StepView*
   const int64_t widest = std::max<int64_t>(std::max<int64_t>(2 * m->Ld * m->D, (int64_t)m->Ld * 3 * m->J), (int64_t)m->Ld * 2 * m->F);
   if (widest * v->mul > 0x7FFFFFFFll)
     return fail(m, MSD_ERR_UNSUPPORTED, "a stride of %d table rows does not fit the GEMM epilogues' 32-bit row stride", v->mul);
-  if (K == N && sampler != MSD_SAMPLER_DPMPP_2M) return MSD_OK;   // the handle's own tables
+  v->invert = invert;
+  if (K == N && sampler != MSD_SAMPLER_DPMPP_2M && !invert) return MSD_OK;   // the handle's own tables
   msd_model::StepTables& t = m->step_tables[K];
   if (K == N) {
     t.coef = m->d_coef;
@@ -2199,6 +2229,16 @@ static int make_step_view(msd_model* m, int K, int sampler, bool keep, StepView*
     }
     v->coef_ms = t.coef_ms;
     if (int rc = ensure(m, &m->x0_prev, (size_t)m->Bmax * m->T * m->ND)) return rc;
+  }
+  if (invert) {
+    if (!t.coef_inv) {
+      std::vector<float> inv;
+      build_invert_rows(K == N ? m->h_coef : t.h_coef, &inv);
+      if (int rc = dalloc(m, &t.coef_inv, inv.size())) return rc;
+      HIP_TRY(m, copy_sync(m, t.coef_inv, inv.data(), inv.size() * sizeof(float), hipMemcpyHostToDevice));
+    }
+    v->coef_inv = t.coef_inv;
+    if (int rc = ensure(m, &m->d_row_wt, (size_t)m->Bmax)) return rc;
   }
   return MSD_OK;
 }
@@ -2247,6 +2287,12 @@ static int choose_stream(msd_model* m, void* stream, hipStream_t* s) {
 // z, its planes and -- known frames -- xk and the frames' release words, at the scan index the call starts at
 static int write_initial_state(msd_model* m, const SampleCall& c, hipStream_t s) {
   const int64_t n = (int64_t)c.batch * m->T * m->ND;
+  if (c.invert_mel) {   // level 0 of the inversion: the mel as the context enters, scale_features(clip=True), and its planes
+    hipLaunchKernelGGL(scale_clip_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, c.invert_mel, m->z, (int)n, m->cfg.feature_min, m->cfg.feature_max);
+    HIP_TRY(m, hipGetLastError());
+    split_z(m, n, s);
+    return MSD_OK;
+  }
   if (c.init_z) {
     HIP_TRY(m, hipMemcpyAsync(m->z, c.init_z, n * sizeof(float), hipMemcpyDeviceToDevice, s));
   } else {
@@ -2319,7 +2365,7 @@ static int capture_steps(msd_model* m, const StepView& view, const StepPlan& pla
 }
 
 static msd_model::GraphKey step_graph_key(const StepView& view, const StepPlan& plan) {
-  return {plan, view.steps, view.sampler, view.keep, view.guided};
+  return {plan, view.steps, view.sampler, view.keep, view.guided, view.invert};
 }
 
 // The graphs of (plan, view), from the handle's cache or captured now.  One graph = `graph_steps` consecutive steps (the
@@ -2605,6 +2651,56 @@ int msd_sample_guided(msd_model* m, int batch, int rng, int per_row, const uint6
   c.weights = weights_host; c.n_weights = n_weights; c.guide_lo = guide_lo; c.guide_hi = guide_hi;
   if (all_one) c.guide_lo = c.guide_hi = 0;   // every row follows the cond_wt == 1 branch: no guided step, K one-pass steps
   return sample_body(m, c);
+}
+
+// ---- msd_invert: deterministic DDIM inversion (kernel: invert_tail.h) --------------------------------------------------
+// The phases of a sampling call on a scan that counts up: the view with the inversion's side table, level 0 written from the
+// mel, the scan words armed at 0, the graphs of (plan, view) from the step-graph cache, K steps replayed, z copied out.
+int msd_invert(msd_model* m, const msd_invert_args* a, void* stream) {
+  if (!m) return MSD_ERR_INVALID_ARGUMENT;
+  if (!a || a->struct_size != (int32_t)sizeof(msd_invert_args))
+    return fail(m, MSD_ERR_INVALID_ARGUMENT, "msd_invert_args.struct_size %d != %d", a ? a->struct_size : 0, (int)sizeof(msd_invert_args));
+  // every refusal in front of any device work
+  if (int rc = check_encoded_call(m, a->batch, MSD_RNG_PHILOX, /*per_row=*/false)) return rc;
+  if (!a->mel_dev || !a->out_dev) return fail(m, MSD_ERR_INVALID_ARGUMENT, "mel_dev or out_dev is null");
+  if (a->num_steps < 0 || (a->num_steps > 0 && m->N % a->num_steps))
+    return fail(m, MSD_ERR_INVALID_ARGUMENT, "num_steps %d does not divide the handle's %d steps; it takes 0 (= %d) or one of %s",
+                a->num_steps, m->N, m->N, divisors_of(m->N).c_str());
+  const int n_weights = a->weights_host ? a->n_weights : 0;
+  if (n_weights != 0 && n_weights != 1 && n_weights != a->batch)
+    return fail(m, MSD_ERR_INVALID_ARGUMENT, "guidance takes 1 weight or one per row (%d), got %d", a->batch, n_weights);
+  bool all_one = true;
+  for (int b = 0; b < n_weights; ++b) {
+    if (!std::isfinite(a->weights_host[b])) return fail(m, MSD_ERR_INVALID_ARGUMENT, "guidance weight %d is not finite", b);
+    all_one = all_one && a->weights_host[b] == 1.0f;
+  }
+  const int64_t row_n = (int64_t)m->T * m->ND;
+  if (n_weights > 1 && row_n % kRngRowBlock)   // a block of the sampler launch would straddle two rows' weights
+    return fail(m, MSD_ERR_UNSUPPORTED, "per-row guidance weights need targets_length * n_dims %% %d == 0 (got %lld)", (int)kRngRowBlock, (long long)row_n);
+  if (row_n % 4) return fail(m, MSD_ERR_UNSUPPORTED, "the inversion needs targets_length * n_dims %% 4 == 0 (got %lld)", (long long)row_n);
+  if (!all_one && m->passes == 1)   // (a weight-1 handle has buffers for one pass only)
+    return fail(m, MSD_ERR_UNSUPPORTED, "a handle created with cfg_weight 1 holds one pass's buffers and takes no per-call guidance: "
+                "create the handle with any weight != 1");
+  const int K = a->num_steps > 0 ? a->num_steps : m->N;
+  StepView view;
+  if (int rc = make_step_view(m, K, MSD_SAMPLER_DDIM, /*keep=*/false, &view, /*invert=*/true)) return rc;
+  hipStream_t s;
+  if (int rc = choose_stream(m, stream, &s)) return rc;
+  if (int rc = arm_range(m, s)) return rc;
+  SampleCall c = plain_call(m, a->batch, MSD_RNG_PHILOX, SampleKeys(), nullptr, nullptr, a->out_dev, stream);
+  c.steps = K; c.start_step = 0; c.sampler = MSD_SAMPLER_DDIM; c.invert_mel = a->mel_dev;
+  if (int rc = write_initial_state(m, c, s)) return rc;
+  m->h_row_wt.assign((size_t)m->Bmax, n_weights ? a->weights_host[0] : 1.0f);   // a member: the copy may still read it when this returns
+  for (int b = 0; b < a->batch && n_weights > 1; ++b) m->h_row_wt[b] = a->weights_host[b];
+  HIP_TRY(m, hipMemcpyAsync(m->d_row_wt, m->h_row_wt.data(), m->h_row_wt.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  // (the key table and the noise slot are written as every call writes them; the inversion kernel reads neither)
+  if (int rc = arm_scan(m, c.batch, c.rng, c.keys, /*noise=*/nullptr, /*start_step=*/0, /*reset_tickets=*/true, s)) return rc;
+  const StepPlan plan = all_one ? plan_step(m, c.batch, 1, true, false) : plan_cfg_step(m, c.batch);
+  msd_model::StepGraphs* g = nullptr;
+  if (int rc = find_graphs(m, view, plan, K, s, &g)) return rc;
+  if (int rc = replay(m, *g, K, s)) return rc;
+  HIP_TRY(m, hipMemcpyAsync(a->out_dev, m->z, (size_t)c.batch * m->T * m->ND * sizeof(float), hipMemcpyDeviceToDevice, s));
+  return check_range(m, s, "msd_invert");   // the call's single synchronisation at its end (arm_scan's idles the stream in front of the steps, as in every sampling call)
 }
 
 int msd_reset_graph(msd_model* m) {
@@ -2982,3 +3078,4 @@ int msd_vocoder_decode(msd_vocoder* v, int batch, int n_frames, const float* log
 #include "multistep_tail.h"     // ... and behind it, for the same reason
 #include "guided_tail.h"        // ... and the guided instances behind those
 #include "loss_tail.h"          // ... and the two kernels of msd_loss behind everything
+#include "invert_tail.h"        // ... and the inversion's instances behind those

@@ -1,5 +1,5 @@
 // The msd_op_* entry points: the library's building blocks one at a time, for the unit tests (tests/test_gpu_ops.py,
-// test_gpu_fused_ops.py, test_gpu_gemm_sites.py, test_gpu_attention_forms.py (+ attention_forms.py, test_attention_forms_host.py), test_gpu_keep_frames.py, test_gpu_edit_strength.py, test_gpu_few_steps.py, test_gpu_threefry.py).  Host code only, and no
+// test_gpu_fused_ops.py, test_gpu_gemm_sites.py, test_gpu_attention_forms.py (+ attention_forms.py, test_attention_forms_host.py), test_gpu_keep_frames.py, test_gpu_edit_strength.py, test_gpu_few_steps.py, test_gpu_threefry.py, test_gpu_invert.py).  Host code only, and no
 // part of the product's paths; the file belongs to msd_api.hip alone, which includes it behind its own entry points and
 // in front of the vocoder's.
 // Every GEMM here runs through the product's dispatch (gemm / gemm_on on a site's TileTable), so its tile is an entry of
@@ -1010,6 +1010,56 @@ int msd_op_sampler_step_multistep_guided(const msd_config* cfg, int step_index, 
   SamplerOpForm f;
   f.x0_prev = x0_prev_inout_dev; f.first = first; f.guided = true; f.weights = weights_host; f.rows = rows;
   return op_sampler_step(cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, z_out_dev, n, stream, f);
+}
+
+// sampler_invert_kernel alone (tests/test_gpu_invert.py): one step up the scan on the caller's arrays, the row weights from
+// the caller's host floats, z and its planes out.  No draw: no noise slot, no key table.
+int msd_op_invert_step(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
+                       const float* out_uncond_dev, const float* weights_host, int rows, float* z_out_dev,
+                       float* z_planes_out_dev, int64_t n, void* stream) {
+  if (!cfg || cfg->struct_size != (int32_t)sizeof(msd_config) || !z_dev || !out_cond_dev || !z_out_dev || !z_planes_out_dev ||
+      !weights_host || rows < 1 || n <= 0 || n % 4 || n > 0x7FFFFFFFll - 1023 || n % rows || (n / rows) % kRngRowBlock ||
+      step_index < 0 || step_index >= cfg->num_steps)
+    return MSD_ERR_INVALID_ARGUMENT;   // (n: the last block's element index, blocks of 1024, stays an int)
+  bool all_one = true;
+  for (int b = 0; b < rows; ++b) {
+    if (!std::isfinite(weights_host[b])) return MSD_ERR_INVALID_ARGUMENT;
+    all_one = all_one && weights_host[b] == 1.0f;
+  }
+  if (all_one != (out_uncond_dev == nullptr)) return MSD_ERR_INVALID_ARGUMENT;
+  const int NP = op_planes(cfg->precision);
+  if (NP < 0) return MSD_ERR_UNSUPPORTED;
+  std::vector<float> coef, inv;
+  std::string why;
+  if (!build_coef_rows(*cfg, &coef, &why)) return MSD_ERR_INVALID_ARGUMENT;
+  build_invert_rows(coef, &inv);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  OpKit kit(s, NP);
+  Planes zp;
+  if (!kit.init_flags() || !kit.planes((size_t)n, &zp)) return MSD_ERR_HIP;
+  const int passes = all_one ? 1 : 2;
+  const int st[2] = {step_index, step_index};
+  SamplerInvertParams ip;
+  float* eps = kit.get<float>((size_t)passes * n);
+  ip.coef = kit.put(coef.data(), coef.size());
+  ip.coef_inv = kit.put(inv.data(), inv.size());
+  ip.row_wt = kit.put(weights_host, (size_t)rows);
+  ip.step_ptr = kit.put(st, 2);
+  if (!eps || !ip.coef || !ip.coef_inv || !ip.row_wt || !ip.step_ptr) return MSD_ERR_HIP;
+  if (hipMemcpyAsync(eps, out_cond_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+      (passes == 2 && hipMemcpyAsync(eps + n, out_uncond_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess) ||
+      hipMemcpyAsync(z_out_dev, z_dev, n * sizeof(float), hipMemcpyDeviceToDevice, s) != hipSuccess ||
+      hipStreamSynchronize(s) != hipSuccess)
+    return MSD_ERR_HIP;
+  ip.eps = eps; ip.noise_slot = nullptr; ip.rng_key = nullptr;   // (the form makes no draw and reads neither)
+  ip.row_blocks = (int)(n / rows / kRngRowBlock);
+  ip.n = (int)n; ip.passes = passes; ip.cond_wt = 1.0f; ip.clip_x0 = cfg->clip_x0; ip.ddim = 1;
+  ip.model_output = cfg->model_output; ip.step_from_slot1 = 1;
+  kit.z_out_to(ip, z_out_dev, zp);   // (the kernel updates z in place: z_out_dev holds the caller's z)
+  launch_sampler_invert(ip, s);
+  if (hipGetLastError() != hipSuccess) return MSD_ERR_HIP;
+  kit.back(zp, z_planes_out_dev, (size_t)n);
+  return kit.finish();
 }
 
 int msd_op_diffuse_to_step(const msd_config* cfg, int step_index, const float* mel_dev, const float* eps_dev,

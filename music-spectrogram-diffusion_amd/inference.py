@@ -306,6 +306,21 @@ def plan_guidance(guidance, guidance_interval, b: int, num_steps_of_call: int, m
   return np.ascontiguousarray(np.broadcast_to(np.asarray(w, np.float32), (b,))), g_lo, g_hi
 
 
+def plan_invert(guidance, steps, b: int, num_steps: int, model_weight: float):
+  """invert's guidance / steps -> (weights, K): a list of 1 or b Python floats (float32's values) and the call's step count.
+  guidance: a finite float or [b] of them; None = 1.0 -- NOT the model's weight, unlike predict: one decoder pass per step,
+  and inversion under a large weight is unstable.  steps: a divisor of the model's num_steps (plan_steps); None = all of
+  them.  A model created with weight 1 holds one pass's buffers and takes weight 1 only.  Pure: no device; every ValueError
+  invert raises for the two is raised here."""
+  k = num_steps if steps is None else steps
+  plan_steps(num_steps, k)   # (its checks: a ValueError that names the divisors)
+  w = native.check_guidance(1.0 if guidance is None else _to_numpy(guidance) if np.ndim(guidance) else guidance, b)
+  if model_weight == 1.0 and any(x != 1.0 for x in w):
+    raise ValueError('this model was created with guidance weight 1 and holds one pass\'s buffers: inversion under another '
+                     'weight needs a model created with any weight != 1')
+  return w, int(k)
+
+
 def check_strength(strength, flags, b: int, t: int):
   """predict's strength -- a scalar, [b] or [b, t] -- as float64 [b, t], with 0 on the frames `flags` (int [b, t] or None)
   names.  A shape that is none of the three is a ValueError; the values are plan_strength's to check."""
@@ -734,6 +749,123 @@ class InferenceModel(object):
     if return_torch:
       return out, torch.zeros((b,), dtype=torch.float32, device=dev)
     return out.cpu().numpy(), scores
+
+  # -- inversion: the noise that renders a given mel under given tokens ----------------------------------------------
+  def invert(self, batch: Mapping[str, Any], steps: Optional[int] = None, guidance=None, return_torch: bool = False):
+    """Deterministic DDIM inversion on the device (msd_invert): the init_z from which
+    predict(batch, init_z=, sampler='ddim', steps=K, guidance=w) renders batch['decoder_target_tokens'] again, up to the
+    inversion's own error -- "same performance, other notes": invert the old mel under the old tokens, render the new tokens
+    from that noise (rerender).
+
+    batch: predict's features; the mel is ``decoder_target_tokens`` [B, T, n] in mel units, exactly as loss() takes it
+      (values outside the codec's range are clipped, as the context's are); tokens and context as predict takes them.
+    steps (K): the levels of the inversion, a divisor of the model's N (plan_steps; a ValueError names the divisors);
+      None = N.  Step i = 0 .. K - 1 is one decoder evaluation of the state it has at time (i + 1) / K and
+      z' = a_i z + b_i eps with eps frozen at that state: the exact inverse of the K-step DDIM step where the model's
+      prediction does not move between the two levels (and where train and sampler schedule agree), first order in 1 / K
+      otherwise.  No noise is drawn.
+    guidance: a finite float or [B] floats; None = **1.0** here -- this differs from predict, whose None is the model's
+      eval_condition_weight: weight 1 runs ONE decoder pass per step (half the rows in every launch), and inversion under
+      a large weight is known to be unstable.  Render with the same weight you inverted with.
+    The sampler's clip_x0 is ignored (the clip is not invertible where it binds), so a round trip through a clipping model
+    is not exact even as K grows.  The range fallback repeats the call on the bfloat16-plane build, as predict does.
+    NOT built, each a ValueError or absent: fixed-point refinement of a step, stopping below level K, inversion under DDPM
+    noise or 'dpmpp_2m', keep / strength / resample, per-frame weights, K that does not divide N.
+    Returns the noise float32 [B, T, n] in MODEL units (NumPy; ``return_torch``: the device tensor).  Argument errors are
+    ValueErrors raised before any device work."""
+    if 'decoder_target_tokens' not in batch:
+      raise ValueError("invert() needs batch['decoder_target_tokens']: the mel to invert, [batch, %d, %d]"
+                       % (self.targets_length, self.audio_codec.n_dims))
+    b, t, n = np.shape(batch['encoder_input_tokens'])[0], self.targets_length, self.audio_codec.n_dims
+    if tuple(np.shape(batch['decoder_target_tokens'])) != (b, t, n):
+      raise ValueError('decoder_target_tokens must be [batch, %d, %d] = %r: got %r'
+                       % (t, n, (b, t, n), tuple(np.shape(batch['decoder_target_tokens']))))
+    weights, k = plan_invert(guidance, steps, b, self.spec.diffusion.sampler.schedule.num_steps,
+                             self.spec.diffusion.classifier_free_guidance.eval_condition_weight)
+    try:
+      return self._invert_once(batch, k, weights, return_torch)
+    except native.RangeError:
+      if not (self.range_fallback and self.precision in ('f16x3', 'f16')):
+        raise
+      import warnings
+      new = 'bf16x3' if self.precision == 'f16x3' else 'bf16'
+      warnings.warn("an activation left the half-plane range (|x| > 65504): switching this model from precision "
+                    "'%s' to '%s' (bfloat16 planes) and repeating the call" % (self.precision, new), RuntimeWarning)
+      self.precision = new
+      if self._native is not None:
+        self._native.close()
+      self._native = None
+      return self._invert_once(batch, k, weights, return_torch)
+
+  def _invert_once(self, batch, k, weights, return_torch):
+    torch = self._torch
+    nm = self._get_native()
+    dev = self.device
+    tokens = _to_numpy(batch['encoder_input_tokens'])
+    if tokens.dtype.kind not in 'iu':
+      raise ValueError('Input type must be an integer or unsigned integer.')
+    tokens = np.ascontiguousarray(tokens, dtype=np.int32)
+    b = tokens.shape[0]
+    if tokens.ndim != 2 or tokens.shape[1] != self.inputs_length:
+      raise ValueError('encoder_input_tokens must be [batch, %d]' % self.inputs_length)
+    if b > self.batch_size:
+      raise ValueError('batch %d exceeds batch_size %d' % (b, self.batch_size))
+    t, n = self.targets_length, self.audio_codec.n_dims
+    t0 = time.perf_counter()
+    with torch.cuda.device(dev):
+      self._stream.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.device(dev), torch.cuda.stream(self._stream):
+      s = self._stream.cuda_stream
+      ctx = cmask = None
+      if self.targets_context_length is not None:
+        ctx = _to_device(torch, batch['encoder_continuous_inputs'], dev, torch.float32)
+        if tuple(ctx.shape) != (b, self.targets_context_length, n):
+          raise ValueError('encoder_continuous_inputs must be [batch, %d, %d]' % (self.targets_context_length, n))
+        cmask = np.ascontiguousarray(_to_numpy(batch['encoder_continuous_mask']), dtype=np.int32)
+        if cmask.shape != (b, self.targets_context_length):
+          raise ValueError('encoder_continuous_mask must be [batch, %d]' % self.targets_context_length)
+      nm.encode(b, tokens, ctx, cmask, stream=s)
+      t1 = time.perf_counter()
+      mel = _to_device(torch, batch['decoder_target_tokens'], dev, torch.float32).contiguous()
+      out = torch.empty((b, t, n), dtype=torch.float32, device=dev)
+      nm.invert(b, out, mel, steps=k, guidance=weights if len(weights) > 1 else weights[0], stream=s)
+      self._stream.synchronize()
+    t2 = time.perf_counter()
+    self.last_timing = {'encode_s': t1 - t0, 'sample_s': t2 - t1, 'total_s': t2 - t0}
+    return out if return_torch else out.cpu().numpy()
+
+  def rerender(self, song, old_tokens: Sequence[np.ndarray], new_tokens: Sequence[np.ndarray], steps: Optional[int] = None,
+               guidance=None, render_guidance=None, always_mask_context: bool = False, return_torch: bool = False):
+    """The same performance with other notes or another instrument: every segment of `song` ([1, K * T, n], mel units;
+    NumPy or a device tensor; K == len(old_tokens) == len(new_tokens)) is inverted under the tokens it was rendered from
+    and rendered again from that noise under the new ones.  Per segment k:
+      noise_k = invert(old tokens k, old mel k, context = OLD segment k - 1, steps=, guidance=)
+      new_k   = predict(new tokens k, context = NEW segment k - 1, init_z=noise_k, sampler='ddim', steps=, guidance=render_guidance)
+    (zeros and mask 0 for segment 0 and ``always_mask_context``).  guidance: invert's (None = 1.0); render_guidance:
+    predict's (None = the model's own weight) -- pass the same number to both for a round trip.  rerender(song, tokens,
+    tokens) at equal weights returns the song up to the inversion's error.  Returns the new song [1, K * T, n] (NumPy;
+    ``return_torch``: the device tensor)."""
+    t = self.targets_length
+    self._check_song(song, old_tokens)
+    self._check_song(song, new_tokens)
+    # both directions' arguments, planned once before the first segment runs (each call plans its own again)
+    n_steps, own = self.spec.diffusion.sampler.schedule.num_steps, self.spec.diffusion.classifier_free_guidance.eval_condition_weight
+    plan_invert(guidance, steps, 1, n_steps, own)
+    plan_call(None, None, None, steps, 'ddim', 1, t, self.audio_codec.n_dims, n_steps, guidance=render_guidance, model_weight=own)
+    torch = self._torch
+    old = _to_device(torch, song, self.device, torch.float32)
+    outs = []
+    for k, (toks_old, toks_new) in enumerate(zip(old_tokens, new_tokens)):
+      no_ctx = always_mask_context or k == 0 or self.targets_context_length is None
+      batch = self._segment_batch(toks_old, None if no_ctx else old[:, (k - 1) * t:k * t].clone(), no_ctx)
+      batch['decoder_target_tokens'] = old[:, k * t:(k + 1) * t].clone()
+      noise = self.invert(batch, steps=steps, guidance=guidance, return_torch=True)
+      batch = self._segment_batch(toks_new, None if no_ctx else outs[-1].clone(), no_ctx)
+      kw = {} if render_guidance is None else {'guidance': render_guidance}
+      out, _ = self.predict(batch, init_z=noise, sampler='ddim', steps=steps, return_torch=True, **kw)
+      outs.append(out[:1].to(self.device))
+    new = torch.cat(outs, dim=1)
+    return new if return_torch else new.cpu().numpy()
 
   def _jax_noise(self, seed: int, b: int, steps: int):
     """Device-resident (init_z, noise) of jax_random.reference_noise, cached for the last (seed, b, steps)."""

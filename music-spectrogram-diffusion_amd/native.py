@@ -81,7 +81,9 @@ EXPORTED_SYMBOLS = (
     # (appended to ABI 7) a guidance weight per call or per row, applied in an interval of the scan
     'msd_sample_guided', 'msd_op_sampler_step_guided', 'msd_op_sampler_step_multistep_guided',
     # (appended to ABI 7) the denoising loss of a mel under the encoded tokens
-    'msd_loss', 'msd_op_diffusion_loss')
+    'msd_loss', 'msd_op_diffusion_loss',
+    # (appended to ABI 7) deterministic DDIM inversion: the noise that renders a mel under the encoded tokens
+    'msd_invert', 'msd_op_invert_step')
 
 
 LOSS_CONDITIONINGS = {'cond': 0, 'uncond': 1, 'both': 2}   # MSD_LOSS_COND, _UNCOND, _BOTH
@@ -123,6 +125,33 @@ class LossArgs(ctypes.Structure):
       ('target_dev', ctypes.c_void_p), ('mask_dev', ctypes.c_void_p), ('eps_dev', ctypes.c_void_p),
       ('times_host', ctypes.POINTER(ctypes.c_int32))] + [
           (n, ctypes.c_int32) for n in ('n_times', 'conditioning', 'loss_type', 'loss_norm')] + [('out_dev', ctypes.c_void_p)]
+
+
+class InvertArgs(ctypes.Structure):
+  """msd_invert_args of include/msd_amd.h, field for field."""
+  _fields_ = [('struct_size', ctypes.c_int32), ('batch', ctypes.c_int32), ('mel_dev', ctypes.c_void_p),
+              ('num_steps', ctypes.c_int32), ('n_weights', ctypes.c_int32), ('weights_host', ctypes.POINTER(ctypes.c_float)),
+              ('out_dev', ctypes.c_void_p)]
+
+
+def invert_rows(logsnr_t, logsnr_s) -> np.ndarray:
+  """The Python twin of build_invert_rows (csrc/msd_api.hip): the inversion's side table [K, 4] = {a, b, 0, 0} from the
+  float32 log-SNRs of a K-step call's coefficient rows (row i: logsnr_t at time (i + 1) / K, logsnr_s at i / K; words 0 and 1
+  of NativeModel.schedule()'s rows for K = N).  alpha = sqrt(sigmoid(logsnr)), sigma = sqrt(sigmoid(-logsnr)); a =
+  alpha_t / alpha_s and b = sigma_t - a sigma_s, row 0 (alpha_t, sigma_t); in double, rounded once.  No device needed."""
+  lt = np.asarray(logsnr_t, np.float32).astype(np.float64).reshape(-1)
+  ls = np.asarray(logsnr_s, np.float32).astype(np.float64).reshape(-1)
+  if lt.shape != ls.shape or lt.size < 1:
+    raise ValueError('logsnr_t and logsnr_s must be two arrays of K >= 1 values: got %r and %r' % (lt.shape, ls.shape))
+  alpha_t, sigma_t = np.sqrt(1.0 / (1.0 + np.exp(-lt))), np.sqrt(1.0 / (1.0 + np.exp(lt)))
+  alpha_s, sigma_s = np.sqrt(1.0 / (1.0 + np.exp(-ls))), np.sqrt(1.0 / (1.0 + np.exp(ls)))
+  a = alpha_t / alpha_s
+  a[0] = alpha_t[0]
+  b = sigma_t - a * sigma_s
+  b[0] = sigma_t[0]
+  out = np.zeros((lt.size, 4), np.float32)
+  out[:, 0], out[:, 1] = a, b
+  return out
 
 
 def check_guidance(guidance, batch: int):
@@ -390,6 +419,9 @@ def load(planes: str = 'f16') -> ctypes.CDLL:
   if 'msd_loss' in present:   # (appended to ABI 7)
     lib.msd_loss.argtypes = [vp, c.POINTER(LossArgs), vp]
     lib.msd_op_diffusion_loss.argtypes = [c.POINTER(MsdConfig), i32, i32, i32, vp, vp, vp, vp, vp, i32, vp, i64, vp]
+  if 'msd_invert' in present:   # (appended to ABI 7)
+    lib.msd_invert.argtypes = [vp, c.POINTER(InvertArgs), vp]
+    lib.msd_op_invert_step.argtypes = [c.POINTER(MsdConfig), i32, vp, vp, vp, c.POINTER(c.c_float), i32, vp, vp, i64, vp]
   if 'msd_fill_normal_threefry' in present:
     lib.msd_fill_normal_threefry.argtypes = [u64, i64, vp, i64, vp]
   if 'msd_op_threefry' in present:
@@ -682,6 +714,27 @@ class NativeModel:
     a.times_host, a.n_times = (ctypes.c_int32 * len(idx))(*idx), len(idx)
     a.conditioning, a.loss_type, a.loss_norm = LOSS_CONDITIONINGS[conditioning], LOSS_TYPES[loss_type], LOSS_NORMS[loss_norm]
     _check(self.lib, self.handle, self.lib.msd_loss(self.handle, ctypes.byref(a), stream), 'msd_loss')
+
+  def invert(self, batch: int, out, mel, steps: Optional[int] = None, guidance=None, stream: int = 0):
+    """Deterministic DDIM inversion under the encoded tokens (msd_invert): mel (float32 device tensor [batch, T, n], mel
+    units) -> out (float32 device tensor [batch, T, n]): z at the top level of a K-step scan, in MODEL units -- the init_z
+    with which sample(steps=K, sampler='ddim', guidance=...) renders the mel again, up to the inversion's own error.
+    steps: K, a divisor of the handle's num_steps (plan_steps); None = all of them.  guidance: a finite float or `batch` of
+    them; None = 1.0 (NOT the handle's weight: one decoder pass per step, and inversion under a large weight is
+    unstable).  The sampler's clip is ignored (it cannot be inverted).  Argument errors are raised before the library is
+    called."""
+    if steps is not None:
+      plan_steps(self.cfg.num_steps, steps)   # (its checks: a ValueError that names the divisors)
+    weights = check_guidance(1.0 if guidance is None else guidance, batch)
+    want = batch * self.cfg.targets_length * self.cfg.n_dims
+    for name, t in (('mel', mel), ('out', out)):
+      if t is None or int(np.prod(tuple(t.shape))) != want:
+        raise ValueError('%s must hold %d float32 values: got %s' % (name, want, None if t is None else tuple(t.shape)))
+    a = InvertArgs()
+    a.struct_size, a.batch, a.num_steps = ctypes.sizeof(InvertArgs), batch, int(steps or 0)
+    a.mel_dev, a.out_dev = _ptr(mel), _ptr(out)
+    a.weights_host, a.n_weights = (ctypes.c_float * len(weights))(*weights), len(weights)
+    _check(self.lib, self.handle, self.lib.msd_invert(self.handle, ctypes.byref(a), stream), 'msd_invert')
 
   def set_touch_carrier(self, touch_carrier: Optional[int]):
     """msd_config.touch_carrier of this handle from the next sampling call on (None = the library's choice, 1, 2)."""
@@ -978,6 +1031,19 @@ def op_sampler_step_multistep(cfg: MsdConfig, step_index: int, z, out_cond, out_
   _op_check(lib.msd_op_sampler_step_multistep(ctypes.byref(cfg), step_index, _ptr(z), _ptr(out_cond), _ptr(out_uncond),
                                               _ptr(x0_prev), int(bool(first)), _ptr(z_out), z.numel(), stream),
             'msd_op_sampler_step_multistep')
+
+
+def op_invert_step(cfg: MsdConfig, step_index: int, z, out_cond, out_uncond, weights, z_out, z_planes_out, stream: int = 0):
+  """One inversion update (msd_op_invert_step): z is [rows, ...] and row b combines with weights[b] (host floats); z_out =
+  fmaf(b, eps, a * z) at step_index of cfg's tables and z_planes_out its operand planes of cfg.precision merged back to
+  float32.  out_uncond: None if and only if every weight is 1.  A row's element count must be a multiple of 1024."""
+  lib = load(_PLANES_OF[cfg.precision])
+  cfg.struct_size = config_struct_size(lib)
+  if not (z.numel() == out_cond.numel() == z_out.numel() == z_planes_out.numel()):
+    raise ValueError('z, out_cond and the two outputs must have the same element count')
+  w = (ctypes.c_float * len(weights))(*[float(x) for x in weights])
+  _op_check(lib.msd_op_invert_step(ctypes.byref(cfg), step_index, _ptr(z), _ptr(out_cond), _ptr(out_uncond), w, len(weights),
+                                   _ptr(z_out), _ptr(z_planes_out), z.numel(), stream), 'msd_op_invert_step')
 
 
 def op_diffuse_to_step(cfg: MsdConfig, step_index: int, mel, eps, z_out, z_planes_out, xk_out, stream: int = 0):

@@ -11,6 +11,7 @@ beam/evaluation.py:161-223) on the MI355X path.
       [--vary STRENGTH (--edit-mel old_mel.npy | --edit-audio old.wav)]
       [--resample JUMP:TIMES]   (with --regenerate or --vary)
       [--guidance W] [--guidance-interval LO:HI]
+  python -m msd_amd.synthesize new.mid --rerender old.mid (--edit-mel old_mel.npy | --edit-audio old.wav) [--steps K] [--guidance W]
   python -m msd_amd.synthesize song.mid (--score MEL.npy | --score-audio REC.wav) [--score-times K]
       [--score-conditioning cond|uncond|both]
 
@@ -52,6 +53,12 @@ DPM-Solver++(2M), deterministic after the initial draw.  Not with --regenerate /
 model; --guidance-interval LO:HI (fractions of diffusion time, 0 <= LO < HI <= 1) applies the guidance only inside that
 part of the scan, and every step outside it runs one decoder pass instead of two (InferenceModel.predict(guidance=,
 guidance_interval=)).  Not with --regenerate / --vary, nor with --cfg-weight 1.
+
+--rerender OLD.mid renders the same performance with this MIDI file's notes: every segment of the old rendering (--edit-mel /
+--edit-audio) is inverted under OLD.mid's tokens -- deterministic DDIM inversion on the device, --steps K levels -- and this
+file's tokens are rendered with ddim in K steps from that noise (InferenceModel.rerender).  Both files must tokenise to the
+same number of segments.  --guidance W is the weight of BOTH directions and defaults to 1 here (one decoder pass per step;
+inversion under a large weight is unstable), not to --cfg-weight.  Not with --regenerate / --vary / --score.
 
 --dry-run tokenises only (no GPU): prints the segment / token statistics the synthesis would see, and with --regenerate
 the plan: the segments touched and the frames each keeps."""
@@ -111,6 +118,10 @@ def main(argv=None) -> int:
                   help='a variation of --edit-mel / --edit-audio at this distance, 0 .. 1 (1 = a fresh rendering)')
   ap.add_argument('--resample', default=None, metavar='JUMP:TIMES',
                   help='with --regenerate / --vary: RePaint resampling jumps -- every block of JUMP steps is descended TIMES times')
+  ap.add_argument('--rerender', default=None, metavar='OLD.mid',
+                  help='the same performance with these notes: invert --edit-mel / --edit-audio under OLD.mid\'s tokens (DDIM '
+                       'inversion on the device) and render this MIDI file from that noise; --steps K levels, --guidance W '
+                       'for both directions (default 1: one decoder pass per step)')
   ap.add_argument('--edit-mel', default=None, metavar='OLD.npy', help='the old rendering as mel frames [frames, 128]')
   ap.add_argument('--edit-audio', default=None, metavar='OLD.wav',
                   help='the old rendering as a 16 kHz PCM recording (encoded on the device)')
@@ -141,6 +152,14 @@ def main(argv=None) -> int:
     ap.error("--score / --score-audio draw on the device: --rng philox or threefry")
   if not scoring and (args.score_times != 16 or args.score_conditioning != 'cond'):
     ap.error('--score-times / --score-conditioning go with --score MEL.npy or --score-audio REC.wav')
+  if args.rerender and (args.regenerate or args.vary is not None or scoring):
+    ap.error('--rerender does not go with --regenerate / --vary / --score / --score-audio: give one')
+  if args.rerender and not (args.edit_mel or args.edit_audio):
+    ap.error('--rerender needs the old rendering: --edit-mel OLD.npy or --edit-audio OLD.wav')
+  if args.rerender and (args.sampler or args.guidance_interval is not None or args.batch_segments != 1 or args.context_audio
+                        or args.rng == 'jax'):
+    ap.error('--rerender inverts and renders with ddim, segment by segment, and draws nothing: no --sampler / '
+             '--guidance-interval / --batch-segments / --context-audio / --rng jax')
   if args.regenerate and args.vary is not None:
     ap.error('--regenerate and --vary are two edits: give one')
   if args.regenerate and not (args.edit_mel or args.edit_audio):
@@ -149,8 +168,8 @@ def main(argv=None) -> int:
     ap.error('--vary needs the old rendering: --edit-mel OLD.npy or --edit-audio OLD.wav')
   if args.edit_mel and args.edit_audio:
     ap.error('--edit-mel and --edit-audio are two sources of the same thing: give one')
-  if (args.edit_mel or args.edit_audio) and not (args.regenerate or args.vary is not None):
-    ap.error('--edit-mel / --edit-audio need the edit to make: --regenerate START:STOP or --vary STRENGTH')
+  if (args.edit_mel or args.edit_audio) and not (args.regenerate or args.vary is not None or args.rerender):
+    ap.error('--edit-mel / --edit-audio need the edit to make: --regenerate START:STOP, --vary STRENGTH or --rerender OLD.mid')
   if (args.regenerate or args.vary is not None) and (args.batch_segments != 1 or args.context_audio):
     ap.error('--regenerate / --vary sample their segments one by one with the song as context: no --batch-segments / --context-audio')
   if args.vary is not None and not 0.0 <= args.vary <= 1.0:
@@ -193,7 +212,14 @@ def main(argv=None) -> int:
     few['steps'] = args.steps
   if args.sampler:
     few['sampler'] = args.sampler
-  if args.guidance is not None or args.guidance_interval is not None:
+  if args.rerender:
+    from msd_amd import inference
+    try:
+      inference.plan_invert(args.guidance, args.steps, 1, spec.diffusion.sampler.schedule.num_steps,
+                            spec.diffusion.classifier_free_guidance.eval_condition_weight)
+    except ValueError as e:
+      ap.error('--rerender: %s' % e)
+  elif args.guidance is not None or args.guidance_interval is not None:
     from msd_amd import inference
     k = spec.diffusion.sampler.schedule.num_steps if args.steps is None else args.steps
     w = spec.diffusion.classifier_free_guidance.eval_condition_weight
@@ -221,6 +247,34 @@ def main(argv=None) -> int:
   print('%s: %d notes, %.2f s -> %d segments of %d frames; tokens per segment min/mean/max %d/%.0f/%d (%.3f s)'
         % (args.midi, len(ns.notes), ns.total_time, len(segments), cfg.segment_frames, min(n_tok),
            float(np.mean(n_tok)), max(n_tok), t_tok), file=sys.stderr)
+  rerender = None
+  if args.rerender:   # the old notes' segments and the old rendering's length, before any device work
+    from msd_amd import audio_codecs, vocoder
+    codec = audio_codecs.get_codec(spec.audio_codec)
+    try:
+      old_segments = tokenizer.note_sequence_to_model_inputs(midi_io.midi_file_to_note_sequence(args.rerender), cfg,
+                                                             on_too_long=args.on_too_long)
+      if len(old_segments) != len(segments):
+        raise ValueError('%s has %d segments, %s has %d: --rerender keeps the performance segment by segment'
+                         % (args.rerender, len(old_segments), args.midi, len(segments)))
+      if args.edit_mel:
+        old = np.load(args.edit_mel)
+        old = old[0] if old.ndim == 3 and old.shape[0] == 1 else old
+        if old.ndim != 2 or old.shape[1] != codec.n_dims:
+          raise ValueError('%s must hold mel frames [frames, %d]: got %r' % (args.edit_mel, codec.n_dims, old.shape))
+        old_frames = old.shape[0]
+      else:
+        old = vocoder.read_wav(args.edit_audio, codec.sample_rate)
+        old_frames = -(-old.size // codec.hop_size)
+      if old_frames > len(segments) * cfg.segment_frames:
+        raise ValueError('the old rendering has %d frames, the MIDI file only %d (%d segments)'
+                         % (old_frames, len(segments) * cfg.segment_frames, len(segments)))
+    except (ValueError, OSError) as e:
+      ap.error(str(e))
+    print('rerender %d segments: %d inversion steps and %d ddim steps each, guidance %g'
+          % (len(segments), args.steps or spec.diffusion.sampler.schedule.num_steps,
+             args.steps or spec.diffusion.sampler.schedule.num_steps, 1.0 if args.guidance is None else args.guidance))
+    rerender = (old, old_segments)
   edit = None
   if args.regenerate or args.vary is not None:
     # everything about the edit that needs no device: the region in frames, the old rendering's length, the plan
@@ -295,6 +349,8 @@ def main(argv=None) -> int:
     model.check_batch_segments(args.batch_segments, args.always_mask_context, args.context_audio)
   except ValueError as e:
     ap.error(str(e))
+  if rerender is not None:
+    return _rerender(args, model, segments, rerender, ns, cfg)
   if edit is not None:
     return _regenerate(args, model, segments, edit, ns, cfg)
   init_context = None
@@ -422,6 +478,29 @@ def _regenerate(args, model, segments, edit, ns, cfg) -> int:
     print('varied %d frames at strength %g in %.3f s' % (mel.shape[0], args.vary, time.perf_counter() - t0), file=sys.stderr)
   else:
     print('regenerated frames [%d, %d) of %d in %.3f s' % (start, stop, mel.shape[0], time.perf_counter() - t0), file=sys.stderr)
+  _write_outputs(args, model, mel_dev, mel)
+  return 0
+
+
+def _rerender(args, model, segments, rerender, ns, cfg) -> int:
+  """--rerender: InferenceModel.rerender of the old rendering (padded to whole segments with the codec's pad value) from
+  the old notes' tokens to this file's, one weight for both directions."""
+  old, old_segments = rerender
+  torch = model._torch
+  if args.edit_mel:
+    song = torch.as_tensor(np.ascontiguousarray(old, np.float32)).to(model.device)[None]
+  else:
+    song = model.vocoder.encode(np.asarray(old, np.float32)[None], return_torch=True)
+  song = pad_to_segments(song, len(segments) * cfg.segment_frames, model.audio_codec.pad_value)
+  w = 1.0 if args.guidance is None else args.guidance
+  own = model.spec.diffusion.classifier_free_guidance.eval_condition_weight
+  t0 = time.perf_counter()
+  mel_dev = model.rerender(song, old_segments, segments, steps=args.steps, guidance=w,
+                           render_guidance=None if w == own else w, always_mask_context=args.always_mask_context,
+                           return_torch=True)
+  frames = int(np.ceil(ns.total_time * cfg.frame_rate))
+  mel = mel_dev.cpu().numpy()[0, :max(frames, 1)]
+  print('rerendered %d frames in %.3f s' % (mel.shape[0], time.perf_counter() - t0), file=sys.stderr)
   _write_outputs(args, model, mel_dev, mel)
   return 0
 
