@@ -56,7 +56,9 @@ extern "C" {
                                       msd_sample_guided, msd_op_sampler_step_guided and
                                       msd_op_sampler_step_multistep_guided (a guidance weight per call or per row, applied
                                       in an interval of the scan); msd_loss and msd_op_diffusion_loss;
-                                      msd_invert and msd_op_invert_step (deterministic DDIM inversion).
+                                      msd_invert and msd_op_invert_step (deterministic DDIM inversion);
+                                      msd_op_sampler_step_planes (a sampler update of any form with its operand planes,
+                                      range flag and published scan index, for the tests).
                                    6: cross_merge_in_launch, cross_q_fold, mlp_in_persistent appended to msd_config.
                                    5: dedup_layer0, cross_key_split, keep_raw_weights, kv_touch_ahead appended to msd_config.
                                    4: every caller-selectable knob is a msd_config field (attn_q_planes / attn_p_planes
@@ -928,6 +930,44 @@ int msd_invert(msd_model* m, const msd_invert_args* args, void* stream);
 int msd_op_invert_step(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
                        const float* out_uncond_dev, const float* weights_host, int rows, float* z_out_dev,
                        float* z_planes_out_dev, int64_t n, void* stream);
+
+/* (appended to ABI 7) One sampler update in ANY form of the msd_op_sampler_step* entry points above, with what those leave
+ * out: the launch also writes z_out's operand planes of cfg->precision and feeds the half-plane range flag, as every step
+ * of a sampling call does (unit test of the kernels' plane tails: tests/test_gpu_sampler_planes.py).
+ * The form follows from the pointers, which mean what they mean above: weights_host != NULL = guided (`rows` rows, with
+ * either update); x0_prev_inout_dev != NULL = the multistep update (noise_dev is not read); known_scaled_dev != NULL = known
+ * frames (plain update only, not guided: MSD_ERR_INVALID_ARGUMENT otherwise), keep_dev holding msd_op_sampler_step_keep's
+ * flags when keep_is_flags != 0 and msd_op_sampler_step_release's words otherwise.  z_out_dev holds the bits of the
+ * corresponding entry point above.  z_planes_out_dev float [n]: the planes merged back to float32.
+ * MSD_ERR_UNSUPPORTED: cfg->precision is a precision of the other library build.  MSD_ERR_RANGE: the half-plane range flag
+ * was set (|z_out| > 65504 somewhere; half-plane build only); the outputs and the ran_* fields are written all the same.
+ * Synchronises. */
+typedef struct msd_sampler_planes_args {
+  int32_t struct_size;            /* sizeof(msd_sampler_planes_args) */
+  int32_t step_index;             /* scan index, 0 .. cfg->num_steps - 1 */
+  int32_t n_dims;                 /* known frames: elements per frame (% 4 == 0, n % n_dims == 0) */
+  int32_t keep_is_flags;          /* known frames: keep_dev holds flags (any non-zero = known throughout), not release words */
+  int32_t first;                  /* multistep: != 0 = the call's first step (x0_prev is not read) */
+  int32_t rows;                   /* guided: rows of z = entries of weights_host; (n / rows) % 1024 == 0 */
+  /* out */
+  int32_t ran_range_flag;         /* the half-plane range flag after the launch (0 = clean) */
+  int32_t ran_next_step;          /* the scan index the launch published for the next step: step_index - 1 */
+  int64_t n;                      /* elements of z; % 4 == 0 */
+  const msd_config* cfg;
+  /* operands (device, float32 [n] unless said otherwise) */
+  const float* z_dev;
+  const float* out_cond_dev;
+  const float* out_uncond_dev;    /* may be NULL iff one pass is read (not guided and cfg_weight == 1) */
+  const float* noise_dev;         /* this step's draw, or NULL = zeros */
+  const float* known_scaled_dev;  /* or NULL */
+  const int32_t* keep_dev;        /* int32 [n / n_dims] */
+  float* x0_prev_inout_dev;       /* or NULL */
+  const float* weights_host;      /* HOST floats [rows], or NULL */
+  /* results (device, float32 [n]) */
+  float* z_out_dev;
+  float* z_planes_out_dev;
+} msd_sampler_planes_args;
+int msd_op_sampler_step_planes(msd_sampler_planes_args* args, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,5 +1,5 @@
 // The msd_op_* entry points: the library's building blocks one at a time, for the unit tests (tests/test_gpu_ops.py,
-// test_gpu_fused_ops.py, test_gpu_gemm_sites.py, test_gpu_attention_forms.py (+ attention_forms.py, test_attention_forms_host.py), test_gpu_keep_frames.py, test_gpu_edit_strength.py, test_gpu_few_steps.py, test_gpu_threefry.py, test_gpu_invert.py).  Host code only, and no
+// test_gpu_fused_ops.py, test_gpu_gemm_sites.py, test_gpu_attention_forms.py (+ attention_forms.py, test_attention_forms_host.py), test_gpu_keep_frames.py, test_gpu_edit_strength.py, test_gpu_few_steps.py, test_gpu_threefry.py, test_gpu_invert.py, test_gpu_sampler_planes.py).  Host code only, and no
 // part of the product's paths; the file belongs to msd_api.hip alone, which includes it behind its own entry points and
 // in front of the vocoder's.
 // Every GEMM here runs through the product's dispatch (gemm / gemm_on on a site's TileTable), so its tile is an entry of
@@ -540,15 +540,28 @@ struct SamplerOpForm {
   int rows = 0;
 };
 
+// What msd_op_sampler_step_planes asks of the launch beyond z, and what it returns
+struct SamplerOpPlanes {
+  float* planes_out = nullptr;   // device [n]: z_out's operand planes of cfg->precision, merged back to float32
+  unsigned range_flag = 0;       // the activation range flag as finish() read it
+  int next_step = 0;             // the scan index the launch published
+};
+
 // One launch of the sampler update on the caller's arrays, in form f.  What the forms share, in ONE place: the argument
 // checks, the coefficient rows of cfg, the staged operands -- the passes of the model output side by side (the guided forms
 // stage the unconditional output whatever cfg->cfg_weight is: their weights come from a table), z copied into z_out (the
 // kernel updates in place), the scan index in both slots -- and the SamplerParams every form starts from (no planes).
 // Then the draw (noise, slot, key rows) or the multistep side table, staged once each, and the launch of the form's arguments.
+// With `po` (msd_op_sampler_step_planes) the launch also writes z_out's operand planes of cfg->precision and feeds the range
+// flag, as the product's launches do (z_out), and the op returns what it would otherwise leave behind: the planes merged
+// back to float32, the flag word and the scan index the launch published (slot 0: step_from_slot1).
 int op_sampler_step(const msd_config* cfg, int step_index, const float* z_dev, const float* out_cond_dev,
-                    const float* out_uncond_dev, float* z_out_dev, int64_t n, void* stream, const SamplerOpForm& f) {
+                    const float* out_uncond_dev, float* z_out_dev, int64_t n, void* stream, const SamplerOpForm& f,
+                    SamplerOpPlanes* po = nullptr) {
   hipStream_t s = static_cast<hipStream_t>(stream);
-  OpKit kit(s, 1);
+  const int NP = po && cfg && cfg->struct_size == (int32_t)sizeof(msd_config) ? op_planes(cfg->precision) : 1;
+  if (NP < 0) return MSD_ERR_UNSUPPORTED;
+  OpKit kit(s, NP);
   SamplerMultistepGuidedParams sp;   // the widest form's arguments; the other forms' are its bases
   if (f.guided) {
     if (!f.weights || f.rows < 1 || n <= 0 || n % f.rows || (n / f.rows) % kRngRowBlock) return MSD_ERR_INVALID_ARGUMENT;
@@ -566,6 +579,9 @@ int op_sampler_step(const msd_config* cfg, int step_index, const float* z_dev, c
   std::vector<float> rows, ms;
   std::string why;
   if (!build_coef_rows(*cfg, &rows, &why)) return MSD_ERR_INVALID_ARGUMENT;
+  Planes zp;
+  if (po && !po->planes_out) return MSD_ERR_INVALID_ARGUMENT;
+  if (po && (!kit.init_flags() || !kit.planes((size_t)n, &zp))) return MSD_ERR_HIP;
   const int st[2] = {step_index, step_index};
   float* eps = kit.get<float>((size_t)passes * n);
   sp.coef = kit.put(rows.data(), rows.size());
@@ -580,6 +596,7 @@ int op_sampler_step(const msd_config* cfg, int step_index, const float* z_dev, c
   sp.n = (int)n; sp.passes = passes; sp.cond_wt = cfg->cfg_weight; sp.clip_x0 = cfg->clip_x0;
   sp.ddim = 0; sp.model_output = cfg->model_output;
   sp.z_hi = nullptr; sp.z_lo = nullptr; sp.step_from_slot1 = 1;
+  if (po) kit.z_out_to(sp, z_out_dev, zp);   // (every form below starts from a copy of sp)
   if (f.x0_prev) {   // (noise_slot / rng_key stay null: the form makes no draw and reads neither)
     build_multistep_rows(rows, &ms);
     sp.coef_ms = kit.put(ms.data(), ms.size());
@@ -620,7 +637,15 @@ int op_sampler_step(const msd_config* cfg, int step_index, const float* z_dev, c
     launch_sampler_step(static_cast<const SamplerParams&>(sp), s);
   }
   if (hipGetLastError() != hipSuccess) return MSD_ERR_HIP;
-  return hipStreamSynchronize(s) == hipSuccess ? MSD_OK : MSD_ERR_HIP;
+  if (!po) return hipStreamSynchronize(s) == hipSuccess ? MSD_OK : MSD_ERR_HIP;
+  kit.back(zp, po->planes_out, (size_t)n);
+  int published[2] = {0, 0};
+  if (hipGetLastError() != hipSuccess ||
+      hipMemcpyAsync(published, sp.step_ptr, sizeof(published), hipMemcpyDeviceToHost, s) != hipSuccess)
+    return MSD_ERR_HIP;
+  const int frc = kit.finish();   // synchronises
+  po->range_flag = kit.range_flag; po->next_step = published[0];
+  return frc;
 }
 
 // ---- one attention launch the way the decoder fills it (tests/test_gpu_attention_forms.py) ---------------------------
@@ -1010,6 +1035,27 @@ int msd_op_sampler_step_multistep_guided(const msd_config* cfg, int step_index, 
   SamplerOpForm f;
   f.x0_prev = x0_prev_inout_dev; f.first = first; f.guided = true; f.weights = weights_host; f.rows = rows;
   return op_sampler_step(cfg, step_index, z_dev, out_cond_dev, out_uncond_dev, z_out_dev, n, stream, f);
+}
+
+// any of the forms above with z_out's planes, the range flag and the published scan index (tests/test_gpu_sampler_planes.py):
+// the form follows from the pointers, each checked as its own entry point checks it
+int msd_op_sampler_step_planes(msd_sampler_planes_args* a, void* stream) {
+  if (!a || a->struct_size != (int32_t)sizeof(msd_sampler_planes_args) || !a->z_planes_out_dev) return MSD_ERR_INVALID_ARGUMENT;
+  SamplerOpForm f;
+  f.noise = a->noise_dev;
+  if (a->weights_host) { f.guided = true; f.weights = a->weights_host; f.rows = a->rows; }
+  if (a->x0_prev_inout_dev) { f.x0_prev = a->x0_prev_inout_dev; f.first = a->first; f.noise = nullptr; }
+  if (a->known_scaled_dev) {
+    if (f.guided || f.x0_prev || !a->keep_dev || a->n_dims <= 0 || a->n_dims % 4 || a->n <= 0 || a->n % a->n_dims)
+      return MSD_ERR_INVALID_ARGUMENT;
+    f.known = a->known_scaled_dev; f.keep = a->keep_dev; f.n_dims = a->n_dims; f.flags = a->keep_is_flags != 0;
+  }
+  SamplerOpPlanes po;
+  po.planes_out = a->z_planes_out_dev;
+  const int rc = op_sampler_step(a->cfg, a->step_index, a->z_dev, a->out_cond_dev, a->out_uncond_dev, a->z_out_dev, a->n,
+                                 stream, f, &po);
+  a->ran_range_flag = (int32_t)po.range_flag; a->ran_next_step = po.next_step;
+  return rc;
 }
 
 // sampler_invert_kernel alone (tests/test_gpu_invert.py): one step up the scan on the caller's arrays, the row weights from

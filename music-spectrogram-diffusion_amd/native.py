@@ -83,7 +83,9 @@ EXPORTED_SYMBOLS = (
     # (appended to ABI 7) the denoising loss of a mel under the encoded tokens
     'msd_loss', 'msd_op_diffusion_loss',
     # (appended to ABI 7) deterministic DDIM inversion: the noise that renders a mel under the encoded tokens
-    'msd_invert', 'msd_op_invert_step')
+    'msd_invert', 'msd_op_invert_step',
+    # (appended to ABI 7) a sampler update of any form with its operand planes, range flag and published scan index
+    'msd_op_sampler_step_planes')
 
 
 LOSS_CONDITIONINGS = {'cond': 0, 'uncond': 1, 'both': 2}   # MSD_LOSS_COND, _UNCOND, _BOTH
@@ -304,6 +306,15 @@ class CarrierArgs(ctypes.Structure):
 CARRIER_FORMS = {'none': 0, 'wave': 1, 'blocks': 2}   # msd_carrier_args.form
 
 
+class SamplerPlanesArgs(ctypes.Structure):
+  """msd_sampler_planes_args of include/msd_amd.h, field for field."""
+  _INTS = ('struct_size', 'step_index', 'n_dims', 'keep_is_flags', 'first', 'rows', 'ran_range_flag', 'ran_next_step')
+  _PTRS = ('z', 'out_cond', 'out_uncond', 'noise', 'known_scaled', 'keep', 'x0_prev')
+  _fields_ = [(n, ctypes.c_int32) for n in _INTS] + [('n', ctypes.c_int64), ('cfg', ctypes.POINTER(MsdConfig))] + [
+      (n, ctypes.c_void_p) for n in _PTRS] + [('weights', ctypes.POINTER(ctypes.c_float)), ('z_out', ctypes.c_void_p),
+                                              ('z_planes_out', ctypes.c_void_p)]
+
+
 class AttentionLaunchArgs(ctypes.Structure):
   """msd_attention_launch_args of include/msd_amd.h, field for field."""
   _INTS = ('struct_size', 'precision', 'qp', 'heads', 'segs', 'q_rows_per_seg', 'repeats', 'ksplit', 'merge_in_launch',
@@ -422,6 +433,8 @@ def load(planes: str = 'f16') -> ctypes.CDLL:
   if 'msd_invert' in present:   # (appended to ABI 7)
     lib.msd_invert.argtypes = [vp, c.POINTER(InvertArgs), vp]
     lib.msd_op_invert_step.argtypes = [c.POINTER(MsdConfig), i32, vp, vp, vp, c.POINTER(c.c_float), i32, vp, vp, i64, vp]
+  if 'msd_op_sampler_step_planes' in present:   # (appended to ABI 7)
+    lib.msd_op_sampler_step_planes.argtypes = [c.POINTER(SamplerPlanesArgs), vp]
   if 'msd_fill_normal_threefry' in present:
     lib.msd_fill_normal_threefry.argtypes = [u64, i64, vp, i64, vp]
   if 'msd_op_threefry' in present:
@@ -1031,6 +1044,36 @@ def op_sampler_step_multistep(cfg: MsdConfig, step_index: int, z, out_cond, out_
   _op_check(lib.msd_op_sampler_step_multistep(ctypes.byref(cfg), step_index, _ptr(z), _ptr(out_cond), _ptr(out_uncond),
                                               _ptr(x0_prev), int(bool(first)), _ptr(z_out), z.numel(), stream),
             'msd_op_sampler_step_multistep')
+
+
+def op_sampler_step_planes(cfg: MsdConfig, step_index: int, z, out_cond, out_uncond, z_out, z_planes_out, noise=None,
+                           known_scaled=None, keep_mask=None, release=None, x0_prev=None, first: bool = False, weights=None,
+                           stream: int = 0):
+  """One sampler update in any form of the op_sampler_step* functions above, with z_out's operand planes of cfg.precision
+  merged back to float32 in z_planes_out (msd_op_sampler_step_planes; the library of cfg.precision's plane format runs it).
+  The form follows from the arguments: known_scaled with keep_mask (flags) or release (words) = known frames; x0_prev
+  (and first) = the multistep update; weights (host floats, one per row) = guided.  Returns (range flag word, the scan
+  index the launch published); RangeError when the flag was set."""
+  lib = load(_PLANES_OF[cfg.precision])
+  cfg.struct_size = config_struct_size(lib)
+  if not (z.numel() == out_cond.numel() == z_out.numel() == z_planes_out.numel()):
+    raise ValueError('z, out_cond and the two outputs must have the same element count')
+  if (keep_mask is not None) and (release is not None):
+    raise ValueError('keep_mask (flags) or release (words), not both')
+  a = SamplerPlanesArgs()
+  a.struct_size = ctypes.sizeof(SamplerPlanesArgs)
+  a.step_index, a.n, a.cfg = step_index, z.numel(), ctypes.pointer(cfg)
+  a.z, a.out_cond, a.out_uncond, a.noise = _ptr(z), _ptr(out_cond), _ptr(out_uncond), _ptr(noise)
+  if known_scaled is not None:
+    a.known_scaled, a.n_dims = _ptr(known_scaled), int(known_scaled.shape[-1])
+    a.keep, a.keep_is_flags = _ptr(keep_mask if keep_mask is not None else release), int(keep_mask is not None)
+  if x0_prev is not None:
+    a.x0_prev, a.first = _ptr(x0_prev), int(bool(first))
+  if weights is not None:
+    a.weights, a.rows = (ctypes.c_float * len(weights))(*[float(x) for x in weights]), len(weights)
+  a.z_out, a.z_planes_out = _ptr(z_out), _ptr(z_planes_out)
+  _op_check(lib.msd_op_sampler_step_planes(ctypes.byref(a), stream), 'msd_op_sampler_step_planes')
+  return a.ran_range_flag, a.ran_next_step
 
 
 def op_invert_step(cfg: MsdConfig, step_index: int, z, out_cond, out_uncond, weights, z_out, z_planes_out, stream: int = 0):

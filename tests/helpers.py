@@ -81,6 +81,60 @@ def bits(a):
   return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
+def round_to_plane(x32, precision):
+  """float32 -> the plane type of `precision` (IEEE half via numpy, subnormals kept; bfloat16 via torch on the CPU), round
+  to nearest even -> float32."""
+  x32 = np.ascontiguousarray(x32, np.float32)
+  if precision.startswith('bf16'):
+    import torch
+    return torch.from_numpy(x32).to(torch.bfloat16).to(torch.float32).numpy()
+  with np.errstate(over='ignore'):
+    return x32.astype(np.float16).astype(np.float32)
+
+
+def planes_merged(z32, precision):
+  """What the device's operand planes of z merge back to, exactly: hi = P(z), lo = P(z - hi) (split2_h16, common.h) and
+  hi + lo in float32 (merge_planes_kernel) -- hi + 0 for the one-plane precisions 'f16' / 'bf16', the kernel's expression
+  (it turns a hi of -0 into +0).  z - hi and hi + lo are exact in float32 for both plane types
+  (tests/test_planes_merged_host.py holds this function against a nearest-representable search in float64), so the device's
+  merged planes must equal this array bit for bit, subnormal lo values included."""
+  assert precision in ('f16', 'f16x3', 'bf16', 'bf16x3'), precision
+  z32 = np.ascontiguousarray(z32, np.float32)
+  hi = round_to_plane(z32, precision)
+  if not precision.endswith('x3'):
+    return hi + np.float32(0.0)
+  with np.errstate(invalid='ignore'):   # (a NaN or Inf in z stays visible: NaN out)
+    return hi + round_to_plane(z32 - hi, precision)
+
+
+# The range cases of the ops whose output is one product plus one fmaf of their arguments (msd_op_invert_step,
+# _diffuse_to_step, _renoise): an exact 65504 cannot be constructed there, so one output element is aimed 2^-12 below the
+# half-plane limit (must pass) and 2^-12 above it (RangeError on the half-plane build, fine with bfloat16 planes).  The
+# margin is ~4000 times the float32 error of those two operations: the float32 specification alone decides the side.
+HALF_MAX = 65504.0
+RANGE_TARGETS = [('inside', HALF_MAX * (1 - 2.0 ** -12)), ('outside', HALF_MAX * (1 + 2.0 ** -12))]
+
+
+def check_range_case(call, side, precision, spec32, spec64, target, e):
+  """call() -> (z, merged planes) runs the op on inputs whose float64 specification spec64 puts `target` at flat element e:
+  asserts on the host that the float32 specification lies on the intended side of 65504 there, then the device's verdict."""
+  from msd_amd import native
+  v32, v64 = float(np.asarray(spec32).reshape(-1)[e]), float(np.asarray(spec64).reshape(-1)[e])
+  assert abs(v64 / target - 1) < 2.0 ** -20, (v64, target)
+  assert (v32 < HALF_MAX) if side == 'inside' else (v32 > HALF_MAX), (side, v32)
+  others = np.delete(np.abs(np.asarray(spec64)).reshape(-1), e)
+  assert others.max() < 100.0   # (the one large element decides)
+  if side == 'outside' and not precision.startswith('bf16'):
+    with pytest.raises(native.RangeError):
+      call()
+    return
+  z, zp = call()   # no RangeError: the flag word stayed 0
+  got = float(z.reshape(-1)[e])
+  print('range case %s %s: device %.9g, float32 spec %.9g, float64 spec %.9g' % (side, precision, got, v32, v64))
+  assert abs(got / v64 - 1) < 2.0 ** -20 and ((got < HALF_MAX) if side == 'inside' else (got > HALF_MAX)), (side, got)
+  np.testing.assert_array_equal(bits(zp), bits(planes_merged(z, precision)))
+
+
 def known_mel(shape, seed=21):
   """A mel that leaves the codec's range [log 1e-5, 4] at both ends."""
   return np.random.default_rng(seed).uniform(-13.0, 5.0, shape).astype(np.float32)

@@ -98,12 +98,45 @@ def test_op_diffuse_to_step_vs_spec(torch, n, precision):
     e_f32 = np.abs(refs['f32'] - refs['f64']).max() / scale
     print('diffuse n=%d %s i=%d: scaled error device %.3e / float32 %.3e' % (n, precision, i, e_dev, e_f32))
     assert e_dev <= 1e-6 + 4 * e_f32, (i, e_dev, e_f32)
-    # the planes merge back to z: hi = half(z) leaves <= 2^-11 |z|, lo = half(z - hi) leaves <= 2^-11 of that (2^-25
-    # where lo is subnormal); one plane leaves the first
-    z64 = z.astype(np.float64)
-    bound = (2.0 ** -22 if precision == 'f16x3' else 2.0 ** -11) * np.abs(z64) + 2.0 ** -24
-    assert (np.abs(zp.astype(np.float64) - z64) <= bound).all()
+    # the planes merge back to exactly what a hi / lo split of z holds (tests/helpers.py planes_merged); one plane: hi alone
+    np.testing.assert_array_equal(helpers.bits(zp), helpers.bits(helpers.planes_merged(z, precision)))
     assert np.abs(zp - z).max() > 0   # (planes, not a copy of z)
+
+
+@pytest.mark.parametrize('precision', ['f16x3', 'f16', 'bf16x3', 'bf16'])
+@pytest.mark.parametrize('side, target', helpers.RANGE_TARGETS, ids=[s for s, _ in helpers.RANGE_TARGETS])
+def test_op_diffuse_to_step_range_flag(torch, side, target, precision):
+  """The range flag of diffuse_to_step_kernel's tail (xk is clipped to [-1, 1], so the large value comes through eps): one
+  element of the launch's last float4, in a partial block, aimed 2^-12 below 65504 (passes) and 2^-12 above (RangeError
+  with half planes)."""
+  from msd_amd import inference, native
+  from oracle import backend, predict
+  n = 3 * 37 * 128
+  shape = (1, n // 4, 4)
+  e = n - 2
+  spec = helpers.sampler_spec()
+  codec = predict.MelGANCodec()
+  cfg = inference._to_native_config(spec, msd_amd.audio_codecs.MelGAN(), 1, precision)
+  _, dc = helpers.oracle_configs(spec)
+  i = dc.sampler.schedule.num_steps // 2
+  rng = np.random.default_rng(33)
+  mel = rng.uniform(-13.0, 5.0, shape).astype(np.float32)
+  eps = rng.standard_normal(shape).astype(np.float32)
+
+  def spec_of(xp):
+    xk = codec.scale_features(xp, xp.asarray(mel), (-1., 1.), clip=True)
+    return np.asarray(edit_spec.start_state(xp, dc, xk, xp.asarray(eps), i), np.float64)
+  xp64 = backend.NumpyBackend('float64')
+  eps.reshape(-1)[e] = 0.0
+  mean64 = spec_of(xp64).reshape(-1)[e]   # alpha * xk there
+  sigma64 = float(np.asarray(edit_spec.start_coefs(xp64, dc, 1, i)[1]).reshape(-1)[0])
+  eps.reshape(-1)[e] = (target - mean64) / sigma64
+
+  def call():
+    z_t, zp_t, xk_t = (torch.full(shape, float('nan'), dtype=torch.float32, device='cuda') for _ in range(3))
+    native.op_diffuse_to_step(cfg, i, helpers.dev(torch, mel), helpers.dev(torch, eps), z_t, zp_t, xk_t)
+    return z_t.cpu().numpy(), zp_t.cpu().numpy()
+  helpers.check_range_case(call, side, precision, spec_of(backend.NumpyBackend('float32')), spec_of(xp64), target, e)
 
 
 # --------------------------------------------------------------------------------------------------

@@ -63,8 +63,8 @@ def test_op_invert_step_vs_spec(torch, mode):
         print('invert step %s i=%d w=%g: scaled error device %.3e / float32 %.3e' % (mode, i, w, e_dev, e_f32))
         assert e_dev <= 1e-6 + 4 * e_f32, (mode, i, w, e_dev, e_f32)
         rows.setdefault(w, []).append(got[row])
-      z64 = got.astype(np.float64)
-      assert (np.abs(zp.astype(np.float64) - z64) <= 2.0 ** -22 * np.abs(z64) + 2.0 ** -24).all()
+      # the planes merge back to exactly what a hi / lo split of z_out holds (tests/helpers.py planes_merged)
+      np.testing.assert_array_equal(helpers.bits(zp), helpers.bits(helpers.planes_merged(got, 'f16x3')))
       assert np.abs(zp - got).max() > 0   # (planes, not a copy of z)
     # row b of the (1, 5) call: row 0 of (1, 1)'s bits and row 1 of (5, 5)'s
     np.testing.assert_array_equal(helpers.bits(rows[1.0][2]), helpers.bits(rows[1.0][0]))
@@ -81,6 +81,38 @@ def test_op_invert_step_vs_spec(torch, mode):
     native.op_invert_step(cfg, 1, bad, bad, None, [1.0, 5.0], bad, torch.empty_like(bad))
   with pytest.raises(ValueError):
     native.op_invert_step(cfg, 1, bad, bad, bad, [1.0, 1.0], bad, torch.empty_like(bad))
+
+
+@pytest.mark.parametrize('precision', ['f16x3', 'f16', 'bf16x3', 'bf16'])
+@pytest.mark.parametrize('side, target', helpers.RANGE_TARGETS, ids=[s for s, _ in helpers.RANGE_TARGETS])
+def test_op_invert_step_range_flag(torch, side, target, precision):
+  """The range flag of sampler_invert_kernel's tail: eps mode, weight 1 and z = 0 at one element of the launch's last float4
+  make its output b * o there; o aims it 2^-12 below 65504 (passes) and 2^-12 above (RangeError with half planes)."""
+  from msd_amd import inference, native
+  from oracle import backend
+  from tests import guidance_spec as gs
+  spec = helpers.sampler_spec(sampler='ddim', model_output='eps', steps=50)
+  cfg = inference._to_native_config(spec, msd_amd.audio_codecs.MelGAN(), 1, precision)
+  _, dc = helpers.oracle_configs(spec)
+  i = dc.sampler.schedule.num_steps // 2
+  rng = np.random.default_rng(31)
+  shape = (2, 8, 128)
+  e = 2 * 1024 - 2
+  z, oc = (rng.standard_normal(shape).astype(np.float32) for _ in range(2))
+  xp64 = backend.NumpyBackend('float64')
+  b64 = float(np.asarray(inv.coefficients(xp64, dc, 1, i)[1]).reshape(-1)[0])
+  z.reshape(-1)[e] = 0.0
+  oc.reshape(-1)[e] = target / b64
+  refs = {}
+  for name, xp in (('f32', backend.NumpyBackend('float32')), ('f64', xp64)):
+    pred = lambda z, time, include_conditioning, _xp=xp: _xp.asarray(oc)
+    refs[name] = np.asarray(inv.step(xp, gs.with_weight(dc, 1.0), xp.asarray(z), i, pred), np.float64)
+
+  def call():
+    out, planes = (torch.full(shape, float('nan'), dtype=torch.float32, device='cuda') for _ in range(2))
+    native.op_invert_step(cfg, i, helpers.dev(torch, z), helpers.dev(torch, oc), None, [1.0, 1.0], out, planes)
+    return out.cpu().numpy(), planes.cpu().numpy()
+  helpers.check_range_case(call, side, precision, refs['f32'], refs['f64'], target, e)
 
 
 # --------------------------------------------------------------------------------------------------

@@ -47,12 +47,40 @@ def test_op_renoise_vs_spec(torch, precision):
     e_f32 = np.abs(refs['f32'] - refs['f64']).max() / scale
     print('renoise %s %d -> %d: scaled error device %.3e / float32 %.3e' % (precision, lo, hi, e_dev, e_f32))
     assert e_dev <= 1e-6 + 4 * e_f32, (lo, hi, e_dev, e_f32)
-    # the planes merge back to z: hi = half(z) leaves <= 2^-11 |z|, lo = half(z - hi) leaves <= 2^-11 of that (2^-25
-    # where lo is subnormal); one plane leaves the first
-    z64 = z.astype(np.float64)
-    bound = (2.0 ** -22 if precision == 'f16x3' else 2.0 ** -11) * np.abs(z64) + 2.0 ** -24
-    assert (np.abs(zp.astype(np.float64) - z64) <= bound).all()
+    # the planes merge back to exactly what a hi / lo split of z holds (tests/helpers.py planes_merged); one plane: hi alone
+    np.testing.assert_array_equal(helpers.bits(zp), helpers.bits(helpers.planes_merged(z, precision)))
     assert np.abs(zp - z).max() > 0   # (planes, not a copy of z)
+
+
+@pytest.mark.parametrize('precision', ['f16x3', 'f16', 'bf16x3', 'bf16'])
+@pytest.mark.parametrize('side, target', helpers.RANGE_TARGETS, ids=[s for s, _ in helpers.RANGE_TARGETS])
+def test_op_renoise_range_flag(torch, side, target, precision):
+  """The range flag of renoise_kernel's tail: eps = 0 at one element of the launch's last float4, in a partial block, makes
+  its output a * z there; z aims it 2^-12 below 65504 (passes) and 2^-12 above (RangeError with half planes)."""
+  from msd_amd import inference, native
+  from oracle import backend
+  n = 3 * 37 * 128
+  shape = (1, n // 4, 4)
+  e = n - 2
+  spec = helpers.sampler_spec()
+  cfg = inference._to_native_config(spec, msd_amd.audio_codecs.MelGAN(), 1, precision)
+  _, dc = helpers.oracle_configs(spec)
+  lo, hi = 6, 14
+  rng = np.random.default_rng(35)
+  z_in = rng.standard_normal(shape).astype(np.float32)
+  eps = rng.standard_normal(shape).astype(np.float32)
+  xp64 = backend.NumpyBackend('float64')
+  a64 = float(np.asarray(resample_spec.jump_coefs(xp64, dc.sampler.schedule, 1, lo, hi)[0]).reshape(-1)[0])
+  eps.reshape(-1)[e] = 0.0
+  z_in.reshape(-1)[e] = target / a64
+  refs = {name: np.asarray(resample_spec.jump_state(xp, dc, xp.asarray(z_in), xp.asarray(eps), lo, hi), np.float64)
+          for name, xp in (('f32', backend.NumpyBackend('float32')), ('f64', xp64))}
+
+  def call():
+    z_t, zp_t = (torch.full(shape, float('nan'), dtype=torch.float32, device='cuda') for _ in range(2))
+    native.op_renoise(cfg, lo, hi, helpers.dev(torch, z_in), helpers.dev(torch, eps), z_t, zp_t)
+    return z_t.cpu().numpy(), zp_t.cpu().numpy()
+  helpers.check_range_case(call, side, precision, refs['f32'], refs['f64'], target, e)
 
 
 def test_op_renoise_refuses_bad_levels(torch):
