@@ -2169,7 +2169,9 @@ struct SampleCall {
   // takes the cond_wt == 1 branch (one decoder pass) outside; null = the handle's own weight at every step, as ever
   const float* weights = nullptr;   // host
   int n_weights = 0, guide_lo = 0, guide_hi = 0;
-  // msd_invert: the caller's mel [batch, T, n] (device); the scan starts at index 0 from it and counts up.  null = a sampling call
+  // msd_invert: the caller's mel [batch, T, n] (device); the scan starts at index 0 from it and counts up through all of
+  // `steps`, every step on the two-pass plan when guide_lo < guide_hi, else on the one-pass plan; `weights` is always given
+  // and `out` receives z in model units.  null = a sampling call
   const float* invert_mel = nullptr;
 };
 
@@ -2189,6 +2191,34 @@ static std::string divisors_of(int n) {
   for (int k = 1; k <= n; ++k)
     if (n % k == 0) out += (out.empty() ? "" : ", ") + std::to_string(k);
   return out;
+}
+
+// a call's own step count (msd_sample_steps, msd_sample_guided, msd_invert): 0 = the handle's N, or a divisor of it
+static int check_num_steps(msd_model* m, int num_steps) {
+  if (num_steps < 0 || (num_steps > 0 && m->N % num_steps))
+    return fail(m, MSD_ERR_INVALID_ARGUMENT, "num_steps %d does not divide the handle's %d steps; it takes 0 (= %d) or one of %s",
+                num_steps, m->N, m->N, divisors_of(m->N).c_str());
+  return MSD_OK;
+}
+
+// The guidance weights of a call (msd_sample_guided, msd_invert; host): 1 or one per row, finite, whole sampler blocks per
+// row when there is one per row; *all_one: every row takes the cond_wt == 1 branch.  A handle created with cfg_weight 1 holds
+// one pass's buffers: it takes no weights at all, or -- one_pass_ok, the inversion -- none but 1.
+static int check_row_weights(msd_model* m, int batch, const float* weights, int n_weights, bool one_pass_ok, bool* all_one) {
+  if (!weights || (n_weights != 1 && n_weights != batch))
+    return fail(m, MSD_ERR_INVALID_ARGUMENT, "guidance takes 1 weight or one per row (%d), got %d", batch, weights ? n_weights : 0);
+  *all_one = true;
+  for (int b = 0; b < n_weights; ++b) {
+    if (!std::isfinite(weights[b])) return fail(m, MSD_ERR_INVALID_ARGUMENT, "guidance weight %d is not finite", b);
+    *all_one = *all_one && weights[b] == 1.0f;
+  }
+  const int64_t row_n = (int64_t)m->T * m->ND;
+  if (n_weights > 1 && row_n % kRngRowBlock)   // a block of the sampler launch would straddle two rows' weights
+    return fail(m, MSD_ERR_UNSUPPORTED, "per-row guidance weights need targets_length * n_dims %% %d == 0 (got %lld)", (int)kRngRowBlock, (long long)row_n);
+  if (m->passes == 1 && !(one_pass_ok && *all_one))
+    return fail(m, MSD_ERR_UNSUPPORTED, "a handle created with cfg_weight 1 holds one pass's buffers and takes no per-call guidance: "
+                "create the handle with any weight != 1");
+  return MSD_OK;
 }
 
 // The view of a call of K steps with `sampler` (K | N, a known kind) in the keep form or not, every field filled, with what
@@ -2266,9 +2296,6 @@ static int check_call(msd_model* m, const SampleCall& c) {
         return fail(m, MSD_ERR_INVALID_ARGUMENT, "a call with resampling needs stream_id < 2^32 (row %d: %llu)", b, (unsigned long long)c.keys.stream_of(b));
   if (int rc = check_encoded_call(m, c.batch, c.rng, c.keys.per_row())) return rc;
   if (!c.out) return fail(m, MSD_ERR_INVALID_ARGUMENT, "out is null");
-  const int64_t row_n = (int64_t)m->T * m->ND;
-  if (c.weights && c.n_weights > 1 && row_n % kRngRowBlock)   // a block of the sampler launch would straddle two rows' weights
-    return fail(m, MSD_ERR_UNSUPPORTED, "per-row guidance weights need targets_length * n_dims %% %d == 0 (got %lld)", (int)kRngRowBlock, (long long)row_n);
   if (c.known && m->ND % 4)   // a thread of the sampler holds four consecutive elements and ONE frame flag
     return fail(m, MSD_ERR_UNSUPPORTED, "kept frames need n_dims %% 4 == 0 (got %d)", m->ND);
   return MSD_OK;
@@ -2485,13 +2512,23 @@ static int unscale(msd_model* m, const SampleCall& c, hipStream_t s) {
   return MSD_OK;
 }
 
+// the row weights travel next to the key table (arm_scan ends with the stream idle)
+static int upload_row_weights(msd_model* m, const SampleCall& c, hipStream_t s) {
+  m->h_row_wt.assign((size_t)m->Bmax, c.weights[0]);   // a member: the copy may still read it when this returns
+  for (int b = 0; b < c.batch && c.n_weights > 1; ++b) m->h_row_wt[b] = c.weights[b];
+  HIP_TRY(m, hipMemcpyAsync(m->d_row_wt, m->h_row_wt.data(), m->h_row_wt.size() * sizeof(float), hipMemcpyHostToDevice, s));
+  return MSD_OK;
+}
+
 static int sample_body(msd_model* m, const SampleCall& c) {
   if (int rc = check_call(m, c)) return rc;
+  const bool invert = c.invert_mel != nullptr;
   StepView view;
-  if (int rc = make_step_view(m, c.steps, c.sampler, c.known != nullptr, &view)) return rc;   // (+ the handle's buffers and tables)
+  if (int rc = make_step_view(m, c.steps, c.sampler, c.known != nullptr, &view, invert)) return rc;   // (+ the handle's buffers and tables)
   hipStream_t s;
   if (int rc = choose_stream(m, c.stream, &s)) return rc;
-  const int steps = c.start_step + 1;   // the steps the call runs: all of c.steps but for msd_sample_edit's part-way start
+  // the steps the call runs: all of c.steps but for msd_sample_edit's part-way start (the inversion counts up from 0)
+  const int steps = invert ? c.steps : c.start_step + 1;
   if (steps <= 0) {   // (msd_sample_edit: every frame known throughout) no step runs: the caller's mel
     HIP_TRY(m, hipMemcpyAsync(c.out, c.known, (size_t)c.batch * m->T * m->ND * sizeof(float), hipMemcpyDeviceToDevice, s));
     HIP_TRY(m, hipStreamSynchronize(s));
@@ -2501,17 +2538,17 @@ static int sample_body(msd_model* m, const SampleCall& c) {
   if (int rc = write_initial_state(m, c, s)) return rc;
   if (c.times > 1)
     if (int rc = upload_pass_keys(m, c, steps, s)) return rc;
-  if (c.weights) {   // the row weights travel next to the key table (arm_scan ends with the stream idle)
-    m->h_row_wt.assign((size_t)m->Bmax, c.weights[0]);   // a member: the copy may still read it when this returns
-    for (int b = 0; b < c.batch && c.n_weights > 1; ++b) m->h_row_wt[b] = c.weights[b];
-    HIP_TRY(m, hipMemcpyAsync(m->d_row_wt, m->h_row_wt.data(), m->h_row_wt.size() * sizeof(float), hipMemcpyHostToDevice, s));
-  }
+  if (c.weights)
+    if (int rc = upload_row_weights(m, c, s)) return rc;
+  // (the inversion's key table and noise slot are written as every call writes them; its kernel reads neither)
   if (int rc = arm_scan(m, c.batch, c.rng, c.keys, c.noise, c.start_step, /*reset_tickets=*/true, s)) return rc;
   msd_model::StepGraphs* g = nullptr;
-  if (c.weights) {
+  if (c.weights && !invert) {
     if (int rc = replay_guided(m, c, view, steps, s)) return rc;
   } else if (c.times == 1) {
-    if (int rc = find_graphs(m, view, plan_cfg_step(m, c.batch), steps, s, &g)) return rc;
+    // (the inversion: one form of step throughout -- its kernel reads the row weights; the plan is the passes they need)
+    const bool one_pass = invert && c.guide_lo == c.guide_hi;
+    if (int rc = find_graphs(m, view, one_pass ? plan_step(m, c.batch, 1, true, false) : plan_cfg_step(m, c.batch), steps, s, &g)) return rc;
     if (int rc = replay(m, *g, steps, s)) return rc;
   } else {
     // (the single-step graph: needed as soon as one block is no whole number of graphs)
@@ -2519,9 +2556,13 @@ static int sample_body(msd_model* m, const SampleCall& c) {
     if (int rc = find_graphs(m, view, plan_cfg_step(m, c.batch), singles ? 1 : m->graph_steps, s, &g)) return rc;
     if (int rc = replay_resampled(m, c, *g, steps, s)) return rc;
   }
-  if (int rc = unscale(m, c, s)) return rc;
+  if (invert) {   // z as it stands, in model units: the init_z of the call that renders the mel again
+    HIP_TRY(m, hipMemcpyAsync(c.out, m->z, (size_t)c.batch * m->T * m->ND * sizeof(float), hipMemcpyDeviceToDevice, s));
+  } else if (int rc = unscale(m, c, s)) {
+    return rc;
+  }
   // ONE stream synchronisation ends the call (tens of microseconds against a ~1 s segment); behind it the half-plane range flag is read: a bad run fails THIS call
-  return check_range(m, s, "msd_sample");
+  return check_range(m, s, invert ? "msd_invert" : "msd_sample");
 }
 
 // ---- the entry points: each checks what only it knows, fills the call and runs it ----------------------------------
@@ -2603,9 +2644,7 @@ int msd_sample_resample(msd_model* m, int batch, int rng, int per_row, const uin
 static int steps_call(msd_model* m, int batch, int rng, int per_row, const uint64_t* seeds, const uint64_t* stream_ids,
                       const float* init_z_dev, const float* noise_dev, int num_steps, int sampler, float* out_dev,
                       void* stream, SampleCall* out) {
-  if (num_steps < 0 || (num_steps > 0 && m->N % num_steps))
-    return fail(m, MSD_ERR_INVALID_ARGUMENT, "num_steps %d does not divide the handle's %d steps; it takes 0 (= %d) or one of %s",
-                num_steps, m->N, m->N, divisors_of(m->N).c_str());
+  if (int rc = check_num_steps(m, num_steps)) return rc;
   if (sampler != -1 && sampler != MSD_SAMPLER_DDPM && sampler != MSD_SAMPLER_DDIM && sampler != MSD_SAMPLER_DPMPP_2M)
     return fail(m, MSD_ERR_INVALID_ARGUMENT, "Unknown sampler type: %d", sampler);
   SampleCall c = plain_call(m, batch, rng, sample_keys(per_row, seeds, stream_ids), init_z_dev, noise_dev, out_dev, stream);
@@ -2633,20 +2672,12 @@ int msd_sample_guided(msd_model* m, int batch, int rng, int per_row, const uint6
   if (batch < 1 || batch > m->Bmax) return fail(m, MSD_ERR_INVALID_ARGUMENT, "batch %d outside [1, %d]", batch, m->Bmax);
   SampleCall c;
   if (int rc = steps_call(m, batch, rng, per_row, seeds, stream_ids, init_z_dev, noise_dev, num_steps, sampler, out_dev, stream, &c)) return rc;
-  if (!weights_host || (n_weights != 1 && n_weights != batch))
-    return fail(m, MSD_ERR_INVALID_ARGUMENT, "guidance takes 1 weight or one per row (%d), got %d", batch, weights_host ? n_weights : 0);
-  bool all_one = true;
-  for (int b = 0; b < n_weights; ++b) {
-    if (!std::isfinite(weights_host[b])) return fail(m, MSD_ERR_INVALID_ARGUMENT, "guidance weight %d is not finite", b);
-    all_one = all_one && weights_host[b] == 1.0f;
-  }
+  bool all_one;
+  if (int rc = check_row_weights(m, batch, weights_host, n_weights, /*one_pass_ok=*/false, &all_one)) return rc;
   const int K = c.steps;
   if (guide_lo == 0 && guide_hi == 0) guide_hi = K;   // the whole scan
   if (guide_lo < 0 || guide_lo >= guide_hi || guide_hi > K)
     return fail(m, MSD_ERR_INVALID_ARGUMENT, "guidance interval [%d, %d) is not inside the call's scan indices [0, %d)", guide_lo, guide_hi, K);
-  if (m->passes == 1)   // (a weight-1 handle has buffers for one pass only)
-    return fail(m, MSD_ERR_UNSUPPORTED, "a handle created with cfg_weight 1 holds one pass's buffers and takes no per-call guidance: "
-                "create the handle with any weight != 1");
   if (int rc = ensure(m, &m->d_row_wt, (size_t)m->Bmax)) return rc;
   c.weights = weights_host; c.n_weights = n_weights; c.guide_lo = guide_lo; c.guide_hi = guide_hi;
   if (all_one) c.guide_lo = c.guide_hi = 0;   // every row follows the cond_wt == 1 branch: no guided step, K one-pass steps
@@ -2654,53 +2685,26 @@ int msd_sample_guided(msd_model* m, int batch, int rng, int per_row, const uint6
 }
 
 // ---- msd_invert: deterministic DDIM inversion (kernel: invert_tail.h) --------------------------------------------------
-// The phases of a sampling call on a scan that counts up: the view with the inversion's side table, level 0 written from the
-// mel, the scan words armed at 0, the graphs of (plan, view) from the step-graph cache, K steps replayed, z copied out.
+// A sampling call on a scan that counts up (sample_body): the view with the inversion's side table, level 0 written from the
+// mel, the scan words armed at 0, K steps of the one plan the weights need, z copied out.  No draw is made: the keys are Philox's zeros.
 int msd_invert(msd_model* m, const msd_invert_args* a, void* stream) {
   if (!m) return MSD_ERR_INVALID_ARGUMENT;
   if (!a || a->struct_size != (int32_t)sizeof(msd_invert_args))
     return fail(m, MSD_ERR_INVALID_ARGUMENT, "msd_invert_args.struct_size %d != %d", a ? a->struct_size : 0, (int)sizeof(msd_invert_args));
-  // every refusal in front of any device work
-  if (int rc = check_encoded_call(m, a->batch, MSD_RNG_PHILOX, /*per_row=*/false)) return rc;
   if (!a->mel_dev || !a->out_dev) return fail(m, MSD_ERR_INVALID_ARGUMENT, "mel_dev or out_dev is null");
-  if (a->num_steps < 0 || (a->num_steps > 0 && m->N % a->num_steps))
-    return fail(m, MSD_ERR_INVALID_ARGUMENT, "num_steps %d does not divide the handle's %d steps; it takes 0 (= %d) or one of %s",
-                a->num_steps, m->N, m->N, divisors_of(m->N).c_str());
-  const int n_weights = a->weights_host ? a->n_weights : 0;
-  if (n_weights != 0 && n_weights != 1 && n_weights != a->batch)
-    return fail(m, MSD_ERR_INVALID_ARGUMENT, "guidance takes 1 weight or one per row (%d), got %d", a->batch, n_weights);
+  if (int rc = check_num_steps(m, a->num_steps)) return rc;
+  static const float kWeightOne = 1.0f;   // no weights given: ONE weight of 1 (the table is uploaded all the same)
+  const bool given = a->weights_host && a->n_weights != 0;
   bool all_one = true;
-  for (int b = 0; b < n_weights; ++b) {
-    if (!std::isfinite(a->weights_host[b])) return fail(m, MSD_ERR_INVALID_ARGUMENT, "guidance weight %d is not finite", b);
-    all_one = all_one && a->weights_host[b] == 1.0f;
-  }
+  if (given)
+    if (int rc = check_row_weights(m, a->batch, a->weights_host, a->n_weights, /*one_pass_ok=*/true, &all_one)) return rc;
   const int64_t row_n = (int64_t)m->T * m->ND;
-  if (n_weights > 1 && row_n % kRngRowBlock)   // a block of the sampler launch would straddle two rows' weights
-    return fail(m, MSD_ERR_UNSUPPORTED, "per-row guidance weights need targets_length * n_dims %% %d == 0 (got %lld)", (int)kRngRowBlock, (long long)row_n);
   if (row_n % 4) return fail(m, MSD_ERR_UNSUPPORTED, "the inversion needs targets_length * n_dims %% 4 == 0 (got %lld)", (long long)row_n);
-  if (!all_one && m->passes == 1)   // (a weight-1 handle has buffers for one pass only)
-    return fail(m, MSD_ERR_UNSUPPORTED, "a handle created with cfg_weight 1 holds one pass's buffers and takes no per-call guidance: "
-                "create the handle with any weight != 1");
-  const int K = a->num_steps > 0 ? a->num_steps : m->N;
-  StepView view;
-  if (int rc = make_step_view(m, K, MSD_SAMPLER_DDIM, /*keep=*/false, &view, /*invert=*/true)) return rc;
-  hipStream_t s;
-  if (int rc = choose_stream(m, stream, &s)) return rc;
-  if (int rc = arm_range(m, s)) return rc;
   SampleCall c = plain_call(m, a->batch, MSD_RNG_PHILOX, SampleKeys(), nullptr, nullptr, a->out_dev, stream);
-  c.steps = K; c.start_step = 0; c.sampler = MSD_SAMPLER_DDIM; c.invert_mel = a->mel_dev;
-  if (int rc = write_initial_state(m, c, s)) return rc;
-  m->h_row_wt.assign((size_t)m->Bmax, n_weights ? a->weights_host[0] : 1.0f);   // a member: the copy may still read it when this returns
-  for (int b = 0; b < a->batch && n_weights > 1; ++b) m->h_row_wt[b] = a->weights_host[b];
-  HIP_TRY(m, hipMemcpyAsync(m->d_row_wt, m->h_row_wt.data(), m->h_row_wt.size() * sizeof(float), hipMemcpyHostToDevice, s));
-  // (the key table and the noise slot are written as every call writes them; the inversion kernel reads neither)
-  if (int rc = arm_scan(m, c.batch, c.rng, c.keys, /*noise=*/nullptr, /*start_step=*/0, /*reset_tickets=*/true, s)) return rc;
-  const StepPlan plan = all_one ? plan_step(m, c.batch, 1, true, false) : plan_cfg_step(m, c.batch);
-  msd_model::StepGraphs* g = nullptr;
-  if (int rc = find_graphs(m, view, plan, K, s, &g)) return rc;
-  if (int rc = replay(m, *g, K, s)) return rc;
-  HIP_TRY(m, hipMemcpyAsync(a->out_dev, m->z, (size_t)c.batch * m->T * m->ND * sizeof(float), hipMemcpyDeviceToDevice, s));
-  return check_range(m, s, "msd_invert");   // the call's single synchronisation at its end (arm_scan's idles the stream in front of the steps, as in every sampling call)
+  c.steps = a->num_steps > 0 ? a->num_steps : m->N; c.start_step = 0; c.sampler = MSD_SAMPLER_DDIM; c.invert_mel = a->mel_dev;
+  c.weights = given ? a->weights_host : &kWeightOne; c.n_weights = given ? a->n_weights : 1;
+  c.guide_hi = all_one ? 0 : c.steps;   // (every weight 1: the one-pass plan at every step)
+  return sample_body(m, c);
 }
 
 int msd_reset_graph(msd_model* m) {

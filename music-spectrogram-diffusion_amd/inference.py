@@ -26,6 +26,7 @@ tokeniser uses (inference.py:108-111).
 """
 from __future__ import annotations
 
+import contextlib
 import dataclasses
 import os
 import time
@@ -675,8 +676,13 @@ class InferenceModel(object):
     if resample is not None and rng == 'jax':
       raise ValueError("resample= cannot be combined with rng='jax' (host draws): the draws of the jumps and of the passes "
                        "behind them are made on the device; use 'philox' or 'threefry'")
+    return self._with_range_fallback(self._predict_once, batch, seed, segment, init_z, noise, return_torch, rng, call)
+
+  def _with_range_fallback(self, fn, *args):
+    """fn(*args), one of the _once calls.  When an activation leaves the half planes' range (native.RangeError) and
+    range_fallback allows it, the model moves to the bfloat16-plane build for good and the call is repeated, once."""
     try:
-      return self._predict_once(batch, seed, segment, init_z, noise, return_torch, rng, call)
+      return fn(*args)
     except native.RangeError:
       if not (self.range_fallback and self.precision in ('f16x3', 'f16')):
         raise
@@ -688,9 +694,13 @@ class InferenceModel(object):
       if self._native is not None:
         self._native.close()
       self._native = None
-      return self._predict_once(batch, seed, segment, init_z, noise, return_torch, rng, call)
+      return fn(*args)
 
-  def _predict_once(self, batch, seed, segment, init_z, noise, return_torch, rng, call=SampleCall()):
+  @contextlib.contextmanager
+  def _encode_batch(self, batch):
+    """The encode stage of every call that runs the decoder on an encoded state: the tokens checked, the model's stream
+    ordered behind the caller's, the context and its mask uploaded and checked, msd_encode enqueued.  Yields (nm, b, s,
+    t0, t1) -- the handle, the rows, the stream's handle and the stage's two timestamps -- with the model's stream current."""
     torch = self._torch
     nm = self._get_native()
     dev = self.device
@@ -703,7 +713,7 @@ class InferenceModel(object):
       raise ValueError('encoder_input_tokens must be [batch, %d]' % self.inputs_length)
     if b > self.batch_size:
       raise ValueError('batch %d exceeds batch_size %d' % (b, self.batch_size))
-    t, n = self.targets_length, self.audio_codec.n_dims
+    n = self.audio_codec.n_dims
     t0 = time.perf_counter()
     with torch.cuda.device(dev):
       # tensors the caller produced on its own stream (e.g. the previous prediction) are consumed on
@@ -721,7 +731,23 @@ class InferenceModel(object):
         if mask.shape != (b, self.targets_context_length):   # msd_encode copies batch * C ints from it
           raise ValueError('encoder_continuous_mask must be [batch, %d]' % self.targets_context_length)
       nm.encode(b, tokens, ctx, mask, stream=s)
-      t1 = time.perf_counter()
+      yield nm, b, s, t0, time.perf_counter()
+
+  def _check_target(self, batch, caller: str, what: str):
+    """batch['decoder_target_tokens'] of invert / loss: present, and [batch, T, n] for the rows of the tokens."""
+    t, n = self.targets_length, self.audio_codec.n_dims
+    if 'decoder_target_tokens' not in batch:
+      raise ValueError("%s() needs batch['decoder_target_tokens']: the mel to %s, [batch, %d, %d]" % (caller, what, t, n))
+    b = np.shape(batch['encoder_input_tokens'])[0]
+    if tuple(np.shape(batch['decoder_target_tokens'])) != (b, t, n):
+      raise ValueError('decoder_target_tokens must be [batch, %d, %d] = %r: got %r'
+                       % (t, n, (b, t, n), tuple(np.shape(batch['decoder_target_tokens']))))
+    return b, t, n
+
+  def _predict_once(self, batch, seed, segment, init_z, noise, return_torch, rng, call=SampleCall()):
+    torch, dev = self._torch, self.device
+    t, n = self.targets_length, self.audio_codec.n_dims
+    with self._encode_batch(batch) as (nm, b, s, t0, t1):
       out = torch.empty((b, t, n), dtype=torch.float32, device=dev)
       per_row = not (np.isscalar(seed) and np.isscalar(segment))
       if per_row:
@@ -773,59 +799,15 @@ class InferenceModel(object):
     noise or 'dpmpp_2m', keep / strength / resample, per-frame weights, K that does not divide N.
     Returns the noise float32 [B, T, n] in MODEL units (NumPy; ``return_torch``: the device tensor).  Argument errors are
     ValueErrors raised before any device work."""
-    if 'decoder_target_tokens' not in batch:
-      raise ValueError("invert() needs batch['decoder_target_tokens']: the mel to invert, [batch, %d, %d]"
-                       % (self.targets_length, self.audio_codec.n_dims))
-    b, t, n = np.shape(batch['encoder_input_tokens'])[0], self.targets_length, self.audio_codec.n_dims
-    if tuple(np.shape(batch['decoder_target_tokens'])) != (b, t, n):
-      raise ValueError('decoder_target_tokens must be [batch, %d, %d] = %r: got %r'
-                       % (t, n, (b, t, n), tuple(np.shape(batch['decoder_target_tokens']))))
+    b, _, _ = self._check_target(batch, 'invert', 'invert')
     weights, k = plan_invert(guidance, steps, b, self.spec.diffusion.sampler.schedule.num_steps,
                              self.spec.diffusion.classifier_free_guidance.eval_condition_weight)
-    try:
-      return self._invert_once(batch, k, weights, return_torch)
-    except native.RangeError:
-      if not (self.range_fallback and self.precision in ('f16x3', 'f16')):
-        raise
-      import warnings
-      new = 'bf16x3' if self.precision == 'f16x3' else 'bf16'
-      warnings.warn("an activation left the half-plane range (|x| > 65504): switching this model from precision "
-                    "'%s' to '%s' (bfloat16 planes) and repeating the call" % (self.precision, new), RuntimeWarning)
-      self.precision = new
-      if self._native is not None:
-        self._native.close()
-      self._native = None
-      return self._invert_once(batch, k, weights, return_torch)
+    return self._with_range_fallback(self._invert_once, batch, k, weights, return_torch)
 
   def _invert_once(self, batch, k, weights, return_torch):
-    torch = self._torch
-    nm = self._get_native()
-    dev = self.device
-    tokens = _to_numpy(batch['encoder_input_tokens'])
-    if tokens.dtype.kind not in 'iu':
-      raise ValueError('Input type must be an integer or unsigned integer.')
-    tokens = np.ascontiguousarray(tokens, dtype=np.int32)
-    b = tokens.shape[0]
-    if tokens.ndim != 2 or tokens.shape[1] != self.inputs_length:
-      raise ValueError('encoder_input_tokens must be [batch, %d]' % self.inputs_length)
-    if b > self.batch_size:
-      raise ValueError('batch %d exceeds batch_size %d' % (b, self.batch_size))
+    torch, dev = self._torch, self.device
     t, n = self.targets_length, self.audio_codec.n_dims
-    t0 = time.perf_counter()
-    with torch.cuda.device(dev):
-      self._stream.wait_stream(torch.cuda.current_stream(dev))
-    with torch.cuda.device(dev), torch.cuda.stream(self._stream):
-      s = self._stream.cuda_stream
-      ctx = cmask = None
-      if self.targets_context_length is not None:
-        ctx = _to_device(torch, batch['encoder_continuous_inputs'], dev, torch.float32)
-        if tuple(ctx.shape) != (b, self.targets_context_length, n):
-          raise ValueError('encoder_continuous_inputs must be [batch, %d, %d]' % (self.targets_context_length, n))
-        cmask = np.ascontiguousarray(_to_numpy(batch['encoder_continuous_mask']), dtype=np.int32)
-        if cmask.shape != (b, self.targets_context_length):
-          raise ValueError('encoder_continuous_mask must be [batch, %d]' % self.targets_context_length)
-      nm.encode(b, tokens, ctx, cmask, stream=s)
-      t1 = time.perf_counter()
+    with self._encode_batch(batch) as (nm, b, s, t0, t1):
       mel = _to_device(torch, batch['decoder_target_tokens'], dev, torch.float32).contiguous()
       out = torch.empty((b, t, n), dtype=torch.float32, device=dev)
       nm.invert(b, out, mel, steps=k, guidance=weights if len(weights) > 1 else weights[0], stream=s)
@@ -934,62 +916,19 @@ class InferenceModel(object):
       raise ValueError('Unknown diffusion loss_type: %r (one of %s)' % (loss_type, sorted(native.LOSS_TYPES)))
     if loss_norm not in native.LOSS_NORMS:
       raise ValueError('Unknown diffusion loss norm: %r (one of %s)' % (loss_norm, sorted(native.LOSS_NORMS)))
-    if 'decoder_target_tokens' not in batch:
-      raise ValueError("loss() needs batch['decoder_target_tokens']: the mel to score, [batch, %d, %d]"
-                       % (self.targets_length, self.audio_codec.n_dims))
-    b, t, n = np.shape(batch['encoder_input_tokens'])[0], self.targets_length, self.audio_codec.n_dims
-    if tuple(np.shape(batch['decoder_target_tokens'])) != (b, t, n):
-      raise ValueError('decoder_target_tokens must be [batch, %d, %d] = %r: got %r'
-                       % (t, n, (b, t, n), tuple(np.shape(batch['decoder_target_tokens']))))
+    b, t, n = self._check_target(batch, 'loss', 'score')
     mask = batch.get('decoder_target_mask')
     if mask is not None and tuple(np.shape(mask)) != (b, t):
       raise ValueError('decoder_target_mask must be [batch, %d]: got %r' % (t, tuple(np.shape(mask))))
     if eps is not None and tuple(np.shape(eps)) != (len(idx), b, t, n):
       raise ValueError('eps must be [times, batch, %d, %d] = %r: got %r' % (t, n, (len(idx), b, t, n), tuple(np.shape(eps))))
-    args = (batch, idx, seed, segment, rng, conditioning, loss_type, loss_norm, eps)
-    try:
-      return self._loss_once(*args)
-    except native.RangeError:
-      if not (self.range_fallback and self.precision in ('f16x3', 'f16')):
-        raise
-      import warnings
-      new = 'bf16x3' if self.precision == 'f16x3' else 'bf16'
-      warnings.warn("an activation left the half-plane range (|x| > 65504): switching this model from precision "
-                    "'%s' to '%s' (bfloat16 planes) and repeating the call" % (self.precision, new), RuntimeWarning)
-      self.precision = new
-      if self._native is not None:
-        self._native.close()
-      self._native = None
-      return self._loss_once(*args)
+    return self._with_range_fallback(self._loss_once, batch, idx, seed, segment, rng, conditioning, loss_type, loss_norm, eps)
 
   def _loss_once(self, batch, idx, seed, segment, rng, conditioning, loss_type, loss_norm, eps):
-    torch = self._torch
-    nm = self._get_native()
-    dev = self.device
-    tokens = _to_numpy(batch['encoder_input_tokens'])
-    if tokens.dtype.kind not in 'iu':
-      raise ValueError('Input type must be an integer or unsigned integer.')
-    tokens = np.ascontiguousarray(tokens, dtype=np.int32)
-    b = tokens.shape[0]
-    if tokens.ndim != 2 or tokens.shape[1] != self.inputs_length:
-      raise ValueError('encoder_input_tokens must be [batch, %d]' % self.inputs_length)
-    if b > self.batch_size:
-      raise ValueError('batch %d exceeds batch_size %d' % (b, self.batch_size))
-    t, n = self.targets_length, self.audio_codec.n_dims
+    torch, dev = self._torch, self.device
+    t = self.targets_length
     passes = 2 if conditioning == 'both' else 1
-    with torch.cuda.device(dev):
-      self._stream.wait_stream(torch.cuda.current_stream(dev))
-    with torch.cuda.device(dev), torch.cuda.stream(self._stream):
-      s = self._stream.cuda_stream
-      ctx = cmask = None
-      if self.targets_context_length is not None:
-        ctx = _to_device(torch, batch['encoder_continuous_inputs'], dev, torch.float32)
-        if tuple(ctx.shape) != (b, self.targets_context_length, n):
-          raise ValueError('encoder_continuous_inputs must be [batch, %d, %d]' % (self.targets_context_length, n))
-        cmask = np.ascontiguousarray(_to_numpy(batch['encoder_continuous_mask']), dtype=np.int32)
-        if cmask.shape != (b, self.targets_context_length):
-          raise ValueError('encoder_continuous_mask must be [batch, %d]' % self.targets_context_length)
-      nm.encode(b, tokens, ctx, cmask, stream=s)
+    with self._encode_batch(batch) as (nm, b, s, _, _):
       target = _to_device(torch, batch['decoder_target_tokens'], dev, torch.float32).contiguous()
       mask = batch.get('decoder_target_mask')
       mask_d = None if mask is None else _to_device(torch, mask, dev, torch.float32).contiguous()

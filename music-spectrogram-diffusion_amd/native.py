@@ -98,9 +98,7 @@ def plan_loss_times(num_steps: int, times):
   (i + 1) / N).  An integer K with 1 <= K <= N gives the stratified grid i_j = ((2 j + 1) N) // (2 K), j = 0 .. K - 1: the
   middle of each of K equal strata, strictly increasing, every index for K == N.  A sequence gives its own entries, each an
   integer in [0, N), in the given order, repeats allowed.  Anything else is a ValueError.  No device needed."""
-  if isinstance(num_steps, (bool, np.bool_)) or not isinstance(num_steps, (int, np.integer)) or num_steps < 1:
-    raise ValueError('num_steps must be a positive integer: %r' % (num_steps,))
-  n = int(num_steps)
+  n = _check_num_steps(num_steps)
   if isinstance(times, (bool, np.bool_)):
     raise ValueError('times must be an integer in [1, %d] or a sequence of time indices, not a bool' % n)
   if isinstance(times, (int, np.integer)):
@@ -115,7 +113,7 @@ def plan_loss_times(num_steps: int, times):
   if not idx:
     raise ValueError('times is empty: a loss call needs at least one time index')
   for i in idx:
-    if isinstance(i, (bool, np.bool_)) or not isinstance(i, (int, np.integer)) or not 0 <= i < n:
+    if not _is_int(i, 0) or i >= n:
       raise ValueError('time index %r is not an integer in [0, %d)' % (i, n))
   return [int(i) for i in idx]
 
@@ -190,11 +188,23 @@ def divisors(n: int):
   return [k for k in range(1, n + 1) if n % k == 0]
 
 
+def _is_int(v, lo: int) -> bool:
+  """v is an integer (no bool) >= lo."""
+  return not isinstance(v, (bool, np.bool_)) and isinstance(v, (int, np.integer)) and v >= lo
+
+
 def _check_ints(*named):
   """(name, value, lowest) triples: a ValueError unless every value is an integer (no bool) >= its lowest."""
   for name, v, lo in named:
-    if isinstance(v, (bool, np.bool_)) or not isinstance(v, (int, np.integer)) or v < lo:
+    if not _is_int(v, lo):
       raise ValueError('%s must be an integer >= %d: %r' % (name, lo, v))
+
+
+def _check_num_steps(num_steps) -> int:
+  """The step count of a handle, as plan_steps and plan_loss_times take it."""
+  if not _is_int(num_steps, 1):
+    raise ValueError('num_steps must be a positive integer: %r' % (num_steps,))
+  return int(num_steps)
 
 
 def plan_resample(start_step: int, jump: int, times: int):
@@ -236,10 +246,8 @@ def plan_steps(num_steps: int, steps: int):
   = (N / K - 1, N / K) -- step j of the call has the time of table row (j + 1) N / K - 1, because (j + 1) / K and
   (r + 1) / N are the same rational, correctly rounded.  K must be a positive integer that divides N: anything else
   (0, negatives, bools, non-integers, non-divisors) is a ValueError that names the divisors of N.  No device needed."""
-  if isinstance(num_steps, bool) or not isinstance(num_steps, (int, np.integer)) or num_steps < 1:
-    raise ValueError('num_steps must be a positive integer: %r' % (num_steps,))
-  n = int(num_steps)
-  if isinstance(steps, (bool, np.bool_)) or not isinstance(steps, (int, np.integer)) or steps < 1 or n % int(steps):
+  n = _check_num_steps(num_steps)
+  if not _is_int(steps, 1) or n % int(steps):
     raise ValueError('steps must divide the model\'s %d steps: got %r; the divisors are %s'
                      % (n, steps, ', '.join(str(k) for k in divisors(n))))
   return n // int(steps) - 1, n // int(steps)
@@ -644,8 +652,7 @@ class NativeModel:
         flags = keep_mask.detach().cpu().numpy() if hasattr(keep_mask, 'detach') else np.asarray(keep_mask)
         release, keep_mask, edit = np.ascontiguousarray(flags != 0, dtype=np.int32), None, True
     # (1) what the call may not combine or name
-    if rng not in RNGS:
-      raise ValueError('rng must be one of %s: %r' % (sorted(RNGS), rng))
+    _check_rng(rng)
     if few and (keep is not None or keep_mask is not None or edit or start_step is not None):
       raise ValueError('steps / sampler cannot be combined with keep / keep_mask / release / start_step')
     if sampler is not None and sampler not in SAMPLERS:
@@ -663,9 +670,7 @@ class NativeModel:
     elif (keep is None) != (keep_mask is None):
       raise ValueError('keep and keep_mask go together')
     # (2) the keys: one for the whole array, or one per row
-    per_row = not (np.isscalar(seed) and np.isscalar(stream_id))
-    seeds, stream_ids = row_keys(batch if per_row else 1, seed, stream_id)
-    keys = (ctypes.c_uint64 * len(seeds))(*seeds), (ctypes.c_uint64 * len(seeds))(*stream_ids)
+    per_row, *keys = _key_arrays(batch, seed, stream_id)
     # (3) the entry point
     lib, h, kind, draws, tail = self.lib, self.handle, RNGS[rng], (_ptr(init_z), _ptr(noise)), (_ptr(out), stream)
     if guidance is not None or guide_range is not None:
@@ -701,8 +706,7 @@ class NativeModel:
     [batch, T] or None = ones; eps: float32 device [len(times), batch, T, n] or None = drawn under (seed, stream_id) with
     `rng`, scalars or one per row as in sample().  A time index that appears twice draws the same eps twice.  loss_type /
     loss_norm: diffusion_utils.calculate_loss's names.  Argument errors are raised before the library is called."""
-    if rng not in RNGS:
-      raise ValueError('rng must be one of %s: %r' % (sorted(RNGS), rng))
+    _check_rng(rng)
     if conditioning not in LOSS_CONDITIONINGS:
       raise ValueError('conditioning must be one of %s: %r' % (sorted(LOSS_CONDITIONINGS), conditioning))
     if loss_type not in LOSS_TYPES:
@@ -710,19 +714,18 @@ class NativeModel:
     if loss_norm not in LOSS_NORMS:
       raise ValueError('Unknown diffusion loss norm: %r (one of %s)' % (loss_norm, sorted(LOSS_NORMS)))
     idx = plan_loss_times(self.cfg.num_steps, times)
-    per_row = not (np.isscalar(seed) and np.isscalar(stream_id))
-    seeds, stream_ids = row_keys(batch if per_row else 1, seed, stream_id)
+    per_row, seeds, stream_ids = _key_arrays(batch, seed, stream_id)
     passes = 2 if conditioning == 'both' else 1
     frames = batch * self.cfg.targets_length
-    for name, t, want in (('target', target, frames * self.cfg.n_dims), ('out', out, len(idx) * passes * frames),
-                          ('mask', mask, frames), ('eps', eps, len(idx) * frames * self.cfg.n_dims)):
-      if t is None and name in ('mask', 'eps'):
-        continue
-      if t is None or int(np.prod(tuple(t.shape))) != want:
-        raise ValueError('%s must hold %d float32 values: got %s' % (name, want, None if t is None else tuple(t.shape)))
+    _check_holds('target', target, frames * self.cfg.n_dims)
+    _check_holds('out', out, len(idx) * passes * frames)
+    if mask is not None:
+      _check_holds('mask', mask, frames)
+    if eps is not None:
+      _check_holds('eps', eps, len(idx) * frames * self.cfg.n_dims)
     a = LossArgs()
     a.struct_size, a.batch, a.rng, a.per_row = ctypes.sizeof(LossArgs), batch, RNGS[rng], int(per_row)
-    a.seeds, a.stream_ids = (ctypes.c_uint64 * len(seeds))(*seeds), (ctypes.c_uint64 * len(seeds))(*stream_ids)
+    a.seeds, a.stream_ids = seeds, stream_ids
     a.target_dev, a.mask_dev, a.eps_dev, a.out_dev = _ptr(target), _ptr(mask), _ptr(eps), _ptr(out)
     a.times_host, a.n_times = (ctypes.c_int32 * len(idx))(*idx), len(idx)
     a.conditioning, a.loss_type, a.loss_norm = LOSS_CONDITIONINGS[conditioning], LOSS_TYPES[loss_type], LOSS_NORMS[loss_norm]
@@ -740,9 +743,8 @@ class NativeModel:
       plan_steps(self.cfg.num_steps, steps)   # (its checks: a ValueError that names the divisors)
     weights = check_guidance(1.0 if guidance is None else guidance, batch)
     want = batch * self.cfg.targets_length * self.cfg.n_dims
-    for name, t in (('mel', mel), ('out', out)):
-      if t is None or int(np.prod(tuple(t.shape))) != want:
-        raise ValueError('%s must hold %d float32 values: got %s' % (name, want, None if t is None else tuple(t.shape)))
+    _check_holds('mel', mel, want)
+    _check_holds('out', out, want)
     a = InvertArgs()
     a.struct_size, a.batch, a.num_steps = ctypes.sizeof(InvertArgs), batch, int(steps or 0)
     a.mel_dev, a.out_dev = _ptr(mel), _ptr(out)
@@ -810,6 +812,25 @@ def row_keys(batch: int, seed, stream_id) -> Tuple[List[int], List[int]]:
       raise ValueError('%s has %d entries for a batch of %d' % (what, len(v), batch))
     return v
   return rows(seed, 'seed'), rows(stream_id, 'stream_id')
+
+
+def _key_arrays(batch: int, seed, stream_id):
+  """(per_row, seeds, stream_ids) as the entry points take a call's keys: two uint64 arrays, `batch` long for per-row keys
+  (either argument a sequence; a scalar beside it is broadcast), else of the one key."""
+  per_row = not (np.isscalar(seed) and np.isscalar(stream_id))
+  seeds, stream_ids = row_keys(batch if per_row else 1, seed, stream_id)
+  return per_row, (ctypes.c_uint64 * len(seeds))(*seeds), (ctypes.c_uint64 * len(seeds))(*stream_ids)
+
+
+def _check_holds(name: str, t, want: int):
+  """Tensor `name` (torch or NumPy) must hold `want` float32 values."""
+  if t is None or int(np.prod(tuple(t.shape))) != want:
+    raise ValueError('%s must hold %d float32 values: got %s' % (name, want, None if t is None else tuple(t.shape)))
+
+
+def _check_rng(rng):
+  if rng not in RNGS:
+    raise ValueError('rng must be one of %s: %r' % (sorted(RNGS), rng))
 
 
 def fill_normal(out, seed: int, stream_id: int, subseq: int, stream: int = 0):

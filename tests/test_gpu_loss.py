@@ -364,3 +364,26 @@ def test_refusals_leave_the_handle_usable(torch):
     assert rc == rc_want and word in msg, (kw, rc, msg)
   assert raw()[0] == 0
   assert np.array_equal(model.loss(batch, times=[3])['per_frame'], good)   # the handle works afterwards
+
+
+# --------------------------------------------------------------------------------------------------
+# 4. range fallback
+# --------------------------------------------------------------------------------------------------
+def test_range_error_and_fallback(torch):
+  """The scaled-norm model of tests/test_gpu_model.py at the two ends of the time grid: MSD_ERR_RANGE on 'f16x3'; with
+  range_fallback the call is repeated on the bfloat16 planes, as predict's and invert's are."""
+  from tests.test_gpu_model import _overflowing_params
+  spec = msd_amd.config.preset('tiny_context', num_steps=N)
+  big = _overflowing_params(msd_amd.synthetic.init_params(spec, 3, norm_scale_jitter=0.1))
+  batch = _batch(spec, b=1)
+  strict = msd_amd.InferenceModel(big, spec, range_fallback=False)
+  with pytest.raises(native.RangeError, match='bf16x3'):
+    strict.loss(batch, times=[0, N - 1])
+  assert strict.precision == 'f16x3'
+  model = msd_amd.InferenceModel(big, spec, range_fallback=True)
+  with pytest.warns(RuntimeWarning, match='bf16x3'):
+    got = model.loss(batch, times=[0, N - 1])
+  assert model.precision == 'bf16x3' and model._get_native().planes == 'bf16'
+  assert got['times'] == [0, N - 1] and got['per_frame'].shape == (1, 1, 64)
+  for key in ('loss', 'per_row', 'per_frame', 'per_time'):
+    assert np.isfinite(got[key]).all(), key
