@@ -58,7 +58,9 @@ extern "C" {
                                       in an interval of the scan); msd_loss and msd_op_diffusion_loss;
                                       msd_invert and msd_op_invert_step (deterministic DDIM inversion);
                                       msd_op_sampler_step_planes (a sampler update of any form with its operand planes,
-                                      range flag and published scan index, for the tests).
+                                      range flag and published scan index, for the tests);
+                                      msd_op_vocoder_phase, msd_op_vocoder_load_spec and msd_vocoder_debug_read (the
+                                      vocoder's phase update, its row layout and its work buffers, for the tests).
                                    6: cross_merge_in_launch, cross_q_fold, mlp_in_persistent appended to msd_config.
                                    5: dedup_layer0, cross_key_split, keep_raw_weights, kv_touch_ahead appended to msd_config.
                                    4: every caller-selectable knob is a msd_config field (attn_q_planes / attn_p_planes
@@ -968,6 +970,28 @@ typedef struct msd_sampler_planes_args {
   float* z_planes_out_dev;
 } msd_sampler_planes_args;
 int msd_op_sampler_step_planes(msd_sampler_planes_args* args, void* stream);
+
+/* ---- (appended to ABI 7) The vocoder's layout and unit-vector kernels on their own (tests/test_gpu_vocoder_edges.py) ----
+ * Host code around kernels the msd_vocoder_* entry points launch already.  A spectrum row is 1088 floats (real parts at
+ * [0, 513), imaginary parts at [544, 1057), zeros between), a magnitude row 544 (513 bins, zeros behind); a call of
+ * `batch` songs of F frames has batch (F + 1) rows, row b (F + 1) + k = frame k of song b, the rows k = F straddle two
+ * songs.  All three synchronise; null pointers, non-positive sizes and more than 2^20 rows give
+ * MSD_ERR_INVALID_ARGUMENT before any device work. */
+/* The phase update of one Griffin-Lim iteration, launched as msd_vocoder_decode launches it: U = Y - alpha Y_prev,
+ * X = mag U / |U|, (mag, 0) where U = 0.  y_dev, yprev_dev, x_out_dev float [rows, 1088]; mag_dev float [rows, 544]. */
+int msd_op_vocoder_phase(const float* y_dev, const float* yprev_dev, const float* mag_dev, float* x_out_dev, int rows,
+                         float alpha, void* stream);
+/* The caller's spectrum (or phases) into spectrum rows, as msd_vocoder_istft and msd_vocoder_decode launch it:
+ * src_dev float [batch, n_frames, 2, 513]; mag_dev float [batch (n_frames + 1), 544] or NULL (= ones);
+ * x_out_dev float [batch (n_frames + 1), 1088] = mag . src, with normalise != 0: mag . src / |src| per (re, im) pair,
+ * (mag, 0) for the zero pair.  Straddling rows and pad columns come out zero. */
+int msd_op_vocoder_load_spec(const float* src_dev, const float* mag_dev, float* x_out_dev, int batch, int n_frames,
+                             int normalise, void* stream);
+/* One work buffer of the handle as its LAST call left it (in the spirit of msd_debug_read): `buffer` is "audio"
+ * (320 floats per row: the padded signals), "x", "y0", "y1" (1088), "frames" (640) or "mag" (544); *rows_out (may be
+ * NULL) = rows of that call, batch (F + 1); min(rows . floats per row, max_elems) floats are copied to host_out.
+ * MSD_ERR_BAD_STATE: no call has run on the handle.  Waits for the whole device. */
+int msd_vocoder_debug_read(msd_vocoder* v, const char* buffer, float* host_out, int64_t max_elems, int64_t* rows_out);
 
 #ifdef __cplusplus
 }

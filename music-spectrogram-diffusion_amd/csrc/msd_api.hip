@@ -2951,8 +2951,6 @@ int vfail(msd_vocoder* v, int code, const char* fmt, ...) {
   v->err = buf;
   return code;
 }
-constexpr int64_t kVocMaxRows = 1 << 20;   // spectrum rows per call (the elementwise kernels index in 32 bits)
-inline bool voc_shape_ok(int batch, int64_t frames) { return batch > 0 && frames > 0 && (int64_t)batch * (frames + 1) <= kVocMaxRows; }
 // first launch error of a call (a launch wrapper's own hipGetLastError clears the runtime's copy)
 struct VocErr {
   hipError_t e = hipSuccess;
@@ -3005,6 +3003,7 @@ int msd_vocoder_stft(msd_vocoder* v, int batch, int64_t n_samples, const float* 
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int F = (int)frames, rows = batch * (F + 1);
   if (!voc_reserve(v, rows, s)) return vfail(v, MSD_ERR_HIP, "msd_vocoder_stft: cannot allocate %d rows", rows);
+  v->last_rows = (size_t)rows;
   VocErr err;
   voc_pad(v, batch, (int)n_samples, F, audio_dev, s);
   err(voc_forward(v, rows, EpiVocSpecOut{spec_out_dev, F}, s));
@@ -3017,6 +3016,7 @@ int msd_vocoder_istft(msd_vocoder* v, int batch, int n_frames, const float* spec
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int F = n_frames, rows = batch * (F + 1);
   if (!voc_reserve(v, rows, s)) return vfail(v, MSD_ERR_HIP, "msd_vocoder_istft: cannot allocate %d rows", rows);
+  v->last_rows = (size_t)rows;
   hipLaunchKernelGGL(voc_load_spec_kernel, voc_grid_rows(rows), dim3(256), 0, s, spec_dev, (const float*)nullptr, v->w[VB_X], F, rows, 0);
   VocErr err;
   err(voc_inverse(v, batch, F, audio_out_dev, false, s));
@@ -3030,6 +3030,7 @@ int msd_vocoder_encode(msd_vocoder* v, int batch, int64_t n_samples, const float
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int F = (int)frames, rows = batch * (F + 1);
   if (!voc_reserve(v, rows, s)) return vfail(v, MSD_ERR_HIP, "msd_vocoder_encode: cannot allocate %d rows", rows);
+  v->last_rows = (size_t)rows;
   VocErr err;
   voc_pad(v, batch, (int)n_samples, F, audio_dev, s);
   err(voc_forward(v, rows, EpiF32Store{v->w[VB_Y0], kVocSpec}, s));
@@ -3046,6 +3047,7 @@ int msd_vocoder_decode(msd_vocoder* v, int batch, int n_frames, const float* log
   hipStream_t s = static_cast<hipStream_t>(stream);
   const int F = n_frames, rows = batch * (F + 1);
   if (!voc_reserve(v, rows, s)) return vfail(v, MSD_ERR_HIP, "msd_vocoder_decode: cannot allocate %d rows", rows);
+  v->last_rows = (size_t)rows;
   // target magnitudes: max(exp(log-mel) . pinv(mel basis), 0); the straddling rows and pad columns stay zero
   const int64_t n_mel = (int64_t)batch * F * kVocMel;
   VocErr err;
@@ -3074,6 +3076,24 @@ int msd_vocoder_decode(msd_vocoder* v, int batch, int n_frames, const float* log
   }
   if (err.e == hipSuccess) err(voc_inverse(v, batch, F, audio_out_dev, false, s));
   return voc_finish(v, err, s, "msd_vocoder_decode");
+}
+
+int msd_vocoder_debug_read(msd_vocoder* v, const char* buffer, float* host_out, int64_t max_elems, int64_t* rows_out) {
+  if (!v || !buffer || !host_out || max_elems <= 0) return MSD_ERR_INVALID_ARGUMENT;
+  static const struct { const char* name; VocBuf buf; } kNames[] = {
+      {"audio", VB_AUDIO}, {"x", VB_X}, {"y0", VB_Y0}, {"y1", VB_Y1}, {"frames", VB_FRAMES}, {"mag", VB_MAG}};
+  const float* src = nullptr;
+  size_t per_row = 0;
+  for (const auto& n : kNames)
+    if (strcmp(buffer, n.name) == 0) { src = v->w[n.buf]; per_row = kVocPerRow[n.buf]; }
+  if (per_row == 0) return vfail(v, MSD_ERR_INVALID_ARGUMENT, "msd_vocoder_debug_read: unknown buffer '%s'", buffer);
+  if (v->last_rows == 0 || !src) return vfail(v, MSD_ERR_BAD_STATE, "msd_vocoder_debug_read: no call has run on this handle");
+  if (rows_out) *rows_out = (int64_t)v->last_rows;
+  const int64_t count = (int64_t)(v->last_rows * per_row), n = count < max_elems ? count : max_elems;
+  // a debug entry point: waits for the whole device (the entry points synchronise their stream themselves), then copies
+  if (hipDeviceSynchronize() != hipSuccess || hipMemcpy(host_out, src, (size_t)n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess)
+    return vfail(v, MSD_ERR_HIP, "msd_vocoder_debug_read: %s", hipGetErrorString(hipGetLastError()));
+  return MSD_OK;
 }
 
 }  // extern "C"

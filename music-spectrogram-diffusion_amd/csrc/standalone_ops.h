@@ -1,5 +1,5 @@
 // The msd_op_* entry points: the library's building blocks one at a time, for the unit tests (tests/test_gpu_ops.py,
-// test_gpu_fused_ops.py, test_gpu_gemm_sites.py, test_gpu_attention_forms.py (+ attention_forms.py, test_attention_forms_host.py), test_gpu_keep_frames.py, test_gpu_edit_strength.py, test_gpu_few_steps.py, test_gpu_threefry.py, test_gpu_invert.py, test_gpu_sampler_planes.py).  Host code only, and no
+// test_gpu_fused_ops.py, test_gpu_gemm_sites.py, test_gpu_attention_forms.py (+ attention_forms.py, test_attention_forms_host.py), test_gpu_keep_frames.py, test_gpu_edit_strength.py, test_gpu_few_steps.py, test_gpu_threefry.py, test_gpu_invert.py, test_gpu_sampler_planes.py, test_gpu_vocoder_edges.py).  Host code only, and no
 // part of the product's paths; the file belongs to msd_api.hip alone, which includes it behind its own entry points and
 // in front of the vocoder's.
 // Every GEMM here runs through the product's dispatch (gemm / gemm_on on a site's TileTable), so its tile is an entry of
@@ -1366,5 +1366,29 @@ int msd_op_gemm_site_tiles(int precision, int site, int index, int32_t* bm, int3
   bm[1] = bn[1] = ns[1] = 0;
   if (!second.empty()) { bm[1] = second[index].bm; bn[1] = second[index].bn; ns[1] = second[index].ns; }
   return MSD_OK;
+}
+
+// ---- the vocoder's two elementwise kernels with a unit vector in them, on the caller's rows (tests/test_gpu_vocoder_edges.py)
+// voc_phase_kernel as msd_vocoder_decode launches it: Y, Y_prev, X [rows, 1088], mag [rows, 544]
+int msd_op_vocoder_phase(const float* y_dev, const float* yprev_dev, const float* mag_dev, float* x_out_dev, int rows,
+                         float alpha, void* stream) {
+  if (!y_dev || !yprev_dev || !mag_dev || !x_out_dev || rows <= 0 || rows > kVocMaxRows) return MSD_ERR_INVALID_ARGUMENT;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(voc_phase_kernel, voc_grid_rows(rows), dim3(256), 0, s, y_dev, yprev_dev, mag_dev, x_out_dev, rows, alpha);
+  if (hipGetLastError() != hipSuccess) return MSD_ERR_HIP;
+  return hipStreamSynchronize(s) == hipSuccess ? MSD_OK : MSD_ERR_HIP;
+}
+
+// voc_load_spec_kernel as msd_vocoder_istft and msd_vocoder_decode launch it: src [B, F, 2, 513], mag [B (F + 1), 544] or
+// NULL, X [B (F + 1), 1088]
+int msd_op_vocoder_load_spec(const float* src_dev, const float* mag_dev, float* x_out_dev, int batch, int n_frames,
+                             int normalise, void* stream) {
+  if (!src_dev || !x_out_dev || !voc_shape_ok(batch, n_frames)) return MSD_ERR_INVALID_ARGUMENT;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  const int rows = batch * (n_frames + 1);
+  hipLaunchKernelGGL(voc_load_spec_kernel, voc_grid_rows(rows), dim3(256), 0, s, src_dev, mag_dev, x_out_dev, n_frames, rows,
+                     normalise ? 1 : 0);
+  if (hipGetLastError() != hipSuccess) return MSD_ERR_HIP;
+  return hipStreamSynchronize(s) == hipSuccess ? MSD_OK : MSD_ERR_HIP;
 }
 }  // extern "C"

@@ -89,6 +89,8 @@ __global__ void __launch_bounds__(256) voc_exp_kernel(const float* __restrict__ 
 
 // (cos, sin) of the direction of (a, b); (1, 0) for the zero vector.  The pair is scaled by a power of two first so that
 // neither square leaves the float range (a bin of a silent frame is denormal, not zero); one rsqrt is the normalisation.
+// A vector on an axis has an exact direction and gets it -- the rsqrt is within one ulp, and 0.75 * rsq(0.5625) came out
+// as 1 - 2^-24: the DC and Nyquist bins of every frame lie on the real axis (their imaginary parts are exact zeros).
 __device__ __forceinline__ void voc_unit(float a, float b, float& c, float& s) {
   const float m = fmaxf(fabsf(a), fabsf(b));
   const int e = (int)((__float_as_uint(m) >> 23) & 0xffu);
@@ -97,8 +99,8 @@ __device__ __forceinline__ void voc_unit(float a, float b, float& c, float& s) {
   b *= sc;
   const float n2 = a * a + b * b;
   const float r = __builtin_amdgcn_rsqf(n2);
-  c = n2 > 0.f ? a * r : 1.f;
-  s = n2 > 0.f ? b * r : 0.f;
+  c = n2 > 0.f ? (b == 0.f ? copysignf(1.f, a) : a * r) : 1.f;
+  s = n2 > 0.f ? (a == 0.f ? copysignf(1.f, b) : b * r) : 0.f;
 }
 
 // src [B, F, 2, 513] (a spectrum, or cos | sin of a phase) -> spectrum rows X [B (F + 1), 1088], times the magnitude
@@ -215,6 +217,7 @@ struct msd_vocoder {
   float* mel_inv = nullptr;    // pinv(mel basis) [128, 576] (columns >= 513 zero)
   float* inv_norm = nullptr;   // [2][320]
   size_t cap_rows = 0;
+  size_t last_rows = 0;        // spectrum rows of the last call (msd_vocoder_debug_read)
   float* w[msd::VB_COUNT] = {};
 };
 
@@ -272,6 +275,9 @@ inline GemmF32Params voc_gemm(const float* A, int lda, const float* B, int ldb, 
   p.A = A; p.B = B; p.lda = lda; p.ldb = ldb; p.M = M; p.N = N; p.K = K;
   return p;
 }
+
+constexpr int64_t kVocMaxRows = 1 << 20;   // spectrum rows per call (the elementwise kernels index in 32 bits)
+inline bool voc_shape_ok(int batch, int64_t frames) { return batch > 0 && frames > 0 && (int64_t)batch * (frames + 1) <= kVocMaxRows; }
 
 inline dim3 voc_grid_rows(int rows) { return dim3((unsigned)(((size_t)rows * kVocG4 + 255) / 256)); }
 inline dim3 voc_grid_samples(int per_song, int batch) { return dim3((unsigned)((per_song / 4 + 255) / 256), (unsigned)batch); }

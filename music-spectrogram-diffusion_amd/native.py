@@ -85,7 +85,9 @@ EXPORTED_SYMBOLS = (
     # (appended to ABI 7) deterministic DDIM inversion: the noise that renders a mel under the encoded tokens
     'msd_invert', 'msd_op_invert_step',
     # (appended to ABI 7) a sampler update of any form with its operand planes, range flag and published scan index
-    'msd_op_sampler_step_planes')
+    'msd_op_sampler_step_planes',
+    # (appended to ABI 7) the vocoder's phase update, its row layout and its work buffers, for the tests
+    'msd_op_vocoder_phase', 'msd_op_vocoder_load_spec', 'msd_vocoder_debug_read')
 
 
 LOSS_CONDITIONINGS = {'cond': 0, 'uncond': 1, 'both': 2}   # MSD_LOSS_COND, _UNCOND, _BOTH
@@ -477,6 +479,10 @@ def load(planes: str = 'f16') -> ctypes.CDLL:
     lib.msd_vocoder_istft.argtypes = [vp, i32, i32, vp, vp, vp]
     lib.msd_vocoder_encode.argtypes = [vp, i32, i64, vp, vp, vp]
     lib.msd_vocoder_decode.argtypes = [vp, i32, i32, vp, i32, c.c_float, u64, vp, vp, vp]
+  if 'msd_vocoder_debug_read' in present:   # (appended to ABI 7)
+    lib.msd_op_vocoder_phase.argtypes = [vp, vp, vp, vp, i32, c.c_float, vp]
+    lib.msd_op_vocoder_load_spec.argtypes = [vp, vp, vp, i32, i32, i32, vp]
+    lib.msd_vocoder_debug_read.argtypes = [vp, c.c_char_p, vp, i64, c.POINTER(i64)]
   if 'msd_op_gemm_site' in present:   # (appended to ABI 7)
     lib.msd_op_gemm_site.argtypes = [c.POINTER(GemmSiteArgs), vp]
     lib.msd_op_gemm_site_tiles.argtypes = [i32, i32, i32, c.POINTER(c.c_int32), c.POINTER(c.c_int32), c.POINTER(c.c_int32)]
@@ -1095,6 +1101,29 @@ def op_sampler_step_planes(cfg: MsdConfig, step_index: int, z, out_cond, out_unc
   a.z_out, a.z_planes_out = _ptr(z_out), _ptr(z_planes_out)
   _op_check(lib.msd_op_sampler_step_planes(ctypes.byref(a), stream), 'msd_op_sampler_step_planes')
   return a.ran_range_flag, a.ran_next_step
+
+
+def op_vocoder_phase(y, y_prev, mag, x_out, alpha: float, stream: int = 0):
+  """The vocoder's phase update on the caller's rows (msd_op_vocoder_phase): y, y_prev, x_out float32 device tensors
+  [rows, 1088], mag [rows, 544]; x_out = mag . U / |U| with U = y - alpha y_prev."""
+  rows = int(y.shape[0])
+  if tuple(y.shape) != (rows, 1088) or y_prev.shape != y.shape or x_out.shape != y.shape or tuple(mag.shape) != (rows, 544):
+    raise ValueError('y, y_prev and x_out must be [rows, 1088] and mag [rows, 544]')
+  _op_check(load().msd_op_vocoder_phase(_ptr(y), _ptr(y_prev), _ptr(mag), _ptr(x_out), rows, float(alpha), stream),
+            'msd_op_vocoder_phase')
+  return x_out
+
+
+def op_vocoder_load_spec(src, mag, x_out, normalise: bool, stream: int = 0):
+  """The vocoder's spectrum loader on the caller's arrays (msd_op_vocoder_load_spec): src float32 device tensor
+  [B, F, 2, 513], mag [B (F + 1), 544] or None, x_out [B (F + 1), 1088]."""
+  b, f = int(src.shape[0]), int(src.shape[1])
+  if tuple(src.shape) != (b, f, 2, 513) or tuple(x_out.shape) != (b * (f + 1), 1088) or \
+      (mag is not None and tuple(mag.shape) != (b * (f + 1), 544)):
+    raise ValueError('src must be [B, F, 2, 513], x_out [B (F + 1), 1088] and mag [B (F + 1), 544] or None')
+  _op_check(load().msd_op_vocoder_load_spec(_ptr(src), _ptr(mag), _ptr(x_out), b, f, int(bool(normalise)), stream),
+            'msd_op_vocoder_load_spec')
+  return x_out
 
 
 def op_invert_step(cfg: MsdConfig, step_index: int, z, out_cond, out_uncond, weights, z_out, z_planes_out, stream: int = 0):

@@ -140,6 +140,23 @@ class GriffinLimVocoder:
               int(seed) & 0xFFFFFFFFFFFFFFFF, None if ph is None else ph.data_ptr(), out.data_ptr())
     return self._out(out, return_torch)
 
+  DEBUG_BUFFERS = {'audio': 320, 'x': 1088, 'y0': 1088, 'y1': 1088, 'frames': 640, 'mag': 544}   # floats per row
+
+  def debug_read(self, buffer: str) -> np.ndarray:
+    """One work buffer as the last call left it (msd_vocoder_debug_read; for the tests): float32 [rows, floats per row],
+    rows = B (F + 1) of that call."""
+    if buffer not in self.DEBUG_BUFFERS:
+      raise ValueError('buffer must be one of %s' % sorted(self.DEBUG_BUFFERS))
+    rows = ctypes.c_int64(0)
+    probe = np.zeros(1, np.float32)
+    with self._torch.cuda.device(self.device):
+      self._check(self.lib.msd_vocoder_debug_read(self.handle, buffer.encode(), probe.ctypes.data, 1, ctypes.byref(rows)),
+                  'msd_vocoder_debug_read')
+      out = np.zeros((rows.value, self.DEBUG_BUFFERS[buffer]), np.float32)
+      self._check(self.lib.msd_vocoder_debug_read(self.handle, buffer.encode(), out.ctypes.data, out.size, None),
+                  'msd_vocoder_debug_read')
+    return out
+
 
 # ---- 16-bit PCM files (the stdlib wave module; mono) -----------------------------------------------------------------
 def write_wav(path: str, audio, sample_rate: int = 16000) -> float:

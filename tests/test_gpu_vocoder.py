@@ -1,7 +1,10 @@
 """The device vocoder (csrc/vocoder.h behind msd_vocoder_*) against its float64 specification in audio_codecs.py.
 
 Shapes: F = 70 frames (no multiple of the 64-row GEMM tile, and more than one tile) and B = 2 songs (the row that
-straddles two songs in the batched launch).  The GEMM-shaped operations are held to the forward error bound of a
+straddles two songs in the batched launch) -- ONE instance of the batched layout, on a signal without silence.  The other
+shapes (song boundaries on tile edges, one song, one row, three songs), silent songs, sample counts on and next to a
+multiple of the hop, the work buffers' layout invariants, the unit vector's corners and handle reuse across entry points:
+tests/test_gpu_vocoder_edges.py.  The GEMM-shaped operations are held to the forward error bound of a
 float32 dot product, |err| <= (K + 2) 2^-24 (|A| . |B|) elementwise, built here from float64 quantities
 (tools/vocoder_cases.py); a wrong row, sign, window or pad column is O(1) on that scale.  Waveforms of a few Griffin-Lim
 iterations are held to 16x the distance a float32 NumPy restatement keeps from float64; long runs to the spectral

@@ -16,7 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'tools'))
 import vocoder_cases as vc  # noqa: E402  (tools/vocoder_cases.py: shared with tools/vocoder_report.py)
 NEW_SYMBOLS = ('msd_vocoder_create', 'msd_vocoder_destroy', 'msd_vocoder_last_error', 'msd_vocoder_stft',
-               'msd_vocoder_istft', 'msd_vocoder_encode', 'msd_vocoder_decode')
+               'msd_vocoder_istft', 'msd_vocoder_encode', 'msd_vocoder_decode',
+               'msd_op_vocoder_phase', 'msd_op_vocoder_load_spec', 'msd_vocoder_debug_read')
 F = 70
 
 
@@ -52,6 +53,16 @@ def test_symbols_in_header_binding_and_both_libraries():
   assert lib.msd_vocoder_encode(None, 1, 640, buf, buf, None) == 1
   assert lib.msd_vocoder_decode(None, 1, 2, buf, 4, 0.99, 0, None, buf, None) == 1
   assert lib.msd_vocoder_last_error(None) == b'null vocoder'
+  # ... and the test entry points: null pointers, non-positive sizes, more than 2^20 rows
+  assert lib.msd_op_vocoder_phase(None, buf, buf, buf, 1, 0.5, None) == 1
+  assert lib.msd_op_vocoder_phase(buf, buf, buf, None, 1, 0.5, None) == 1
+  assert lib.msd_op_vocoder_phase(buf, buf, buf, buf, 0, 0.5, None) == 1
+  assert lib.msd_op_vocoder_phase(buf, buf, buf, buf, 2 ** 20 + 1, 0.5, None) == 1
+  assert lib.msd_op_vocoder_load_spec(None, None, buf, 1, 1, 0, None) == 1
+  assert lib.msd_op_vocoder_load_spec(buf, None, None, 1, 1, 1, None) == 1
+  assert lib.msd_op_vocoder_load_spec(buf, None, buf, 0, 1, 0, None) == 1
+  assert lib.msd_op_vocoder_load_spec(buf, None, buf, 1, 2 ** 20, 0, None) == 1
+  assert lib.msd_vocoder_debug_read(None, b'mag', buf, 4, None) == 1
   lib.msd_vocoder_destroy(None)
 
 
@@ -125,6 +136,47 @@ def test_silence_decodes_to_silence():
   assert mag.shape == (1, F, 513) and (mag >= 0).all()
   audio = ac.griffin_lim(mag, 32)
   assert audio.shape == (1, F * 320) and np.isfinite(audio).all() and np.abs(audio).max() < 1e-4
+
+
+def test_unit_vector_reference_and_emulation_agree_on_the_corner_table():
+  """The corner pairs fed to the device (tests/test_gpu_vocoder_edges.py), here through the float32 emulation of voc_unit with
+  its reciprocal square root exact and one ulp to either side: within 6 x 2^-24 of the float64 direction, and exact where
+  the table says so."""
+  c = vc.unit_corners()
+  assert c.shape == (18, 2) and c.dtype == np.float32
+  top = np.maximum(np.abs(c[:, 0]), np.abs(c[:, 1]))
+  assert sorted(set(((top.view(np.uint32) >> 23) & 0xFF)[13:].tolist())) == [252, 253, 254]   # where the clamp acts
+  want_c, want_s = vc.unit_reference(c[:, 0], c[:, 1])
+  assert np.allclose(want_c ** 2 + want_s ** 2, 1.0, rtol=0, atol=1e-15)
+  for ulps in (-1, 0, 1):
+    got_c, got_s = vc.unit_emulated(c[:, 0], c[:, 1], ulps)
+    err = np.maximum(np.abs(got_c - want_c), np.abs(got_s - want_s))
+    print('unit vector emulation, rsqrt %+d ulp: max %.2f x 2^-24' % (ulps, err.max() / vc.U))
+    assert (err <= vc.UNIT_BOUND).all()
+    assert np.array_equal(np.stack([got_c, got_s], 1)[:3], [[1, 0]] * 3)   # the zero vector, whatever its signs
+    assert (got_c[6], got_s[6]) == (0, -1) and (got_c[7], got_s[7]) == (-1, 0)   # on an axis (the emulation copies the kernel's select: this keeps the table in step with it; the evidence is the device's, test_gpu_vocoder_edges.test_unit_vector_on_an_axis_is_exact)
+  got_c, got_s = vc.unit_emulated(c[:, 0], c[:, 1])
+  assert abs(got_c[4] + np.sqrt(0.5)) < 1e-7 and abs(got_s[4] - np.sqrt(0.5)) < 1e-7   # a denormal pair is no zero vector
+  pairs = vc.unit_random(np.random.default_rng(20260101), (64, 513))   # the GPU test's block: every exponent, finite
+  assert np.isfinite(pairs).all() and (np.abs(pairs).max(axis=-1) > 0).all()
+  got_c, got_s = vc.unit_emulated(pairs[..., 0], pairs[..., 1], 1)
+  want_c, want_s = vc.unit_reference(pairs[..., 0], pairs[..., 1])
+  assert (np.maximum(np.abs(got_c - want_c), np.abs(got_s - want_s)) <= vc.UNIT_BOUND).all()
+
+
+@pytest.mark.parametrize('shape', vc.EDGE_SHAPES)
+def test_magnitude_bound_holds_for_the_float32_restatement(shape):
+  """(128 + 2 + 4) 2^-24 (exp(logmel) . |pinv|): a float32 NumPy run of exp -> pinv product -> max(., 0) stays inside it
+  on every element (measured: <= 0.06 of it), and the silent song of a batch is the floor in every bin."""
+  b, f = shape
+  logmel = vc.logmel_of(vc.songs(b, f))
+  want = ac.mel_to_linear(logmel.astype(np.float64))
+  bound = vc.mag_bound(logmel)
+  err = np.abs(vc.mag_float32(logmel).astype(np.float64) - want)
+  print('magnitudes %dx%d: float32 NumPy max err / bound %.4f' % (b, f, (err / np.maximum(bound, 1e-300)).max()))
+  assert bound.shape == want.shape == (b, f, 513) and (err <= bound).all()
+  if b > 1:
+    assert (logmel[1] == np.float32(np.log(1e-5))).all() and (logmel[0] > np.float32(np.log(1e-5))).any()
 
 
 def test_wav_round_trip(tmp_path):
