@@ -486,7 +486,13 @@ int msd_get_schedule(const msd_model* m, float* host_out);
  * [Ld][Bmax][S_pad][J] and "cross_vt" [Ld][Bmax][J][S_pad] (keys permuted within every 16: gemm_h16.h vt_perm16), and the
  * load-time tables "film" [N][2 Ld][2 D], "g_table" [N][2 Ld][D] = gamma (film_scale + 1), "bw_self" [N][Ld][3 J] =
  * film_bias_self . (Wq | Wk | Wv) and "bw_mlp" [N][Ld][2 F] = film_bias_mlp . (wi_0 | wi_1) in the gated projection's
- * packed column order (EpiF32StoreGated). */
+ * packed column order (EpiF32StoreGated).  The decoder's per-step buffers hold what the LAST decoder evaluation's last
+ * layer left (pass p in rows [p BT, (p + 1) BT)): "x" [M][D], "ssq" [M][D / 32], "y" [M][D], "qk" [M][2 J], "vt"
+ * [segments][J][T], "ao" [M][J], "g" [M][F], "eps" [M][128], the conditional rows' "cq" (folded projection: [BT][n_cross J],
+ * un-normalised; else [Bmax T][J] per module), "xg" [BT][D] and "qp" [BT][n_cross J] (folded projection only), and, on a
+ * handle with a second cross-attention module (sum_cross_attends with a context encoder), that module's "ao2" [Bmax T][J]
+ * and "cq2" [Bmax T][J] (the second half of "cq"; written by the un-folded projection only) -- on any other handle these
+ * two names are unknown buffers. */
 int msd_debug_read(msd_model* m, const char* buffer, float* host_out, int64_t max_elems,
                    int64_t* n_out);
 

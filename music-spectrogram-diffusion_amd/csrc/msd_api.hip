@@ -2874,6 +2874,10 @@ int msd_debug_read(msd_model* m, const char* buffer, float* host_out, int64_t ma
   else if (b == "ao") { pl = &m->ao; count = Mmax * m->J; }
   else if (b == "g") { pl = &m->g; count = Mmax * m->F; }
   else if (b == "cq") { pl = &m->cq; count = (int64_t)m->n_cross * m->Bmax * m->T * m->J; }
+  // the second module (sum_cross_attends): conditional rows only, [Bmax T, J] each -- ao2 is allocated that size, and cq2
+  // is the second half of cq's allocation (create), which is where the un-folded projection of module 1 writes
+  else if (b == "ao2" && m->n_cross == 2 && m->ao2.p[0]) { pl = &m->ao2; count = (int64_t)m->Bmax * m->T * m->J; }
+  else if (b == "cq2" && m->n_cross == 2 && m->cq2.p[0]) { pl = &m->cq2; count = (int64_t)m->Bmax * m->T * m->J; }
   else if (b == "xg" && m->fold_q) { pl = &m->xg; count = (int64_t)m->Bmax * m->T * m->D; }
   else if (b == "qp" && m->fold_q) { f32 = m->qp; count = (int64_t)m->Bmax * m->T * m->n_cross * m->J; }
   else if (b == "enc") { pl = &m->enc; count = (int64_t)m->S_pad * m->D; }

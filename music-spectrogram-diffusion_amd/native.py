@@ -781,7 +781,27 @@ class NativeModel:
     """An internal buffer as flat float32 (msd_debug_read; 16-bit planes merged).  The encode stage: 'enc' [S_pad, D]
     (the last encoded row), 'cross_k' [Ld, Bmax, S_pad, J], 'cross_vt' [Ld, Bmax, J, S_pad] (keys permuted per 16).  The
     load-time tables: 'film' [N, 2 Ld, 2 D], 'g_table' [N, 2 Ld, D], 'bw_self' [N, Ld, 3 J], 'bw_mlp' [N, Ld, 2 F] (the
-    gated projection's packed column order)."""
+    gated projection's packed column order).
+
+    The decoder's per-step buffers hold what the LAST decoder evaluation left, and of its layers the last one's (they
+    are overwritten layer by layer).  B songs of T frames, BT = B T, pass p in rows [p BT, (p + 1) BT) -- the conditional
+    pass first in a CFG step --, J = heads 64, F = the MLP width, nq = n_cross J (tests/decoder_stage_cases.py reads them
+    this way, tests/test_gpu_decoder_stages.py holds each to float64):
+      'qk'  [M, 2 J]       q | k of the self-attention; layer 0 of a CFG step under dedup_layer0: the first BT rows only
+      'vt'  [M / T, J, T]  v transposed per (pass, song), keys permuted per 16
+      'ao'  [M, J]         conditional rows: the FIRST cross-attention module's output (it overwrites the self-attention
+                           output); unconditional rows: the self-attention output (layer 0 under dedup: not written)
+      'ao2' [Bmax T, J]    the second module's output (sum_cross_attends with a context encoder; else an unknown buffer)
+      'cq'  folded query projection: [BT, nq], the modules' UN-normalised queries (x1 (.) gamma_cross) Wq_e side by side
+            (the attention applies 1 / rms from 'ssq'); un-folded: [Bmax T, J] per module, the normalised queries --
+            'cq2' [Bmax T, J] is the second module's part (un-folded only; an unknown buffer without a second module)
+      'qp'  [BT, nq] float32, 'xg' [BT, D]: (x0 (.) gamma_cross) Wq_e and x0 (.) gamma_cross, x0 = the stream entering
+            the layer (handles with the folded projection only; written on the passes that fold)
+      'g'   [M, F]         the gated product          'x'  [M, D]  the residual stream after the MLP
+      'ssq' [M, D / 32]    partial sums of x^2 per row: the slots ADD UP to sum x^2; which columns a slot covers depends
+                           on the producing tile's width (32 columns each where D has no 48-column tiling; spare slots 0)
+      'y'   [M, D]         x (.) gamma_decoder_norm, un-normalised (the consumer applies 1 / rms)
+      'eps' [M, 128]       the model output of every pass."""
     n = ctypes.c_int64()
     probe = np.zeros(1, np.float32)
     _check(self.lib, self.handle,

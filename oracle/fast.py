@@ -46,7 +46,7 @@ from oracle import sampler as du
 class FastModel:
 
   def __init__(self, xp, cfg, diffusion_config, params, context, precision='f32',
-               codec=None):
+               codec=None, in_proj_planes=False):
     assert cfg.decoder_cross_attend_style in ('concat_encodings', 'sum_cross_attends')
     self.sum_style = cfg.decoder_cross_attend_style == 'sum_cross_attends'
     assert diffusion_config.model_output in ('eps', 'x0', 'v')
@@ -54,6 +54,7 @@ class FastModel:
     self.xp, self.cfg, self.dc = xp, cfg, diffusion_config
     self.context = context
     self.precision = precision
+    self.in_proj_planes = in_proj_planes   # see decoder_pass
     self.codec = codec or predict_lib.MelGANCodec()
     self.p = {k: xp.asarray(v) for k, v in params.items()}
     self._wcache = {}
@@ -145,17 +146,22 @@ class FastModel:
     c = self.cfg
     return self.xp.reshape(x, (x.shape[0], c.num_heads, c.head_dim))
 
-  def _self_attention(self, prefix, h):
+  def _self_attention(self, prefix, h, tr=None):
     q = self.rq(self.mm(h, prefix + '/query/kernel'))
     k = self.rq(self.mm(h, prefix + '/key/kernel'))
     v = self.rq(self.mm(h, prefix + '/value/kernel'))
     a = self.rq(self._attend(self._heads(q), self._heads(k), self._heads(v)))
+    if tr is not None:
+      for name, val in (('q', q), ('k', k), ('v', v), ('self_ao', a)):
+        tr[name].append(val)
     return self.mm(a, prefix + '/out/kernel')
 
-  def _mlp(self, prefix, h):
+  def _mlp(self, prefix, h, tr=None):
     xp = self.xp
-    g = ops.gelu_tanh(xp, self.mm(h, prefix + '/wi_0/kernel')) * self.mm(h, prefix + '/wi_1/kernel')
-    return self.mm(self.rq(g), prefix + '/wo/kernel')
+    g = self.rq(ops.gelu_tanh(xp, self.mm(h, prefix + '/wi_0/kernel')) * self.mm(h, prefix + '/wi_1/kernel'))
+    if tr is not None:
+      tr['g'].append(g)
+    return self.mm(g, prefix + '/wo/kernel')
 
   # -- S2/S3: encoders on the valid positions only ----------------------------
   def _encoder_stack(self, prefix, x):
@@ -220,13 +226,51 @@ class FastModel:
       self.kv.append(mods or None)
 
   # -- one decoder pass --------------------------------------------------------
-  def decoder_pass(self, z, i, cond):
-    """z [B,T,n], scan index i -> eps prediction [B,T,n] (network.py:360-457)."""
+  # in_proj_planes (constructor keyword, opt-in: tests/decoder_stage_cases.py): the decoder's input projection in the
+  # emulated precision.  The device runs it on the operand planes of z (csrc/msd_api.hip in_proj); on half planes that is
+  # float32-class and the plain product models it, on bfloat16 planes it is a 2^-16-class product like the others --
+  # visible where a buffer holds nothing but that product (x0 (.) gamma_cross of layer 0: 4.5e-6 on the MI355X against
+  # 1.7e-7 without this).
+
+  def planes(self, a):
+    """A value the device STORES as operand planes (hi + lo, or one plane): what merges back."""
+    parts = self._split(a)
+    return parts[0] if len(parts) == 1 else parts[0] + parts[1]
+
+  TRACE_LAYER_KEYS = ('x0', 'self_in', 'q', 'k', 'v', 'self_ao', 'x1', 'cross_in', 'cross', 'x2', 'mlp_in', 'g', 'x3')
+
+  def set_film(self, table):
+    """Replace the FiLM table by a given one, [N, 2 Ld, 2 D] laid out as the device's msd_debug_read('film') (slot 2 l + k
+    = layer l's FiLMLayer_k, scale | bias), cast to the backend dtype: a float64 and a float32 evaluation that share the
+    table differ by the decoder's arithmetic alone (the float32 time signal of a table built here is 5e-5 away from the
+    float64 one, a hundred times the arithmetic's own error)."""
+    cfg = self.cfg
+    t = np.asarray(table).reshape(-1, 2 * cfg.num_decoder_layers, 2 * cfg.emb_dim)   # (N = the table's own step count)
+    self.film = [[self.xp.asarray(np.ascontiguousarray(t[:, 2 * l + k])) for k in range(2)]
+                 for l in range(cfg.num_decoder_layers)]
+
+  def decoder_pass(self, z, i, cond, trace=None):
+    """z [B,T,n], scan index i -> eps prediction [B,T,n] (network.py:360-457).
+
+    trace: None, or a list that receives one dict per batch row with the pass's intermediate arrays in the backend's
+    dtype.  Per layer (lists of num_decoder_layers entries; TRACE_LAYER_KEYS): 'x0' the residual stream entering the
+    layer, 'self_in' the FiLM-normed self-attention input, 'q' 'k' 'v' [T, J], 'self_ao' the self-attention output before
+    its projection, 'x1' the stream after the self block, 'cross_in' the cross-attention norm's output and 'cross' a dict
+    {module e: (q_e [T, J], attention output before its projection)} -- None and {} where the pass has no cross-attention
+    (unconditional, or no valid key: then 'x2' IS 'x1') --, 'x2' after the cross block, 'mlp_in' the FiLM-normed MLP
+    input, 'g' the gated product, 'x3' after the MLP.  After the layers: 'y' = rms_norm(x) and 'eps' [T, n].  Tracing
+    changes no arithmetic."""
     xp, p, cfg = self.xp, self.p, self.cfg
     outs = []
     for b in range(z.shape[0]):
-      # continuous_inputs_projection + positions: full precision (K = 128)
-      x = xp.matmul(z[b], p['decoder/continuous_inputs_projection/kernel'])
+      tr = None
+      if trace is not None:
+        tr = {k: [] for k in self.TRACE_LAYER_KEYS}
+        trace.append(tr)
+      # continuous_inputs_projection + positions: full precision (K = 128) -- or, with in_proj_planes, a GEMM on the
+      # operand planes of z like every other one, which is what the device's in_proj launch is
+      w_in = 'decoder/continuous_inputs_projection/kernel'
+      x = self.mm(z[b], w_in) if self.in_proj_planes else xp.matmul(z[b], p[w_in])
       x = x + p['decoder/Embed_0/embedding'][:z.shape[1]]
       d = cfg.emb_dim
       for l in range(cfg.num_decoder_layers):
@@ -234,24 +278,44 @@ class FastModel:
         sb = self.film[l][0][i]
         h = ops.rms_layer_norm(xp, x, p[lp + '/pre_self_attention_layer_norm/scale'])
         h = h * (sb[:d] + 1.0) + sb[d:]
-        x = x + self._self_attention(lp + '/self_attention', h)
+        if tr is not None:
+          tr['x0'].append(x)
+          tr['self_in'].append(h)
+        x = x + self._self_attention(lp + '/self_attention', h, tr)
+        if tr is not None:
+          tr['x1'].append(x)
+        cross_in, cross = None, {}
         if cond and self.kv[b] is not None:  # S4
           h = ops.rms_layer_norm(xp, x, p[lp + '/pre_cross_attention_layer_norm/scale'])
+          cross_in = h
           upd = None
           for e, layers in self.kv[b]:
             ap = lp + '/MultiHeadDotProductAttention_%d' % e
-            q = self._heads(self.rq(self.mm(h, ap + '/query/kernel')))
+            q = self.rq(self.mm(h, ap + '/query/kernel'))
             k, v = layers[l]
-            o = self.mm(self.rq(self._attend(q, k, v)), ap + '/out/kernel')
+            a = self.rq(self._attend(self._heads(q), k, v))
+            cross[e] = (q, a)
+            o = self.mm(a, ap + '/out/kernel')
             upd = o if upd is None else upd + o
           x = x + upd
+        if tr is not None:
+          tr['cross_in'].append(cross_in)
+          tr['cross'].append(cross)
+          tr['x2'].append(x)
         sb = self.film[l][1][i]
         h = ops.rms_layer_norm(xp, x, p[lp + '/pre_mlp_layer_norm/scale'])
         h = h * (sb[:d] + 1.0) + sb[d:]
-        x = x + self._mlp(lp + '/mlp', h)
+        if tr is not None:
+          tr['mlp_in'].append(h)
+        x = x + self._mlp(lp + '/mlp', h, tr)
+        if tr is not None:
+          tr['x3'].append(x)
       y = ops.rms_layer_norm(xp, x, p['decoder/decoder_norm/scale'])
       # spec_out_dense is float32 in the reference (network.py:454) and on the device
-      outs.append(xp.expand_dims(xp.matmul(y, p['decoder/spec_out_dense/kernel']), 0))
+      eps = xp.matmul(y, p['decoder/spec_out_dense/kernel'])
+      if tr is not None:
+        tr['y'], tr['eps'] = y, eps
+      outs.append(xp.expand_dims(eps, 0))
     return xp.concatenate(outs, 0)
 
   # -- sampler (diffusion_utils.py:398-476) ------------------------------------
